@@ -346,6 +346,48 @@ def roofline_render(dev, res=RES, k_pts=K_PTS, batch=BATCH):
             'avg_launch_ms': round(ms, 5), 'bytes_per_launch': nbytes}
 
 
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240601
+
+
+def _dump_arrays(tensors, prefix=''):
+    """Flatten {name: tensor | dict | scalar} into [(name, float32/float64 ndarray)] (nested dicts joined with '.')."""
+    items = []
+    for name in sorted(tensors):
+        v = tensors[name]
+        if isinstance(v, dict):
+            items += _dump_arrays(v, prefix + name + '.')
+        elif isinstance(v, torch.Tensor):
+            t = v.detach()
+            t = t.double() if t.dtype == torch.float64 else t.float()
+            items.append((prefix + name, t.cpu().numpy()))
+        elif isinstance(v, (float, int, np.floating, np.integer)) and not isinstance(v, bool):
+            items.append((prefix + name, np.asarray(v, dtype=np.float64)))
+    return items
+
+
+def dump_outputs(dirpath, tensors, max_bytes=DUMP_MAX_BYTES):
+    """Write what the timed path returned in its last step as DIR/<name>.npy (float32, float64 kept as is).  If the whole set exceeds
+    max_bytes, every array larger than an equal share of the budget is replaced by a fixed sample of its flattened elements: the indices
+    come from RandomState(DUMP_SAMPLE_SEED) and the array's shape only, so two runs with the same arguments sample the same elements.
+    Returns {name: [shape written, 'full' | 'sample of N']}."""
+    items = _dump_arrays(tensors)
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.nbytes for _, a in items)
+    share = max_bytes // max(1, len(items))
+    written = {}
+    for name, a in items:
+        kind = 'full'
+        if total > max_bytes and a.nbytes > share:
+            n = share // a.itemsize
+            idx = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(a.size, size=n, replace=False))
+            kind = 'sample of %d from %s' % (n, 'x'.join(map(str, a.shape)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirpath, name + '.npy'), np.ascontiguousarray(a))
+        written[name] = [list(a.shape), kind]
+    return written
+
+
 def host_cores():
     """Cores this process may actually use: min(affinity mask, cgroup-v2 cpu.max quota)."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
@@ -690,6 +732,7 @@ def bench_rollout(args, conf, dev, rank, world, launched, backend):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     assert bool(torch.isfinite(out['pred_im_seq']).all())
+    dumped = dump_outputs(args.dump_outputs, out) if args.dump_outputs and rank == 0 else None
     if rank == 0:
         frames = world * b * 32 * args.steps
         # translator 7.054 GMAC per frame (Appendix A) + detector / image encoder once per source image
@@ -703,6 +746,8 @@ def bench_rollout(args, conf, dev, rank, world, launched, backend):
                 'step_tflops': round(2 * gmac_frame * 1e9 * frames / dt / 1e12, 2),
                 'step_algorithmic_frac_of_f32_peak': round(2 * gmac_frame * 1e9 * frames / dt / world / 157.3e12, 4),
                 'host_call_wall_ms_per_step': round(t_enq / args.steps * 1e3, 3), 'dist_backend': backend if launched else None}
+        if dumped is not None:
+            line['dumped_outputs'] = dumped
         if world == 1:
             line['roofline'] = roofline_conv_c4(dev)       # the translator's 3x3 layers dominate the rollout; its own launch: a 256-frame slab
         print(json.dumps(line), flush=True)
@@ -730,6 +775,9 @@ def main():
     ap.add_argument('--no-roofline', action='store_true', help='skip the kernel microbenchmarks after the timed steps (clean per-step rocprofv3 kernel statistics)')
     ap.add_argument('--no-also', action='store_true', help='skip the `also` legs (bf16 / c3 / c4 on fresh models after the headline; N = 1, --config c1 --dtype f32 only)')
     ap.add_argument('--roofline-only', action='store_true', help='only the two kernel microbenchmarks (used for the rocprofv3 cross-check)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (losses, forward outputs; c4: the rollout) as DIR/<name>.npy, '
+                         'float32, at most 64 MB in all (larger outputs: a fixed seeded sample).  Rank 0 only')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -832,6 +880,8 @@ def main():
         dt = float(t.item())
     losses = model.loss_values()
     assert np.isfinite(losses['loss_D']) and np.isfinite(losses['loss_G']), losses
+    # (the graphed step's outputs are the capture's static buffers: read before anything else runs a step)
+    dumped = dump_outputs(args.dump_outputs, model.last) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -865,6 +915,8 @@ def main():
                'launch_mode_by_rank': [model.LAUNCH_MODES[m].split(':')[0] for m in modes_by_rank],
                'host_abi_calls_per_step': round(calls_per_step, 1),
                'loss_D': round(losses['loss_D'], 5), 'loss_G': round(losses['loss_G'], 5)}
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         if launched:
             # N > 1 runs under bench.py's supervisor (DP_FORMS): the attempts that failed or hung before this one
             out['dp_graph_form'] = model.dp_graph if model.distributed else None

@@ -268,3 +268,28 @@ def test_bench_attempt_plan_puts_an_explicit_form_first(monkeypatch):
     assert [f for f, _ in bench.dp_attempt_plan()] == ['one', 'segments', 'inline']
     monkeypatch.setenv('KPX_DP_GRAPH', 'inline')
     assert bench.dp_attempt_plan() == [('inline', {'KPX_GRAPH': '0'}), ('segments', {})]
+
+
+def test_bench_dump_outputs_is_float_capped_and_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 / float64 .npy files, nested names joined with '.', at most the byte budget in all,
+    and an over-budget array sampled at the same elements on every run."""
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(64, 64, 64, generator=g)
+    outs = {'d_losses': torch.tensor([1.5, 0.5, 1.0]), 'lr': 1e-4, 'fwd': {'final_output': big, 'mask': big[:1].bfloat16(), 'none': None}}
+    budget = 256 << 10
+    for run in ('a', 'b'):
+        written = bench.dump_outputs(str(tmp_path / run), outs, max_bytes=budget)
+        assert sorted(written) == ['d_losses', 'fwd.final_output', 'fwd.mask', 'lr']
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(n + '.npy' for n in written)
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= budget + 128 * len(files)       # (+ the .npy headers)
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert written['fwd.final_output'][1].startswith('sample of')
+    fo = np.load(tmp_path / 'a' / 'fwd.final_output.npy')
+    assert np.all(np.isin(fo, big.numpy().reshape(-1)))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'd_losses.npy'), np.array([1.5, 0.5, 1.0], np.float32))
