@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 3
+#define KPX_ABI_VERSION 4
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -76,15 +76,20 @@ size_t kpx_wino_u_bytes(int Cin, int Cout);
 int kpx_wino_filter_transform_f32(const float* w_hwio, int Cin, int Cout, int dgrad, float* u, void* stream);
 int kpx_wino_filter_transform_batch_f32(const void* descs, int n, void* stream);
 int kpx_conv3x3_wino_eligible(int N, int H, int W, int K, int Nn, int ldin, const void* in);
+/* Epilogue options of kpx_conv3x3_wino_f32 (all NULL: the plain convolution):
+ *   tile_stats alone: the batch-norm statistics of the OUTPUT as well (tf.contrib.layers.batch_norm follows every generator conv,
+ *     models/networks/layers.py:13-14): tile_stats[N * (H/16) * (W/16)][2][Nn] = per 16x16-pixel tile and channel, the sum and the sum
+ *     of squares of out (fp32, fixed summation order).  kpx_bn_stats_from_tiles_f32 turns a tile range into mean / invstd / moving
+ *     statistics, replacing kpx_bn_stats_f32's pass over the activation.  H, W multiples of 16.
+ *   tile_stats + bn_y + bn_beta: data gradient of a 3x3 layer whose INPUT was bn_y = relu(BN(x)): out = dgrad (written as usual) and,
+ *     per 16x16-pixel tile and channel, tile_stats[tile][2][Nn] = sum(dz), sum(dz * (bn_y - bn_beta)) with dz = out * [bn_y > 0] -- the
+ *     two reductions of that batch norm's backward (bn_y: its output at the same pixels / channels, pixel stride ld_bn_y >= Nn).
+ *     kpx_bn_bwd_from_tiles_f32 consumes them.  No bias, act = KPX_ACT_NONE; H, W multiples of 16.
+ * Any other mix returns KPX_EINVAL. */
 int kpx_conv3x3_wino_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u, const float* bias,
-                         float* out, int Nn, int ldout, int act, void* stream);
-/* The same convolution, additionally writing the batch-norm statistics of its OUTPUT (tf.contrib.layers.batch_norm follows every
- * generator conv, models/networks/layers.py:13-14): tile_stats[N * (H/16) * (W/16)][2][Nn] = per 16x16-pixel tile and channel, the
- * sum and the sum of squares of out (fp32, fixed summation order).  kpx_bn_stats_from_tiles_f32 turns a tile range into mean /
- * invstd / moving statistics, replacing kpx_bn_stats_f32's pass over the activation.  H, W multiples of 16. */
+                         float* out, int Nn, int ldout, int act, float* tile_stats, const float* bn_y, int ld_bn_y,
+                         const float* bn_beta, void* stream);
 size_t kpx_conv3x3_wino_stats_tiles(int N, int H, int W);
-int kpx_conv3x3_wino_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u, const float* bias,
-                               float* out, int Nn, int ldout, int act, float* tile_stats, void* stream);
 
 /* ---- bf16 STORAGE (the bf16 configuration proper, BASELINE configs[2] "bf16 storage + fp32 accumulate"): the same layers.conv call sites
  *      (layers.py:4-10; networks/__init__.py:13-24,50-62,80-97; vgg.py:20-40) with bf16 activation tensors in HBM.  `in` is bf16
@@ -106,7 +111,7 @@ int kpx_conv3x3_bf16s(const void* in, int N, int H, int W, int K, int ldin, cons
                       void* out, int Nn, int ldout, int out_f32, int act, const void* mask, int ldmask, float* stats, void* stream);
 /* Data gradient towards bn_y = relu(batch_norm(.)) (bf16 [N,H,W,Nn]) with that batch norm's backward sums reduced in the epilogue: out = conv3x3(in, wf)
  * gated by bn_y > 0, stats[tile][2][Nn] = sum(dz), sum(dz * (bn_y - beta)) per workgroup -- kpx_bn_train_bwd_bf16 takes them as tile_stats and skips
- * its reduction pass over (dz, x) (the fp32 configuration's kpx_conv3x3_wino43_bnbwd_stats_f32). */
+ * its reduction pass over (dz, x) (the fp32 configuration's kpx_conv3x3_wino43_f32 with tile_stats + bn_y + bn_beta). */
 int kpx_conv3x3_bf16s_bnbwd(const void* in, int N, int H, int W, int K, int ldin, const void* wf, void* out, int Nn, int ldout,
                             const void* bn_y, int ld_bn_y, const float* beta, float* stats, void* stream);
 
@@ -157,12 +162,6 @@ int kpx_bn_stats_f32(const float* x, size_t P, int C, int ldx, float eps,
                      float* mean, float* invstd, float* var_biased,
                      float* moving_mean, float* moving_var, float decay,
                      void* scratch, void* stream);
-/* Data gradient of a 3x3 layer whose INPUT was y = relu(BN(x)): out = dgrad (written as usual) and, per 16x16-pixel tile and channel,
- * tile_stats[tile][2][Nn] = sum(dz), sum(dz * (bn_y - bn_beta)) with dz = out * [bn_y > 0] -- the two reductions of that batch norm's
- * backward (bn_y: its output at the same pixels / channels, pixel stride ld_bn_y).  kpx_bn_bwd_from_tiles_f32 consumes them. */
-int kpx_conv3x3_wino_bnbwd_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u,
-                                     float* out, int Nn, int ldout, const float* bn_y, int ld_bn_y, const float* bn_beta,
-                                     float* tile_stats, void* stream);
 /* Fused Winograd F(4x4,3x3): the same contract as kpx_conv3x3_wino_f32 (forward, or data gradient with dgrad-transformed filters) with
  * 36 instead of 144 multiplies per 4x4 outputs; fp32 error ~2-3e-6 rel-L2 (F(2x2,3x3): ~4e-7).  Eligible when H % 16 == 0, W % 32 == 0,
  * K >= 16, Nn > 32 and the usual 16-B alignment; `u` comes from kpx_wino43_filter_transform(_batch)_f32 (kpx_wino43_u_bytes bytes,
@@ -172,26 +171,28 @@ int kpx_conv3x3_wino43_eligible(int N, int H, int W, int K, int Nn, int ldin, co
 size_t kpx_wino43_u_bytes(int Cin, int Cout);
 int kpx_wino43_filter_transform_f32(const float* w_hwio, int Cin, int Cout, int dgrad, float* u, void* stream);
 int kpx_wino43_filter_transform_batch_f32(const void* descs_dev, int n, void* stream);
+/* Epilogue options, the same for kpx_conv3x3_wino43_f32 and kpx_conv3x3_wino43b_f32 (all NULL: the plain convolution):
+ *   tile_stats alone: the batch-norm statistics of the output, as kpx_conv3x3_wino_f32's but per 4 x 16-pixel strip: tile_stats[strip][2][Nn],
+ *     kpx_conv3x3_wino43_stats_tiles(N, H, W) strips (0 for packed 16 x 16 images: no statistics there), consumed by
+ *     kpx_bn_stats_from_tiles_f32 (tile_pixels 64);
+ *   tile_stats + bn_y + bn_beta: data gradient towards a ReLU'd batch norm's output (the tensor bn_y this convolution read in the forward
+ *     pass): out = dgrad * [bn_y > 0] and tile_stats[strip][2][Nn] = per strip sum(out), sum(out * (bn_y - beta)) -- kpx_bn_train_bwd_f32
+ *     takes them instead of its own reduction pass (tf.gradients of tf.contrib.layers.batch_norm + tf.nn.relu, models/networks/layers.py:13-14).
+ *     No bias, act = KPX_ACT_NONE;
+ *   mask_y and / or pool_y, VGG19's options (models/networks/vgg.py:45-55), no tile_stats: mask_y zeroes the output where mask_y <= 0 (the
+ *     ReLU backward of the tensor this data gradient belongs to); pool_y receives the 2x2 max-pool of the activated output ([N,H/2,W/2,Nn],
+ *     pixel stride ld_pool).
+ *   The bn and mask / pool forms need Nn % 64 == 0 and 16-B aligned rows everywhere.  Any other mix returns KPX_EINVAL. */
 int kpx_conv3x3_wino43_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u, const float* bias,
-                           float* out, int Nn, int ldout, int act, void* stream);
-/* The same with the batch-norm statistics of the output from the epilogue, as kpx_conv3x3_wino_stats_f32 but per 4 x 16-pixel strip:
- * tile_stats[strip][2][Nn], kpx_conv3x3_wino43_stats_tiles(N, H, W) strips, consumed by kpx_bn_stats_from_tiles_f32 (tile_pixels 64). */
-/* ... and with VGG19's two epilogue options: mask_y (or NULL): the output is zeroed where mask_y <= 0 (the ReLU backward of the tensor this
- * data gradient belongs to); pool_y (or NULL): the 2x2 max-pool of the activated output is written too ([N,H/2,W/2,Nn]).  Nn % 64 == 0. */
-int kpx_conv3x3_wino43_ex_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u, const float* bias,
-                              float* out, int Nn, int ldout, int act, const float* mask_y, int ld_mask, float* pool_y, int ld_pool, void* stream);
+                           float* out, int Nn, int ldout, int act, const float* mask_y, int ld_mask, float* pool_y, int ld_pool,
+                           float* tile_stats, const float* bn_y, int ld_bn_y, const float* bn_beta, void* stream);
 size_t kpx_conv3x3_wino43_stats_tiles(int N, int H, int W);
-int kpx_conv3x3_wino43_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u, const float* bias,
-                                 float* out, int Nn, int ldout, int act, float* tile_stats, void* stream);
 /* The same F(4x4,3x3) layers FP32-EQUIVALENT ON THE BF16 MATRIX PIPE (csrc/conv_wino43b.hip): U pre-split into three exact bf16 terms in
  * fragment order by kpx_wino43b_filter_transform(_batch)_f32 (kpx_wino43b_u_bytes bytes; descriptors as for
  * kpx_wino_filter_transform_batch_f32), V split in registers after the input transform, six v_mfma_f32_32x32x16_bf16 products per block,
  * fp32 accumulate: the fp32 configuration's arithmetic (error vs float64 as the fp32-MFMA kernel's), not the bf16 mode.  Eligible when
  * (H % 16 == 0 and W % 32 == 0, or 16 x 16 images in even number: two to a workgroup, no tile_stats), K >= 16, K % 4 == 0, Nn > 32, ldin >= K,
- * 16-B alignment.  One entry for every form of the launch: tile_stats
- * alone = kpx_conv3x3_wino43_stats_f32's statistics strips (kpx_conv3x3_wino43_stats_tiles); tile_stats + bn_y + bn_beta =
- * kpx_conv3x3_wino43_bnbwd_stats_f32 (no bias / act); mask_y / pool_y = kpx_conv3x3_wino43_ex_f32's options (Nn % 64 == 0); all NULL = the
- * plain convolution.  Replaces the same tf.layers.conv2d call sites (reference models/networks/layers.py:4-10 on
+ * 16-B alignment.  Arguments and epilogue options are kpx_conv3x3_wino43_f32's.  Replaces the same tf.layers.conv2d call sites (reference models/networks/layers.py:4-10 on
  * models/networks/__init__.py:13,22,80-97; models/networks/vgg.py:51). */
 int kpx_conv3x3_wino43b_eligible(int N, int H, int W, int K, int Nn, int ldin, const void* in_ptr);
 size_t kpx_wino43b_u_bytes(int Cin, int Cout);
@@ -203,7 +204,7 @@ int kpx_conv3x3_wino43b_f32(const float* in, int N, int H, int W, int K, int ldi
 /* 3x3 stride-1 SAME convolution PRODUCING exactly 16 channels on 16x16x4 MFMA blocks (no cout padding): the forward of the key-point
  * detector's last decoder block (64 -> 16, 16 -> 16 at full resolution, reference models/networks/__init__.py:50-54) and the data gradient
  * of its 16 -> 16 layer.  w_hwio is the layer's own filter: [3][3][K][16] forward, [3][3][16][K] for dgrad (K = gathered channels, a
- * multiple of 16; H, W multiples of 16).  tile_stats (or NULL): per 16x16-pixel tile sums as kpx_conv3x3_wino_stats_f32 writes them. */
+ * multiple of 16; H, W multiples of 16).  tile_stats (or NULL): per 16x16-pixel tile sums as kpx_conv3x3_wino_f32 writes them. */
 int kpx_conv3x3_c16_eligible(int N, int H, int W, int K, int Nn, int ldin, int ldout, const void* in_ptr);
 int kpx_conv3x3_c16_f32(const float* in, int N, int H, int W, int K, int ldin, const float* w_hwio, int dgrad, const float* bias,
                         float* out, int ldout, int act, float* tile_stats, void* stream);
@@ -234,11 +235,8 @@ int kpx_bn_train_bwd_f32(const float* dy, int lddy, const float* x, int ldx, siz
                          float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
                          const float* tile_stats, size_t tiles_per_group, void* scratch, void* stream);
 /* (backward tile_stats, or NULL: per-tile sum(dz), sum(dz * (y - beta)) written by the epilogue of the data-gradient kernel that produced dy --
- *  kpx_conv3x3_wino43_bnbwd_stats_f32 / kpx_conv3x3_wino_bnbwd_stats_f32, tiles_per_group tiles per group -- instead of the reduction pass over
- *  (dy, x); dy must then already be zero wherever the batch norm's ReLU output is, which those kernels guarantee.) */
-int kpx_conv3x3_wino43_bnbwd_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u,
-                                       float* out, int Nn, int ldout, const float* bn_y, int ld_bn_y, const float* bn_beta,
-                                       float* tile_stats, void* stream);
+ *  kpx_conv3x3_wino43(b)_f32 / kpx_conv3x3_wino_f32 with tile_stats + bn_y + bn_beta, tiles_per_group tiles per group -- instead of the
+ *  reduction pass over (dy, x); dy must then already be zero wherever the batch norm's ReLU output is, which those kernels guarantee.) */
 /* Inference-mode batch norm folded into the convolution in front of it (is_training = False: reference keypoint_model.py:48-50,
  * final_model.py:62,68,95): w_out[r][c] = w[r][c] * s[c], b_out[c] = (bias[c] - moving_mean[c]) * s[c] + beta[c] with
  * s = gamma * rsqrt(moving_var + eps); w = [rows = kh*kw*Cin][C] (HWIO), bias may be NULL.  conv(x, w_out) + b_out followed by ReLU then

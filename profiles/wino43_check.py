@@ -14,7 +14,7 @@ def run43(x, w, bias, act, dgrad=False, cin=None):
     check(lib.kpx_wino43_filter_transform_f32(w.data_ptr(), w.shape[2], w.shape[3], int(dgrad), u.data_ptr(), ops._stream()), 'xf')
     y = torch.empty(n, h, wd, nn, device=dev)
     assert lib.kpx_conv3x3_wino43_eligible(n, h, wd, k, nn, ld, x.data_ptr())
-    check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, k, ld, u.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), nn, nn, act, ops._stream()), 'conv')
+    check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, k, ld, u.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(), nn, nn, act, None, 0, None, 0, None, None, 0, None, ops._stream()), 'conv')
     return y, u
 def ref64(x, w, bias, act, dgrad=False):
     xx = x.double().permute(0, 3, 1, 2)
@@ -58,8 +58,8 @@ for shp, ci, co in [((32, 128, 128), 128, 128), ((32, 128, 128), 64, 64), ((32, 
     check(lib.kpx_wino43_filter_transform_f32(w.data_ptr(), ci, co, 0, u43.data_ptr(), ops._stream()), 'xf')
     check(lib.kpx_wino_filter_transform_f32(w.data_ptr(), ci, co, 0, u23.data_ptr(), ops._stream()), 'xf')
     s = ops._stream()
-    t43 = t(lambda: lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, ci, ci, u43.data_ptr(), None, y.data_ptr(), co, co, 0, s))
-    t23 = t(lambda: lib.kpx_conv3x3_wino_f32(x.data_ptr(), n, h, wd, ci, ci, u23.data_ptr(), None, y.data_ptr(), co, co, 0, s))
+    t43 = t(lambda: lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, ci, ci, u43.data_ptr(), None, y.data_ptr(), co, co, 0, None, 0, None, 0, None, None, 0, None, s))
+    t23 = t(lambda: lib.kpx_conv3x3_wino_f32(x.data_ptr(), n, h, wd, ci, ci, u23.data_ptr(), None, y.data_ptr(), co, co, 0, None, None, 0, None, s))
     fl = 2.0 * n * h * wd * 9 * ci * co
     print(shp, ci, co, 'F(4,3) %.4f ms (%.1f eff TF, executed frac %.2f) | F(2,3) %.4f ms (%.1f eff TF)' % (t43, fl / t43 / 1e9, fl / 4 / t43 / 1e9 / 157.3, t23, fl / t23 / 1e9))
 print('packed 16x16:')
@@ -70,7 +70,7 @@ for shp, ci, co in [((64, 16, 16), 512, 512), ((64, 16, 16), 256, 512), ((32, 16
     check(lib.kpx_wino43_filter_transform_f32(w.data_ptr(), ci, co, 0, u43.data_ptr(), ops._stream()), 'xf')
     check(lib.kpx_wino_filter_transform_f32(w.data_ptr(), ci, co, 0, u23.data_ptr(), ops._stream()), 'xf')
     s = ops._stream()
-    t43 = t(lambda: check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, ci, ci, u43.data_ptr(), None, y.data_ptr(), co, co, 0, s), 'c43'))
-    t23 = t(lambda: check(lib.kpx_conv3x3_wino_f32(x.data_ptr(), n, h, wd, ci, ci, u23.data_ptr(), None, y.data_ptr(), co, co, 0, s), 'c23'))
+    t43 = t(lambda: check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, ci, ci, u43.data_ptr(), None, y.data_ptr(), co, co, 0, None, 0, None, 0, None, None, 0, None, s), 'c43'))
+    t23 = t(lambda: check(lib.kpx_conv3x3_wino_f32(x.data_ptr(), n, h, wd, ci, ci, u23.data_ptr(), None, y.data_ptr(), co, co, 0, None, None, 0, None, s), 'c23'))
     fl = 2.0 * n * h * wd * 9 * ci * co
     print(shp, ci, co, 'F(4,3) %.4f ms (%.1f eff TF, executed frac %.2f) | F(2,3) %.4f ms (%.1f eff TF)' % (t43, fl / t43 / 1e9, fl / 4 / t43 / 1e9 / 157.3, t23, fl / t23 / 1e9))

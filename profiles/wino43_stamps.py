@@ -19,7 +19,7 @@ lib = clib
 clib.kpx_debug_w43_stamps.argtypes = [ctypes.c_void_p]
 for dbg in [int(v) for v in sys.argv[1:]] or [0]:
     os.environ['KPX_W43_DBG'] = str(dbg)
-    run = lambda: lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, ci, ci, u43.data_ptr(), None, y.data_ptr(), co, co, 0, s)
+    run = lambda: lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, ci, ci, u43.data_ptr(), None, y.data_ptr(), co, co, 0, None, 0, None, 0, None, None, 0, None, s)
     buf = torch.zeros(64 * 8 * 64, dtype=torch.int64, device=dev)
     clib.kpx_debug_w43_stamps(None)
     for _ in range(100): run()

@@ -16,7 +16,7 @@ for (n, h, w, k, nn) in [(2, 32, 64, 64, 64), (2, 64, 64, 128, 128), (2, 128, 12
     yb = torch.empty(n, h, w, nn, device=dev); yo = torch.empty(n, h, w, nn, device=dev)
     sb = torch.full((tiles * 2 * nn,), float('nan'), device=dev); so = torch.full((tiles * 2 * nn,), float('nan'), device=dev)
     check(lib.kpx_conv3x3_wino43b_f32(x.data_ptr(), n, h, w, k, k, ub.data_ptr(), None, yb.data_ptr(), nn, nn, 0, None, 0, None, 0, sb.data_ptr(), z.data_ptr(), nn, beta.data_ptr(), ops._stream()), 'b')
-    check(lib.kpx_conv3x3_wino43_bnbwd_stats_f32(x.data_ptr(), n, h, w, k, k, uo.data_ptr(), yo.data_ptr(), nn, nn, z.data_ptr(), nn, beta.data_ptr(), so.data_ptr(), ops._stream()), 'o')
+    check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, w, k, k, uo.data_ptr(), None, yo.data_ptr(), nn, nn, 0, None, 0, None, 0, so.data_ptr(), z.data_ptr(), nn, beta.data_ptr(), ops._stream()), 'o')
     torch.cuda.synchronize()
     sb, so = sb.view(tiles, 2, nn).double(), so.view(tiles, 2, nn).double()
     print(n, h, w, k, nn, 'dz new vs old rel %.2e' % float((yb - yo).norm() / yo.norm()), ' nan in new slab:', int(torch.isnan(sb).sum()), ' old:', int(torch.isnan(so).sum()))

@@ -43,7 +43,7 @@ def run_old(x, cin, w, b, cout, act, dgrad=0, ldx=None):
     u = torch.empty(lib.kpx_wino43_u_bytes(w.shape[2], w.shape[3]), dtype=torch.uint8, device=dev)
     check(lib.kpx_wino43_filter_transform_f32(w.data_ptr(), w.shape[2], w.shape[3], dgrad, u.data_ptr(), ops._stream()), 'tf')
     y = torch.empty((n, h, wd, cout), device=dev)
-    check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, cin, ldx, u.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), cout, cout, act, ops._stream()), 'conv')
+    check(lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, wd, cin, ldx, u.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), cout, cout, act, None, 0, None, 0, None, None, 0, None, ops._stream()), 'conv')
     return y, u
 
 
@@ -102,6 +102,6 @@ else:
         yo, uo = run_old(x, c, w, b, co, 0)
         yy = torch.empty_like(y)
         tn = t_ms(lambda: lib.kpx_conv3x3_wino43b_f32(x.data_ptr(), n, h, h, c, c, u.data_ptr(), b.data_ptr(), yy.data_ptr(), co, co, 0, None, 0, None, 0, None, None, 0, None, ops._stream()))
-        to = t_ms(lambda: lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, h, c, c, uo.data_ptr(), b.data_ptr(), yy.data_ptr(), co, co, 0, ops._stream()))
+        to = t_ms(lambda: lib.kpx_conv3x3_wino43_f32(x.data_ptr(), n, h, h, c, c, uo.data_ptr(), b.data_ptr(), yy.data_ptr(), co, co, 0, None, 0, None, 0, None, None, 0, None, ops._stream()))
         fl = 2.0 * 9 * c * co * h * h * n
         print('N%d %dx%d %d->%d : new %.4f ms (%.0f TF alg)  old %.4f ms (%.0f TF)  new/old %.2f  diff %.2e' % (n, h, h, c, co, tn, fl / tn / 1e9, to, fl / to / 1e9, tn / to, rel(y, yo)), flush=True)

@@ -36,7 +36,7 @@ for c in range(cases):
         check(lib.kpx_conv3x3_wino43b_f32(xb.data_ptr(), n, h, w, cin, ldx, u.data_ptr(), b.data_ptr(), y.data_ptr(), cout, cout, act, None, 0, None, 0, None, None, 0, None, ops._stream()), 'conv')
         ys.append(y)
     yo = torch.empty((n, h, w, cout), device=dev)
-    check(lib.kpx_conv3x3_wino43_f32(xb.data_ptr(), n, h, w, cin, ldx, uo.data_ptr(), b.data_ptr(), yo.data_ptr(), cout, cout, act, ops._stream()), 'conv')
+    check(lib.kpx_conv3x3_wino43_f32(xb.data_ptr(), n, h, w, cin, ldx, uo.data_ptr(), b.data_ptr(), yo.data_ptr(), cout, cout, act, None, 0, None, 0, None, None, 0, None, ops._stream()), 'conv')
     torch.cuda.synchronize()
     rel = float((ys[0].double() - yo.double()).norm() / yo.double().norm())
     same = bool(torch.equal(ys[0], ys[1]) and torch.equal(ys[0], ys[2]))

@@ -19,7 +19,7 @@ check(lib.kpx_wino43b_filter_transform_f32(wt.data_ptr(), c1, c2, 1, ub.data_ptr
 check(lib.kpx_wino43_filter_transform_f32(wt.data_ptr(), c1, c2, 1, uo.data_ptr(), ops._stream()), 't')
 yb = torch.empty(n, h, w, c1, device=dev); yo = torch.empty(n, h, w, c1, device=dev)
 check(lib.kpx_conv3x3_wino43b_f32(dy.data_ptr(), n, h, w, c2, c2, ub.data_ptr(), None, yb.data_ptr(), c1, c1, 0, None, 0, None, 0, None, None, 0, None, ops._stream()), 'b')
-check(lib.kpx_conv3x3_wino43_f32(dy.data_ptr(), n, h, w, c2, c2, uo.data_ptr(), None, yo.data_ptr(), c1, c1, 0, ops._stream()), 'o')
+check(lib.kpx_conv3x3_wino43_f32(dy.data_ptr(), n, h, w, c2, c2, uo.data_ptr(), None, yo.data_ptr(), c1, c1, 0, None, 0, None, 0, None, None, 0, None, ops._stream()), 'o')
 for name, y in (('bf16x3', yb), ('fp32 mfma', yo)):
     e = y.cpu().double() - want
     s_true = want.sum((0, 1, 2)); s_err = e.sum((0, 1, 2))

@@ -42,6 +42,22 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.kpx_conv2d_fwd_f32(1, 1, 8, 8, 4, 4, 1, 3, 3, None, 1, 8, 8, 4, 4, 1, 1, 1, 0, 2, None, 0, None) == -1           # arith = 2
     assert lib.kpx_conv2d_dgrad_act_f32(1, 1, 8, 8, 4, 4, 1, 3, 3, 1, 8, 8, 4, 4, 1, 1, 1, 0, None, 4, 2, None, 0, None) == -1   # y_in = NULL
     assert lib.kpx_conv2d_dgrad_act_f32(1, 1, 8, 8, 4, 4, 1, 3, 3, 1, 8, 8, 4, 4, 1, 1, 1, 0, 1, 4, 3, None, 0, None) == -1      # tanh: not an epilogue factor
+    # the two F(4x4,3x3) entries share their arguments and option rules: both refuse the same mixes before any device call
+    a = 1 << 20                                                 # an aligned fake address
+    for entry in (lib.kpx_conv3x3_wino43_f32, lib.kpx_conv3x3_wino43b_f32):
+        def f43(n=2, h=32, w=32, nn=64, bias=None, act=0, mask=None, pool=None, stats=None, bn_y=None, bn_beta=None):
+            return entry(a, n, h, w, 64, 64, a, bias, a, nn, nn, act, mask, nn, pool, nn, stats, bn_y, nn, bn_beta, None)
+        assert f43(bn_y=a, bn_beta=a) == -1                     # bn_y without tile_stats
+        assert f43(stats=a, bn_y=a) == -1                       # bn_y without bn_beta
+        assert f43(stats=a, bn_y=a, bn_beta=a, bias=a) == -1    # the bn form takes no bias ...
+        assert f43(stats=a, bn_y=a, bn_beta=a, act=1) == -1     # ... and no activation
+        assert f43(mask=a, stats=a) == -1                       # mask_y with tile_stats
+        assert f43(h=33, pool=a) == -1                          # pool_y with odd H
+        assert f43(nn=96, pool=a) == -1                         # mask / pool need Nn % 64 == 0
+        assert f43(h=16, w=16, stats=a) == -1                   # packed 16 x 16 images: no statistics strips
+    # F(2x2,3x3): statistics need whole 16 x 16 tiles (8 x 8 images are packed four to a workgroup); the bn form needs tile_stats
+    assert lib.kpx_conv3x3_wino_f32(a, 4, 8, 8, 16, 16, a, None, a, 32, 32, 0, a, None, 0, None, None) == -1
+    assert lib.kpx_conv3x3_wino_f32(a, 2, 32, 32, 16, 16, a, None, a, 32, 32, 0, None, a, 32, a, None) == -1
 
 
 def test_keypoint_head_fold_eligibility_is_a_host_question():

@@ -165,7 +165,7 @@ def test_data_parallel_bf16_exchange_flag_two_gloo_ranks():
         assert out == {'D': True, 'D_close_to_fp32_sum': True, 'G': True}, (rank, out)
 
 
-def test_f43_layer_policy_follows_the_float64_arbiter_findings():
+def test_f43_launch_policy_follows_the_float64_arbiter_findings():
     """Which layers may run the F(4x4,3x3) kernel is host logic (a per-layer attribute declared in networks.py, ops.WINO43): data gradients everywhere, forward only on VGG19
     and the translator's 64x64 / 128x128 layers; the key-point detector, the image encoder and the translator's 32x32 layers keep
     F(2x2,3x3) in the forward direction.  Channel limits: K >= 16 gathered, more than 32 produced."""
@@ -178,20 +178,55 @@ def test_f43_layer_policy_follows_the_float64_arbiter_findings():
         if name.endswith('/kernel') and v.dim() == 4 and v.shape[0] == 3:
             cin, cout = int(v.shape[2]), int(v.shape[3])
             f43 = m.store.layer_attrs[name]['f43_fwd']
-            if ops._wino43_wanted(name, cin, cout, 0, f43):
+            if ops._wino43_wanted(cin, cout, 0, f43):
                 fwd.add(name.split('/conv2d')[0])
-            if ops._wino43_wanted(name, cin, cout, 1, f43):
+            if ops._wino43_wanted(cout, cin, 1, f43):
                 dgrad.add(name.split('/conv2d')[0])
     assert fwd == {'translator/conv_%d_%d' % (i, j) for i in (3, 4, 5) for j in (0, 1)}
     assert not any(n.startswith(('pose_encoder', 'image_encoder', 'translator/conv_1', 'translator/conv_2', 'img_discr')) for n in fwd)
     # data gradients: every 3x3 layer gathering >= 16 and producing > 32 channels, the detector's included; never the 4-channel head's input side
     assert {'translator/conv_1_0', 'translator/conv_2_1', 'pose_encoder/encoder/conv_4', 'pose_encoder/conv_7_0', 'image_encoder/encoder/conv_6'} <= dgrad
     assert not any(n.startswith('translator/conv_6') for n in dgrad | fwd)          # the 4-channel head: K = 4 gathered in the gradient, 4 produced in the forward
-    assert ops._wino43_wanted('vgg/conv3_2', 256, 256, 0) and ops._wino43_wanted('vgg/conv3_2', 256, 256, 1)
-    assert not ops._wino43_wanted('vgg/conv1_1', 3, 64, 0)
-    # the attribute, not the name, decides: the same filter name with the attribute cleared stays off F(4x4,3x3) in the forward direction only
-    assert not ops._wino43_wanted('translator/conv_3_1/conv2d/kernel', 128, 128, 0, False) and ops._wino43_wanted('translator/conv_3_1/conv2d/kernel', 128, 128, 1, False)
-    assert ops._wino43_wanted('pose_encoder/renamed_scope/conv2d/kernel', 128, 128, 0, True)
+    assert ops._wino43_wanted(256, 256, 0) and ops._wino43_wanted(256, 256, 1)
+    assert not ops._wino43_wanted(3, 64, 0)
+    # the attribute decides: with it cleared a layer stays off F(4x4,3x3) in the forward direction only
+    assert not ops._wino43_wanted(128, 128, 0, False) and ops._wino43_wanted(128, 128, 1, False)
+    assert ops._wino43_wanted(128, 128, 0, True)
+
+
+def test_f43_decision_keeps_the_kernel_choice_on_its_corner_cases(monkeypatch):
+    """ops._wino43_plan, the one F(4x4,3x3) decision of _wino_pretransformed and conv3x3_wino43_ex: the launches to try in order, [] = not
+    F(4x4,3x3).  Eligibility is the library's host-side answer for an aligned fake address."""
+    from kpx_amd import ops
+    monkeypatch.setattr(ops, 'WINO43', True)
+    monkeypatch.setattr(ops, 'WINO43B', True)
+    monkeypatch.setattr(ops, 'WINO43_MIN_WORKGROUPS', 0)
+    a, both, f32 = 1 << 20, {'wino43': None, 'wino43b': None}, {'wino43': None}
+    plan = ops._wino43_plan                    # (n, h, w, k, nn, ldin, in_ptr, dgrad, forms, want_stats, bn_src, vgg)
+    plain = [('wino43b', False), ('wino43', False)]
+    assert plan(4, 32, 32, 64, 64, 64, a, 0, both) == plain                        # the bf16x3 kernel; its refusal: the same options on fp32
+    assert plan(4, 32, 32, 64, 64, 64, a, 0, both, want_stats=True) == plain
+    assert plan(4, 32, 32, 64, 64, 64, a, 0, f32) == [('wino43', False)]           # no bf16x3 form for the filter
+    # a forward with statistics on packed 16x16 images goes to F(2x2,3x3) (with statistics); without them it stays on F(4x4,3x3)
+    assert plan(4, 16, 16, 64, 64, 64, a, 0, both, want_stats=True) == []
+    assert plan(4, 16, 16, 64, 64, 64, a, 0, both) == plain
+    # a data gradient towards a ReLU'd batch norm: the fused sums, then F(4x4,3x3) without them if the fp32 kernel refuses them too
+    assert plan(4, 32, 32, 64, 64, 64, a, 1, both, bn_src=True) == [('wino43b', True), ('wino43', True), ('wino43', False)]
+    # ... on 16x16 images or with Nn % 64 != 0: F(4x4,3x3) without the fused sums
+    assert plan(4, 16, 16, 64, 64, 64, a, 1, both, bn_src=True) == plain
+    assert plan(4, 32, 32, 64, 96, 64, a, 1, both, bn_src=True) == plain
+    # K = 20 in a 20-wide buffer: the bf16x3 kernel takes it, the fp32-MFMA kernel does not -- and conv3x3_wino43_ex never runs without it
+    assert plan(4, 32, 32, 20, 64, 20, a, 0, both) == [('wino43b', False)]
+    assert plan(4, 32, 32, 20, 64, 20, a, 0, both, vgg=True) == []
+    assert plan(4, 32, 32, 64, 64, 64, a, 1, both, vgg=True) == plain
+    assert plan(4, 32, 32, 64, 96, 64, a, 1, both, vgg=True) == []                 # the mask / pool epilogue needs Nn % 64 == 0
+    # the module switches, read at call time
+    monkeypatch.setattr(ops, 'WINO43_MIN_WORKGROUPS', 16)
+    assert plan(8, 32, 32, 64, 64, 64, a, 0, both) == [] and plan(8, 32, 64, 64, 64, 64, a, 0, both) == plain    # 16 / 32 workgroups
+    monkeypatch.setattr(ops, 'WINO43B', False)
+    assert plan(8, 32, 64, 64, 64, 64, a, 0, both) == [('wino43', False)]
+    monkeypatch.setattr(ops, 'WINO43', False)
+    assert plan(8, 32, 64, 64, 64, 64, a, 0, both) == []
 
 
 # ------------------------------------------------------------------------------------------------ bench.py supervisor (N > 1 cannot hang)

@@ -742,7 +742,7 @@ def test_against_the_reference_graph_fixture(golden_dir):
             if step == 0:                     # (step 1 starts from weights the two fp32 implementations have separated: aggregate only)
                 # (round 6: 8 % of the variable's norm, was 5 % -- translator/conv_1_0 sits at 5.5 % with its upstream data gradients on the bf16x3
                 #  form of F(4x4,3x3), whose per-layer error against float64 is SMALLER than the fp32-MFMA kernel's (tests/test_ops_gpu.py::
-                #  test_wino43_bf16x3_is_fp32_equivalent_against_float64): the K = 3 softmax of this fixture amplifies any change of rounding)
+                #  test_wino43_bf16x3_entry_is_fp32_equivalent_against_float64): the K = 3 softmax of this fixture amplifies any change of rounding)
                 assert abs(dp) <= (8 if n.endswith('/bias') else 1) * 8e-2 * want[i][0] + 1e-7, (step, n, dp, want[i][0])
         pagg = (pnum / sum(w_[0] ** 2 for w_ in want)) ** 0.5
         print('reference-graph fixture step %d: generator-gradient projections off by %.2e of the gradient norm (aggregate)' % (step, pagg))

@@ -529,7 +529,7 @@ def test_winograd_f43_reads_a_channel_slice_and_writes_a_strided_destination(kpx
 
 
 @pytest.mark.parametrize('n,h,w,cin,cout', [(32, 64, 64, 128, 128), (32, 128, 128, 64, 64), (8, 64, 64, 256, 128), (8, 32, 32, 256, 256), (4, 64, 64, 64, 136)])
-def test_wino43_bf16x3_is_fp32_equivalent_against_float64(kpx, dev, n, h, w, cin, cout):
+def test_wino43_bf16x3_entry_is_fp32_equivalent_against_float64(kpx, dev, n, h, w, cin, cout):
     """The bf16x3 form of F(4x4,3x3) is the fp32 configuration's arithmetic: every transform-domain operand is split EXACTLY into three bf16
     terms (U once per update in fp64 -> fp32 -> split; V in registers after the fp32 input transform), the six products of weight >= 2^-16 are
     exact in fp32 and accumulated in fp32.  Against a float64 convolution, on the profiled launches (translator conv_3_1 / conv_5_1 at B=32)
@@ -551,7 +551,7 @@ def test_wino43_bf16x3_is_fp32_equivalent_against_float64(kpx, dev, n, h, w, cin
         check(lib.kpx_wino43_filter_transform_f32(wg.data_ptr(), cin, cout, dgrad, uo.data_ptr(), ops._stream()), 'transform')
         yb = torch.empty(n, h, w, nn, device=dev); yo = torch.empty(n, h, w, nn, device=dev)
         check(lib.kpx_conv3x3_wino43b_f32(inp.data_ptr(), n, h, w, k, k, ub.data_ptr(), None, yb.data_ptr(), nn, nn, 0, None, 0, None, 0, None, None, 0, None, ops._stream()), 'conv b')
-        check(lib.kpx_conv3x3_wino43_f32(inp.data_ptr(), n, h, w, k, k, uo.data_ptr(), None, yo.data_ptr(), nn, nn, 0, ops._stream()), 'conv')
+        check(lib.kpx_conv3x3_wino43_f32(inp.data_ptr(), n, h, w, k, k, uo.data_ptr(), None, yo.data_ptr(), nn, nn, 0, None, 0, None, 0, None, None, 0, None, ops._stream()), 'conv')
         eb = float((yb.cpu().double() - want).norm() / want.norm()); eo = float((yo.cpu().double() - want).norm() / want.norm())
         assert eb < 1e-5 and eb <= 1.5 * eo, (dgrad, eb, eo)
 
@@ -1006,7 +1006,7 @@ def test_bf16_storage_pointwise_kernels_against_torch_on_the_rounded_inputs(kpx,
 @pytest.mark.parametrize('n,h,w,cin,cout,groups', [(4, 32, 32, 32, 64, 1), (4, 16, 48, 64, 40, 2), (2, 64, 64, 128, 128, 1), (4, 16, 32, 24, 70, 2), (2, 32, 32, 16, 32, 1),
                                                      (2, 32, 32, 16, 16, 1), (4, 32, 48, 64, 16, 2)])      # the last two: 16-cout kernel (conv_c16.hip)
 def test_batch_norm_statistics_from_the_conv_epilogue(kpx, dev, monkeypatch, n, h, w, cin, cout, groups):
-    """conv -> train-mode batch norm with the per-tile channel sums written by the Winograd epilogue (kpx_conv3x3_wino_stats_f32 +
+    """conv -> train-mode batch norm with the per-tile channel sums written by the Winograd epilogue (kpx_conv3x3_wino(43)_f32 with tile_stats +
     kpx_bn_stats_from_tiles_f32) against the oracle AND against the separate statistics pass: same normalised output, same
     moving-statistics update, per-call statistics for ``groups`` weight-sharing calls (reference detector_translator_model.py:166-167)."""
     ops = kpx.ops
@@ -1047,7 +1047,7 @@ def test_batch_norm_statistics_from_the_conv_epilogue(kpx, dev, monkeypatch, n, 
                                                       (2, 128, 128, 16, 64, 64, 2, True)])
 def test_batch_norm_backward_sums_from_the_dgrad_epilogue(kpx, dev, n, h, w, c0, c1, c2, groups, f43):
     """conv_a -> BN+ReLU -> conv_b: the data gradient of conv_b (Winograd kernel) also reduces BN's backward sums in its epilogue --
-    F(2x2,3x3): kpx_conv3x3_wino_bnbwd_stats_f32, F(4x4,3x3): kpx_conv3x3_wino43_bnbwd_stats_f32 (which also stores the ReLU-masked gradient) --
+    kpx_conv3x3_wino_f32 / kpx_conv3x3_wino43(b)_f32 with tile_stats + bn_y + bn_beta (F(4x4,3x3) also stores the ReLU-masked gradient) --
     and kpx_bn_train_bwd_f32 takes the per-tile sums instead of its reduction pass.  Gradients wrt the input, gamma, beta and conv_a's filter
     against torch autograd over the oracle, and against the path with the separate reduction pass."""
     ops = kpx.ops

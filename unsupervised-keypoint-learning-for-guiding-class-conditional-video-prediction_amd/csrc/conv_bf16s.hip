@@ -134,7 +134,7 @@ struct S16Tile {
 // STATS: 0 none; 1 per-workgroup channel sums and sums of squares of the fp32 outputs before the activation -> stats[tile][2][Nn] (the batch
 // norm BEHIND a forward convolution); 2 (data gradient towards y = relu(batch norm)): `mask` is y, `bias` is the batch norm's beta -- the
 // gradient is gated by y > 0 and the workgroup writes sum(dz), sum(dz * (y - beta)) per channel: the batch norm's backward sums
-// (x_hat = (y - beta) / gamma wherever dz != 0), as kpx_conv3x3_wino43_bnbwd_stats_f32 does in the fp32 configuration
+// (x_hat = (y - beta) / gamma wherever dz != 0), as kpx_conv3x3_wino43_f32 with bn_y does in the fp32 configuration
 template <int WN, int Q, int P, int BW, int STATS>
 __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(const S16Geom g, const int TH, const int G) {
     using T = S16Tile<WN, Q, P, BW>;

@@ -9,7 +9,7 @@
 // which feeds the four k-steps of that tap: k-step s of lane group g is channel 4g + s, and the filter fragment is indexed to match
 // (fragment-ordered through LDS: one ds_read_b128 per tap).  Double-buffered patch and filter, one barrier per chunk.
 // Epilogue: bias + activation, 64 contiguous bytes per pixel; optional batch-norm sums per 16x16-pixel tile in the slab format of
-// kpx_conv3x3_wino_stats_f32 (bitwise reproducible: fixed shuffle / LDS order).
+// kpx_conv3x3_wino_f32 with tile_stats (bitwise reproducible: fixed shuffle / LDS order).
 #include "kpx_common.h"
 #include "kpx_env.h"
 #include <stdlib.h>

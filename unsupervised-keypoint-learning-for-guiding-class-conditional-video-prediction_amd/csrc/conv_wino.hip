@@ -469,28 +469,10 @@ extern "C" int kpx_wino_filter_transform_batch_f32(const void* descs_dev, int n,
     return kpx_launch_status();
 }
 
-// forward: in = x (K = Cin), out = y (Nn = Cout);  dgrad: in = dy (K = Cout), out = dx (Nn = Cin); U: fragment-ordered filters for (K, Nn)
-static int wino_launch(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
-                       float* out, int Nn, int ldout, int act, float* tile_stats, void* stream,
-                       const float* mask_y = nullptr, int ld_mask = 0, const float* bn_beta = nullptr);
-extern "C" int kpx_conv3x3_wino_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
-                                    float* out, int Nn, int ldout, int act, void* stream) {
-    return wino_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, nullptr, stream);
-}
 extern "C" size_t kpx_conv3x3_wino_stats_tiles(int N, int H, int W) {
     return (H % 16 || W % 16 || N <= 0) ? 0 : (size_t)N * (H / 16) * (W / 16);
 }
-extern "C" int kpx_conv3x3_wino_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
-                                          float* out, int Nn, int ldout, int act, float* tile_stats, void* stream) {
-    if (!tile_stats || H % 16 || W % 16) return KPX_EINVAL;       // (8x8 images are packed four to a workgroup: no per-image tiles)
-    return wino_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, tile_stats, stream);
-}
-extern "C" int kpx_conv3x3_wino_bnbwd_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U,
-                                                float* out, int Nn, int ldout, const float* bn_y, int ld_bn_y, const float* bn_beta,
-                                                float* tile_stats, void* stream) {
-    if (!tile_stats || !bn_y || !bn_beta || ld_bn_y < Nn || H % 16 || W % 16) return KPX_EINVAL;
-    return wino_launch(in, N, H, W, K, ldin, U, nullptr, out, Nn, ldout, KPX_ACT_NONE, tile_stats, stream, bn_y, ld_bn_y, bn_beta);
-}
+// forward: in = x (K = Cin), out = y (Nn = Cout);  dgrad: in = dy (K = Cout), out = dx (Nn = Cin); U: fragment-ordered filters for (K, Nn)
 static int wino_launch(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
                        float* out, int Nn, int ldout, int act, float* tile_stats, void* stream,
                        const float* mask_y, int ld_mask, const float* bn_beta) {
@@ -522,13 +504,23 @@ static int wino_launch(const float* in, int N, int H, int W, int K, int ldin, co
     return kpx_launch_status();
 }
 
+// tile_stats (or NULL): per 16x16-pixel tile batch-norm sums of the output (H, W multiples of 16);  tile_stats + bn_y + bn_beta: data
+// gradient towards bn_y = relu(batch norm)'s output, masked, with that batch norm's backward sums (no bias / act).
+extern "C" int kpx_conv3x3_wino_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
+                                    float* out, int Nn, int ldout, int act, float* tile_stats, const float* bn_y, int ld_bn_y,
+                                    const float* bn_beta, void* stream) {
+    if (tile_stats && (H % 16 || W % 16)) return KPX_EINVAL;          // (8x8 images are packed four to a workgroup: no per-image tiles)
+    if ((bn_y || bn_beta) && (!tile_stats || !bn_y || !bn_beta || ld_bn_y < Nn || bias || act != KPX_ACT_NONE)) return KPX_EINVAL;
+    return wino_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, tile_stats, stream, bn_y, ld_bn_y, bn_beta);
+}
+
 // used by kpx_conv2d_fwd_f32 / kpx_conv2d_dgrad_f32 (conv_igemm.hip) when the caller did not pre-transform: transform into the
 // workspace, then run
 extern "C" __attribute__((visibility("hidden"))) int kpx_wino_conv3x3(const float* in, int N, int H, int W, int K, int ldin, const float* w_hwio, int Cin, int Cout, int dgrad,
                                 const float* bias, int act, float* out, int Nn, int ldout, float* U_ws, hipStream_t s) {
     int rc = kpx_wino_filter_transform_f32(w_hwio, Cin, Cout, dgrad, U_ws, (void*)s);
     if (rc) return rc;
-    return kpx_conv3x3_wino_f32(in, N, H, W, K, ldin, U_ws, bias, out, Nn, ldout, act, (void*)s);
+    return kpx_conv3x3_wino_f32(in, N, H, W, K, ldin, U_ws, bias, out, Nn, ldout, act, nullptr, nullptr, 0, nullptr, (void*)s);
 }
 
 // ------------------------------------------------------------------------------------------ Winograd weight gradient

@@ -26,6 +26,7 @@
 //   * STATS: per-strip batch-norm sums from the epilogue; PACK: two 16 x 16 images per workgroup.
 #include "kpx_common.h"
 #include "kpx_env.h"
+#include "wino43_options.h"
 #include <stdlib.h>
 
 struct Wino43Geom {
@@ -526,8 +527,7 @@ extern "C" int kpx_wino43_filter_transform_batch_f32(const void* descs_dev, int 
 }
 static int w43_launch(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
                       float* out, int Nn, int ldout, int act, float* tile_stats, void* stream,
-                      const float* mask_y = nullptr, int ld_mask = 0, float* pool_y = nullptr, int ld_pool = 0, const float* bn_beta = nullptr) {
-    if (!in || !U || !out || ldin < K || ldout < Nn || act < 0 || act > 2 || !kpx_conv3x3_wino43_eligible(N, H, W, K, Nn, ldin, in)) return KPX_EINVAL;
+                      const float* mask_y, int ld_mask, float* pool_y, int ld_pool, const float* bn_beta) {
     if (kpx_first_use_on_device(&w43_attr_mask)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino43_kernel<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, w43_lds_bytes());
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino43_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, w43_lds_bytes());
@@ -540,7 +540,6 @@ static int w43_launch(const float* in, int N, int H, int W, int K, int ldin, con
     g.N = N; g.H = H; g.W = W; g.Cin = K; g.ldx = ldin; g.Cout = Nn; g.ldy = ldout; g.act = act;
     g.Kp = (K + 7) & ~7; g.Np = (Nn + 63) & ~63;
     const bool pack = W == 16;
-    if (pack && tile_stats) return KPX_EINVAL;           // (no batch-norm layer of the path is 16 x 16 with a forward on this kernel)
     g.tiles_y = H / 16; g.tiles_x = pack ? 1 : W / 32;
     g.stats = tile_stats;
     g.mask_y = mask_y; g.ld_mask = ld_mask; g.pool_y = pool_y; g.ld_pool = ld_pool; g.bn_beta = bn_beta;
@@ -551,40 +550,18 @@ static int w43_launch(const float* in, int N, int H, int W, int K, int ldin, con
     else hipLaunchKernelGGL((conv_wino43_kernel<0, false>), dim3(blocks), dim3(512), w43_lds_bytes(), kpx_stream(stream), g);
     return kpx_launch_status();
 }
+// One entry for every form of the launch, with kpx_conv3x3_wino43b_f32's arguments and option rules (wino43_options.h).
 extern "C" int kpx_conv3x3_wino43_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
-                                      float* out, int Nn, int ldout, int act, void* stream) {
-    return w43_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, nullptr, stream);
+                                      float* out, int Nn, int ldout, int act, const float* mask_y, int ld_mask, float* pool_y, int ld_pool,
+                                      float* tile_stats, const float* bn_y, int ld_bn_y, const float* bn_beta, void* stream) {
+    if (!wino43_options_valid(in, H, W, K, ldin, U, bias, out, Nn, ldout, act, mask_y, ld_mask, pool_y, ld_pool, tile_stats, bn_y, ld_bn_y, bn_beta) ||
+        !kpx_conv3x3_wino43_eligible(N, H, W, K, Nn, ldin, in))
+        return KPX_EINVAL;
+    const bool bnbwd = bn_y != nullptr;
+    return w43_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, tile_stats, stream, bnbwd ? bn_y : mask_y, bnbwd ? ld_bn_y : ld_mask,
+                      pool_y, ld_pool, bn_beta);
 }
 // 4 x 16-pixel strips per tensor: the unit of the statistics slab (kpx_bn_stats_from_tiles_f32 with tile_pixels = 64)
 extern "C" size_t kpx_conv3x3_wino43_stats_tiles(int N, int H, int W) {
     return (H % 16 || W % 32 || N <= 0) ? 0 : (size_t)N * (H / 16) * (W / 32) * 8;          // (0: no statistics for packed 16 x 16 images)
-}
-extern "C" int kpx_conv3x3_wino43_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
-                                            float* out, int Nn, int ldout, int act, float* tile_stats, void* stream) {
-    if (!tile_stats) return KPX_EINVAL;
-    return w43_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, tile_stats, stream);
-}
-
-// The same with the two epilogue options VGG19 uses (reference models/networks/vgg.py:45-55): mask_y (or NULL) -- the output is zeroed
-// where mask_y <= 0, i.e. the ReLU backward of the tensor this data gradient belongs to; pool_y (or NULL) -- the 2x2 max-pool of the
-// activated output is written as well ([N,H/2,W/2,Nn], pixel stride ld_pool).  Needs Nn % 64 == 0 and 16-B aligned rows everywhere.
-extern "C" int kpx_conv3x3_wino43_ex_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U, const float* bias,
-                                         float* out, int Nn, int ldout, int act, const float* mask_y, int ld_mask, float* pool_y, int ld_pool, void* stream) {
-    if (Nn % 64 || ldout % 4 || (((uintptr_t)out) & 15) || (mask_y && (ld_mask % 4 || ld_mask < Nn || (((uintptr_t)mask_y) & 15))) ||
-        (pool_y && (ld_pool % 4 || ld_pool < Nn || (((uintptr_t)pool_y) & 15) || (H & 1) || (W & 1))))
-        return KPX_EINVAL;
-    return w43_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, nullptr, stream, mask_y, ld_mask, pool_y, ld_pool);
-}
-
-// Data gradient towards a ReLU'd batch norm's output (the tensor `bn_y` this convolution read in the forward pass): out = dgrad * [bn_y > 0]
-// and tile_stats[strip][2][Nn] = per 4 x 16-pixel strip sum(out), sum(out * (bn_y - beta)) -- kpx_bn_train_bwd_f32 takes them instead of
-// its own reduction pass (tf.gradients of tf.contrib.layers.batch_norm + tf.nn.relu, models/networks/layers.py:13-14 behind
-// models/networks/__init__.py:10-24).  Nn a multiple of 64, H % 16 == 0, W % 32 == 0, 16-B aligned rows.
-extern "C" int kpx_conv3x3_wino43_bnbwd_stats_f32(const float* in, int N, int H, int W, int K, int ldin, const float* U,
-                                                  float* out, int Nn, int ldout, const float* bn_y, int ld_bn_y, const float* bn_beta,
-                                                  float* tile_stats, void* stream) {
-    if (!tile_stats || !bn_y || !bn_beta || Nn % 64 || ldout % 4 || (((uintptr_t)out) & 15) || ld_bn_y % 4 || ld_bn_y < Nn || (((uintptr_t)bn_y) & 15) ||
-        (((uintptr_t)bn_beta) & 15) || W == 16)
-        return KPX_EINVAL;
-    return w43_launch(in, N, H, W, K, ldin, U, nullptr, out, Nn, ldout, KPX_ACT_NONE, tile_stats, stream, bn_y, ld_bn_y, nullptr, 0, bn_beta);
 }

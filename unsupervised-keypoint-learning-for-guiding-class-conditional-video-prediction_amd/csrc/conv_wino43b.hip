@@ -36,6 +36,7 @@
 // images side by side in one 16 x 32 region (VGG19 conv4_*, the 16 x 16 data gradients of the encoders), each with its own zero halo in the patch.
 #include "kpx_common.h"
 #include "kpx_env.h"
+#include "wino43_options.h"
 #include <type_traits>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -789,21 +790,14 @@ extern "C" int kpx_wino43b_filter_transform_batch_f32(const void* descs_dev, int
     return kpx_launch_status();
 }
 
-// One entry for every form of the launch (the options are those of kpx_conv3x3_wino43_f32 / _stats_f32 / _ex_f32 / _bnbwd_stats_f32):
-//   tile_stats alone: batch-norm sums of the output per 4 x 16-pixel strip;  tile_stats + bn_y + bn_beta: data gradient towards a ReLU'd batch
-//   norm's output, masked, with that batch norm's backward sums;  mask_y / pool_y: VGG19's fused ReLU backward / 2x2 max-pool.
+// One entry for every form of the launch, with kpx_conv3x3_wino43_f32's arguments and option rules (wino43_options.h).
 extern "C" int kpx_conv3x3_wino43b_f32(const float* in, int N, int H, int W, int K, int ldin, const void* U, const float* bias,
                                        float* out, int Nn, int ldout, int act, const float* mask_y, int ld_mask, float* pool_y, int ld_pool,
                                        float* tile_stats, const float* bn_y, int ld_bn_y, const float* bn_beta, void* stream) {
-    if (!in || !U || !out || ldin < K || ldout < Nn || act < 0 || act > 2 || !kpx_conv3x3_wino43b_eligible(N, H, W, K, Nn, ldin, in)) return KPX_EINVAL;
-    const bool bnbwd = bn_y != nullptr || bn_beta != nullptr;
-    if (bnbwd && (!tile_stats || !bn_y || !bn_beta || mask_y || pool_y || bias || act != KPX_ACT_NONE || Nn % 64 || ldout % 4 || (((uintptr_t)out) & 15) ||
-                  ld_bn_y % 4 || ld_bn_y < Nn || (((uintptr_t)bn_y) & 15) || (((uintptr_t)bn_beta) & 15)))
+    if (!wino43_options_valid(in, H, W, K, ldin, U, bias, out, Nn, ldout, act, mask_y, ld_mask, pool_y, ld_pool, tile_stats, bn_y, ld_bn_y, bn_beta) ||
+        !kpx_conv3x3_wino43b_eligible(N, H, W, K, Nn, ldin, in))
         return KPX_EINVAL;
-    if ((mask_y || pool_y) && (tile_stats || Nn % 64 || ldout % 4 || (((uintptr_t)out) & 15) ||
-                               (mask_y && (ld_mask % 4 || ld_mask < Nn || (((uintptr_t)mask_y) & 15))) ||
-                               (pool_y && (ld_pool % 4 || ld_pool < Nn || (((uintptr_t)pool_y) & 15) || (H & 1) || (W & 1)))))
-        return KPX_EINVAL;
+    const bool bnbwd = bn_y != nullptr;
     if (kpx_first_use_on_device(&w4b_attr_mask)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino43b_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, w4b_lds_bytes());
         if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wino43b_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, w4b_lds_bytes());
@@ -816,7 +810,6 @@ extern "C" int kpx_conv3x3_wino43b_f32(const float* in, int N, int H, int W, int
     g.N = N; g.H = H; g.W = W; g.Cin = K; g.ldx = ldin; g.Cout = Nn; g.ldy = ldout; g.act = act;
     g.Kp = (K + 15) & ~15; g.Np = (Nn + 63) & ~63;
     const bool pack = W == 16;
-    if (pack && tile_stats) return KPX_EINVAL;           // (no statistics epilogue for packed images: kpx_conv3x3_wino43_stats_tiles is 0 for them)
     g.tiles_y = H / 16; g.tiles_x = pack ? 1 : W / 32;
     g.stats = tile_stats;
     g.mask_y = bnbwd ? bn_y : mask_y; g.ld_mask = bnbwd ? ld_bn_y : ld_mask; g.pool_y = pool_y; g.ld_pool = ld_pool; g.bn_beta = bn_beta;

@@ -280,7 +280,7 @@ extern "C" int kpx_bn_stats_f32(const float* x, size_t P, int C, int ldx, float 
 }
 
 // Batch-norm backward sums from per-tile sums written by the epilogue of the data-gradient kernel that PRODUCED dy
-// (kpx_conv3x3_wino_bnbwd_stats_f32): tile_stats[tile][2][C] = sum(dz), sum(dz * (y - beta)); x_hat = (y - beta) / gamma wherever dz != 0.
+// (kpx_conv3x3_wino_f32 with tile_stats + bn_y): tile_stats[tile][2][C] = sum(dz), sum(dz * (y - beta)); x_hat = (y - beta) / gamma wherever dz != 0.
 __global__ __launch_bounds__(256) void bn_bwd_from_tiles_kernel(const float* __restrict__ ts, size_t tile0, size_t ntiles, int C,
                                                                const float* __restrict__ gamma, float* dgamma, float* dbeta, float* sums, int accumulate) {
     const int c = blockIdx.x;
@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void bn_bwd_from_tiles_kernel(const float* __r
     sums[c] = (float)s; sums[C + c] = (float)q;
 }
 
-// Batch statistics from the per-tile sums a convolution epilogue wrote (kpx_conv3x3_wino_stats_f32): tile_stats[tile][2][C] floats.
+// Batch statistics from the per-tile sums a convolution epilogue wrote (kpx_conv3x3_wino_f32 with tile_stats): tile_stats[tile][2][C] floats.
 // One workgroup per channel adds the tiles [tile0, tile0 + ntiles) in a fixed order in fp64 (same tree as kpx_sum_partials).
 __global__ __launch_bounds__(256) void bn_stats_from_tiles_kernel(const float* __restrict__ ts, size_t tile0, size_t ntiles, int C, double count, float eps,
                                                                  float* mean, float* invstd, float* var_biased, float* mm, float* mv, float decay) {

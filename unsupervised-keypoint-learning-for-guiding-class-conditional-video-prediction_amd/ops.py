@@ -285,13 +285,11 @@ def _bf16s_bnbwd(dy, lddy, k, w, dx, lddx, nn, bn_y, beta):
     return slab, Fraction(tiles, n)
 
 
-# prepared (fragment-ordered bf16) filters of the bf16-storage 3x3 kernel: (filter data_ptr, dgrad) -> (Wf, owning FilterBank or None, weak ref, (Cin, Cout))
-_bf16s_w = {}
 conv_kernel_uses_bf16s = [0]
 
 
 def _bf16s_prepared(w, dgrad):
-    ent = _cached_u(_bf16s_w, w, dgrad)
+    ent = _cached_u('bf16s', w, dgrad)
     if ent is None:
         # a filter nobody registered (tests, one-off layers): prepare per call
         cin, cout = int(w.shape[2]), int(w.shape[3])
@@ -348,31 +346,14 @@ def _bf16s_conv(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=
     return True
 
 
-# ----------------------------------------------------------------------------------------------- pre-transformed Winograd filters
-# U = G g G^T is a function of the filter only.  Constant filters (VGG19) are transformed once; the trainable 3x3 filters of a
-# VariableStore are transformed together in ONE launch (kpx_wino_filter_transform_batch_f32) the first time a convolution needs
-# them after the store changed (optimiser update / restore), instead of once per convolution call.
-import ctypes as _ctypes
+# ----------------------------------------------------------------------------------------------- derived filter forms
+# U = G g G^T (and the bf16 kernel's fragment order) is a function of the filter only.  Constant filters (VGG19) are transformed once;
+# the trainable 3x3 filters of a VariableStore are transformed together in ONE launch per form (the batched transform entries) the first
+# time a convolution needs them after the store changed (optimiser update / restore), instead of once per convolution call.
+import collections as _collections
 import struct as _struct
-
-_wino_u = {}          # (filter data_ptr, dgrad) -> (U tensor, owning FilterBank or None, weak reference to the filter tensor, (Cin, Cout))
-_wino43_u = {}        # the same for the F(4x4,3x3) form of the filters whose layers may use it
-_wino43b_u = {}       # ... and its bf16x3 form (three exact bf16 planes in fragment order) for csrc/conv_wino43b.hip
 import weakref as _weakref
 
-
-def _cached_u(table, w, dgrad):
-    """The cached transform of filter ``w``, or None.  The key is the filter's ADDRESS, so an entry is only trusted while the tensor it
-    was made from is allocated (a bank keeps its filters alive itself; a constant / folded filter is tracked by a weak reference to its storage) and has this
-    shape -- the allocator hands a freed filter's address to unrelated tensors."""
-    key = (w.data_ptr(), 1 if dgrad else 0)
-    ent = table.get(key)
-    if ent is None:
-        return None
-    if (ent[2] is not None and ent[2]() is None) or ent[3] != (int(w.shape[2]), int(w.shape[3])):
-        table.pop(key, None)
-        return None
-    return ent
 conv_kernel_uses = {'wino43': 0, 'wino43b': 0}      # diagnostics / tests: launches of the F(4x4,3x3) kernels (fp32-MFMA form / bf16x3 form; 'wino43' counts both)
 
 # F(4x4,3x3) (csrc/conv_wino43.hip) does 2.25x fewer multiplies than F(2x2,3x3) at ~6x its rounding error (2-3e-6 rel-L2 per layer, still
@@ -395,27 +376,62 @@ DEBUG_FINITE = _os.environ.get('KPX_DEBUG_FINITE', '0') == '1'      # assert the
 WINO43_MIN_WORKGROUPS = 0          # (a module constant the model-level parity tests set to 128 and back)
 WINO43_NMIN = 33                   # produced channels from which a layer takes the 64-cout F(4x4,3x3) workgroups (32 / 16 measured: no change)
 # F(4x4,3x3) with the transform-domain GEMMs fp32-EQUIVALENT on the bf16 matrix pipe (csrc/conv_wino43b.hip: exact three-term operands, six
-# products): the same layers and directions as WINO43, same per-layer policy; the shapes it takes (no packed 16x16 images, K % 4 == 0) and
-# where it is preferred over the fp32-MFMA kernel: _wino43b_preferred.  KPX_WINO43B=0: the fp32-MFMA F(4x4,3x3) kernel everywhere (A/B, tests).
+# products): the same layers and directions as WINO43, same per-layer policy; it runs wherever it takes the shape (no packed 16x16 images with
+# statistics, K % 4 == 0: _wino43_plan).  KPX_WINO43B=0: the fp32-MFMA F(4x4,3x3) kernel everywhere (A/B, tests).
 WINO43B = _os.environ.get('KPX_WINO43B', '1') != '0'
 WINO43B_MAX_CHANNELS = 512         # gathered x produced channels up to which the bf16x3 form is prepared (its U is 1.5x the fp32 U: L2 traffic)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _kn(cin, cout, dgrad):
+    """(K gathered, Nn produced) channels of a [3,3,Cin,Cout] filter's launches in one direction."""
+    return (cout, cin) if dgrad else (cin, cout)
 
 
 def _wino43b_form_wanted(k, nn):
     return WINO43B and k >= 16 and k % 4 == 0 and nn >= WINO43_NMIN and max(k, nn) <= WINO43B_MAX_CHANNELS
 
 
-def _wino43b_preferred(n, h, wd, k, nn):
-    """Launch shapes on which the bf16x3 kernel is the faster F(4x4,3x3) form (profiles/r06_wino43b_layers.txt)."""
-    return True
+def _wino43_wanted(k, nn, dgrad, f43_fwd=True):
+    """Whether the (K gathered, Nn produced) launches of a layer in this direction may run F(4x4,3x3); f43_fwd: the layer's attribute
+    (layers.conv(..., f43_fwd=))."""
+    return bool(WINO43 and k >= 16 and nn >= WINO43_NMIN and (dgrad or f43_fwd))
 
 
-def _wino43_wanted(name, cin, cout, dgrad, f43_fwd=True):
-    """f43_fwd: the layer's attribute (layers.conv(..., f43_fwd=)); name: unused (kept for the callers' signatures)."""
-    k, nn = (cout, cin) if dgrad else (cin, cout)
-    if not (WINO43 and k >= 16 and nn >= WINO43_NMIN):
-        return False
-    return bool(dgrad or f43_fwd)
+# A derived form of the 3x3 filters: nbytes(Cin, Cout, dgrad), the single and the batched transform entry, the element type of its tensors,
+# wanted(K, Nn, dgrad, f43_fwd): whether a (filter, direction) gets it, and desc_last(Nn): the last field of its 32-byte batch descriptor.
+_Form = _collections.namedtuple('_Form', 'nbytes transform transform_batch dtype wanted desc_last')
+_FORMS = {
+    'wino': _Form(lambda cin, cout, dgrad: lib.kpx_wino_u_bytes(cin, cout), 'kpx_wino_filter_transform_f32',
+                  'kpx_wino_filter_transform_batch_f32', torch.float32, lambda k, nn, dgrad, f43_fwd: True, lambda nn: 0),
+    'wino43': _Form(lambda cin, cout, dgrad: lib.kpx_wino43_u_bytes(cin, cout), 'kpx_wino43_filter_transform_f32',
+                    'kpx_wino43_filter_transform_batch_f32', torch.float32, _wino43_wanted, lambda nn: 0),
+    'wino43b': _Form(lambda cin, cout, dgrad: lib.kpx_wino43b_u_bytes(cin, cout), 'kpx_wino43b_filter_transform_f32',
+                     'kpx_wino43b_filter_transform_batch_f32', torch.uint8,
+                     lambda k, nn, dgrad, f43_fwd: _wino43_wanted(k, nn, dgrad, f43_fwd) and _wino43b_form_wanted(k, nn), lambda nn: 0),
+    'bf16s': _Form(lambda cin, cout, dgrad: lib.kpx_conv3x3_bf16s_weights_bytes(*_kn(cin, cout, dgrad)), 'kpx_conv3x3_bf16s_prepare_f32',
+                   'kpx_conv3x3_bf16s_prepare_batch_f32', torch.uint8, lambda k, nn, dgrad, f43_fwd: True, lambda nn: (nn + 127) // 128 * 4),
+}
+_WINO_FORMS = ('wino', 'wino43', 'wino43b')          # the fp32 Winograd kernels' forms: made at once, refreshed together in this order
+
+_filter_forms = {}   # (form, filter data_ptr, dgrad) -> (tensor, owning FilterBank or None, weak reference to the filter's storage, (Cin, Cout))
+
+
+def _cached_u(form, w, dgrad):
+    """The cached ``form`` of filter ``w``, or None.  The key is the filter's ADDRESS, so an entry is only trusted while the tensor it
+    was made from is allocated (a bank keeps its filters alive itself; a constant / folded filter is tracked by a weak reference to its storage) and has this
+    shape -- the allocator hands a freed filter's address to unrelated tensors."""
+    key = (form, w.data_ptr(), 1 if dgrad else 0)
+    ent = _filter_forms.get(key)
+    if ent is None:
+        return None
+    if (ent[2] is not None and ent[2]() is None) or ent[3] != (int(w.shape[2]), int(w.shape[3])):
+        _filter_forms.pop(key, None)
+        return None
+    return ent
 
 
 class FilterBank:
@@ -428,64 +444,36 @@ class FilterBank:
         self.synced = -1
         self.filters = [(n, w) for n, w in named_filters if w.dim() == 4 and w.shape[0] == 3 and w.shape[1] == 3]
         self.device = device
+        self.f43_fwd = [attrs.get(n, {}).get('f43_fwd', True) for n, _ in self.filters]
+        self.tables = {}            # form -> (arena, device descriptor table or None, descriptor count); 'bf16s' made on first use
         if not self.filters or torch.device(device).type != 'cuda':
             self.filters = []
             return
-        sizes = [lib.kpx_wino_u_bytes(int(w.shape[2]), int(w.shape[3])) // 4 for _, w in self.filters]
-        sizes43 = [lib.kpx_wino43_u_bytes(int(w.shape[2]), int(w.shape[3])) // 4 for _, w in self.filters]
-        want43 = [[_wino43_wanted(n, int(w.shape[2]), int(w.shape[3]), d, attrs.get(n, {}).get('f43_fwd', True)) for d in (0, 1)] for n, w in self.filters]
-        self.arena = torch.empty(2 * sum(sizes) + sum(n43 * sum(wt) for n43, wt in zip(sizes43, want43)), dtype=torch.float32, device=device)
-        table, table43, off = b'', b'', 0
-        for (_, w), n, n43, wt in zip(self.filters, sizes, sizes43, want43):
-            for dgrad in (0, 1):
-                u = self.arena[off:off + n]
-                off += n
-                _wino_u[(w.data_ptr(), dgrad)] = (u, self, None, (int(w.shape[2]), int(w.shape[3])))
-                table += _struct.pack('<QQiiii', w.data_ptr(), u.data_ptr(), int(w.shape[2]), int(w.shape[3]), dgrad, 0)
-                if wt[dgrad]:
-                    u = self.arena[off:off + n43]
-                    off += n43
-                    _wino43_u[(w.data_ptr(), dgrad)] = (u, self, None, (int(w.shape[2]), int(w.shape[3])))
-                    table43 += _struct.pack('<QQiiii', w.data_ptr(), u.data_ptr(), int(w.shape[2]), int(w.shape[3]), dgrad, 0)
-        self.n_desc = 2 * len(self.filters)
-        self.table = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(device)
-        self.n_desc43 = len(table43) // 32
-        self.table43 = torch.frombuffer(bytearray(table43), dtype=torch.uint8).to(device) if table43 else None
-        # the bf16x3 form of the same (filter, direction) pairs where the kernel can take the layer
-        want43b = [[wt[d] and _wino43b_form_wanted(*((int(w.shape[3]), int(w.shape[2])) if d else (int(w.shape[2]), int(w.shape[3])))) for d in (0, 1)]
-                   for (_, w), wt in zip(self.filters, want43)]
-        sizes43b = [lib.kpx_wino43b_u_bytes(int(w.shape[2]), int(w.shape[3])) for _, w in self.filters]
-        self.arena43b = torch.empty(sum(nb * sum(wb) for nb, wb in zip(sizes43b, want43b)) or 1, dtype=torch.uint8, device=device)
-        table43b, off = b'', 0
-        for (_, w), nb, wb in zip(self.filters, sizes43b, want43b):
-            for dgrad in (0, 1):
-                if wb[dgrad]:
-                    u = self.arena43b[off:off + nb]
-                    off += nb
-                    _wino43b_u[(w.data_ptr(), dgrad)] = (u, self, None, (int(w.shape[2]), int(w.shape[3])))
-                    table43b += _struct.pack('<QQiiii', w.data_ptr(), u.data_ptr(), int(w.shape[2]), int(w.shape[3]), dgrad, 0)
-        self.n_desc43b = len(table43b) // 32
-        self.table43b = torch.frombuffer(bytearray(table43b), dtype=torch.uint8).to(device) if table43b else None
+        for form in _WINO_FORMS:
+            self._build(form)
 
     def touch(self):
         self.version += 1
 
-    def _build_bf16s(self):
-        """The fragment-ordered bf16 copies of every filter for the bf16-storage kernel (both directions), one arena, one descriptor table."""
-        sizes = [[lib.kpx_conv3x3_bf16s_weights_bytes(*((int(w.shape[3]), int(w.shape[2])) if d else (int(w.shape[2]), int(w.shape[3])))) for d in (0, 1)]
-                 for _, w in self.filters]
-        self.arena16 = torch.empty(sum(sum(sz) for sz in sizes), dtype=torch.uint8, device=self.device)
+    def _build(self, form):
+        """One arena and one descriptor table for every (filter, direction) that ``form`` is wanted for."""
+        f = _FORMS[form]
+        pairs = [(w, int(w.shape[2]), int(w.shape[3]), dgrad) for (_, w), f43 in zip(self.filters, self.f43_fwd) for dgrad in (0, 1)
+                 if f.wanted(*_kn(int(w.shape[2]), int(w.shape[3]), dgrad), dgrad, f43)]
+        sizes = [f.nbytes(cin, cout, dgrad) // f.dtype.itemsize for _, cin, cout, dgrad in pairs]
+        arena = torch.empty(sum(sizes), dtype=f.dtype, device=self.device)
         table, off = b'', 0
-        for (_, w), sz in zip(self.filters, sizes):
-            cin, cout = int(w.shape[2]), int(w.shape[3])
-            for dgrad in (0, 1):
-                wf = self.arena16[off:off + sz[dgrad]]
-                off += sz[dgrad]
-                _bf16s_w[(w.data_ptr(), dgrad)] = (wf, self, None, (cin, cout))
-                nn = cin if dgrad else cout
-                table += _struct.pack('<QQiiii', w.data_ptr(), wf.data_ptr(), cin, cout, dgrad, (nn + 127) // 128 * 4)
-        self.table16 = torch.frombuffer(bytearray(table), dtype=torch.uint8).to(self.device)
-        self.n_desc16 = len(table) // 32
+        for (w, cin, cout, dgrad), size in zip(pairs, sizes):
+            u = arena[off:off + size]
+            off += size
+            _filter_forms[(form, w.data_ptr(), dgrad)] = (u, self, None, (cin, cout))
+            table += _struct.pack('<QQiiii', w.data_ptr(), u.data_ptr(), cin, cout, dgrad, f.desc_last(_kn(cin, cout, dgrad)[1]))
+        self.tables[form] = (arena, torch.frombuffer(bytearray(table), dtype=torch.uint8).to(self.device) if table else None, len(pairs))
+
+    def _refresh(self, form):
+        _, table, n = self.tables[form]
+        if n:
+            check(getattr(lib, _FORMS[form].transform_batch)(table.data_ptr(), n, _stream()), _FORMS[form].transform_batch)
 
     def ensure_fresh(self, form=None):
         """Refresh the derived filter forms a convolution is about to read, if the filters changed since they were made.  form: 'wino' (the
@@ -500,17 +488,14 @@ class FilterBank:
                 self.ensure_fresh('wino')                # an earlier step fell back to an fp32 Winograd kernel: refresh that form before the fork too
         if form == 'bf16s':
             if getattr(self, 'synced16', -1) != self.version:
-                if getattr(self, 'table16', None) is None:
-                    self._build_bf16s()
-                check(lib.kpx_conv3x3_bf16s_prepare_batch_f32(self.table16.data_ptr(), self.n_desc16, _stream()), 'kpx_conv3x3_bf16s_prepare_batch_f32')
+                if 'bf16s' not in self.tables:
+                    self._build('bf16s')
+                self._refresh('bf16s')
                 self.synced16 = self.version
             return
         if self.synced != self.version:
-            check(lib.kpx_wino_filter_transform_batch_f32(self.table.data_ptr(), self.n_desc, _stream()), 'kpx_wino_filter_transform_batch_f32')
-            if self.n_desc43:
-                check(lib.kpx_wino43_filter_transform_batch_f32(self.table43.data_ptr(), self.n_desc43, _stream()), 'kpx_wino43_filter_transform_batch_f32')
-            if self.n_desc43b:
-                check(lib.kpx_wino43b_filter_transform_batch_f32(self.table43b.data_ptr(), self.n_desc43b, _stream()), 'kpx_wino43b_filter_transform_batch_f32')
+            for f in _WINO_FORMS:
+                self._refresh(f)
             self.synced = self.version
             # A LAZY refresh (an fp32 3x3 fall-back inside the bf16 configuration, whose pre-fork ensure_fresh() only refreshes the bf16
             # fragments) runs on whichever stream reaches it first: later readers on OTHER streams must wait for these launches
@@ -531,155 +516,117 @@ class FilterBank:
 
 
 def register_constant_filter(w, name='', f43_fwd=True):
-    """Transform a filter that never changes (VGG19, reference vgg.py:57-61 tf.constant) once, for both directions.
-    f43_fwd: whether the layer's forward may run F(4x4,3x3) (see WINO43 above).
-    Returns the cache keys; the owner must pass them to release_filters() when the filter memory is given up."""
+    """Transform a filter that never changes (VGG19, reference vgg.py:57-61 tf.constant) once, for both directions, into every form its
+    launches want.  name: the caller's label for the filter (not used by the policy); f43_fwd: whether the layer's forward may run
+    F(4x4,3x3) (see WINO43 above).  Returns the cache keys; the owner must pass them to release_filters() when the filter memory is given up."""
     if w.dim() != 4 or w.shape[0] != 3 or w.shape[1] != 3 or not w.is_cuda:
         return []
-    n = lib.kpx_wino_u_bytes(int(w.shape[2]), int(w.shape[3])) // 4
-    keys = []
+    cin, cout = int(w.shape[2]), int(w.shape[3])
     for dgrad in (0, 1):
-        u = torch.empty(n, dtype=torch.float32, device=w.device)
-        check(lib.kpx_wino_filter_transform_f32(w.data_ptr(), int(w.shape[2]), int(w.shape[3]), dgrad, u.data_ptr(), _stream()), 'kpx_wino_filter_transform_f32')
-        _wino_u[(w.data_ptr(), dgrad)] = (u, None, _weakref.ref(w.untyped_storage()), (int(w.shape[2]), int(w.shape[3])))
-        keys.append((w.data_ptr(), dgrad))
-        if _wino43_wanted(name, int(w.shape[2]), int(w.shape[3]), dgrad, f43_fwd):
-            u = torch.empty(lib.kpx_wino43_u_bytes(int(w.shape[2]), int(w.shape[3])) // 4, dtype=torch.float32, device=w.device)
-            check(lib.kpx_wino43_filter_transform_f32(w.data_ptr(), int(w.shape[2]), int(w.shape[3]), dgrad, u.data_ptr(), _stream()), 'kpx_wino43_filter_transform_f32')
-            _wino43_u[(w.data_ptr(), dgrad)] = (u, None, _weakref.ref(w.untyped_storage()), (int(w.shape[2]), int(w.shape[3])))
-            kk, nn_ = (int(w.shape[3]), int(w.shape[2])) if dgrad else (int(w.shape[2]), int(w.shape[3]))
-            if _wino43b_form_wanted(kk, nn_):
-                ub = torch.empty(lib.kpx_wino43b_u_bytes(int(w.shape[2]), int(w.shape[3])), dtype=torch.uint8, device=w.device)
-                check(lib.kpx_wino43b_filter_transform_f32(w.data_ptr(), int(w.shape[2]), int(w.shape[3]), dgrad, ub.data_ptr(), _stream()), 'kpx_wino43b_filter_transform_f32')
-                _wino43b_u[(w.data_ptr(), dgrad)] = (ub, None, _weakref.ref(w.untyped_storage()), (int(w.shape[2]), int(w.shape[3])))
-        if _compute_dtype[0] == 'bf16' and int(w.shape[2]) % 8 == 0:
-            cin, cout = int(w.shape[2]), int(w.shape[3])
-            k, nn = (cout, cin) if dgrad else (cin, cout)
-            wf = torch.empty(lib.kpx_conv3x3_bf16s_weights_bytes(k, nn), dtype=torch.uint8, device=w.device)
-            check(lib.kpx_conv3x3_bf16s_prepare_f32(w.data_ptr(), cin, cout, dgrad, wf.data_ptr(), _stream()), 'kpx_conv3x3_bf16s_prepare_f32')
-            _bf16s_w[(w.data_ptr(), dgrad)] = (wf, None, _weakref.ref(w.untyped_storage()), (cin, cout))
-    return keys
+        for form, f in _FORMS.items():
+            if not f.wanted(*_kn(cin, cout, dgrad), dgrad, f43_fwd) or (form == 'bf16s' and not (_compute_dtype[0] == 'bf16' and cin % 8 == 0)):
+                continue
+            u = torch.empty(f.nbytes(cin, cout, dgrad) // f.dtype.itemsize, dtype=f.dtype, device=w.device)
+            check(getattr(lib, f.transform)(w.data_ptr(), cin, cout, dgrad, u.data_ptr(), _stream()), f.transform)
+            _filter_forms[(form, w.data_ptr(), dgrad)] = (u, None, _weakref.ref(w.untyped_storage()), (cin, cout))
+    return [(w.data_ptr(), dgrad) for dgrad in (0, 1)]
 
 
 def release_filters(keys):
-    """Forget cached Winograd forms (the address of a freed filter may be handed to an unrelated tensor later)."""
-    for k in keys:
-        _wino_u.pop(k, None)
-        _wino43_u.pop(k, None)
-        _wino43b_u.pop(k, None)
-        _bf16s_w.pop(k, None)
+    """Forget the cached forms of these (filter address, dgrad) keys (the address of a freed filter may be handed to an unrelated tensor later)."""
+    for ptr, dgrad in keys:
+        for form in _FORMS:
+            _filter_forms.pop((form, ptr, dgrad), None)
+
+
+def _wino43_plan(n, h, wd, k, nn, ld_in, in_ptr, dgrad, forms, want_stats=False, bn_src=False, vgg=False):
+    """The F(4x4,3x3) decision of one launch: [(form, fused bn sums), ...], the launches to try in this order until a kernel takes the
+    options (the entries return KPX_EINVAL on a mix they do not take), or [] = not F(4x4,3x3).  forms: the filter's cached forms ('wino43',
+    'wino43b'); want_stats: the forward's statistics strips; bn_src: a data gradient towards a ReLU'd batch norm's output; vgg: VGG19's mask /
+    pool options (conv3x3_wino43_ex: the fp32 kernel must take the launch and Nn % 64 == 0)."""
+    if not (WINO43 and 'wino43' in forms):
+        return []
+    wgs = (n // 2 if wd == 16 else n * (h // 16) * (wd // 32)) * ((nn + 63) // 64)
+    f32 = bool(lib.kpx_conv3x3_wino43_eligible(n, h, wd, k, nn, ld_in, in_ptr))
+    if wgs <= WINO43_MIN_WORKGROUPS or (vgg and (nn % 64 or not f32)):
+        return []
+    if want_stats and not lib.kpx_conv3x3_wino43_stats_tiles(n, h, wd):
+        return []            # packed 16 x 16 images have no statistics strips: a forward that wants them takes F(2x2,3x3)
+    # the fused bn sums need Nn % 64 == 0 and unpacked images; elsewhere the data gradient runs F(4x4,3x3) without them (the batch norm then
+    # makes its own reduction pass), as it does when the fp32 kernel refuses them
+    bn = bool(bn_src and dgrad and nn % 64 == 0 and wd != 16)
+    plan = []
+    if WINO43B and 'wino43b' in forms and lib.kpx_conv3x3_wino43b_eligible(n, h, wd, k, nn, ld_in, in_ptr):
+        plan.append(('wino43b', bn))
+    if f32:
+        plan += [('wino43', bn)] + ([('wino43', False)] if bn else [])
+    return plan
+
+
+def _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, want_stats=False, bn_src=None, mask=None, pool=None):
+    """Make the first launch of ``plan`` that its kernel takes: (slab, tiles per image) when it wrote sums, True, or False if none ran."""
+    n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
+    for form, bn in plan:
+        entry = 'kpx_conv3x3_wino43b_f32' if form == 'wino43b' else 'kpx_conv3x3_wino43_f32'
+        tiles = lib.kpx_conv3x3_wino43_stats_tiles(n, h, wd)
+        slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=inp.device) if (want_stats or bn) else None
+        rc = getattr(lib, entry)(inp.data_ptr(), n, h, wd, k, ld_in, forms[form][0].data_ptr(), None if bn else _ptr(bias), out.data_ptr(), nn,
+                                 ld_out, ACT_NONE if bn else act, _ptr(mask), mask.shape[3] if mask is not None else 0, _ptr(pool),
+                                 pool.shape[3] if pool is not None else 0, _ptr(slab), bn_src[0].data_ptr() if bn else None,
+                                 bn_src[0].shape[3] if bn else 0, bn_src[1].data_ptr() if bn else None, _stream())
+        if rc != -1:
+            check(rc, entry)
+            conv_kernel_uses['wino43'] += 1
+            if form == 'wino43b':
+                conv_kernel_uses['wino43b'] += 1
+            return (slab, tiles // n) if slab is not None else True
+    return False
+
+
+def _f43_forms(w, dgrad):
+    return {form: ent for form in ('wino43', 'wino43b') if (ent := _cached_u(form, w, dgrad)) is not None}
 
 
 def _wino_pretransformed(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=False, bn_src=None):
-    """Run the fused Winograd kernel on a cached U; False when there is none for this filter or the shape is not eligible.
-    want_stats: also have the epilogue write the per-tile batch-norm sums of the output; returns (slab, tiles per image) then."""
-    ent = _cached_u(_wino_u, w, dgrad)
+    """Run a fused Winograd kernel on the cached forms of ``w``; False when there is none for this filter or the shape is not eligible.
+    want_stats: also have the epilogue write the per-tile batch-norm sums of the output; bn_src = (bn_y, beta): the data gradient towards a
+    ReLU'd batch norm's output, whose backward sums the epilogue reduces where it can.  Returns (slab, tiles per image) when it wrote sums."""
+    ent = _cached_u('wino', w, dgrad)
     if ent is None:
         return False
     n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
     if not lib.kpx_conv3x3_wino_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr()):
         return False
-    u, bank = ent[0], ent[1]
-    if bank is not None:
-        bank.ensure_fresh('wino')
-    bptr = bias.data_ptr() if bias is not None else None
-    ent43 = _cached_u(_wino43_u, w, dgrad) if WINO43 else None
-    tiles = lib.kpx_conv3x3_wino43_stats_tiles(n, h, wd) if want_stats else 1      # 0: no statistics from this kernel for the shape (16 x 16)
-    # (WINO43_MIN_WORKGROUPS: see its definition -- 0 by default)
-    wgs43 = (n // 2 if wd == 16 else n * (h // 16) * (wd // 32)) * ((nn + 63) // 64)
-    # the bf16x3 form of F(4x4,3x3) (same policy, same epilogue options) where it is prepared, eligible and the faster one
-    ent43b = _cached_u(_wino43b_u, w, dgrad) if (WINO43B and ent43 is not None) else None
-    if (ent43b is not None and tiles and wgs43 > WINO43_MIN_WORKGROUPS and _wino43b_preferred(n, h, wd, k, nn)
-            and lib.kpx_conv3x3_wino43b_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr())):
-        bnbwd = bn_src is not None and dgrad and nn % 64 == 0 and wd != 16        # (packed 16 x 16 images: no statistics epilogue, as on the fp32-MFMA form)
-        slab = None
-        if bnbwd or want_stats:
-            slab = torch.empty(lib.kpx_conv3x3_wino43_stats_tiles(n, h, wd) * 2 * nn, dtype=torch.float32, device=inp.device)
-        rc = lib.kpx_conv3x3_wino43b_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent43b[0].data_ptr(), None if bnbwd else bptr, out.data_ptr(), nn, ld_out,
-                                         ACT_NONE if bnbwd else act, None, 0, None, 0, slab.data_ptr() if slab is not None else None,
-                                         bn_src[0].data_ptr() if bnbwd else None, bn_src[0].shape[3] if bnbwd else 0, bn_src[1].data_ptr() if bnbwd else None, _stream())
-        if rc != -1:
-            check(rc, 'kpx_conv3x3_wino43b_f32')
-            conv_kernel_uses['wino43'] += 1
-            conv_kernel_uses['wino43b'] += 1
-            return (slab, lib.kpx_conv3x3_wino43_stats_tiles(n, h, wd) // n) if slab is not None else True
-    if (ent43 is not None and bn_src is not None and dgrad and wd != 16 and nn % 64 == 0 and wgs43 > WINO43_MIN_WORKGROUPS
-            and lib.kpx_conv3x3_wino43_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr())):
-        # data gradient towards a ReLU'd batch norm's output on F(4x4,3x3): its epilogue masks the gradient and reduces the batch norm's backward sums
-        bn_y, beta = bn_src
-        tiles43 = lib.kpx_conv3x3_wino43_stats_tiles(n, h, wd)
-        slab = torch.empty(tiles43 * 2 * nn, dtype=torch.float32, device=inp.device)
-        rc = lib.kpx_conv3x3_wino43_bnbwd_stats_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent43[0].data_ptr(), out.data_ptr(), nn, ld_out,
-                                                    bn_y.data_ptr(), bn_y.shape[3], beta.data_ptr(), slab.data_ptr(), _stream())
-        if rc != -1:
-            check(rc, 'kpx_conv3x3_wino43_bnbwd_stats_f32')
-            conv_kernel_uses['wino43'] += 1
-            return slab, tiles43 // n
-    # (a layer F(4x4,3x3) takes but whose shape its statistics epilogue does not -- 16x16 images, a produced-channel count that is not a
-    #  multiple of 64 -- stays on F(4x4,3x3) without the sums: the batch norm then makes its own reduction pass)
-    if (ent43 is not None and tiles and wgs43 > WINO43_MIN_WORKGROUPS
-            and lib.kpx_conv3x3_wino43_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr())):
-        conv_kernel_uses['wino43'] += 1
-        if want_stats:
-            slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=inp.device)
-            check(lib.kpx_conv3x3_wino43_stats_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent43[0].data_ptr(), bptr, out.data_ptr(), nn, ld_out, act,
-                                                   slab.data_ptr(), _stream()), 'kpx_conv3x3_wino43_stats_f32')
-            return slab, tiles // n
-        check(lib.kpx_conv3x3_wino43_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent43[0].data_ptr(), bptr, out.data_ptr(), nn, ld_out, act, _stream()),
-              'kpx_conv3x3_wino43_f32')
-        return True
-    if bn_src is not None and dgrad and h % 16 == 0 and wd % 16 == 0:
-        bn_y, beta = bn_src                              # the gathered tensor's consumer-side twin: y = relu(BN(.)) that this conv read
-        tiles = lib.kpx_conv3x3_wino_stats_tiles(n, h, wd)
-        slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=inp.device)
-        check(lib.kpx_conv3x3_wino_bnbwd_stats_f32(inp.data_ptr(), n, h, wd, k, ld_in, u.data_ptr(), out.data_ptr(), nn, ld_out,
-                                                   bn_y.data_ptr(), bn_y.shape[3], beta.data_ptr(), slab.data_ptr(), _stream()),
-              'kpx_conv3x3_wino_bnbwd_stats_f32')
-        return slab, tiles // n
-    if want_stats and h % 16 == 0 and wd % 16 == 0:
-        tiles = lib.kpx_conv3x3_wino_stats_tiles(n, h, wd)
-        slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=inp.device)
-        check(lib.kpx_conv3x3_wino_stats_f32(inp.data_ptr(), n, h, wd, k, ld_in, u.data_ptr(), bptr, out.data_ptr(), nn, ld_out, act,
-                                             slab.data_ptr(), _stream()), 'kpx_conv3x3_wino_stats_f32')
-        return slab, tiles // n
-    check(lib.kpx_conv3x3_wino_f32(inp.data_ptr(), n, h, wd, k, ld_in, u.data_ptr(), bptr, out.data_ptr(), nn, ld_out, act, _stream()),
-          'kpx_conv3x3_wino_f32')
-    return True
+    if ent[1] is not None:
+        ent[1].ensure_fresh('wino')
+    forms = _f43_forms(w, dgrad)
+    plan = _wino43_plan(n, h, wd, k, nn, ld_in, inp.data_ptr(), dgrad, forms, want_stats=want_stats, bn_src=bn_src is not None)
+    r = _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, want_stats=want_stats, bn_src=bn_src)
+    if r:
+        return r
+    # F(2x2,3x3): sums per 16x16-pixel tile where the images are whole tiles (8x8 images are packed four to a workgroup)
+    bn = bn_src is not None and dgrad and h % 16 == 0 and wd % 16 == 0
+    stats = bn or (want_stats and h % 16 == 0 and wd % 16 == 0)
+    tiles = lib.kpx_conv3x3_wino_stats_tiles(n, h, wd)
+    slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=inp.device) if stats else None
+    check(lib.kpx_conv3x3_wino_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent[0].data_ptr(), None if bn else _ptr(bias), out.data_ptr(), nn, ld_out,
+                                   ACT_NONE if bn else act, _ptr(slab), bn_src[0].data_ptr() if bn else None, bn_src[0].shape[3] if bn else 0,
+                                   bn_src[1].data_ptr() if bn else None, _stream()), 'kpx_conv3x3_wino_f32')
+    return (slab, tiles // n) if stats else True
 
 
 def conv3x3_wino43_ex(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, mask=None, pool_out=None):
     """The F(4x4,3x3) kernel with VGG19's epilogue options: ``mask`` -- zero the output where mask <= 0 (ReLU backward of the tensor the
     data gradient belongs to), ``pool_out`` -- also write the 2x2 max-pool of the activated output.  True if it ran; False when the
     layer / launch is not one the kernel takes (the caller then uses the plain path and the separate kernels)."""
-    ent43 = _cached_u(_wino43_u, w, dgrad) if WINO43 else None
-    if ent43 is None or nn % 64:
-        return False
+    forms = _f43_forms(w, dgrad)
     n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
-    wgs43 = (n // 2 if wd == 16 else n * (h // 16) * (wd // 32)) * ((nn + 63) // 64)
-    if wgs43 <= WINO43_MIN_WORKGROUPS or not lib.kpx_conv3x3_wino43_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr()):
+    plan = _wino43_plan(n, h, wd, k, nn, ld_in, inp.data_ptr(), dgrad, forms, vgg=True)
+    if not plan:
         return False
-    if ent43[1] is not None:
-        ent43[1].ensure_fresh('wino')
-    ent43b = _cached_u(_wino43b_u, w, dgrad) if WINO43B else None
-    if (ent43b is not None and _wino43b_preferred(n, h, wd, k, nn) and lib.kpx_conv3x3_wino43b_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr())):
-        rc = lib.kpx_conv3x3_wino43b_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent43b[0].data_ptr(), bias.data_ptr() if bias is not None else None,
-                                         out.data_ptr(), nn, ld_out, act, mask.data_ptr() if mask is not None else None,
-                                         mask.shape[3] if mask is not None else 0, pool_out.data_ptr() if pool_out is not None else None,
-                                         pool_out.shape[3] if pool_out is not None else 0, None, None, 0, None, _stream())
-        if rc != -1:
-            check(rc, 'kpx_conv3x3_wino43b_f32')
-            conv_kernel_uses['wino43'] += 1
-            conv_kernel_uses['wino43b'] += 1
-            return True
-    rc = lib.kpx_conv3x3_wino43_ex_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent43[0].data_ptr(), bias.data_ptr() if bias is not None else None,
-                                       out.data_ptr(), nn, ld_out, act, mask.data_ptr() if mask is not None else None,
-                                       mask.shape[3] if mask is not None else 0, pool_out.data_ptr() if pool_out is not None else None,
-                                       pool_out.shape[3] if pool_out is not None else 0, _stream())
-    if rc == -1:                                         # KPX_EINVAL: alignment / channel-count preconditions of the options
-        return False
-    check(rc, 'kpx_conv3x3_wino43_ex_f32')
-    conv_kernel_uses['wino43'] += 1
-    return True
+    if forms['wino43'][1] is not None:
+        forms['wino43'][1].ensure_fresh('wino')
+    return _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, mask=mask, pool=pool_out)
 
 
 # ----------------------------------------------------------------------------------------------- raw launchers
