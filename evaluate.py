@@ -2,9 +2,11 @@
 """Evaluation entry point with the reference's CLI (reference: evaluate.py:13-163):
 
     python evaluate.py --config configs/penn.yaml --checkpoint_stage1 S1.npz --checkpoint_stage2 S2.npz [--save_dir results/eval]
-                       [--synthetic N] [--no-save]
+                       [--synthetic N] [--colors_seed S] [--no-save]
 
-One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  The
+One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
+reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
+pred_points/ (:96-97, :107-109, :126-128) in the palette of ``random.Random(--colors_seed)``.  The
 test subset of ``paths.data_dir`` is read through kpx_amd.data.SequenceDataLoader (the reference's data/sequence_dataloader.py);
 ``--synthetic N`` feeds N random images with random one-hot action codes instead.  Checkpoints: the ``.npz`` containers written
 by this repo or TensorFlow V2 bundle prefixes (TF variable names either way).
@@ -52,6 +54,7 @@ def main(argv=None):
     parser.add_argument('--save_dir', type=str, required=False, help='root dir to save results', default='results/eval')
     parser.add_argument('--synthetic', type=int, default=0)
     parser.add_argument('--batch', type=int, default=8)             # reference :27
+    parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette (the reference draws it unseeded)')
     parser.add_argument('--no-save', action='store_true')
     args = parser.parse_args(argv)
     config = load_config(args.config)
@@ -60,7 +63,7 @@ def main(argv=None):
             raise Exception('checkpoint not found at %s' % p)
     import kpx_amd
     dev = torch.device('cuda', 0)
-    model = kpx_amd.FinalModel(config, device=dev)
+    model = kpx_amd.FinalModel(config, device=dev, point_maps=not args.no_save, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
     model.restore(None, args.checkpoint_stage1)                      # reference :76-77: two partial restores by name
@@ -81,10 +84,12 @@ def main(argv=None):
                     d = osp.join(args.save_dir, '%04d' % sample_idx)
                     os.makedirs(d, exist_ok=True)
                     _save_img(osp.join(d, 'input_im.png'), o['im'][batch_idx], rescale=True)
+                    _save_img(osp.join(d, 'current_points.png'), o['current_points'][batch_idx], rescale=False)
                     _save_img_sequence(osp.join(d, 'real_seq'), real[batch_idx], rescale=True)
                     _save_img_sequence(osp.join(d, 'pred_seq'), o['pred_im_seq'][batch_idx], rescale=True)
                     _save_img_sequence(osp.join(d, 'mask'), o['mask'][batch_idx], rescale=False)
                     _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
+                    _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                     sample_idx += 1
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
@@ -102,9 +107,11 @@ def main(argv=None):
                 d = osp.join(args.save_dir, '%04d' % sample_idx)
                 os.makedirs(d, exist_ok=True)
                 _save_img(osp.join(d, 'input_im.png'), o['im'][batch_idx], rescale=True)
+                _save_img(osp.join(d, 'current_points.png'), o['current_points'][batch_idx], rescale=False)
                 _save_img_sequence(osp.join(d, 'pred_seq'), o['pred_im_seq'][batch_idx], rescale=True)
                 _save_img_sequence(osp.join(d, 'mask'), o['mask'][batch_idx], rescale=False)
                 _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
+                _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                 sample_idx += 1
     torch.cuda.synchronize()
     print('iteration through synthetic set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))

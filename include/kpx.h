@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 4
+#define KPX_ABI_VERSION 5
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -291,6 +291,12 @@ int kpx_keypoint_head_proj_bwd_f32(const float* dmu, const float* mu, const floa
 int kpx_gaussian_maps_fwd_f32(const float* mu, int B, int K, int H, int W, double inv_std, float* maps, int ldy, void* stream);
 int kpx_gaussian_maps_bwd_f32(const float* dmaps, int lddy, const float* mu, int B, int K, int H, int W, double inv_std,
                               float* dmu, void* stream);
+
+/* ---- colourised key-point maps: colorize_point_maps(get_gaussian_maps(mu, [H,W], inv_std), colors) (utils/model.py:42-60) in one pass.
+ * mu [N,K,2] (x,y), colors [K,3] fp32 on the device -> out [N,H,W,3] contiguous: out[n,h,w,c] = max_k g[n,h,w,k] * colors[k][c], g with the
+ * bits of kpx_gaussian_maps_fwd_f32.  K in [1,64], H and W in [2,1024], inv_std > 0; nothing else is read or written (no [N,H,W,K] maps).
+ * Added in ABI version 5. */
+int kpx_point_maps_rgb_f32(const float* mu, int N, int K, int H, int W, double inv_std, const float* colors, float* out, void* stream);
 
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */

@@ -7,8 +7,8 @@
 // expectation with wave shuffles.
 // Renderer: model_utils.get_gaussian_maps (utils/model.py:49-60) written straight in NHWC (the reference builds BKHW
 // and transposes): a pure write stream, 16 B per lane.
-// linspace follows tf.linspace in fp32 (start + step*i, two roundings) via __fmul_rn/__fadd_rn so that hipcc's
-// default fp-contraction cannot fuse it.
+// linspace follows tf.linspace in fp32 (start + step*i) via __fmul_rn/__fadd_rn; hipcc may still contract those into one fma (they are not
+// contraction barriers: see kpx_mul_rn below), which the renderers then share.
 #include "kpx_common.h"
 #include "kpx_env.h"
 #include <stdlib.h>
@@ -414,9 +414,23 @@ extern "C" int kpx_keypoint_head_proj_bwd_f32(const float* dmu, const float* mu,
 // square(y - mu_y) + square(x - mu_x), times float32(inv_std**2), negate, exp (utils/model.py:56-59); exp is the hardware
 // exp2 path (__expf: |err| <= ~2 ulp of a result in [0,1], inside the 2e-6 absolute budget).  Because both renderers call
 // this function, a map element has the same bits whether it is rendered contiguously or into a channel slice.
+// The operations go through kpx_*_rn: hipcc contracts the __f*_rn intrinsics like plain operators (their bodies carry the contract flag), and
+// the fixed-column loop of gauss_fwd_reg_kernel was compiled to fma(dy, dy, dx2), an ulp of dist away from the other renderers.
+__device__ __forceinline__ float kpx_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float kpx_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float kpx_sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
 __device__ __forceinline__ float kpx_gauss(float yv, float xv, float my, float mx, float inv2) {
-    const float dy = __fsub_rn(yv, my), dx = __fsub_rn(xv, mx);
-    const float dist = __fmul_rn(__fadd_rn(__fmul_rn(dy, dy), __fmul_rn(dx, dx)), inv2);
+    const float dy = kpx_sub_rn(yv, my), dx = kpx_sub_rn(xv, mx);
+    const float dist = kpx_mul_rn(kpx_add_rn(kpx_mul_rn(dy, dy), kpx_mul_rn(dx, dx)), inv2);
     return __expf(-dist);
 }
 
@@ -486,8 +500,8 @@ __global__ __launch_bounds__(512) void gauss_fwd_reg_kernel(const float* __restr
             int wj = w + carry[j];
             rowc[j] = wj >= W;
             if (rowc[j]) wj -= W;
-            const float dx = __fsub_rn(kpx_linspace(wj, W), mx[j]);
-            dx2[j] = __fmul_rn(dx, dx);
+            const float dx = kpx_sub_rn(kpx_linspace(wj, W), mx[j]);
+            dx2[j] = kpx_mul_rn(dx, dx);
         }
         const int step_rows = step_pix / W;
         for (int it = 0; it < iters; ++it) {
@@ -496,8 +510,8 @@ __global__ __launch_bounds__(512) void gauss_fwd_reg_kernel(const float* __restr
                 f32x4 r;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float dy = __fsub_rn(rowc[j] ? y1 : y0, my[j]);
-                    const float dist = __fmul_rn(__fadd_rn(__fmul_rn(dy, dy), dx2[j]), inv2);
+                    const float dy = kpx_sub_rn(rowc[j] ? y1 : y0, my[j]);
+                    const float dist = kpx_mul_rn(kpx_add_rn(kpx_mul_rn(dy, dy), dx2[j]), inv2);
                     r[j] = __expf(-dist);
                 }
                 if (NT) __builtin_nontemporal_store(r, ob + i); else ob[i] = r;
@@ -615,5 +629,105 @@ extern "C" int kpx_gaussian_maps_bwd_f32(const float* dmaps, int lddy, const flo
     if (!dmaps || !mu || !dmu || B <= 0 || K <= 0 || K > 256 || H < 2 || W < 2 || lddy < K) return KPX_EINVAL;
     const float inv2 = (float)(inv_std * inv_std);
     hipLaunchKernelGGL(gauss_bwd_kernel, dim3(B), dim3(256), 0, kpx_stream(stream), dmaps, lddy, mu, K, H, W, inv2, dmu);
+    return kpx_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------ colourised key-point maps
+// colorize_point_maps(get_gaussian_maps(mu, [H,W]), colors) (utils/model.py:42-46 over :49-60) in one pass: out[n,h,w,c] = max_k g[n,h,w,k] *
+// colors[k][c], with g the bits of kpx_gaussian_maps_fwd_f32 (kpx_gauss's rounding sequence, operation for operation) and the max starting at
+// +0 (every product is >= +0).  The [N,H,W,K] map tensor is never formed: the kernel writes 12 B per pixel and reads nothing but mu / colors.
+// Tile: 256 threads = 16 quads (64 pixels) x 16 row groups of PM_R rows; a thread owns 4 adjacent pixels in PM_R consecutive rows and loops over
+// k (wave-uniform: mu / colors of the frame are scalar loads), so (x - mu_x)^2 is formed once per (column, k) and (y - mu_y)^2 once per (row, k).
+// Exact culling: dist = fl(fl(dy2 + dx2) * inv2) >= fl(dy2 * inv2) by monotonic rounding (dx2 >= 0), and __expf(-dist) is v_exp_f32 of
+// fl(-dist * log2 e); for dist >= 128 that argument is <= -184 and the result is exactly +0 (the smallest denormal is 2^-149), so its products
+// leave the max unchanged: a (row, k) with fl(dy2 * inv2) >= 128 is skipped for the whole row.
+#define PM_R 4
+#define PM_CULL 128.0f
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void point_maps_rgb_kernel(const float* __restrict__ mu, int K, int H, int W, float inv2,
+                                                             const float* __restrict__ colors, float* __restrict__ out, int tiles_x, int tiles) {
+    const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;   // frame, then its tiles (row-major)
+    const int tq = threadIdx.x & 15, tr = threadIdx.x >> 4;
+    const int w0 = ((tile % tiles_x) * 16 + tq) * 4;
+    const int h0 = (tile / tiles_x) * (16 * PM_R) + tr * PM_R;
+    float xs[4], ys[PM_R];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xs[j] = kpx_linspace(w0 + j, W);
+#pragma unroll
+    for (int r = 0; r < PM_R; ++r) ys[r] = kpx_linspace(h0 + r, H);
+    float acc[PM_R][4][3];
+#pragma unroll
+    for (int r = 0; r < PM_R; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[r][j][0] = acc[r][j][1] = acc[r][j][2] = 0.f;
+    const float* mun = mu + (size_t)n * K * 2;
+    // two points per iteration: acc = max3(acc, ga * c, gb * c) (a lone fmaxf per product also paid a canonicalising v_max_f32 of acc);
+    // for odd K the last point is taken twice (max is idempotent)
+    for (int k = 0; k < K; k += 2) {
+        const int k1 = k + 1 < K ? k + 1 : k;
+        const float mxa = mun[2 * k], mya = mun[2 * k + 1], mxb = mun[2 * k1], myb = mun[2 * k1 + 1];
+        const float a0 = colors[3 * k], a1 = colors[3 * k + 1], a2 = colors[3 * k + 2];
+        const float b0 = colors[3 * k1], b1 = colors[3 * k1 + 1], b2 = colors[3 * k1 + 2];
+        float dxa[4], dxb[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float d = kpx_sub_rn(xs[j], mxa); dxa[j] = kpx_mul_rn(d, d);
+            d = kpx_sub_rn(xs[j], mxb); dxb[j] = kpx_mul_rn(d, d);
+        }
+#pragma unroll
+        for (int r = 0; r < PM_R; ++r) {
+            float d = kpx_sub_rn(ys[r], mya);
+            const float dya = kpx_mul_rn(d, d);
+            d = kpx_sub_rn(ys[r], myb);
+            const float dyb = kpx_mul_rn(d, d);
+            // a culled point of a live pair is still evaluated: its products are exactly +0
+            if (h0 + r < H && (kpx_mul_rn(dya, inv2) < PM_CULL || kpx_mul_rn(dyb, inv2) < PM_CULL)) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float ga = __expf(-kpx_mul_rn(kpx_add_rn(dya, dxa[j]), inv2));
+                    const float gb = __expf(-kpx_mul_rn(kpx_add_rn(dyb, dxb[j]), inv2));
+                    acc[r][j][0] = fmaxf(acc[r][j][0], fmaxf(kpx_mul_rn(ga, a0), kpx_mul_rn(gb, b0)));
+                    acc[r][j][1] = fmaxf(acc[r][j][1], fmaxf(kpx_mul_rn(ga, a1), kpx_mul_rn(gb, b1)));
+                    acc[r][j][2] = fmaxf(acc[r][j][2], fmaxf(kpx_mul_rn(ga, a2), kpx_mul_rn(gb, b2)));
+                }
+            }
+        }
+    }
+    if (w0 >= W) return;
+#pragma unroll
+    for (int r = 0; r < PM_R; ++r) {
+        const int h = h0 + r;
+        if (h >= H) break;
+        float* o = out + (((size_t)n * H + h) * W + w0) * 3;
+        if (VEC) {                                      // W % 4 == 0 and a 16-B aligned base: the quad is 48 contiguous, aligned bytes
+            f32x4 v0 = {acc[r][0][0], acc[r][0][1], acc[r][0][2], acc[r][1][0]};
+            f32x4 v1 = {acc[r][1][1], acc[r][1][2], acc[r][2][0], acc[r][2][1]};
+            f32x4 v2 = {acc[r][2][2], acc[r][3][0], acc[r][3][1], acc[r][3][2]};
+            __builtin_nontemporal_store(v0, reinterpret_cast<f32x4*>(o));
+            __builtin_nontemporal_store(v1, reinterpret_cast<f32x4*>(o) + 1);
+            __builtin_nontemporal_store(v2, reinterpret_cast<f32x4*>(o) + 2);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (w0 + j < W)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) __builtin_nontemporal_store(acc[r][j][c], o + 3 * j + c);
+        }
+    }
+}
+
+extern "C" int kpx_point_maps_rgb_f32(const float* mu, int N, int K, int H, int W, double inv_std, const float* colors, float* out, void* stream) {
+    if (!mu || !colors || !out || N < 1 || K < 1 || K > 64 || H < 2 || H > 1024 || W < 2 || W > 1024 || !(inv_std > 0)) return KPX_EINVAL;
+    const float inv2 = (float)(inv_std * inv_std);          // as kpx_gaussian_maps_fwd_f32 (utils/model.py:58)
+    const int tiles_x = (W + 63) / 64, tiles_y = (H + 16 * PM_R - 1) / (16 * PM_R);
+    if ((size_t)N * tiles_x * tiles_y > 0x7fffffff) return KPX_EINVAL;
+    const int tiles = tiles_x * tiles_y;
+    const dim3 grid((unsigned)(N * tiles)), block(256);
+    hipStream_t s = kpx_stream(stream);
+    if (W % 4 == 0 && (((uintptr_t)out) & 15) == 0)
+        hipLaunchKernelGGL(point_maps_rgb_kernel<true>, grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles);
+    else
+        hipLaunchKernelGGL(point_maps_rgb_kernel<false>, grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles);
     return kpx_launch_status();
 }

@@ -1,11 +1,15 @@
 """Full evaluation pipeline (reference: models/final_model.py) -- SURVEY 8f row 1 / BASELINE configs[4]:
 detector -> stage-2 vae_decoder (z ~ N(0,1), 32 LSTM steps) -> translator on B*32 frames, inference-mode batch norm.
 
-Only the tensors evaluate.py saves are produced; the colourised key-point visualisations (utils/model.py:13-46, unseeded
-``random``) are out of scope.  ``z`` can be injected for deterministic parity tests (the reference draws it unseeded, :71).
+Outputs are the tensors evaluate.py saves.  With ``point_maps=True`` they include the colourised key-point maps ``current_points``
+[B,R,R,3] and ``future_points`` [B,32,R,R,3] (reference :101-110, R = ``image_size``), rendered by one fused kernel per output
+(``model_utils.render_point_maps``).  The palette ``self.colors`` is the reference's ``get_n_colors`` (:37) drawn from
+``random.Random(colors_seed)``: the reference draws it from the unseeded module-level ``random``, so ``colors_seed=s`` reproduces its
+palette after ``random.seed(s)``.  ``z`` can be injected for deterministic parity tests (the reference draws it unseeded, :71).
 """
 import logging
 import os
+import random
 
 import torch
 
@@ -25,7 +29,7 @@ log = logging.getLogger('kpx')
 class FinalModel(BaseModel):
     name = 'final'            # reference :21
 
-    def __init__(self, config, device='cuda', image_size=IMAGE_SIZE, frames_per_launch=256, seed=1234):
+    def __init__(self, config, device='cuda', image_size=IMAGE_SIZE, frames_per_launch=256, seed=1234, point_maps=False, colors_seed=0):
         super(FinalModel, self).__init__(False)
         model_config = config['model']
         self.log_dir = config['paths']['log_dir']
@@ -39,6 +43,10 @@ class FinalModel(BaseModel):
         self.device = ops.normalize_device(device)
         self.store = variables.VariableStore(device=self.device, seed=seed)
         self._graphs, self._eager_runs, self._graph_failed = {}, {}, False
+        self.colors = model_utils.get_n_colors(self.n_points, pastel_factor=0.0, rng=random.Random(colors_seed))   # :37 (factor ignored there too)
+        self.point_maps = point_maps
+        # fp32 on the device once: TF casts the float64 palette constant to the maps' dtype
+        self._colors_dev = torch.tensor(self.colors, dtype=torch.float32, device=self.device) if point_maps else None
 
     def build(self, inputs=None):
         r, k, b = self.image_size, self.n_points, 2
@@ -132,10 +140,14 @@ class FinalModel(BaseModel):
                 f_, c_, m_ = ops.head_blend_tiled(im[s // t:s // t + nb], raw4, t, clip=True)                       # :96-99
                 finals.append(f_); crudes.append(c_); masks.append(m_)
             cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, dim=0)
-            return {'im': im, 'real_im_seq': feed_dict.get('real_im_seq'),
-                    'pred_im_seq': cat(finals).reshape(b, t, r, r, 3), 'mask': cat(masks).reshape(b, t, r, r, 1),
-                    'pred_im_crude': cat(crudes).reshape(b, t, r, r, 3), 'fut_pt_raw': pred_seq.reshape(b, t, k, 2),
-                    'first_pt': first_pt}
+            out = {'im': im, 'real_im_seq': feed_dict.get('real_im_seq'),
+                   'pred_im_seq': cat(finals).reshape(b, t, r, r, 3), 'mask': cat(masks).reshape(b, t, r, r, 1),
+                   'pred_im_crude': cat(crudes).reshape(b, t, r, r, 3), 'fut_pt_raw': pred_seq.reshape(b, t, k, 2),
+                   'first_pt': first_pt}
+            if self.point_maps:                                                                  # :101-110
+                out['current_points'] = model_utils.render_point_maps(first_pt.reshape(b, k, 2), (r, r), self._colors_dev)
+                out['future_points'] = model_utils.render_point_maps(pred_pts, (r, r), self._colors_dev).reshape(b, t, r, r, 3)
+            return out
 
     def train_step(self, sess, feed_dict, step, batch_size, should_write_log=False, should_write_summary=False):
         raise NotImplementedError          # reference :127-136

@@ -1369,6 +1369,26 @@ def gaussian_maps(mu, h, w, inv_std=14.3):
     return GaussianMapsFn.apply(mu, h, w, inv_std)
 
 
+def point_maps_rgb(mu, h, w, colors, inv_std=14.3, out=None):
+    """colorize_point_maps(get_gaussian_maps(mu, [h, w], inv_std), colors) (reference utils/model.py:42-60) in one launch, forward only:
+    mu [N,K,2] (x,y), colors [K,3] fp32 on mu's device -> [N,h,w,3].  The Gaussian factor has the bits of ``gaussian_maps``."""
+    _require_gpu(mu)
+    _require_gpu(colors)
+    mu = mu.contiguous()
+    colors = colors.contiguous()
+    n, k, _ = mu.shape
+    if mu.dtype != torch.float32 or colors.dtype != torch.float32 or tuple(colors.shape) != (k, 3) or colors.device != mu.device:
+        raise _lib.KpxError('point_maps_rgb: mu [N,K,2] and colors [K,3], fp32 on one device (got %s %s, %s %s)'
+                            % (tuple(mu.shape), mu.dtype, tuple(colors.shape), colors.dtype))
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.float32, device=mu.device)
+    elif tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != mu.device:
+        raise _lib.KpxError('point_maps_rgb: out must be a contiguous fp32 [%d,%d,%d,3] tensor on %s' % (n, h, w, mu.device))
+    check(lib.kpx_point_maps_rgb_f32(mu.data_ptr(), n, k, int(h), int(w), float(inv_std), colors.data_ptr(), out.data_ptr(), _stream()),
+          'kpx_point_maps_rgb_f32')
+    return out
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
