@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 5
+#define KPX_ABI_VERSION 6
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -79,12 +79,12 @@ int kpx_conv3x3_wino_eligible(int N, int H, int W, int K, int Nn, int ldin, cons
 /* Epilogue options of kpx_conv3x3_wino_f32 (all NULL: the plain convolution):
  *   tile_stats alone: the batch-norm statistics of the OUTPUT as well (tf.contrib.layers.batch_norm follows every generator conv,
  *     models/networks/layers.py:13-14): tile_stats[N * (H/16) * (W/16)][2][Nn] = per 16x16-pixel tile and channel, the sum and the sum
- *     of squares of out (fp32, fixed summation order).  kpx_bn_stats_from_tiles_f32 turns a tile range into mean / invstd / moving
- *     statistics, replacing kpx_bn_stats_f32's pass over the activation.  H, W multiples of 16.
+ *     of squares of out (fp32, fixed summation order).  kpx_bn_train_fwd_f32 takes them as tile_stats instead of its pass over the
+ *     activation.  H, W multiples of 16.
  *   tile_stats + bn_y + bn_beta: data gradient of a 3x3 layer whose INPUT was bn_y = relu(BN(x)): out = dgrad (written as usual) and,
  *     per 16x16-pixel tile and channel, tile_stats[tile][2][Nn] = sum(dz), sum(dz * (bn_y - bn_beta)) with dz = out * [bn_y > 0] -- the
  *     two reductions of that batch norm's backward (bn_y: its output at the same pixels / channels, pixel stride ld_bn_y >= Nn).
- *     kpx_bn_bwd_from_tiles_f32 consumes them.  No bias, act = KPX_ACT_NONE; H, W multiples of 16.
+ *     kpx_bn_train_bwd_f32 takes them as tile_stats.  No bias, act = KPX_ACT_NONE; H, W multiples of 16.
  * Any other mix returns KPX_EINVAL. */
 int kpx_conv3x3_wino_f32(const float* in, int N, int H, int W, int K, int ldin, const float* u, const float* bias,
                          float* out, int Nn, int ldout, int act, float* tile_stats, const float* bn_y, int ld_bn_y,
@@ -150,18 +150,56 @@ int kpx_act_bwd_f32(const float* dy, const float* y, float* dz, size_t n, int ac
 
 /* ---- per-channel reductions over P pixels: sum[c] = sum_p x[p,c] (double accumulation).
  *      Used for the conv bias gradient (tf.layers.conv2d use_bias, layers.py:9).
- *      `scratch` (also for kpx_bn_stats_f32 / kpx_bn_bwd_f32) needs kpx_chan_reduce_scratch_bytes(C) bytes. */
+ *      `scratch` needs kpx_chan_reduce_scratch_bytes(C) bytes. */
 size_t kpx_chan_reduce_scratch_bytes(int C);
 int kpx_chan_sum_f32(const float* x, size_t P, int C, int ldx, float* sum_out, void* scratch, void* stream);
 
-/* ---- batch norm: replaces tf.contrib.layers.batch_norm(eps=1e-5, center, scale) (layers.py:13-14).
- * train forward, step 1: batch mean / biased variance over P pixels (fp64 accumulation) ->
- *   mean[C], invstd[C] = rsqrt(var+eps); if moving_mean/moving_var != NULL they are updated in place with
- *   decay (TF fused-BN rule: unbiased variance, moving -= (moving-batch)*(1-decay)). */
-int kpx_bn_stats_f32(const float* x, size_t P, int C, int ldx, float eps,
-                     float* mean, float* invstd, float* var_biased,
-                     float* moving_mean, float* moving_var, float decay,
-                     void* scratch, void* stream);
+/* ---- batch norm: replaces tf.contrib.layers.batch_norm(eps=1e-5, center, scale) (layers.py:13-14) and the tf.nn.relu after it
+ *      (networks/__init__.py:12...): act in {KPX_ACT_NONE, KPX_ACT_RELU}.
+ *
+ * Train mode: `groups` calls with batch statistics of their own, batched along N (the weight-sharing pose_encoder calls of a pair, reference
+ * detector_translator_model.py:166-167): x = [groups][P pixels][C], one launch per phase for all groups.  groups = 1 is the single call.  A
+ * group's results do not depend on how many groups share the call: `groups` calls with groups = 1, one per slice, give the same bits.
+ *   forward: per group the batch mean and biased variance over P pixels (fp64 accumulation in a fixed order) -> mean, invstd = rsqrt(var + eps),
+ *     [groups][C] (outputs, kept for the backward); moving_mean / moving_var (or NULL) updated in place once per group, in order, by the TF
+ *     fused-BN rule (unbiased variance, moving -= (moving - batch) * (1 - decay)); then y = act((x - mean) * invstd * gamma + beta).
+ *     tile_stats, or NULL for a reduction pass over x: the per-tile sums and sums of squares [tile][2][C] a convolution epilogue wrote
+ *     (kpx_conv3x3_wino_f32, _wino43(b)_f32, _c16_f32, kpx_conv3x3_bf16s), tiles_per_group tiles per group.
+ *   backward: dx, and dgamma / dbeta summed over the groups in order (accumulate != 0: added to what the destinations hold).  tile_stats, or
+ *     NULL for a reduction pass over (dy, x): the per-tile sum(dz), sum(dz * (y - beta)) the epilogue of the data-gradient kernel that produced
+ *     dy wrote (kpx_conv3x3_wino(43)(b)_f32 with tile_stats + bn_y + bn_beta, kpx_conv3x3_bf16s_bnbwd), tiles_per_group tiles per group; act
+ *     must then be KPX_ACT_RELU and dy already zero wherever the output is, which those kernels guarantee.
+ *   scratch: kpx_bn_train_scratch_bytes(C, groups) bytes.
+ *   _bf16: x bf16; y bf16 (y_f32 = 0) or fp32 (y_f32 = 1: the tensor the fp32 key-point head reads); dy bf16 (dy_f32 = 0) or fp32; dx bf16.
+ *     C and the pixel strides (elements) multiples of 8, pointers 16-byte aligned.  Statistics and parameter gradients stay fp32. */
+size_t kpx_bn_train_scratch_bytes(int C, int groups);
+int kpx_bn_train_fwd_f32(const float* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
+                         float eps, const float* gamma, const float* beta, float* mean, float* invstd,
+                         float* moving_mean, float* moving_var, float decay, float* y, int ldy, int act, void* scratch, void* stream);
+int kpx_bn_train_bwd_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int groups, int C,
+                         const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
+                         float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
+                         const float* tile_stats, size_t tiles_per_group, void* scratch, void* stream);
+int kpx_bn_train_fwd_bf16(const void* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
+                          float eps, const float* gamma, const float* beta, float* mean, float* invstd,
+                          float* moving_mean, float* moving_var, float decay, void* y, int ldy, int y_f32, int act, void* scratch, void* stream);
+int kpx_bn_train_bwd_bf16(const void* dy, int lddy, int dy_f32, const void* x, int ldx, size_t P, int groups, int C,
+                          const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
+                          void* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
+                          const float* tile_stats, size_t tiles_per_group, void* scratch, void* stream);
+/* Inference mode (is_training = False: models/keypoint_model.py:48-50, final_model.py:62,68,95), from the moving statistics:
+ *   kpx_bn_invstd_f32: invstd[c] = rsqrt(moving_var[c] + eps);
+ *   kpx_bn_apply_f32: y = act((x - mean) * invstd * gamma + beta) over P pixels;
+ *   kpx_bn_fold_conv_f32: the batch norm folded into the convolution in front of it: w_out[r][c] = w[r][c] * s[c], b_out[c] = (bias[c] -
+ *     moving_mean[c]) * s[c] + beta[c] with s = gamma * rsqrt(moving_var + eps); w = [rows = kh*kw*Cin][C] (HWIO), bias may be NULL.
+ *     conv(x, w_out) + b_out followed by ReLU then equals relu(batch_norm(conv(x, w) + bias)) up to fp32 rounding, without the pass over
+ *     the activation. */
+int kpx_bn_invstd_f32(const float* var, int C, float eps, float* invstd, void* stream);
+int kpx_bn_apply_f32(const float* x, size_t P, int C, int ldx, const float* mean, const float* invstd,
+                     const float* gamma, const float* beta, float* y, int ldy, int act, void* stream);
+int kpx_bn_fold_conv_f32(const float* w, const float* bias, size_t rows, int C, const float* gamma, const float* beta,
+                         const float* moving_mean, const float* moving_var, float eps, float* w_out, float* b_out, void* stream);
+
 /* Fused Winograd F(4x4,3x3): the same contract as kpx_conv3x3_wino_f32 (forward, or data gradient with dgrad-transformed filters) with
  * 36 instead of 144 multiplies per 4x4 outputs; fp32 error ~2-3e-6 rel-L2 (F(2x2,3x3): ~4e-7).  Eligible when H % 16 == 0, W % 32 == 0,
  * K >= 16, Nn > 32 and the usual 16-B alignment; `u` comes from kpx_wino43_filter_transform(_batch)_f32 (kpx_wino43_u_bytes bytes,
@@ -173,8 +211,8 @@ int kpx_wino43_filter_transform_f32(const float* w_hwio, int Cin, int Cout, int 
 int kpx_wino43_filter_transform_batch_f32(const void* descs_dev, int n, void* stream);
 /* Epilogue options, the same for kpx_conv3x3_wino43_f32 and kpx_conv3x3_wino43b_f32 (all NULL: the plain convolution):
  *   tile_stats alone: the batch-norm statistics of the output, as kpx_conv3x3_wino_f32's but per 4 x 16-pixel strip: tile_stats[strip][2][Nn],
- *     kpx_conv3x3_wino43_stats_tiles(N, H, W) strips (0 for packed 16 x 16 images: no statistics there), consumed by
- *     kpx_bn_stats_from_tiles_f32 (tile_pixels 64);
+ *     kpx_conv3x3_wino43_stats_tiles(N, H, W) strips (0 for packed 16 x 16 images: no statistics there), taken by kpx_bn_train_fwd_f32 as
+ *     tile_stats;
  *   tile_stats + bn_y + bn_beta: data gradient towards a ReLU'd batch norm's output (the tensor bn_y this convolution read in the forward
  *     pass): out = dgrad * [bn_y > 0] and tile_stats[strip][2][Nn] = per strip sum(out), sum(out * (bn_y - beta)) -- kpx_bn_train_bwd_f32
  *     takes them instead of its own reduction pass (tf.gradients of tf.contrib.layers.batch_norm + tf.nn.relu, models/networks/layers.py:13-14).
@@ -208,52 +246,6 @@ int kpx_conv3x3_wino43b_f32(const float* in, int N, int H, int W, int K, int ldi
 int kpx_conv3x3_c16_eligible(int N, int H, int W, int K, int Nn, int ldin, int ldout, const void* in_ptr);
 int kpx_conv3x3_c16_f32(const float* in, int N, int H, int W, int K, int ldin, const float* w_hwio, int dgrad, const float* bias,
                         float* out, int ldout, int act, float* tile_stats, void* stream);
-/* kpx_bn_bwd_f32 (act must be KPX_ACT_RELU) with the channel reductions taken from those tile sums over tiles [tile0, tile0+ntiles). */
-int kpx_bn_bwd_from_tiles_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int C,
-                              const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
-                              float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
-                              const float* tile_stats, size_t tile0, size_t ntiles, void* scratch, void* stream);
-/* kpx_bn_stats_f32 from per-tile sums (tile_stats[tile][2][C], `tile_pixels` pixels per tile) over tiles [tile0, tile0 + ntiles):
- * fp64 fixed-order reduction; same outputs and moving-statistics rule. */
-int kpx_bn_stats_from_tiles_f32(const float* tile_stats, size_t tile0, size_t ntiles, int tile_pixels, int C, float eps,
-                                float* mean, float* invstd, float* var_biased,
-                                float* moving_mean, float* moving_var, float decay, void* stream);
-/* invstd[c] = rsqrt(moving_var[c]+eps) for inference-mode BN (models/keypoint_model.py:48-50). */
-/* Train-mode batch norm of `groups` weight-sharing calls batched along N (the two pose_encoder calls of a pair, reference
- * detector_translator_model.py:166-167, each with batch statistics of its own; layers.py:13-14): x = [groups][P pixels][C], one launch per
- * phase for all groups.  Forward: statistics per group -- from tile_stats (per-tile sums of a convolution epilogue, tiles_per_group tiles per
- * group, or NULL: a reduction pass over x) -- mean / invstd [groups][C] (outputs, kept for the backward), moving statistics updated once per
- * group IN ORDER, then y = act(gamma * (x - mean) * invstd + beta).  Backward: dx, and dgamma / dbeta summed over the groups in order
- * (accumulate != 0: added to what the destinations hold).  Bitwise identical to `groups` calls of kpx_bn_stats(_from_tiles)_f32 +
- * kpx_bn_apply_f32 / of kpx_bn_bwd_f32.  scratch: kpx_bn_train_scratch_bytes(C, groups) bytes. */
-size_t kpx_bn_train_scratch_bytes(int C, int groups);
-int kpx_bn_train_fwd_f32(const float* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
-                         float eps, const float* gamma, const float* beta, float* mean, float* invstd,
-                         float* moving_mean, float* moving_var, float decay, float* y, int ldy, int act, void* scratch, void* stream);
-int kpx_bn_train_bwd_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int groups, int C,
-                         const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
-                         float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
-                         const float* tile_stats, size_t tiles_per_group, void* scratch, void* stream);
-/* (backward tile_stats, or NULL: per-tile sum(dz), sum(dz * (y - beta)) written by the epilogue of the data-gradient kernel that produced dy --
- *  kpx_conv3x3_wino43(b)_f32 / kpx_conv3x3_wino_f32 with tile_stats + bn_y + bn_beta, tiles_per_group tiles per group -- instead of the
- *  reduction pass over (dy, x); dy must then already be zero wherever the batch norm's ReLU output is, which those kernels guarantee.) */
-/* Inference-mode batch norm folded into the convolution in front of it (is_training = False: reference keypoint_model.py:48-50,
- * final_model.py:62,68,95): w_out[r][c] = w[r][c] * s[c], b_out[c] = (bias[c] - moving_mean[c]) * s[c] + beta[c] with
- * s = gamma * rsqrt(moving_var + eps); w = [rows = kh*kw*Cin][C] (HWIO), bias may be NULL.  conv(x, w_out) + b_out followed by ReLU then
- * equals relu(batch_norm(conv(x, w) + bias)) up to fp32 rounding, without the pass over the activation. */
-int kpx_bn_fold_conv_f32(const float* w, const float* bias, size_t rows, int C, const float* gamma, const float* beta,
-                         const float* moving_mean, const float* moving_var, float eps, float* w_out, float* b_out, void* stream);
-int kpx_bn_invstd_f32(const float* var, int C, float eps, float* invstd, void* stream);
-/* step 2: y = act((x-mean)*invstd*gamma + beta), act in {NONE, RELU} (tf.nn.relu networks/__init__.py:12...). */
-int kpx_bn_apply_f32(const float* x, size_t P, int C, int ldx, const float* mean, const float* invstd,
-                     const float* gamma, const float* beta, float* y, int ldy, int act, void* stream);
-/* backward of y = act(BN_train(x)): dx, dgamma, dbeta from dy (gradient wrt y) and the saved x, mean, invstd.
- * accumulate != 0: dgamma / dbeta are ADDED to (a second call of a weight-sharing batch norm with its own statistics,
- * models/detector_translator_model.py:166-167). */
-int kpx_bn_bwd_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int C,
-                   const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
-                   float* dx, int lddx, float* dgamma, float* dbeta, int accumulate, void* scratch, void* stream);
-
 /* ---- tf.image.resize_images(x, 2x) legacy bilinear (models/networks/__init__.py:63,98). */
 int kpx_resize2x_fwd_f32(const float* x, int N, int H, int W, int C, int ldx, float* y, int ldy, void* stream);
 int kpx_resize2x_bwd_f32(const float* dy, int N, int H, int W, int C, int lddy, float* dx, int lddx, void* stream);
@@ -430,15 +422,6 @@ int kpx_conv3x3_wgrad_bf16(const void* x, int N, int H, int W, int Cin, int ldx,
  * kind 3 = f32 -> bf16 into a contiguous 8-channel tensor (lddst = 8, C <= 8) whose channels C .. 7 are written as zeros. */
 int kpx_cast_channels(const void* src, int ldsrc, void* dst, int lddst, size_t P, int C, int kind, void* stream);
 int kpx_chan_sum_bf16(const void* x, size_t P, int C, int ldx, float* sum_out, void* scratch, void* stream);
-/* layers.batch_norm, train mode, all weight-sharing groups in one launch per phase (kpx_bn_train_fwd_f32 / _bwd_f32): x bf16, y bf16
- * (y_f32 = 0) or fp32 (y_f32 = 1: the tensor the fp32 key-point head reads); backward: dy bf16 (dy_f32 = 0) or fp32, dx bf16. */
-int kpx_bn_train_fwd_bf16(const void* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
-                          float eps, const float* gamma, const float* beta, float* mean, float* invstd,
-                          float* moving_mean, float* moving_var, float decay, void* y, int ldy, int y_f32, int act, void* scratch, void* stream);
-int kpx_bn_train_bwd_bf16(const void* dy, int lddy, int dy_f32, const void* x, int ldx, size_t P, int groups, int C,
-                          const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
-                          void* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
-                          const float* tile_stats, size_t tiles_per_group, void* scratch, void* stream);
 int kpx_act_bwd_bf16(const void* dy, const void* y, void* dz, size_t n, int act, void* stream);
 int kpx_resize2x_fwd_bf16(const void* x, int N, int H, int W, int C, int ldx, void* y, int ldy, void* stream);
 int kpx_resize2x_bwd_bf16(const void* dy, int N, int H, int W, int C, int lddy, void* dx, int lddx, void* stream);

@@ -35,7 +35,12 @@ def test_library_exports_every_declared_symbol():
 def test_bad_arguments_are_rejected_without_a_gpu():
     from kpx_amd._lib import lib
     assert lib.kpx_conv2d_fwd_f32(None, 1, 8, 8, 4, 4, None, 3, 3, None, None, 8, 8, 4, 4, 1, 1, 1, 0, 0, None, 0, None) == -1
-    assert lib.kpx_bn_stats_f32(None, 10, 4, 4, 1e-5, None, None, None, None, None, 0.999, None, None) == -1
+    # the batch-norm train entries (groups = 1: the single call) refuse a null x / dy before any device call
+    a = 1 << 20                                                 # an aligned fake address
+    assert lib.kpx_bn_train_fwd_f32(None, 64, 1, 8, 8, None, 0, 1e-5, a, a, a, a, None, None, 0.999, a, 8, 1, a, None) == -1
+    assert lib.kpx_bn_train_fwd_bf16(None, 64, 1, 8, 8, None, 0, 1e-5, a, a, a, a, None, None, 0.999, a, 8, 0, 1, a, None) == -1
+    assert lib.kpx_bn_train_bwd_f32(None, 8, a, 8, 64, 1, 8, a, a, a, a, 1, a, 8, a, a, 0, None, 0, a, None) == -1
+    assert lib.kpx_bn_train_bwd_bf16(None, 8, 0, a, 8, 64, 1, 8, a, a, a, a, 1, a, 8, a, a, 0, None, 0, a, None) == -1
     assert lib.kpx_conv2d_wgrad_workspace_bytes(32, 128, 128, 64, 64, 3, 3) > 0
     assert lib.kpx_conv2d_wgrad_workspace_bytes(1, 4, 4, 1024, 2048, 4, 4) == 0
     # per-call arithmetic selector and the activation-backward factor: range-checked before anything touches a device
@@ -43,7 +48,6 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.kpx_conv2d_dgrad_act_f32(1, 1, 8, 8, 4, 4, 1, 3, 3, 1, 8, 8, 4, 4, 1, 1, 1, 0, None, 4, 2, None, 0, None) == -1   # y_in = NULL
     assert lib.kpx_conv2d_dgrad_act_f32(1, 1, 8, 8, 4, 4, 1, 3, 3, 1, 8, 8, 4, 4, 1, 1, 1, 0, 1, 4, 3, None, 0, None) == -1      # tanh: not an epilogue factor
     # the two F(4x4,3x3) entries share their arguments and option rules: both refuse the same mixes before any device call
-    a = 1 << 20                                                 # an aligned fake address
     for entry in (lib.kpx_conv3x3_wino43_f32, lib.kpx_conv3x3_wino43b_f32):
         def f43(n=2, h=32, w=32, nn=64, bias=None, act=0, mask=None, pool=None, stats=None, bn_y=None, bn_beta=None):
             return entry(a, n, h, w, 64, 64, a, bias, a, nn, nn, act, mask, nn, pool, nn, stats, bn_y, nn, bn_beta, None)

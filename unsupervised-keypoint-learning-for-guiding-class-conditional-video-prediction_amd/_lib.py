@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/kpx.h one to one (tests/test_abi.py checks header vs this table)
-ABI_VERSION = 5        # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
+ABI_VERSION = 6        # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
 SIGNATURES = {
     'kpx_abi_version': (c_int, []),
     'kpx_reload_env': (c_int, []),
@@ -63,8 +63,6 @@ SIGNATURES = {
     'kpx_conv3x3_wino43b_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, c_int, P, P]),
     'kpx_conv3x3_wino43_stats_tiles': (c_size_t, [c_int, c_int, c_int]),
     'kpx_conv3x3_wino_stats_tiles': (c_size_t, [c_int, c_int, c_int]),
-    'kpx_bn_bwd_from_tiles_f32': (c_int, [P, c_int, P, c_int, c_size_t, c_int, P, P, P, P, c_int, P, c_int, P, P, c_int, P, c_size_t, c_size_t, P, P]),
-    'kpx_bn_stats_from_tiles_f32': (c_int, [P, c_size_t, c_size_t, c_int, c_int, c_float, P, P, P, P, P, c_float, P]),
     'kpx_conv3x3_bf16s_weights_bytes': (c_size_t, [c_int, c_int]),
     'kpx_conv3x3_bf16s_eligible': (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'kpx_conv3x3_bf16s_stats_tiles': (c_int, [c_int, c_int, c_int, c_int, c_int]),
@@ -94,14 +92,12 @@ SIGNATURES = {
     'kpx_act_bwd_f32': (c_int, [P, P, P, c_size_t, c_int, P]),
     'kpx_chan_reduce_scratch_bytes': (c_size_t, [c_int]),
     'kpx_chan_sum_f32': (c_int, [P, c_size_t, c_int, c_int, P, P, P]),
-    'kpx_bn_stats_f32': (c_int, [P, c_size_t, c_int, c_int, c_float, P, P, P, P, P, c_float, P, P]),
     'kpx_bn_invstd_f32': (c_int, [P, c_int, c_float, P, P]),
     'kpx_bn_fold_conv_f32': (c_int, [P, P, c_size_t, c_int, P, P, P, P, c_float, P, P, P]),
     'kpx_bn_train_scratch_bytes': (c_size_t, [c_int, c_int]),
     'kpx_bn_train_fwd_f32': (c_int, [P, c_size_t, c_int, c_int, c_int, P, c_size_t, c_float, P, P, P, P, P, P, c_float, P, c_int, c_int, P, P]),
     'kpx_bn_train_bwd_f32': (c_int, [P, c_int, P, c_int, c_size_t, c_int, c_int, P, P, P, P, c_int, P, c_int, P, P, c_int, P, c_size_t, P, P]),
     'kpx_bn_apply_f32': (c_int, [P, c_size_t, c_int, c_int, P, P, P, P, P, c_int, c_int, P]),
-    'kpx_bn_bwd_f32': (c_int, [P, c_int, P, c_int, c_size_t, c_int, P, P, P, P, c_int, P, c_int, P, P, c_int, P, P]),
     'kpx_resize2x_fwd_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
     'kpx_resize2x_bwd_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
     'kpx_copy_channels_f32': (c_int, [P, c_int, P, c_int, c_size_t, c_int, P]),

@@ -561,7 +561,7 @@ extern "C" int kpx_conv3x3_wino43_f32(const float* in, int N, int H, int W, int 
     return w43_launch(in, N, H, W, K, ldin, U, bias, out, Nn, ldout, act, tile_stats, stream, bnbwd ? bn_y : mask_y, bnbwd ? ld_bn_y : ld_mask,
                       pool_y, ld_pool, bn_beta);
 }
-// 4 x 16-pixel strips per tensor: the unit of the statistics slab (kpx_bn_stats_from_tiles_f32 with tile_pixels = 64)
+// 4 x 16-pixel strips per tensor: the unit of the statistics slab (the tile_stats of kpx_bn_train_fwd_f32, 64 pixels per tile)
 extern "C" size_t kpx_conv3x3_wino43_stats_tiles(int N, int H, int W) {
     return (H % 16 || W % 32 || N <= 0) ? 0 : (size_t)N * (H / 16) * (W / 32) * 8;          // (0: no statistics for packed 16 x 16 images)
 }

@@ -187,17 +187,21 @@ __global__ __launch_bounds__(256) void chan_reduce_kernel(const RedArgs a) {
     }
 }
 
-static int launch_chan_reduce(int mode, RedArgs a, int* nb_out, hipStream_t s, int groups = 1) {
-    const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (((uintptr_t)a.x) & 15) == 0 &&
-                     (mode != 2 || ((a.lddy % 4 == 0) && (((uintptr_t)a.dy) & 15) == 0));
-    const int G = vec ? a.C / 4 : a.C;
-    const int Gb = G < 256 ? G : 256;
-    const int PPB = 256 / Gb;
-    size_t nb = a.P / ((size_t)PPB * 8);
+// Grid of a reduction launch over G channel groups: 256 threads = Gb groups x PPB pixel rows, blocks along the pixels for about eight
+// pixels per thread, at most KPX_RED_BLOCKS (the partials the scratch holds); blockIdx.y slices G beyond 256, blockIdx.z = group
+static dim3 chan_reduce_grid(size_t P, int G, int groups, int* nb_out) {
+    const int Gb = G < 256 ? G : 256, PPB = 256 / Gb;
+    size_t nb = P / ((size_t)PPB * 8);
     if (nb < 1) nb = 1;
     if (nb > KPX_RED_BLOCKS) nb = KPX_RED_BLOCKS;
     *nb_out = (int)nb;
-    const dim3 grid((unsigned)nb, (unsigned)((G + Gb - 1) / Gb), (unsigned)groups), block(256);
+    return dim3((unsigned)nb, (unsigned)((G + Gb - 1) / Gb), (unsigned)groups);
+}
+
+static int launch_chan_reduce(int mode, RedArgs a, int* nb_out, hipStream_t s, int groups = 1) {
+    const bool vec = (a.C % 4 == 0) && (a.ldx % 4 == 0) && (((uintptr_t)a.x) & 15) == 0 &&
+                     (mode != 2 || ((a.lddy % 4 == 0) && (((uintptr_t)a.dy) & 15) == 0));
+    const dim3 grid = chan_reduce_grid(a.P, vec ? a.C / 4 : a.C, groups, nb_out), block(256);
 #define KPX_RED(M) \
     do { if (vec) hipLaunchKernelGGL((chan_reduce_kernel<M, true>), grid, block, 0, s, a); \
          else hipLaunchKernelGGL((chan_reduce_kernel<M, false>), grid, block, 0, s, a); } while (0)
@@ -206,35 +210,48 @@ static int launch_chan_reduce(int mode, RedArgs a, int* nb_out, hipStream_t s, i
     return kpx_launch_status();
 }
 
-// partial sums [KPX_RED_BLOCKS][2][C] doubles, then 2*C floats where bn_bwd parks the finished channel sums
+// partial sums [KPX_RED_BLOCKS][2][C] doubles, then 2*C floats that no entry uses any more (the size is kept as callers know it)
 extern "C" size_t kpx_chan_reduce_scratch_bytes(int C) {
     const size_t c = (size_t)(C > 0 ? C : 1);
     return (size_t)KPX_RED_BLOCKS * 2 * c * sizeof(double) + ((2 * c * sizeof(float) + 15) & ~(size_t)15);
 }
 
-// 256 threads per channel: the (up to 1024) block partials are summed in a fixed order -- thread t takes partials t, t+256, ..;
-// shuffle tree per wavefront, then the four wave sums in LDS order -- so the result does not depend on timing.  (One wavefront per
-// channel took 7-10 us of dependent-load latency per launch, 120 launches per step.)
-__device__ __forceinline__ void kpx_sum_partials(const double* part, int nb, int C, int c, double& s, double& q) {
+// Fixed-order channel sums, so the result does not depend on timing.  The items of channel c are rows of a [n][2][C] slab: the block partials
+// of a reduction kernel (part, doubles, nb items) or the per-tile sums a convolution epilogue wrote (ts, floats, items [t0, t0 + ntiles)).
+// A 256-thread segment of the workgroup adds one slab: thread t takes items t, t + 256, ..; shuffle tree per wavefront; the four wave sums
+// go to the segment's LDS slot w, and chan_sum4 adds them as (w0 + w1) + (w2 + w3).  Every thread of the workgroup calls chan_wave_sums
+// (on = false in a segment without a slab: zeros): it holds the barriers, so the slots are ready when it returns and free for the next call.
+// (One wavefront per channel took 7-10 us of dependent-load latency per launch, 120 launches per step.)
+__device__ __forceinline__ void chan_wave_sums(const double* part, int nb, const float* ts, size_t t0, size_t ntiles, bool on, int C, int c,
+                                               double (&w)[2][4]) {
+    const int t = threadIdx.x & 255;
     double a0 = 0.0, a1 = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) {
-        a0 += part[((size_t)b * 2) * C + c];
-        a1 += part[((size_t)b * 2 + 1) * C + c];
+    if (on) {
+        if (ts) {
+            for (size_t b = t; b < ntiles; b += 256) {
+                a0 += (double)ts[((t0 + b) * 2) * C + c];
+                a1 += (double)ts[((t0 + b) * 2 + 1) * C + c];
+            }
+        } else {
+            for (int b = t; b < nb; b += 256) {
+                a0 += part[((size_t)b * 2) * C + c];
+                a1 += part[((size_t)b * 2 + 1) * C + c];
+            }
+        }
     }
     a0 = kpx_wave_sum_d(a0);
     a1 = kpx_wave_sum_d(a1);
-    __shared__ double sm[2][4];
-    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = a0; sm[1][threadIdx.x >> 6] = a1; }
+    __syncthreads();                                       // (the slot may still be read from the previous call)
+    if ((t & 63) == 0) { w[0][t >> 6] = a0; w[1][t >> 6] = a1; }
     __syncthreads();
-    s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
-    q = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
 }
+__device__ __forceinline__ double chan_sum4(const double (&w)[4]) { return (w[0] + w[1]) + (w[2] + w[3]); }
 
 __global__ __launch_bounds__(256) void chan_sum_finalize_kernel(const double* part, int nb, int C, float* out) {
     const int c = blockIdx.x;
-    double s, q;
-    kpx_sum_partials(part, nb, C, c, s, q);
-    if (threadIdx.x == 0) out[c] = (float)s;
+    __shared__ double sm[2][4];
+    chan_wave_sums(part, nb, nullptr, 0, 0, true, C, c, sm);
+    if (threadIdx.x == 0) out[c] = (float)chan_sum4(sm[0]);
 }
 extern "C" int kpx_chan_sum_f32(const float* x, size_t P, int C, int ldx, float* sum_out, void* scratch, void* stream) {
     if (!x || !sum_out || !scratch || C <= 0 || ldx < C || P == 0) return KPX_EINVAL;
@@ -246,102 +263,6 @@ extern "C" int kpx_chan_sum_f32(const float* x, size_t P, int C, int ldx, float*
 }
 
 // ------------------------------------------------------------------------------------------ batch norm
-__global__ __launch_bounds__(256) void bn_stats_finalize_kernel(const double* part, int nb, int C, double count, float eps,
-                                                               float* mean, float* invstd, float* var_biased,
-                                                               float* mm, float* mv, float decay) {
-    const int c = blockIdx.x;
-    double s, q;
-    kpx_sum_partials(part, nb, C, c, s, q);
-    if (threadIdx.x != 0) return;
-    const double m = s / count;
-    double v = q / count - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mf = (float)m, vf = (float)v;
-    mean[c] = mf;
-    if (var_biased) var_biased[c] = vf;
-    invstd[c] = 1.0f / sqrtf(vf + eps);
-    if (mm && mv) {   // TF fused batch norm: moving -= (moving - batch) * (1 - decay), variance Bessel-corrected
-        const float one_minus = 1.0f - decay;
-        const float unb = (float)(v * (count / (count > 1.0 ? count - 1.0 : 1.0)));
-        mm[c] = mm[c] - (mm[c] - mf) * one_minus;
-        mv[c] = mv[c] - (mv[c] - unb) * one_minus;
-    }
-}
-extern "C" int kpx_bn_stats_f32(const float* x, size_t P, int C, int ldx, float eps,
-                                float* mean, float* invstd, float* var_biased,
-                                float* moving_mean, float* moving_var, float decay, void* scratch, void* stream) {
-    if (!x || !mean || !invstd || !scratch || C <= 0 || ldx < C || P == 0) return KPX_EINVAL;
-    RedArgs a{}; a.x = x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch;
-    int nb; int rc = launch_chan_reduce(1, a, &nb, kpx_stream(stream));
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(C), dim3(256), 0, kpx_stream(stream), (const double*)scratch, nb, C,
-                       (double)P, eps, mean, invstd, var_biased, moving_mean, moving_var, decay);
-    return kpx_launch_status();
-}
-
-// Batch-norm backward sums from per-tile sums written by the epilogue of the data-gradient kernel that PRODUCED dy
-// (kpx_conv3x3_wino_f32 with tile_stats + bn_y): tile_stats[tile][2][C] = sum(dz), sum(dz * (y - beta)); x_hat = (y - beta) / gamma wherever dz != 0.
-__global__ __launch_bounds__(256) void bn_bwd_from_tiles_kernel(const float* __restrict__ ts, size_t tile0, size_t ntiles, int C,
-                                                               const float* __restrict__ gamma, float* dgamma, float* dbeta, float* sums, int accumulate) {
-    const int c = blockIdx.x;
-    double a0 = 0.0, a1 = 0.0;
-    for (size_t b = threadIdx.x; b < ntiles; b += 256) {
-        a0 += (double)ts[((tile0 + b) * 2) * C + c];
-        a1 += (double)ts[((tile0 + b) * 2 + 1) * C + c];
-    }
-    a0 = kpx_wave_sum_d(a0);
-    a1 = kpx_wave_sum_d(a1);
-    __shared__ double sm[2][4];
-    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = a0; sm[1][threadIdx.x >> 6] = a1; }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const double s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
-    const double ga = (double)gamma[c];
-    const double q = ga != 0.0 ? ((sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3])) / ga : 0.0;
-    if (accumulate) { dbeta[c] += (float)s; dgamma[c] += (float)q; } else { dbeta[c] = (float)s; dgamma[c] = (float)q; }
-    sums[c] = (float)s; sums[C + c] = (float)q;
-}
-
-// Batch statistics from the per-tile sums a convolution epilogue wrote (kpx_conv3x3_wino_f32 with tile_stats): tile_stats[tile][2][C] floats.
-// One workgroup per channel adds the tiles [tile0, tile0 + ntiles) in a fixed order in fp64 (same tree as kpx_sum_partials).
-__global__ __launch_bounds__(256) void bn_stats_from_tiles_kernel(const float* __restrict__ ts, size_t tile0, size_t ntiles, int C, double count, float eps,
-                                                                 float* mean, float* invstd, float* var_biased, float* mm, float* mv, float decay) {
-    const int c = blockIdx.x;
-    double a0 = 0.0, a1 = 0.0;
-    for (size_t b = threadIdx.x; b < ntiles; b += 256) {
-        a0 += (double)ts[((tile0 + b) * 2) * C + c];
-        a1 += (double)ts[((tile0 + b) * 2 + 1) * C + c];
-    }
-    a0 = kpx_wave_sum_d(a0);
-    a1 = kpx_wave_sum_d(a1);
-    __shared__ double sm[2][4];
-    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = a0; sm[1][threadIdx.x >> 6] = a1; }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    const double s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]), q = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
-    const double m = s / count;
-    double v = q / count - m * m;
-    if (v < 0.0) v = 0.0;
-    const float mf = (float)m, vf = (float)v;
-    mean[c] = mf;
-    if (var_biased) var_biased[c] = vf;
-    invstd[c] = 1.0f / sqrtf(vf + eps);
-    if (mm && mv) {
-        const float one_minus = 1.0f - decay;
-        const float unb = (float)(v * (count / (count > 1.0 ? count - 1.0 : 1.0)));
-        mm[c] = mm[c] - (mm[c] - mf) * one_minus;
-        mv[c] = mv[c] - (mv[c] - unb) * one_minus;
-    }
-}
-extern "C" int kpx_bn_stats_from_tiles_f32(const float* tile_stats, size_t tile0, size_t ntiles, int tile_pixels, int C, float eps,
-                                           float* mean, float* invstd, float* var_biased,
-                                           float* moving_mean, float* moving_var, float decay, void* stream) {
-    if (!tile_stats || !mean || !invstd || C <= 0 || ntiles == 0 || tile_pixels <= 0) return KPX_EINVAL;
-    hipLaunchKernelGGL(bn_stats_from_tiles_kernel, dim3(C), dim3(256), 0, kpx_stream(stream), tile_stats, tile0, ntiles, C,
-                       (double)ntiles * (double)tile_pixels, eps, mean, invstd, var_biased, moving_mean, moving_var, decay);
-    return kpx_launch_status();
-}
-
 __global__ void bn_invstd_kernel(const float* var, int C, float eps, float* invstd) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) invstd[c] = 1.0f / sqrtf(var[c] + eps);
@@ -352,32 +273,34 @@ extern "C" int kpx_bn_invstd_f32(const float* var, int C, float eps, float* invs
     return kpx_launch_status();
 }
 
-template <bool VEC>
+// Scalar forms of the two streaming passes, for rows the strip kernels below cannot take (C % 4 != 0 or rows not 16-B aligned).
+// blockIdx.z = group of a batched launch, as in the strip kernels.
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* x, size_t P, int C, int ldx, const float* mean, const float* invstd,
                                                        const float* gamma, const float* beta, float* y, int ldy, int act) {
-    constexpr int W = VEC ? 4 : 1;
-    const int G = C / W;
-    const size_t total = P * (size_t)G;
+    x += (size_t)blockIdx.z * P * ldx; y += (size_t)blockIdx.z * P * ldy; mean += blockIdx.z * C; invstd += blockIdx.z * C;
+    const size_t total = P * (size_t)C;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t p = i / G;
-        const int c0 = (int)(i - p * G) * W;
-        float v[W];
-        if (VEC) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(x + p * ldx + c0);
-#pragma unroll
-            for (int j = 0; j < W; ++j) v[j] = xv[j];
-        } else v[0] = x[p * ldx + c0];
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const float xh = (v[j] - mean[c0 + j]) * invstd[c0 + j];
-            float r = fmaf(xh, gamma[c0 + j], beta[c0 + j]);
-            if (act == KPX_ACT_RELU) r = fmaxf(r, 0.f);
-            v[j] = r;
-        }
-        if (VEC) {
-            f32x4 o = {v[0], v[W > 1 ? 1 : 0], v[W > 2 ? 2 : 0], v[W > 3 ? 3 : 0]};
-            *reinterpret_cast<f32x4*>(y + p * ldy + c0) = o;
-        } else y[p * ldy + c0] = v[0];
+        const size_t p = i / C;
+        const int c = (int)(i - p * C);
+        const float xh = (x[p * ldx + c] - mean[c]) * invstd[c];
+        float r = fmaf(xh, gamma[c], beta[c]);
+        if (act == KPX_ACT_RELU) r = fmaxf(r, 0.f);
+        y[p * ldy + c] = r;
+    }
+}
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int lddy, const float* x, int ldx, size_t P, int C,
+                                                           const float* mean, const float* invstd, const float* gamma, const float* beta,
+                                                           int act, const float* sums, float inv_count, float* dx, int lddx) {
+    dy += (size_t)blockIdx.z * P * lddy; x += (size_t)blockIdx.z * P * ldx; dx += (size_t)blockIdx.z * P * lddx;
+    mean += blockIdx.z * C; invstd += blockIdx.z * C; sums += blockIdx.z * 2 * C;
+    const size_t total = P * (size_t)C;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t p = i / C;
+        const int c = (int)(i - p * C);
+        const float xh = (x[p * ldx + c] - mean[c]) * invstd[c];
+        const float yv = fmaf(xh, gamma[c], beta[c]);
+        const float dz = (act == KPX_ACT_RELU && !(yv > 0.f)) ? 0.f : dy[p * lddy + c];
+        dx[p * lddx + c] = gamma[c] * invstd[c] * (dz - sums[c] * inv_count - xh * (sums[C + c] * inv_count));
     }
 }
 // Strip mapping for the 16-B-vector case: a thread keeps ONE channel group (4 channels) for its whole life, so the per-channel
@@ -454,8 +377,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_strip_kernel(const float* __
         }
     }
 }
-static inline dim3 strip_grid(size_t P, int C, int groups = 1) {
-    const int G = C >> 2, Gb = G < 256 ? G : 256, PPB = 256 / Gb;
+// Grid of the strip kernels (fp32: W = 4 channels per thread, bf16: W = 8): four pixels per thread and trip, blockIdx.z = group
+static inline dim3 strip_grid(size_t P, int C, int W, int groups) {
+    const int G = C / W, Gb = G < 256 ? G : 256, PPB = 256 / Gb;
     size_t nb = (P + (size_t)PPB * 4 - 1) / ((size_t)PPB * 4);
     if (nb < 1) nb = 1;
     if (nb > KPX_MAX_BLOCKS) nb = KPX_MAX_BLOCKS;
@@ -467,92 +391,8 @@ extern "C" int kpx_bn_apply_f32(const float* x, size_t P, int C, int ldx, const 
     if (!x || !y || !mean || !invstd || !gamma || !beta || C <= 0 || ldx < C || ldy < C || act < 0 || act > 1) return KPX_EINVAL;
     if (P == 0) return 0;
     const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
-    if (vec) hipLaunchKernelGGL(bn_apply_strip_kernel, strip_grid(P, C), dim3(256), 0, kpx_stream(stream), x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
-    else hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(grid_for(P * C)), dim3(256), 0, kpx_stream(stream), x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
-    return kpx_launch_status();
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double* part, int nb, int C, float* dgamma, float* dbeta, float* sums, int accumulate) {
-    const int c = blockIdx.x;
-    double s, q;
-    kpx_sum_partials(part, nb, C, c, s, q);
-    if (threadIdx.x != 0) return;
-    if (accumulate) { dbeta[c] += (float)s; dgamma[c] += (float)q; } else { dbeta[c] = (float)s; dgamma[c] = (float)q; }
-    sums[c] = (float)s; sums[C + c] = (float)q;
-}
-template <bool VEC>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, int lddy, const float* x, int ldx, size_t P, int C,
-                                                           const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                                           int act, const float* sums, float inv_count, float* dx, int lddx) {
-    constexpr int W = VEC ? 4 : 1;
-    const int G = C / W;
-    const size_t total = P * (size_t)G;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const size_t p = i / G;
-        const int c0 = (int)(i - p * G) * W;
-        float xv[W], gv[W];
-        if (VEC) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(x + p * ldx + c0);
-            const f32x4 d = *reinterpret_cast<const f32x4*>(dy + p * lddy + c0);
-#pragma unroll
-            for (int j = 0; j < W; ++j) { xv[j] = a[j]; gv[j] = d[j]; }
-        } else { xv[0] = x[p * ldx + c0]; gv[0] = dy[p * lddy + c0]; }
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const int c = c0 + j;
-            const float xh = (xv[j] - mean[c]) * invstd[c];
-            const float yv = fmaf(xh, gamma[c], beta[c]);
-            const float dz = (act == KPX_ACT_RELU && !(yv > 0.f)) ? 0.f : gv[j];
-            xv[j] = gamma[c] * invstd[c] * (dz - sums[c] * inv_count - xh * (sums[C + c] * inv_count));
-        }
-        if (VEC) {
-            f32x4 o = {xv[0], xv[W > 1 ? 1 : 0], xv[W > 2 ? 2 : 0], xv[W > 3 ? 3 : 0]};
-            *reinterpret_cast<f32x4*>(dx + p * lddx + c0) = o;
-        } else dx[p * lddx + c0] = xv[0];
-    }
-}
-extern "C" int kpx_bn_bwd_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int C,
-                              const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
-                              float* dx, int lddx, float* dgamma, float* dbeta, int accumulate, void* scratch, void* stream) {
-    if (!dy || !x || !mean || !invstd || !gamma || !beta || !dx || !dgamma || !dbeta || !scratch || C <= 0 ||
-        ldx < C || lddy < C || lddx < C || act < 0 || act > 1 || P == 0)
-        return KPX_EINVAL;
-    hipStream_t s = kpx_stream(stream);
-    RedArgs a{}; a.x = x; a.ldx = ldx; a.dy = dy; a.lddy = lddy; a.P = P; a.C = C;
-    a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta; a.act = act; a.part = (double*)scratch;
-    int nb; int rc = launch_chan_reduce(2, a, &nb, s);
-    if (rc) return rc;
-    // the per-channel sums are parked (as floats) behind the partials in the scratch buffer
-    float* sums = reinterpret_cast<float*>((double*)scratch + (size_t)KPX_RED_BLOCKS * 2 * C);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, s, (const double*)scratch, nb, C, dgamma, dbeta, sums, accumulate);
-    rc = kpx_launch_status();
-    if (rc) return rc;
-    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) && (lddx % 4 == 0) &&
-                     ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0;
-    const float inv_count = (float)(1.0 / (double)P);
-    if (vec) hipLaunchKernelGGL(bn_bwd_apply_strip_kernel, strip_grid(P, C), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
-    else hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid_for(P * C)), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
-    return kpx_launch_status();
-}
-
-/* kpx_bn_bwd_f32 with the two channel reductions taken from per-tile sums (see bn_bwd_from_tiles_kernel) instead of a pass over (dy, x). */
-extern "C" int kpx_bn_bwd_from_tiles_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int C,
-                                         const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
-                                         float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
-                                         const float* tile_stats, size_t tile0, size_t ntiles, void* scratch, void* stream) {
-    if (!dy || !x || !mean || !invstd || !gamma || !beta || !dx || !dgamma || !dbeta || !scratch || !tile_stats || C <= 0 ||
-        ldx < C || lddy < C || lddx < C || act != KPX_ACT_RELU || P == 0 || ntiles == 0)
-        return KPX_EINVAL;
-    hipStream_t s = kpx_stream(stream);
-    float* sums = reinterpret_cast<float*>((double*)scratch + (size_t)KPX_RED_BLOCKS * 2 * C);
-    hipLaunchKernelGGL(bn_bwd_from_tiles_kernel, dim3(C), dim3(256), 0, s, tile_stats, tile0, ntiles, C, gamma, dgamma, dbeta, sums, accumulate);
-    int rc = kpx_launch_status();
-    if (rc) return rc;
-    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) && (lddx % 4 == 0) &&
-                     ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0;
-    const float inv_count = (float)(1.0 / (double)P);
-    if (vec) hipLaunchKernelGGL(bn_bwd_apply_strip_kernel, strip_grid(P, C), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
-    else hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid_for(P * C)), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
+    if (vec) hipLaunchKernelGGL(bn_apply_strip_kernel, strip_grid(P, C, 4, 1), dim3(256), 0, kpx_stream(stream), x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
+    else hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(P * C)), dim3(256), 0, kpx_stream(stream), x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
     return kpx_launch_status();
 }
 
@@ -580,52 +420,34 @@ extern "C" int kpx_bn_fold_conv_f32(const float* w, const float* bias, size_t ro
     return kpx_launch_status();
 }
 
-// ------------------------------------------------------------------------------------------ batched batch norm
+// ------------------------------------------------------------------------------------------ batch norm, train mode
 // The weight-sharing calls of the path (the two pose_encoder calls of one pair, reference detector_translator_model.py:166-167) run as ONE
 // batch with `groups` sets of statistics: consecutive groups of P pixels, mean / invstd [groups][C], moving statistics updated once per
 // group IN ORDER, gamma / beta gradients summed over the groups in order.  One launch per phase for all groups (blockIdx.z), one finalize
-// workgroup per channel looping over the groups -- the same partial sums in the same order as `groups` separate calls: same bits.
-// (up to four groups side by side: segment sg = threadIdx.x / 256 of a 256 x min(groups, 4)-thread workgroup sums group g0 + sg exactly as the
-//  single-group kernels do -- thread t of the segment takes partials t, t + 256, ..; shuffle tree per wavefront; the four wave sums in LDS
-//  order -- and thread 0 then finishes the groups IN ORDER: the moving statistics / gradient sums see the same numbers in the same order)
+// workgroup per channel looping over the groups.  A group's results do not depend on how many groups share the launch: groups = 1 is the
+// single call, and `groups` of those give the same bits.
+// (up to four groups side by side: segment sg = threadIdx.x / 256 of a 256 x min(groups, 4)-thread workgroup sums group g0 + sg by
+//  chan_wave_sums -- thread t of the segment takes items t, t + 256, ..; shuffle tree per wavefront; the four wave sums in LDS order -- and
+//  thread 0 then finishes the groups IN ORDER: the moving statistics / gradient sums see the same numbers in the same order)
 __global__ __launch_bounds__(1024) void bn_stats_finalize_groups_kernel(const double* part, size_t part_gstride, int nb, const float* __restrict__ ts, size_t tiles_per_group,
                                                                        int groups, int C, double count, float eps, float* mean, float* invstd,
                                                                        float* mm, float* mv, float decay) {
-    const int c = blockIdx.x, sg = threadIdx.x >> 8, t = threadIdx.x & 255, nseg = blockDim.x >> 8;
+    const int c = blockIdx.x, sg = threadIdx.x >> 8, nseg = blockDim.x >> 8;
     __shared__ double sm[4][2][4];
     for (int g0 = 0; g0 < groups; g0 += nseg) {
         const int g = g0 + sg;
-        double a0 = 0.0, a1 = 0.0;
-        if (g < groups) {
-            if (ts) {                                      // per-tile sums from a convolution epilogue (floats)
-                const size_t t0 = (size_t)g * tiles_per_group;
-                for (size_t b = t; b < tiles_per_group; b += 256) {
-                    a0 += (double)ts[((t0 + b) * 2) * C + c];
-                    a1 += (double)ts[((t0 + b) * 2 + 1) * C + c];
-                }
-            } else {                                       // block partials of chan_reduce_kernel<1> (doubles)
-                const double* gp = part + (size_t)g * part_gstride;
-                for (int b = t; b < nb; b += 256) {
-                    a0 += gp[((size_t)b * 2) * C + c];
-                    a1 += gp[((size_t)b * 2 + 1) * C + c];
-                }
-            }
-        }
-        a0 = kpx_wave_sum_d(a0);
-        a1 = kpx_wave_sum_d(a1);
-        __syncthreads();                                   // (sm is reused per batch of groups)
-        if ((t & 63) == 0) { sm[sg][0][t >> 6] = a0; sm[sg][1][t >> 6] = a1; }
-        __syncthreads();
+        // ts: per-tile sums from a convolution epilogue; else the block partials of the reduction pass
+        chan_wave_sums(part + (size_t)g * part_gstride, nb, ts, (size_t)g * tiles_per_group, tiles_per_group, g < groups, C, c, sm[sg]);
         if (threadIdx.x == 0) {
             for (int j = 0; j < nseg && g0 + j < groups; ++j) {
-                const double s = (sm[j][0][0] + sm[j][0][1]) + (sm[j][0][2] + sm[j][0][3]), q = (sm[j][1][0] + sm[j][1][1]) + (sm[j][1][2] + sm[j][1][3]);
+                const double s = chan_sum4(sm[j][0]), q = chan_sum4(sm[j][1]);
                 const double m = s / count;
                 double v = q / count - m * m;
                 if (v < 0.0) v = 0.0;
                 const float mf = (float)m, vf = (float)v;
                 mean[(g0 + j) * C + c] = mf;
                 invstd[(g0 + j) * C + c] = 1.0f / sqrtf(vf + eps);
-                if (mm && mv) {
+                if (mm && mv) {   // TF fused batch norm: moving -= (moving - batch) * (1 - decay), variance Bessel-corrected
                     const float one_minus = 1.0f - decay;
                     const float unb = (float)(v * (count / (count > 1.0 ? count - 1.0 : 1.0)));
                     mm[c] = mm[c] - (mm[c] - mf) * one_minus;
@@ -635,68 +457,20 @@ __global__ __launch_bounds__(1024) void bn_stats_finalize_groups_kernel(const do
         }
     }
 }
-extern "C" int kpx_bn_train_fwd_f32(const float* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
-                                    float eps, const float* gamma, const float* beta, float* mean, float* invstd,
-                                    float* moving_mean, float* moving_var, float decay, float* y, int ldy, int act, void* scratch, void* stream) {
-    if (!x || !y || !gamma || !beta || !mean || !invstd || !scratch || groups <= 0 || groups > 65535 || C <= 0 || ldx < C || ldy < C || act < 0 || act > 1 || P == 0)
-        return KPX_EINVAL;
-    hipStream_t s = kpx_stream(stream);
-    const size_t gstride = (size_t)KPX_RED_BLOCKS * 2 * C;
-    int nb = 0;
-    if (!tile_stats) {
-        RedArgs a{}; a.x = x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch; a.part_gstride = gstride;
-        int rc = launch_chan_reduce(1, a, &nb, s, groups);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(bn_stats_finalize_groups_kernel, dim3(C), dim3(256 * (groups < 4 ? groups : 4)), 0, s, (const double*)scratch, gstride, nb, tile_stats, tiles_per_group,
-                       groups, C, (double)P, eps, mean, invstd, moving_mean, moving_var, decay);
-    int rc = kpx_launch_status();
-    if (rc) return rc;
-    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
-    if (vec) {
-        hipLaunchKernelGGL(bn_apply_strip_kernel, strip_grid(P, C, groups), dim3(256), 0, s, x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
-        return kpx_launch_status();
-    }
-    for (int g = 0; g < groups; ++g) {
-        hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(grid_for(P * C)), dim3(256), 0, s, x + (size_t)g * P * ldx, P, C, ldx, mean + g * C, invstd + g * C,
-                           gamma, beta, y + (size_t)g * P * ldy, ldy, act);
-        if ((rc = kpx_launch_status())) return rc;
-    }
-    return 0;
-}
 
 __global__ __launch_bounds__(1024) void bn_bwd_finalize_groups_kernel(const double* part, size_t part_gstride, int nb, const float* __restrict__ ts, size_t tiles_per_group,
                                                                      const float* __restrict__ gamma, int groups, int C,
                                                                      float* dgamma, float* dbeta, float* sums, int accumulate) {
-    const int c = blockIdx.x, sg = threadIdx.x >> 8, t = threadIdx.x & 255, nseg = blockDim.x >> 8;
+    const int c = blockIdx.x, sg = threadIdx.x >> 8, nseg = blockDim.x >> 8;
     __shared__ double sm[4][2][4];
     for (int g0 = 0; g0 < groups; g0 += nseg) {
         const int g = g0 + sg;
-        double a0 = 0.0, a1 = 0.0;
-        if (g < groups) {
-            if (ts) {                                      // per-tile sums from the data-gradient epilogue that produced dy: sum(dz), sum(dz * (y - beta))
-                const size_t t0 = (size_t)g * tiles_per_group;
-                for (size_t b = t; b < tiles_per_group; b += 256) {
-                    a0 += (double)ts[((t0 + b) * 2) * C + c];
-                    a1 += (double)ts[((t0 + b) * 2 + 1) * C + c];
-                }
-            } else {
-                const double* gp = part + (size_t)g * part_gstride;
-                for (int b = t; b < nb; b += 256) {
-                    a0 += gp[((size_t)b * 2) * C + c];
-                    a1 += gp[((size_t)b * 2 + 1) * C + c];
-                }
-            }
-        }
-        a0 = kpx_wave_sum_d(a0);
-        a1 = kpx_wave_sum_d(a1);
-        __syncthreads();
-        if ((t & 63) == 0) { sm[sg][0][t >> 6] = a0; sm[sg][1][t >> 6] = a1; }
-        __syncthreads();
+        // ts: per-tile sum(dz), sum(dz * (y - beta)) from the data-gradient epilogue that produced dy; else the block partials
+        chan_wave_sums(part + (size_t)g * part_gstride, nb, ts, (size_t)g * tiles_per_group, tiles_per_group, g < groups, C, c, sm[sg]);
         if (threadIdx.x == 0) {
             for (int j = 0; j < nseg && g0 + j < groups; ++j) {
-                const double s = (sm[j][0][0] + sm[j][0][1]) + (sm[j][0][2] + sm[j][0][3]);
-                double q = (sm[j][1][0] + sm[j][1][1]) + (sm[j][1][2] + sm[j][1][3]);
+                const double s = chan_sum4(sm[j][0]);
+                double q = chan_sum4(sm[j][1]);
                 if (ts) { const double ga = (double)gamma[c]; q = ga != 0.0 ? q / ga : 0.0; }      // x_hat = (y - beta) / gamma wherever dz != 0
                 if (accumulate || g0 + j > 0) { dbeta[c] += (float)s; dgamma[c] += (float)q; } else { dbeta[c] = (float)s; dgamma[c] = (float)q; }
                 sums[(size_t)(g0 + j) * 2 * C + c] = (float)s; sums[(size_t)(g0 + j) * 2 * C + C + c] = (float)q;
@@ -704,6 +478,53 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_groups_kernel(const doub
         }
     }
 }
+
+static int launch_chan_reduce_bf16(int mode, bool dyf32, RedArgs a, int* nb_out, hipStream_t s, int groups);   // (bf16 section below)
+
+// The phases in front of the streaming pass, shared by the fp32 and bf16 entries: the reduction pass (over x for the statistics, over
+// (dy, x) for the backward sums; none when tile_stats hold per-tile sums already), then the finalize.  a.part = scratch: per group
+// KPX_RED_BLOCKS x 2 x C doubles of partials, then the backward sums [groups][2][C] (floats) behind all of them.
+static int bn_train_stats(RedArgs a, bool bf16, int groups, const float* tile_stats, size_t tiles_per_group, float eps,
+                          float* mean, float* invstd, float* mm, float* mv, float decay, hipStream_t s) {
+    a.part_gstride = (size_t)KPX_RED_BLOCKS * 2 * a.C;
+    int nb = 0;
+    if (!tile_stats) {
+        const int rc = bf16 ? launch_chan_reduce_bf16(1, false, a, &nb, s, groups) : launch_chan_reduce(1, a, &nb, s, groups);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(bn_stats_finalize_groups_kernel, dim3(a.C), dim3(256 * (groups < 4 ? groups : 4)), 0, s, (const double*)a.part, a.part_gstride, nb,
+                       tile_stats, tiles_per_group, groups, a.C, (double)a.P, eps, mean, invstd, mm, mv, decay);
+    return kpx_launch_status();
+}
+static int bn_train_bwd_sums(RedArgs a, bool bf16, bool dyf32, int groups, const float* tile_stats, size_t tiles_per_group,
+                             float* dgamma, float* dbeta, int accumulate, float** sums, hipStream_t s) {
+    a.part_gstride = (size_t)KPX_RED_BLOCKS * 2 * a.C;
+    int nb = 0;
+    if (!tile_stats) {
+        const int rc = bf16 ? launch_chan_reduce_bf16(2, dyf32, a, &nb, s, groups) : launch_chan_reduce(2, a, &nb, s, groups);
+        if (rc) return rc;
+    }
+    *sums = reinterpret_cast<float*>(a.part + (size_t)groups * a.part_gstride);
+    hipLaunchKernelGGL(bn_bwd_finalize_groups_kernel, dim3(a.C), dim3(256 * (groups < 4 ? groups : 4)), 0, s, (const double*)a.part, a.part_gstride, nb,
+                       tile_stats, tiles_per_group, a.gamma, groups, a.C, dgamma, dbeta, *sums, accumulate);
+    return kpx_launch_status();
+}
+
+extern "C" int kpx_bn_train_fwd_f32(const float* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
+                                    float eps, const float* gamma, const float* beta, float* mean, float* invstd,
+                                    float* moving_mean, float* moving_var, float decay, float* y, int ldy, int act, void* scratch, void* stream) {
+    if (!x || !y || !gamma || !beta || !mean || !invstd || !scratch || groups <= 0 || groups > 65535 || C <= 0 || ldx < C || ldy < C || act < 0 || act > 1 || P == 0)
+        return KPX_EINVAL;
+    hipStream_t s = kpx_stream(stream);
+    RedArgs a{}; a.x = x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch;
+    const int rc = bn_train_stats(a, false, groups, tile_stats, tiles_per_group, eps, mean, invstd, moving_mean, moving_var, decay, s);
+    if (rc) return rc;
+    const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0;
+    if (vec) hipLaunchKernelGGL(bn_apply_strip_kernel, strip_grid(P, C, 4, groups), dim3(256), 0, s, x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
+    else hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(P * C), 1, groups), dim3(256), 0, s, x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
+    return kpx_launch_status();
+}
+
 extern "C" int kpx_bn_train_bwd_f32(const float* dy, int lddy, const float* x, int ldx, size_t P, int groups, int C,
                                     const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
                                     float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
@@ -712,32 +533,18 @@ extern "C" int kpx_bn_train_bwd_f32(const float* dy, int lddy, const float* x, i
         ldx < C || lddy < C || lddx < C || act < 0 || act > 1 || P == 0 || (tile_stats && (act != KPX_ACT_RELU || tiles_per_group == 0)))
         return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
-    const size_t gstride = (size_t)KPX_RED_BLOCKS * 2 * C;
-    int nb = 0, rc = 0;
-    if (!tile_stats) {                                   // (with tile_stats the data-gradient epilogue that produced dy already reduced the two sums)
-        RedArgs a{}; a.x = x; a.ldx = ldx; a.dy = dy; a.lddy = lddy; a.P = P; a.C = C;
-        a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta; a.act = act; a.part = (double*)scratch; a.part_gstride = gstride;
-        rc = launch_chan_reduce(2, a, &nb, s, groups);
-        if (rc) return rc;
-    }
-    float* sums = reinterpret_cast<float*>((double*)scratch + (size_t)groups * gstride);          // [groups][2][C] behind the partials
-    hipLaunchKernelGGL(bn_bwd_finalize_groups_kernel, dim3(C), dim3(256 * (groups < 4 ? groups : 4)), 0, s, (const double*)scratch, gstride, nb, tile_stats, tiles_per_group,
-                       gamma, groups, C, dgamma, dbeta, sums, accumulate);
-    if ((rc = kpx_launch_status())) return rc;
+    RedArgs a{}; a.x = x; a.ldx = ldx; a.dy = dy; a.lddy = lddy; a.P = P; a.C = C;
+    a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta; a.act = act; a.part = (double*)scratch;
+    float* sums;
+    const int rc = bn_train_bwd_sums(a, false, false, groups, tile_stats, tiles_per_group, dgamma, dbeta, accumulate, &sums, s);
+    if (rc) return rc;
     const bool vec = (C % 4 == 0) && (ldx % 4 == 0) && (lddy % 4 == 0) && (lddx % 4 == 0) && ((((uintptr_t)x) | ((uintptr_t)dy) | ((uintptr_t)dx)) & 15) == 0;
     const float inv_count = (float)(1.0 / (double)P);
-    if (vec) {
-        hipLaunchKernelGGL(bn_bwd_apply_strip_kernel, strip_grid(P, C, groups), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
-        return kpx_launch_status();
-    }
-    for (int g = 0; g < groups; ++g) {
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid_for(P * C)), dim3(256), 0, s, dy + (size_t)g * P * lddy, lddy, x + (size_t)g * P * ldx, ldx, P, C,
-                           mean + g * C, invstd + g * C, gamma, beta, act, sums + (size_t)g * 2 * C, inv_count, dx + (size_t)g * P * lddx, lddx);
-        if ((rc = kpx_launch_status())) return rc;
-    }
-    return 0;
+    if (vec) hipLaunchKernelGGL(bn_bwd_apply_strip_kernel, strip_grid(P, C, 4, groups), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
+    else hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(P * C), 1, groups), dim3(256), 0, s, dy, lddy, x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, dx, lddx);
+    return kpx_launch_status();
 }
-// scratch of the two entries above: per group the partials of kpx_chan_reduce_scratch_bytes + 2 C floats
+// scratch of the train entries: per group the partials of kpx_chan_reduce_scratch_bytes + 2 C floats
 extern "C" size_t kpx_bn_train_scratch_bytes(int C, int groups) {
     const size_t c = (size_t)(C > 0 ? C : 1), g = (size_t)(groups > 0 ? groups : 1);
     return g * ((size_t)KPX_RED_BLOCKS * 2 * c * sizeof(double) + ((2 * c * sizeof(float) + 15) & ~(size_t)15));
@@ -1244,13 +1051,8 @@ __global__ __launch_bounds__(256) void chan_reduce_bf16_kernel(const RedArgs a) 
         }
     }
 }
-static int launch_chan_reduce_bf16(int mode, bool dyf32, RedArgs a, int* nb_out, hipStream_t s, int groups = 1) {
-    const int G = a.C / 8, Gb = G < 256 ? G : 256, PPB = 256 / Gb;
-    size_t nb = a.P / ((size_t)PPB * 8);
-    if (nb < 1) nb = 1;
-    if (nb > KPX_RED_BLOCKS) nb = KPX_RED_BLOCKS;
-    *nb_out = (int)nb;
-    const dim3 grid((unsigned)nb, (unsigned)((G + Gb - 1) / Gb), (unsigned)groups), block(256);
+static int launch_chan_reduce_bf16(int mode, bool dyf32, RedArgs a, int* nb_out, hipStream_t s, int groups) {
+    const dim3 grid = chan_reduce_grid(a.P, a.C / 8, groups, nb_out), block(256);
     if (mode == 0) hipLaunchKernelGGL((chan_reduce_bf16_kernel<0, false>), grid, block, 0, s, a);
     else if (mode == 1) hipLaunchKernelGGL((chan_reduce_bf16_kernel<1, false>), grid, block, 0, s, a);
     else if (dyf32) hipLaunchKernelGGL((chan_reduce_bf16_kernel<2, true>), grid, block, 0, s, a);
@@ -1261,7 +1063,7 @@ static int launch_chan_reduce_bf16(int mode, bool dyf32, RedArgs a, int* nb_out,
 extern "C" int kpx_chan_sum_bf16(const void* x, size_t P, int C, int ldx, float* sum_out, void* scratch, void* stream) {
     if (!x || !sum_out || !scratch || C <= 0 || C % 8 || ldx % 8 || ldx < C || P == 0 || !pw_al16(x)) return KPX_EINVAL;
     RedArgs a{}; a.x = (const float*)x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch;
-    int nb; int rc = launch_chan_reduce_bf16(0, false, a, &nb, kpx_stream(stream));
+    int nb; int rc = launch_chan_reduce_bf16(0, false, a, &nb, kpx_stream(stream), 1);
     if (rc) return rc;
     hipLaunchKernelGGL(chan_sum_finalize_kernel, dim3(C), dim3(256), 0, kpx_stream(stream), (const double*)scratch, nb, C, sum_out);
     return kpx_launch_status();
@@ -1299,13 +1101,6 @@ __global__ __launch_bounds__(256) void bn_apply_strip_bf16_kernel(const bf16_t* 
         }
     }
 }
-static inline dim3 strip_grid8(size_t P, int C, int groups) {
-    const int G = C >> 3, Gb = G < 256 ? G : 256, PPB = 256 / Gb;
-    size_t nb = (P + (size_t)PPB * 4 - 1) / ((size_t)PPB * 4);
-    if (nb < 1) nb = 1;
-    if (nb > KPX_MAX_BLOCKS) nb = KPX_MAX_BLOCKS;
-    return dim3((unsigned)nb, (unsigned)((G + Gb - 1) / Gb), (unsigned)groups);
-}
 // x bf16 [groups*P, C]; y bf16 (y_f32 = 0) or fp32 (y_f32 = 1); tile_stats as kpx_bn_train_fwd_f32 (kpx_conv3x3_bf16s writes them)
 extern "C" int kpx_bn_train_fwd_bf16(const void* x, size_t P, int groups, int C, int ldx, const float* tile_stats, size_t tiles_per_group,
                                      float eps, const float* gamma, const float* beta, float* mean, float* invstd,
@@ -1314,19 +1109,11 @@ extern "C" int kpx_bn_train_fwd_bf16(const void* x, size_t P, int groups, int C,
         act < 0 || act > 1 || P == 0 || !pw_al16(x, y))
         return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
-    const size_t gstride = (size_t)KPX_RED_BLOCKS * 2 * C;
-    int nb = 0;
-    if (!tile_stats) {
-        RedArgs a{}; a.x = (const float*)x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch; a.part_gstride = gstride;
-        int rc = launch_chan_reduce_bf16(1, false, a, &nb, s, groups);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(bn_stats_finalize_groups_kernel, dim3(C), dim3(256 * (groups < 4 ? groups : 4)), 0, s, (const double*)scratch, gstride, nb, tile_stats, tiles_per_group,
-                       groups, C, (double)P, eps, mean, invstd, moving_mean, moving_var, decay);
-    int rc = kpx_launch_status();
+    RedArgs a{}; a.x = (const float*)x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch;
+    const int rc = bn_train_stats(a, true, groups, tile_stats, tiles_per_group, eps, mean, invstd, moving_mean, moving_var, decay, s);
     if (rc) return rc;
-    if (y_f32) hipLaunchKernelGGL(bn_apply_strip_bf16_kernel<true>, strip_grid8(P, C, groups), dim3(256), 0, s, (const bf16_t*)x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
-    else hipLaunchKernelGGL(bn_apply_strip_bf16_kernel<false>, strip_grid8(P, C, groups), dim3(256), 0, s, (const bf16_t*)x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
+    if (y_f32) hipLaunchKernelGGL(bn_apply_strip_bf16_kernel<true>, strip_grid(P, C, 8, groups), dim3(256), 0, s, (const bf16_t*)x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
+    else hipLaunchKernelGGL(bn_apply_strip_bf16_kernel<false>, strip_grid(P, C, 8, groups), dim3(256), 0, s, (const bf16_t*)x, P, C, ldx, mean, invstd, gamma, beta, y, ldy, act);
     return kpx_launch_status();
 }
 
@@ -1390,21 +1177,14 @@ extern "C" int kpx_bn_train_bwd_bf16(const void* dy, int lddy, int dy_f32, const
         (tile_stats && (act != KPX_ACT_RELU || tiles_per_group == 0)))
         return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
-    const size_t gstride = (size_t)KPX_RED_BLOCKS * 2 * C;
-    int nb = 0, rc = 0;
     RedArgs a{}; a.x = (const float*)x; a.ldx = ldx; a.dy = (const float*)dy; a.lddy = lddy; a.P = P; a.C = C;
-    a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta; a.act = act; a.part = (double*)scratch; a.part_gstride = gstride;
-    if (!tile_stats) {                                   // (with tile_stats the data-gradient epilogue that produced dy already reduced the two sums)
-        rc = launch_chan_reduce_bf16(2, dy_f32 != 0, a, &nb, s, groups);
-        if (rc) return rc;
-    }
-    float* sums = reinterpret_cast<float*>((double*)scratch + (size_t)groups * gstride);
-    hipLaunchKernelGGL(bn_bwd_finalize_groups_kernel, dim3(C), dim3(256 * (groups < 4 ? groups : 4)), 0, s, (const double*)scratch, gstride, nb, tile_stats, tiles_per_group,
-                       gamma, groups, C, dgamma, dbeta, sums, accumulate);
-    if ((rc = kpx_launch_status())) return rc;
+    a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.beta = beta; a.act = act; a.part = (double*)scratch;
+    float* sums;
+    const int rc = bn_train_bwd_sums(a, true, dy_f32 != 0, groups, tile_stats, tiles_per_group, dgamma, dbeta, accumulate, &sums, s);
+    if (rc) return rc;
     const float inv_count = (float)(1.0 / (double)P);
-    if (dy_f32) hipLaunchKernelGGL(bn_bwd_apply_strip_bf16_kernel<true>, strip_grid8(P, C, groups), dim3(256), 0, s, dy, lddy, (const bf16_t*)x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, (bf16_t*)dx, lddx);
-    else hipLaunchKernelGGL(bn_bwd_apply_strip_bf16_kernel<false>, strip_grid8(P, C, groups), dim3(256), 0, s, dy, lddy, (const bf16_t*)x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, (bf16_t*)dx, lddx);
+    if (dy_f32) hipLaunchKernelGGL(bn_bwd_apply_strip_bf16_kernel<true>, strip_grid(P, C, 8, groups), dim3(256), 0, s, dy, lddy, (const bf16_t*)x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, (bf16_t*)dx, lddx);
+    else hipLaunchKernelGGL(bn_bwd_apply_strip_bf16_kernel<false>, strip_grid(P, C, 8, groups), dim3(256), 0, s, dy, lddy, (const bf16_t*)x, ldx, P, C, mean, invstd, gamma, beta, act, sums, inv_count, (bf16_t*)dx, lddx);
     return kpx_launch_status();
 }
 

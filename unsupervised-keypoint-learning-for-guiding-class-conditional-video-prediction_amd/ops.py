@@ -1018,22 +1018,7 @@ class BatchNormFn(torch.autograd.Function):
             x = cast(x, torch.float32)
         ctx.x16 = x.dtype == BF16
         y = torch.empty(x.shape, dtype=torch.float32 if (out_f32 or not ctx.x16) else BF16, device=dev)
-        if train and ctx.x16:
-            mean = torch.empty((groups, c), dtype=torch.float32, device=dev)
-            invstd = torch.empty((groups, c), dtype=torch.float32, device=dev)
-            ng = n // groups
-            pix = ng * h * w
-            sc = scratch.get('bn%d' % groups, lib.kpx_bn_train_scratch_bytes(c, groups), dev)
-            slab_ptr, tpg = None, 0
-            if tile_stats is not None:
-                slab, tpi = tile_stats
-                fused_bn_uses['stats_from_conv_epilogue'] += groups
-                slab_ptr, tpg = slab.data_ptr(), int(ng * tpi)
-            check(lib.kpx_bn_train_fwd_bf16(x.data_ptr(), pix, groups, c, c, slab_ptr, tpg, BN_EPS, gamma.data_ptr(), beta.data_ptr(),
-                                            mean.data_ptr(), invstd.data_ptr(), moving_mean.data_ptr() if update_moving else None,
-                                            moving_var.data_ptr() if update_moving else None, BN_DECAY, y.data_ptr(), c, 1 if y.dtype == torch.float32 else 0, act,
-                                            sc.data_ptr(), _stream()), 'kpx_bn_train_fwd_bf16')
-        elif train:
+        if train:
             # all `groups` weight-sharing calls in one launch per phase (statistics finalize + apply; + one reduction pass when the
             # producing convolution's epilogue did not deliver the per-tile sums)
             mean = torch.empty((groups, c), dtype=torch.float32, device=dev)
@@ -1046,10 +1031,12 @@ class BatchNormFn(torch.autograd.Function):
                 slab, tpi = tile_stats
                 fused_bn_uses['stats_from_conv_epilogue'] += groups
                 slab_ptr, tpg = slab.data_ptr(), int(ng * tpi)
-            check(lib.kpx_bn_train_fwd_f32(x.data_ptr(), pix, groups, c, c, slab_ptr, tpg, BN_EPS, gamma.data_ptr(), beta.data_ptr(),
-                                           mean.data_ptr(), invstd.data_ptr(), moving_mean.data_ptr() if update_moving else None,
-                                           moving_var.data_ptr() if update_moving else None, BN_DECAY, y.data_ptr(), c, act, sc.data_ptr(), _stream()),
-                  'kpx_bn_train_fwd_f32')
+            entry = 'kpx_bn_train_fwd_bf16' if ctx.x16 else 'kpx_bn_train_fwd_f32'
+            y_f32 = (1 if y.dtype == torch.float32 else 0,) if ctx.x16 else ()      # (the bf16 entry's output type)
+            check(getattr(lib, entry)(x.data_ptr(), pix, groups, c, c, slab_ptr, tpg, BN_EPS, gamma.data_ptr(), beta.data_ptr(),
+                                      mean.data_ptr(), invstd.data_ptr(), moving_mean.data_ptr() if update_moving else None,
+                                      moving_var.data_ptr() if update_moving else None, BN_DECAY, y.data_ptr(), c, *y_f32, act,
+                                      sc.data_ptr(), _stream()), entry)
         else:
             mean = moving_mean.reshape(1, c)
             invstd = torch.empty((1, c), dtype=torch.float32, device=dev)
@@ -1086,22 +1073,17 @@ class BatchNormFn(torch.autograd.Function):
         # kernel that produced dy (per-tile sums, ng * tiles-per-image tiles per group)
         sc = scratch.get('bn%d' % groups, lib.kpx_bn_train_scratch_bytes(c, groups), dev)
         if ctx.x16:
-            if ent is not None:
-                fused_bn_uses['backward_sums_from_dgrad_epilogue'] += groups
-            check(lib.kpx_bn_train_bwd_bf16(dy.data_ptr(), c, 1 if dy.dtype == torch.float32 else 0, x.data_ptr(), c, pix, groups, c, mean.data_ptr(), invstd.data_ptr(),
-                                            gamma.data_ptr(), beta.data_ptr(), ctx.act, dx.data_ptr(), c, dg.data_ptr(), db.data_ptr(), 0 if fresh else 1,
-                                            ent[0].data_ptr() if ent is not None else None, int(ng * ent[1]) if ent is not None else 0,
-                                            sc.data_ptr(), _stream()), 'kpx_bn_train_bwd_bf16')
-            return (dx, None if ctx.g_grad_out is not None else dg, None if ctx.b_grad_out is not None else db,
-                    None, None, None, None, None, None, None, None, None, None, None)
-        if dy.dtype == BF16:
-            dy = cast(dy, torch.float32)
+            entry, dy_f32 = 'kpx_bn_train_bwd_bf16', (1 if dy.dtype == torch.float32 else 0,)
+        else:
+            if dy.dtype == BF16:
+                dy = cast(dy, torch.float32)
+            entry, dy_f32 = 'kpx_bn_train_bwd_f32', ()
         if ent is not None:
             fused_bn_uses['backward_sums_from_dgrad_epilogue'] += groups
-        check(lib.kpx_bn_train_bwd_f32(dy.data_ptr(), c, x.data_ptr(), c, pix, groups, c, mean.data_ptr(), invstd.data_ptr(),
-                                       gamma.data_ptr(), beta.data_ptr(), ctx.act, dx.data_ptr(), c, dg.data_ptr(), db.data_ptr(),
-                                       0 if fresh else 1, ent[0].data_ptr() if ent is not None else None, ng * ent[1] if ent is not None else 0,
-                                       sc.data_ptr(), _stream()), 'kpx_bn_train_bwd_f32')
+        check(getattr(lib, entry)(dy.data_ptr(), c, *dy_f32, x.data_ptr(), c, pix, groups, c, mean.data_ptr(), invstd.data_ptr(),
+                                  gamma.data_ptr(), beta.data_ptr(), ctx.act, dx.data_ptr(), c, dg.data_ptr(), db.data_ptr(), 0 if fresh else 1,
+                                  ent[0].data_ptr() if ent is not None else None, int(ng * ent[1]) if ent is not None else 0,
+                                  sc.data_ptr(), _stream()), entry)
         return (dx, None if ctx.g_grad_out is not None else dg, None if ctx.b_grad_out is not None else db,
                 None, None, None, None, None, None, None, None, None, None, None)
 
