@@ -133,3 +133,63 @@ def same_pad_table():
             (32, 3, 2, 0): (0, 1, 16), (128, 4, 2, 1): (1, 1, 65), (65, 4, 2, 1): (1, 2, 34),
             (34, 4, 2, 1): (1, 1, 18), (18, 4, 2, 1): (1, 1, 10), (10, 4, 2, 1): (1, 1, 6),
             (6, 4, 2, 1): (1, 1, 4), (4, 3, 1, 1): (1, 1, 6), (16, 3, 1, 0): (1, 1, 16), (128, 1, 1, 0): (0, 0, 128)}
+
+
+def _sigmoid(v):
+    return 1.0 / (1.0 + math.exp(-v))
+
+
+def lstm_cell(x, h, c, kernel, bias, forget_bias=1.0):
+    """One tf.nn.rnn_cell.LSTMCell step (layers.py:17-21), element by element: gates = [x, h] @ kernel + bias split as i, j, f, o;
+    c' = c*sigmoid(f + forget_bias) + sigmoid(i)*tanh(j); h' = tanh(c')*sigmoid(o).  x [B,In], h / c [B,U] -> (h', c')."""
+    x, h, c = (np.asarray(a, np.float64) for a in (x, h, c))
+    kernel, bias = np.asarray(kernel, np.float64), np.asarray(bias, np.float64)
+    b, n_in = x.shape
+    u = h.shape[1]
+    h2, c2 = np.zeros((b, u)), np.zeros((b, u))
+    for bi in range(b):
+        xin = np.concatenate([x[bi], h[bi]])
+        for k in range(u):
+            g = [bias[q * u + k] + sum(xin[r] * kernel[r, q * u + k] for r in range(n_in + u)) for q in range(4)]
+            i, j, f, o = g
+            c2[bi, k] = c[bi, k] * _sigmoid(f + forget_bias) + _sigmoid(i) * math.tanh(j)
+            h2[bi, k] = math.tanh(c2[bi, k]) * _sigmoid(o)
+    return h2, c2
+
+
+def dynamic_rnn(x, kernels, biases):
+    """tf.nn.dynamic_rnn over a MultiRNNCell of LSTMCells with zero initial state: x [B,T,In] -> top-layer outputs [B,T,U]."""
+    x = np.asarray(x, np.float64)
+    b, t, _ = x.shape
+    state = [(np.zeros((b, k.shape[1] // 4)), np.zeros((b, k.shape[1] // 4))) for k in kernels]
+    out = []
+    for step in range(t):
+        xin = x[:, step]
+        for l, (k, bias) in enumerate(zip(kernels, biases)):
+            h, c = lstm_cell(xin, state[l][0], state[l][1], k, bias)
+            state[l] = (h, c)
+            xin = h
+        out.append(xin)
+    return np.stack(out, axis=1)
+
+
+def vae_sample_kl(mu, stddev, eps):
+    """z = mu + stddev*eps (motion_generator_model.py:146); kl = mean over b of 0.5*sum_v(mu^2 + s^2 - log(1e-8 + s^2) - 1) (:291-293)."""
+    mu, sd, eps = (np.asarray(a, np.float64) for a in (mu, stddev, eps))
+    b, v = mu.shape
+    z = np.zeros((b, v))
+    total = 0.0
+    for bi in range(b):
+        row = 0.0
+        for k in range(v):
+            z[bi, k] = mu[bi, k] + sd[bi, k] * eps[bi, k]
+            row += mu[bi, k] ** 2 + sd[bi, k] ** 2 - math.log(1e-8 + sd[bi, k] ** 2) - 1.0
+        total += 0.5 * row
+    return z, total / b
+
+
+def vae_sample_kl_grad(mu, stddev, eps, dz, gkl):
+    """Closed-form gradient of (z, kl) above: d/dmu = dz + gkl*mu/B, d/ds = dz*eps + gkl*(s - s/(1e-8 + s^2))/B."""
+    mu, sd, eps, dz = (np.asarray(a, np.float64) for a in (mu, stddev, eps, dz))
+    b = mu.shape[0]
+    return dz + gkl * mu / b, dz * eps + gkl * (sd - sd / (1e-8 + sd * sd)) / b

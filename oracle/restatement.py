@@ -661,8 +661,8 @@ def vae_decoder(p, x, f_pt, act_code, cell_info, n_pts):
     s = 'vae_decoder'
     inp = F.relu(torch.cat([x, f_pt, act_code], dim=-1) @ p[s + '/fully_connected/weights'] + p[s + '/fully_connected/biases'])
     b = x.shape[0]
-    c = [torch.zeros(b, u) for u in cell_info]
-    h = [torch.zeros(b, u) for u in cell_info]
+    c = [torch.zeros(b, u, dtype=inp.dtype) for u in cell_info]                  # zero state in the input's dtype (float64 arbiter)
+    h = [torch.zeros(b, u, dtype=inp.dtype) for u in cell_info]
     outs = []
     for step in range(N_FUTURE_FRAMES):
         xin = inp if step == 0 else torch.zeros_like(inp)
@@ -742,8 +742,8 @@ def init_motion_generator(n_pts, n_action=9, cell_info=(1024, 1024), vae_dim=64,
 def _dynamic_rnn(p, scope, x, cell_info):
     """tf.nn.dynamic_rnn over a MultiRNNCell of LSTMCells with zero initial state: x [B,T,In] -> top-layer outputs [B,T,U]."""
     b, t, _ = x.shape
-    c = [torch.zeros(b, u) for u in cell_info]
-    h = [torch.zeros(b, u) for u in cell_info]
+    c = [torch.zeros(b, u, dtype=x.dtype) for u in cell_info]
+    h = [torch.zeros(b, u, dtype=x.dtype) for u in cell_info]
     outs = []
     for step in range(t):
         xin = x[:, step]
@@ -774,6 +774,13 @@ def seq_discr(p, x, discr_cells=(1024, 1024)):
     return logit[:, -1, :]
 
 
+def vae_sample_kl(mu, stddev, eps):
+    """Reparameterisation (:146) and KL term (:291-293): z = mu + stddev*eps, kl = mean_b(0.5*sum_v(mu^2 + s^2 - log(1e-8 + s^2) - 1))."""
+    z = mu + stddev * eps
+    kl = (0.5 * torch.sum(mu * mu + stddev * stddev - torch.log(1e-8 + stddev * stddev) - 1, dim=1)).mean()
+    return z, kl
+
+
 def motion_generator_losses(p, keypoints, real_seq, action_code, eps, n_pts, cell_info=(1024, 1024), vae_dim=64, discr_cells=(1024, 1024)):
     """MotionGeneratorModel._define_forward_pass (training branch, :137-150) + _compute_loss_D / _compute_loss_G (:257-308);
     ``eps`` is the N(0,1) draw of tf.random_normal (:146), injected."""
@@ -781,21 +788,23 @@ def motion_generator_losses(p, keypoints, real_seq, action_code, eps, n_pts, cel
     first_pt = keypoints.reshape(b, n_pts * 2)
     real = real_seq.reshape(b, N_FUTURE_FRAMES, n_pts * 2)
     mu, stddev = vae_encoder(p, real, first_pt, action_code, cell_info, vae_dim)
-    z = mu + stddev * eps
+    z, kl = vae_sample_kl(mu, stddev, eps)
     pred = vae_decoder(p, z, first_pt, action_code, cell_info, n_pts)
     real_, fake_ = seq_discr(p, real, discr_cells), seq_discr(p, pred, discr_cells)
     loss_d_real = sigmoid_xent(real_, 1.0).mean()
     loss_d_fake = sigmoid_xent(fake_, 0.0).mean()
     recon = (1000 * torch.abs(pred - real)).mean()
-    kl = (0.5 * torch.sum(mu * mu + stddev * stddev - torch.log(1e-8 + stddev * stddev) - 1, dim=1)).mean()
     adv = sigmoid_xent(fake_, 1.0).mean()
     return dict(loss_D=loss_d_real + loss_d_fake, loss_D_real=loss_d_real, loss_D_fake=loss_d_fake,
                 loss_G=kl + recon + adv, loss_G_recon=recon, loss_G_kl=kl, loss_G_adv=adv, pred_seq=pred, mu=mu, stddev=stddev)
 
 
 class MotionTrainState:
-    def __init__(self, params, n_pts, n_action=9, cell_info=(1024, 1024), vae_dim=64, discr_cells=(1024, 1024), lr_cfg=None):
-        self.params = OrderedDict((k, torch.as_tensor(np.asarray(v)).clone()) for k, v in params.items())
+    def __init__(self, params, n_pts, n_action=9, cell_info=(1024, 1024), vae_dim=64, discr_cells=(1024, 1024), lr_cfg=None,
+                 dtype=torch.float32):
+        """``dtype=torch.float64`` runs the stage-2 restatement in double precision (the arbiter, as for ``TrainState``)."""
+        self.dtype = dtype
+        self.params = OrderedDict((k, torch.as_tensor(np.asarray(v)).clone().to(dtype)) for k, v in params.items())
         self.cfg = dict(n_pts=n_pts, cell_info=tuple(cell_info), vae_dim=vae_dim, discr_cells=tuple(discr_cells))
         self.d_names = [n for n in self.params if 'discr' in n]                # :176-178
         self.g_names = [n for n in self.params if 'discr' not in n]
@@ -808,14 +817,15 @@ class MotionTrainState:
 def motion_train_step(state, keypoints, real_seq, action_code, eps_D, eps_G):
     """MotionGeneratorModel.train_step (:80-104): D-run then G-run, each a full forward (with its own random_normal draw)."""
     p = state.params
-    kp, rs, ac = (torch.as_tensor(a) for a in (keypoints, real_seq, action_code))
+    dtype = getattr(state, 'dtype', torch.float32)
+    kp, rs, ac, e_d, e_g = (torch.as_tensor(a).to(dtype) for a in (keypoints, real_seq, action_code, eps_D, eps_G))
     lr = exponential_decay(state.lr_cfg['start_val'], state.global_step, state.lr_cfg['step'], state.lr_cfg['decay'])
     for n in state.d_names + state.g_names:
         p[n].requires_grad_(True)
-    out_d = motion_generator_losses(p, kp, rs, ac, torch.as_tensor(eps_D), **state.cfg)
+    out_d = motion_generator_losses(p, kp, rs, ac, e_d, **state.cfg)
     g_d = _grads(out_d['loss_D'], p, state.d_names)
     state.opt_D.step(p, g_d, lr)
-    out_g = motion_generator_losses(p, kp, rs, ac, torch.as_tensor(eps_G), **state.cfg)
+    out_g = motion_generator_losses(p, kp, rs, ac, e_g, **state.cfg)
     g_g = _grads(out_g['loss_G'], p, state.g_names)
     state.opt_G.step(p, g_g, lr)
     state.global_step += 1

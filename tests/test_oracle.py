@@ -192,3 +192,103 @@ def test_lean_gradient_arbiter_equals_the_full_train_step():
     assert lean['grads_T'] and all(n.startswith('translator/') for n in lean['grads_T'])
     for n, g in lean['grads_T'].items():
         np.testing.assert_allclose(g.numpy(), full['grads_G'][n].numpy(), rtol=1e-5, atol=1e-9, err_msg=n)
+
+
+# --------------------------------------------------------------------------- stage 2: LSTMCell, dynamic_rnn, VAE sample / KL
+def _lstm_params(rs, n_in, cells):
+    ks, bs, prev = [], [], n_in
+    for u in cells:
+        ks.append(rs.uniform(-0.6, 0.6, size=(prev + u, 4 * u)))
+        bs.append(rs.randn(4 * u) * 0.3)
+        prev = u
+    return ks, bs
+
+
+def test_stage2_lstm_restatement_vs_f64_loops():
+    """R._dynamic_rnn and R.vae_decoder in float64 against the element-by-element LSTMCell of f64_loops (gate order i, j, f, o;
+    forget_bias 1.0; zero initial state), and the default fp32 restatement stays fp32."""
+    rs = np.random.RandomState(11)
+    b, t, n_in, cells = 3, 6, 5, (4, 3)
+    ks, bs = _lstm_params(rs, n_in, cells)
+    x = rs.randn(b, t, n_in)
+    p = {}
+    for l, (k, bias) in enumerate(zip(ks, bs)):
+        p['s/multi_rnn_cell/cell_%d/basic_lstm_cell/kernel' % l] = torch.from_numpy(k)
+        p['s/multi_rnn_cell/cell_%d/basic_lstm_cell/bias' % l] = torch.from_numpy(bias)
+    got = R._dynamic_rnn(p, 's', torch.from_numpy(x), cells)
+    assert got.dtype == torch.float64
+    want = L.dynamic_rnn(x, ks, bs)
+    assert rel_l2(got.numpy(), want) < 1e-13
+    p32 = {n: v.float() for n, v in p.items()}
+    got32 = R._dynamic_rnn(p32, 's', torch.from_numpy(x).float(), cells)
+    assert got32.dtype == torch.float32 and rel_l2(got32.numpy(), want) < 2e-6
+    # vae_decoder: fc(relu) -> the stack with the fc output at step 0 and zeros afterwards -> tanh(h W + b), 32 steps
+    n_pts, vae, n_act = 2, 3, 4
+    fc_w, fc_b = rs.randn(vae + 2 * n_pts + n_act, 4) * 0.5, rs.randn(4) * 0.1
+    ks, bs = _lstm_params(rs, 4, cells)
+    w_out, b_out = rs.randn(cells[-1], 2 * n_pts), rs.randn(2 * n_pts) * 0.1
+    pd = {'vae_decoder/fully_connected/weights': fc_w, 'vae_decoder/fully_connected/biases': fc_b,
+          'vae_decoder/fully_connected/W': w_out, 'vae_decoder/fully_connected/b': b_out}
+    for l, (k, bias) in enumerate(zip(ks, bs)):
+        pd['vae_decoder/multi_rnn_cell/cell_%d/basic_lstm_cell/kernel' % l] = k
+        pd['vae_decoder/multi_rnn_cell/cell_%d/basic_lstm_cell/bias' % l] = bias
+    z, fpt, act = rs.randn(b, vae), rs.rand(b, 2 * n_pts) * 2 - 1, np.eye(n_act)[rs.randint(0, n_act, size=b)]
+    got = R.vae_decoder({n: torch.from_numpy(v) for n, v in pd.items()}, torch.from_numpy(z), torch.from_numpy(fpt), torch.from_numpy(act), cells, n_pts)
+    inp = np.maximum(np.concatenate([z, fpt, act], 1) @ fc_w + fc_b, 0)
+    state = [(np.zeros((b, u)), np.zeros((b, u))) for u in cells]
+    want = np.zeros((b, 32, 2 * n_pts))
+    for step in range(32):
+        xin = inp if step == 0 else np.zeros_like(inp)
+        for l in range(len(cells)):
+            h, c = L.lstm_cell(xin, state[l][0], state[l][1], ks[l], bs[l])
+            state[l] = (h, c)
+            xin = h
+        want[:, step] = np.tanh(xin @ w_out + b_out)
+    assert got.dtype == torch.float64 and rel_l2(got.numpy(), want) < 1e-13
+
+
+def test_vae_sample_kl_and_its_gradient_vs_f64_loops():
+    """R.vae_sample_kl (z and the KL term with log(1e-8 + s^2)) against the loop derivation, and its autograd gradient against the closed
+    form of vae_sample_kl_bwd_kernel, at stddev exactly 0, tiny (1e-6, where d/ds is ~ -1/s), ordinary and large."""
+    rs = np.random.RandomState(12)
+    b, v = 4, 9
+    mu = np.maximum(rs.randn(b, v), 0)                       # the encoder's ReLU: mu and stddev are >= 0, many exactly 0
+    sd = np.abs(rs.randn(b, v))
+    sd[0, :3] = 0.0
+    sd[1, :3] = (1e-6, 3e-6, 1e-4)
+    sd[2, :2] = (30.0, 1e3)
+    eps, dz = rs.randn(b, v), rs.randn(b, v)
+    mu_t, sd_t = torch.from_numpy(mu).requires_grad_(True), torch.from_numpy(sd).requires_grad_(True)
+    z, kl = R.vae_sample_kl(mu_t, sd_t, torch.from_numpy(eps))
+    z64, kl64 = L.vae_sample_kl(mu, sd, eps)
+    assert rel_l2(z.detach().numpy(), z64) < 1e-15 and abs(kl.item() - kl64) <= 1e-13 * abs(kl64)
+    gkl = 2.5
+    (z * torch.from_numpy(dz)).sum().add(gkl * kl).backward()
+    dmu, dsd = L.vae_sample_kl_grad(mu, sd, eps, dz, gkl)
+    np.testing.assert_allclose(mu_t.grad.numpy(), dmu, rtol=1e-12, atol=0)
+    np.testing.assert_allclose(sd_t.grad.numpy(), dsd, rtol=1e-10, atol=1e-14)
+    assert abs(dsd[1, 0] - (dz[1, 0] * eps[1, 0] + gkl / b * (1e-6 - 1e-6 / (1e-8 + 1e-12)))) < 1e-9        # ~ -1/s near 0
+    # fp32 restatement (the default dtype) against the same loops
+    z32, kl32 = R.vae_sample_kl(torch.from_numpy(mu).float(), torch.from_numpy(sd).float(), torch.from_numpy(eps).float())
+    assert z32.dtype == torch.float32 and rel_l2(z32.numpy(), z64) < 1e-7 and abs(float(kl32) - kl64) <= 2e-6 * abs(kl64)
+
+
+def test_stage2_train_state_dtype():
+    """MotionTrainState(dtype=float64) runs the whole step in double precision; the default stays fp32 and within fp32 noise of it."""
+    k, a, cells, vae, discr, b = 3, 4, (8, 8), 4, (8, 8), 2
+    params = R.init_motion_generator(k, a, cells, vae, discr, seed=5)
+    rs = np.random.RandomState(1)
+    kp = (rs.rand(b, k, 2) * 1.6 - 0.8).astype(np.float32)
+    seq = (rs.rand(b, 32, k, 2) * 1.6 - 0.8).astype(np.float32)
+    ac = np.eye(a, dtype=np.float32)[rs.randint(0, a, size=b)]
+    e_d, e_g = rs.randn(b, vae).astype(np.float32), rs.randn(b, vae).astype(np.float32)
+    s32 = R.MotionTrainState(params, k, a, cells, vae, discr)
+    s64 = R.MotionTrainState(params, k, a, cells, vae, discr, dtype=torch.float64)
+    r32 = R.motion_train_step(s32, kp, seq, ac, e_d, e_g)
+    r64 = R.motion_train_step(s64, kp, seq, ac, e_d, e_g)
+    assert all(t.dtype == torch.float32 for t in s32.params.values()) and r32['pred_seq'].dtype == torch.float32
+    assert all(t.dtype == torch.float64 for t in s64.params.values()) and r64['pred_seq'].dtype == torch.float64
+    assert all(g.dtype == torch.float64 for g in list(r64['grads_D'].values()) + list(r64['grads_G'].values()))
+    for key in ('loss_D', 'loss_G', 'loss_G_kl', 'loss_G_recon'):
+        assert abs(r32[key] - r64[key]) <= 1e-5 * max(1.0, abs(r64[key])), key
+    assert rel_l2(r32['pred_seq'].numpy(), r64['pred_seq'].numpy()) < 1e-5
