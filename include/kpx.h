@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 6
+#define KPX_ABI_VERSION 7
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -289,6 +289,25 @@ int kpx_gaussian_maps_bwd_f32(const float* dmaps, int lddy, const float* mu, int
  * bits of kpx_gaussian_maps_fwd_f32.  K in [1,64], H and W in [2,1024], inv_std > 0; nothing else is read or written (no [N,H,W,K] maps).
  * Added in ABI version 5. */
 int kpx_point_maps_rgb_f32(const float* mu, int N, int K, int H, int W, double inv_std, const float* colors, float* out, void* stream);
+
+/* ---- a strip of colourised pose frames (motion_generator_model.py:225-248): for every frame t of mu [N,T,K,2] (x,y), the frame of
+ * kpx_point_maps_rgb_f32 (same bits) goes to columns [t*W, (t+1)*W) of out [N,H,T*W,3] (tf.concat(axis=2)).  recolour != 0 fuses the
+ * reference's second colorize_point_maps over the 3-channel strip: out[...,c] = max_{i<3} strip[...,i] * colors[i][c] in fp32 (needs K >= 3).
+ * K in [1,64], H and W in [2,1024], T*W <= 65536, inv_std > 0.  Added in ABI version 7. */
+int kpx_point_seq_strip_rgb_f32(const float* mu, int N, int T, int K, int H, int W, double inv_std, const float* colors, int recolour,
+                                float* out, void* stream);
+
+/* ---- image summaries: TF 1.12 SummaryImageOp's float -> uint8 conversion (NormalizeFloatImage, summary_image_op.cc) per image, with the
+ * reference's pre-map fused into both passes (never written out).  x fp32 NHWC [N,H,W,C], C in {1,3,4}; out uint8 [N,H,W,C].
+ *   premap: KPX_PREMAP_IDENTITY x | KPX_PREMAP_X255 x*255 | KPX_PREMAP_UNIT255 (x+1)/2*255 | KPX_PREMAP_UNIT255_CLIP clip((x+1)/2*255, 0, 255)
+ *           (clip_by_value = min then max, compare-select: NaN stays NaN, +-inf clips).
+ *   A pixel is finite when all its channels are; min / max over finite pixels; min < 0: scale = 127/max(|min|,|max|), offset 128, else
+ *   scale = 255/max, offset 0; scale 0 below 1e-6; finite pixels -> uint8(trunc(fl(fl(x*scale) + offset))), others -> (255,0,0,255)[:C].
+ * Two launches (per-slice finite min / max into `work`, then per-image reduce + convert); work holds 2 * KPX_SUMMARY_SLICES * N floats.
+ * Deterministic; no allocation, copy or synchronisation (capturable).  Added in ABI version 7. */
+#define KPX_SUMMARY_SLICES 64
+enum { KPX_PREMAP_IDENTITY = 0, KPX_PREMAP_X255 = 1, KPX_PREMAP_UNIT255 = 2, KPX_PREMAP_UNIT255_CLIP = 3 };
+int kpx_summary_image_u8_f32(const float* x, int N, int H, int W, int C, int premap, float* work, uint8_t* out, void* stream);
 
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */

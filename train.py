@@ -46,7 +46,7 @@ def _train_motion_generator(args, config, dev, rank, world):
     import numpy as np
     import kpx_amd
     paths_config, train_config, model_config = config['paths'], config['training'], config['model']
-    model = _get_model_by_mode('motion_generator', config, 0, device=dev)
+    model = _get_model_by_mode('motion_generator', config, 0, device=dev, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']
@@ -72,14 +72,22 @@ def _train_motion_generator(args, config, dev, rank, world):
     print('training start')
     for step in range(model.global_step, n_steps):
         feed = next(train_it) if train_it is not None else synthetic(step * world + rank)
-        model.train_step(None, feed, step, batch_size, should_write_log=step % train_config['log_interval'] == 0 and rank == 0)
+        model.train_step(None, feed, step, batch_size, should_write_log=step % train_config['log_interval'] == 0 and rank == 0,
+                         should_write_summary=_should_write_summary(train_config, step, rank))
         if step % train_config['checkpoint_interval'] == 0 and rank == 0:
             model.save_checkpoint(None, step, fmt=args.ckpt_format)
         if step % train_config['test_interval'] == 0 and rank == 0:
             feeds = test_batches() if test_batches is not None else [synthetic(10 ** 6)]
             model.collect_test_results([model.test_step(None, f, step, i, f['keypoints'].shape[0]) for i, f in enumerate(feeds)], step)
+    model.close_loggers()
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def _should_write_summary(train_config, step, rank):
+    """reference train.py:88 (step % summary_interval == 0), rank 0 only; a config without summary_interval writes no summaries."""
+    interval = train_config.get('summary_interval')
+    return bool(interval) and step % int(interval) == 0 and rank == 0
 
 
 def main(argv=None):
@@ -96,6 +104,8 @@ def main(argv=None):
     parser.add_argument('--batch-per-run', action='store_true',
                         help="feed a NEW batch to the G update like the reference's two sess.run (train.py:46-50); default: one batch per "
                              'step with a shared generator forward')
+    parser.add_argument('--colors_seed', type=int, default=0,
+                        help='seed of the key-point palette of the image summaries (the reference draws it from the unseeded random module)')
     args = parser.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
 
@@ -118,7 +128,7 @@ def main(argv=None):
         if not args.synthetic_vgg:
             raise Exception('file of pretrained vgg19 does not exist at: %s (pass --synthetic-vgg for benchmarking)' % paths_config.get('vggnet'))
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev)
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg)
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']          # per process, like the reference's single-device batch
@@ -152,7 +162,7 @@ def main(argv=None):
                 pair = synthetic_pair(batch_size, res=model.image_size, seed0=s2, seed1=s2 + 1)
                 feed_dict.update({k + '_G': torch.from_numpy(v).to(dev) for k, v in pair.items()})
         model.train_step(None, feed_dict, step, batch_size, should_write_log=should_write_log and rank == 0,
-                         should_write_summary=False)
+                         should_write_summary=_should_write_summary(train_config, step, rank))
         if step % train_config['checkpoint_interval'] == 0 and rank == 0:
             model.save_checkpoint(None, step, fmt=args.ckpt_format)
         if step % train_config['test_interval'] == 0 and rank == 0:
@@ -162,6 +172,7 @@ def main(argv=None):
                 tp = synthetic_pair(batch_size, res=model.image_size, seed0=10 ** 6, seed1=10 ** 6 + 1)
                 results = [model.test_step(None, {k: torch.from_numpy(v).to(dev) for k, v in tp.items()}, step, 0, batch_size)]
             model.collect_test_results(results, step)
+    model.close_loggers()
     if world > 1:
         torch.distributed.destroy_process_group()
 

@@ -10,6 +10,7 @@ from abc import ABC, abstractmethod
 from os import path as osp
 
 import numpy as np
+import torch
 
 
 class BaseModel(ABC):
@@ -21,6 +22,8 @@ class BaseModel(ABC):
         self.is_training = is_training
         self.log_dir = None
         self.store = None
+        self.train_writer = None
+        self.test_writer = None
 
     @abstractmethod
     def build(self, inputs):
@@ -39,9 +42,30 @@ class BaseModel(ABC):
         raise NotImplementedError
 
     def initialize_loggers(self, log_dir, sess=None):
-        """reference :62-75 (the TensorBoard FileWriters are out of scope; the checkpoint directory is created)."""
+        """reference :62-75: the checkpoint directory, and -- for a training model on rank 0 -- the TensorBoard event writers of
+        ``<log_dir>/<name>/train`` and ``<log_dir>/<name>/test`` (summary.EventFileWriter).  The reference's train writer also records
+        ``sess.graph``; there is no TF graph here, so that event is not written."""
         self.log_dir = log_dir
-        os.makedirs(osp.join(log_dir, self.__class__.name), exist_ok=True)
+        name = self.__class__.name
+        os.makedirs(osp.join(log_dir, name), exist_ok=True)
+        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+        if self.is_training and rank == 0:
+            from .summary import EventFileWriter
+            self.close_loggers()
+            self.train_writer = EventFileWriter(osp.join(log_dir, name, 'train'))
+            self.test_writer = EventFileWriter(osp.join(log_dir, name, 'test'))
+
+    def close_loggers(self):
+        for w in (self.train_writer, self.test_writer):
+            if w is not None:
+                w.close()
+        self.train_writer = self.test_writer = None
+
+    def _write_summaries(self, writer, step, summaries):
+        """One add_summary per merged summary, in order (the reference's add_summary calls)."""
+        if writer is not None:
+            for values in summaries:
+                writer.add_summary(values, step)
 
     def checkpoint_arrays(self):
         """Everything tf.train.Saver(tf.global_variables()) would hold (reference :74)."""

@@ -414,20 +414,8 @@ extern "C" int kpx_keypoint_head_proj_bwd_f32(const float* dmu, const float* mu,
 // square(y - mu_y) + square(x - mu_x), times float32(inv_std**2), negate, exp (utils/model.py:56-59); exp is the hardware
 // exp2 path (__expf: |err| <= ~2 ulp of a result in [0,1], inside the 2e-6 absolute budget).  Because both renderers call
 // this function, a map element has the same bits whether it is rendered contiguously or into a channel slice.
-// The operations go through kpx_*_rn: hipcc contracts the __f*_rn intrinsics like plain operators (their bodies carry the contract flag), and
-// the fixed-column loop of gauss_fwd_reg_kernel was compiled to fma(dy, dy, dx2), an ulp of dist away from the other renderers.
-__device__ __forceinline__ float kpx_mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float kpx_add_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float kpx_sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-    return a - b;
-}
+// The operations go through kpx_*_rn (kpx_common.h): hipcc contracts the __f*_rn intrinsics like plain operators, and the fixed-column loop
+// of gauss_fwd_reg_kernel was compiled to fma(dy, dy, dx2), an ulp of dist away from the other renderers.
 __device__ __forceinline__ float kpx_gauss(float yv, float xv, float my, float mx, float inv2) {
     const float dy = kpx_sub_rn(yv, my), dx = kpx_sub_rn(xv, mx);
     const float dist = kpx_mul_rn(kpx_add_rn(kpx_mul_rn(dy, dy), kpx_mul_rn(dx, dx)), inv2);
@@ -641,12 +629,16 @@ extern "C" int kpx_gaussian_maps_bwd_f32(const float* dmaps, int lddy, const flo
 // Exact culling: dist = fl(fl(dy2 + dx2) * inv2) >= fl(dy2 * inv2) by monotonic rounding (dx2 >= 0), and __expf(-dist) is v_exp_f32 of
 // fl(-dist * log2 e); for dist >= 128 that argument is <= -184 and the result is exactly +0 (the smallest denormal is 2^-149), so its products
 // leave the max unchanged: a (row, k) with fl(dy2 * inv2) >= 128 is skipped for the whole row.
+// Frames of a pose strip (kpx_point_seq_strip_rgb_f32) are the same pixels: frame f = n*T + t of the [N*T] frames goes to columns
+// [t*W, (t+1)*W) of image n, whose rows are ldo pixels long (T = 1, ldo = W: the contiguous [N,H,W,3] output).  RECOLOUR applies the
+// second colorize_point_maps of the strip to the finished pixel: out[c] = max_{i<3} acc[i] * colors[i][c] (fp32 products, all >= +0).
 #define PM_R 4
 #define PM_CULL 128.0f
 
-template <bool VEC>
+template <bool VEC, bool RECOLOUR>
 __global__ __launch_bounds__(256) void point_maps_rgb_kernel(const float* __restrict__ mu, int K, int H, int W, float inv2,
-                                                             const float* __restrict__ colors, float* __restrict__ out, int tiles_x, int tiles) {
+                                                             const float* __restrict__ colors, float* __restrict__ out, int tiles_x, int tiles,
+                                                             int T, int ldo) {
     const int n = blockIdx.x / tiles, tile = blockIdx.x - n * tiles;   // frame, then its tiles (row-major)
     const int tq = threadIdx.x & 15, tr = threadIdx.x >> 4;
     const int w0 = ((tile % tiles_x) * 16 + tq) * 4;
@@ -695,11 +687,28 @@ __global__ __launch_bounds__(256) void point_maps_rgb_kernel(const float* __rest
         }
     }
     if (w0 >= W) return;
+    if (RECOLOUR) {
+        float rc[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rc[i][c] = colors[3 * i + c];
+#pragma unroll
+        for (int r = 0; r < PM_R; ++r)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float g0 = acc[r][j][0], g1 = acc[r][j][1], g2 = acc[r][j][2];
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    acc[r][j][c] = fmaxf(fmaxf(kpx_mul_rn(g0, rc[0][c]), kpx_mul_rn(g1, rc[1][c])), kpx_mul_rn(g2, rc[2][c]));
+            }
+    }
+    const int img = n / T, t = n - img * T;
 #pragma unroll
     for (int r = 0; r < PM_R; ++r) {
         const int h = h0 + r;
         if (h >= H) break;
-        float* o = out + (((size_t)n * H + h) * W + w0) * 3;
+        float* o = out + (((size_t)img * H + h) * ldo + (size_t)t * W + w0) * 3;
         if (VEC) {                                      // W % 4 == 0 and a 16-B aligned base: the quad is 48 contiguous, aligned bytes
             f32x4 v0 = {acc[r][0][0], acc[r][0][1], acc[r][0][2], acc[r][1][0]};
             f32x4 v1 = {acc[r][1][1], acc[r][1][2], acc[r][2][0], acc[r][2][1]};
@@ -717,17 +726,35 @@ __global__ __launch_bounds__(256) void point_maps_rgb_kernel(const float* __rest
     }
 }
 
-extern "C" int kpx_point_maps_rgb_f32(const float* mu, int N, int K, int H, int W, double inv_std, const float* colors, float* out, void* stream) {
-    if (!mu || !colors || !out || N < 1 || K < 1 || K > 64 || H < 2 || H > 1024 || W < 2 || W > 1024 || !(inv_std > 0)) return KPX_EINVAL;
+static int point_maps_rgb_launch(const float* mu, int N, int T, int K, int H, int W, double inv_std, const float* colors, bool recolour,
+                                 float* out, void* stream) {
     const float inv2 = (float)(inv_std * inv_std);          // as kpx_gaussian_maps_fwd_f32 (utils/model.py:58)
     const int tiles_x = (W + 63) / 64, tiles_y = (H + 16 * PM_R - 1) / (16 * PM_R);
-    if ((size_t)N * tiles_x * tiles_y > 0x7fffffff) return KPX_EINVAL;
-    const int tiles = tiles_x * tiles_y;
-    const dim3 grid((unsigned)(N * tiles)), block(256);
+    if ((size_t)N * T * tiles_x * tiles_y > 0x7fffffff) return KPX_EINVAL;
+    const int tiles = tiles_x * tiles_y, ldo = T * W;
+    const dim3 grid((unsigned)(N * T * tiles)), block(256);
     hipStream_t s = kpx_stream(stream);
-    if (W % 4 == 0 && (((uintptr_t)out) & 15) == 0)
-        hipLaunchKernelGGL(point_maps_rgb_kernel<true>, grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles);
+    const bool vec = W % 4 == 0 && (((uintptr_t)out) & 15) == 0;       // (then every frame's column offset and row stride are 16-B multiples)
+    if (vec && recolour)
+        hipLaunchKernelGGL((point_maps_rgb_kernel<true, true>), grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles, T, ldo);
+    else if (vec)
+        hipLaunchKernelGGL((point_maps_rgb_kernel<true, false>), grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles, T, ldo);
+    else if (recolour)
+        hipLaunchKernelGGL((point_maps_rgb_kernel<false, true>), grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles, T, ldo);
     else
-        hipLaunchKernelGGL(point_maps_rgb_kernel<false>, grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles);
+        hipLaunchKernelGGL((point_maps_rgb_kernel<false, false>), grid, block, 0, s, mu, K, H, W, inv2, colors, out, tiles_x, tiles, T, ldo);
     return kpx_launch_status();
+}
+
+extern "C" int kpx_point_maps_rgb_f32(const float* mu, int N, int K, int H, int W, double inv_std, const float* colors, float* out, void* stream) {
+    if (!mu || !colors || !out || N < 1 || K < 1 || K > 64 || H < 2 || H > 1024 || W < 2 || W > 1024 || !(inv_std > 0)) return KPX_EINVAL;
+    return point_maps_rgb_launch(mu, N, 1, K, H, W, inv_std, colors, false, out, stream);
+}
+
+extern "C" int kpx_point_seq_strip_rgb_f32(const float* mu, int N, int T, int K, int H, int W, double inv_std, const float* colors, int recolour,
+                                           float* out, void* stream) {
+    if (!mu || !colors || !out || N < 1 || T < 1 || K < 1 || K > 64 || H < 2 || H > 1024 || W < 2 || W > 1024 || (size_t)T * W > 65536 ||
+        !(inv_std > 0) || (recolour && K < 3))
+        return KPX_EINVAL;
+    return point_maps_rgb_launch(mu, N, T, K, H, W, inv_std, colors, recolour != 0, out, stream);
 }

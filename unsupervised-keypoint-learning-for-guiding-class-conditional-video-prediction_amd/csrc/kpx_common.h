@@ -41,6 +41,21 @@ __device__ __forceinline__ float kpx_wave_max(float v) {
     return v;
 }
 
+// Non-contractable fp32 operations: one rounding each, never fused into an fma.  hipcc contracts the __f*_rn intrinsics like plain
+// operators (their bodies carry the contract flag); these carry `fp contract(off)` themselves.
+__device__ __forceinline__ float kpx_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float kpx_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float kpx_sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+
 // d(act)/d(pre-activation) from the ACTIVATED value y (relu / leaky relu keep the sign of their argument)
 __device__ __forceinline__ float kpx_act_grad_from_y(float y, int act) {
     return act == KPX_ACT_RELU ? (y > 0.f ? 1.f : 0.f) : act == KPX_ACT_LRELU ? (y > 0.f ? 1.f : 0.01f) : 1.f;

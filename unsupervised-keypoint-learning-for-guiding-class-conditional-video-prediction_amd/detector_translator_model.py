@@ -10,13 +10,14 @@ all-reduce (RCCL) per flat gradient bucket per optimiser update, 1/world scaling
 import contextlib
 import logging
 import os
+import random
 import time
 from datetime import datetime
 
 import numpy as np
 import torch
 
-from . import model_utils, networks, ops, variables
+from . import model_utils, networks, ops, summary, variables
 from .base_model import BaseModel
 from .variables import Sym
 from .vgg import Vgg19
@@ -70,7 +71,7 @@ class DetectorTranslatorModel(BaseModel):
     name = 'detector_translator'       # reference :15 (checkpoint sub-directory)
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', vgg=None, process_group=None,
-                 image_size=128, seed=1234):
+                 image_size=128, seed=1234, colors_seed=0):
         super(DetectorTranslatorModel, self).__init__(is_training)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None      # reference :24-27
@@ -99,6 +100,10 @@ class DetectorTranslatorModel(BaseModel):
         # Adam state (two optimisers, reference :198 and :201): fp32 beta powers like TF's beta{1,2}_power variables
         self.beta1, self.beta2, self.adam_eps = np.float32(0.5), np.float32(0.999), np.float32(1e-8)
         self.beta_power = {'D': [np.float32(0.5), np.float32(0.999)], 'G': [np.float32(0.5), np.float32(0.999)]}
+        # key-point palette of the image summaries (reference :37): get_n_colors from random.Random(colors_seed) -- the reference draws it
+        # from the unseeded module-level random, so colors_seed=s reproduces its palette after random.seed(s) (as FinalModel)
+        self.colors = model_utils.get_n_colors(self.n_points, rng=random.Random(colors_seed))
+        self._colors_dev = None
         self.last = {}
         self._graphs = {}               # input shape -> captured step (graph, static inputs, outputs)
         self._eager_steps = {}          # input shape -> eager steps taken so far
@@ -271,6 +276,12 @@ class DetectorTranslatorModel(BaseModel):
             self._train_step_graphed(feed_dict)
         else:
             self._train_step_eager(feed_dict)
+        if should_write_summary and self.train_writer is not None:
+            # built from self.last after the step, outside any capture: a step without a summary launches nothing more
+            g_feed = ('image_G', 'future_image_G') if 'image_G' in feed_dict else ('image', 'future_image')
+            vals = self.loss_values()
+            self._write_summaries(self.train_writer, step, self._summaries(vals, self.last['fwd'], feed_dict[g_feed[0]], feed_dict[g_feed[1]])
+                                  + [[summary.scalar_value('lr', self.last['lr'])]])
         if should_write_log:
             vals = self.loss_values()
             duration = time.time() - start_time
@@ -664,16 +675,44 @@ class DetectorTranslatorModel(BaseModel):
                     loss_G_recon=recon, loss_G_adv=adv, loss_G=recon + adv, lr=self.last['lr'])
 
     def test_step(self, sess, feed_dict, step, test_idx, batch_size):
-        """reference test_step (:119-141): losses only, BN in batch-statistics mode, no updates."""
+        """reference test_step (:119-141): losses only, BN in batch-statistics mode, no updates.  The first batch of a
+        test pass (test_idx == 0) also writes the d-loss, g-loss and image summaries to the test writer, when there is one."""
         im, future_im = feed_dict['image'], feed_dict['future_image']
         start_time = time.time()
         with variables.as_default(self.store), torch.no_grad():
             fwd = self._define_forward_pass(im, future_im, update_moving=False)
             d = self._loss_D(fwd['final_output'], future_im)
             recon, adv = self._loss_G(fwd['final_output'], future_im)
-        loss_d = float(d.cpu()[0])
+        d_host = d.cpu().numpy()
+        loss_d = float(d_host[0])
         loss_g = float(recon.cpu()[0]) + float(adv.cpu()[0])
-        return loss_d, loss_g, time.time() - start_time, batch_size
+        duration = time.time() - start_time
+        if test_idx == 0 and self.test_writer is not None:
+            vals = dict(loss_D_real=float(d_host[1]), loss_D_fake=float(d_host[2]), loss_G_recon=float(recon.cpu()[0]),
+                        loss_G_adv=float(adv.cpu()[0]))
+            self._write_summaries(self.test_writer, step, self._summaries(vals, fwd, im, future_im))
+        return loss_d, loss_g, duration, batch_size
+
+    # ------------------------------------------------------------------------------------------------ summaries
+    def colors_tensor(self):
+        if self._colors_dev is None:
+            self._colors_dev = torch.tensor(self.colors, dtype=torch.float32, device=self.device)
+        return self._colors_dev
+
+    def _summaries(self, vals, fwd, im, future_im):
+        """The reference's merged summaries (:205-244) in add_summary order: [D_real, D_fake], [reconstruction_metric, G_adv_loss], the
+        image summary (max_outputs=2; key-point maps at image_size, colorize_point_maps(get_gaussian_maps(mu, [R, R])))."""
+        r, m = self.image_size, 2
+        colors = self.colors_tensor()
+        cur = model_utils.render_point_maps(fwd['current_points'][:m], (r, r), colors)
+        fut = model_utils.render_point_maps(fwd['future_points'][:m], (r, r), colors)
+        images = summary.image_summary([('future_im', future_im, 'unit255'), ('im', im, 'unit255'),
+                                        ('current_points', cur, 'identity'), ('future_points', fut, 'identity'),
+                                        ('future_im_crude', fwd['crude_output'], 'unit255_clip'),
+                                        ('future_im_pred', fwd['final_output'], 'unit255_clip'), ('mask', fwd['mask'], 'x255')], max_outputs=m)
+        return [[summary.scalar_value('D_real', vals['loss_D_real']), summary.scalar_value('D_fake', vals['loss_D_fake'])],
+                [summary.scalar_value('reconstruction_metric', vals['loss_G_recon']), summary.scalar_value('G_adv_loss', vals['loss_G_adv'])],
+                images]
 
     def collect_test_results(self, results, step):
         """reference collect_test_results (:143-158)."""

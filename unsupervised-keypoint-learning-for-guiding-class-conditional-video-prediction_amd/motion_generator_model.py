@@ -8,13 +8,14 @@ The matmuls run on the implicit-GEMM conv kernels (1x1 "convolutions" over [B,1,
 cross entropy and Adam are HIP kernels; the weight gradient of an LSTM layer is one GEMM over all T*B rows.
 """
 import logging
+import random
 import time
 from datetime import datetime
 
 import numpy as np
 import torch
 
-from . import networks, ops, variables
+from . import model_utils, networks, ops, summary, variables
 from .base_model import BaseModel
 from .variables import Sym
 
@@ -26,7 +27,7 @@ class MotionGeneratorModel(BaseModel):
     name = 'motion_generator'          # reference :16 (checkpoint sub-directory)
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777,
-                 discr_cells=(1024, 1024)):
+                 discr_cells=(1024, 1024), colors_seed=0):
         super(MotionGeneratorModel, self).__init__(is_training)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
@@ -45,6 +46,9 @@ class MotionGeneratorModel(BaseModel):
         self.store = variables.VariableStore(device=self.device, seed=seed)
         self.beta1, self.beta2, self.adam_eps = np.float32(0.5), np.float32(0.999), np.float32(1e-8)
         self.beta_power = {'D': [np.float32(0.5), np.float32(0.999)], 'G': [np.float32(0.5), np.float32(0.999)]}
+        # key-point palette of the image summaries (reference :37), drawn as DetectorTranslatorModel / FinalModel draw theirs
+        self.colors = model_utils.get_n_colors(self.n_points, rng=random.Random(colors_seed))
+        self._colors_dev = None
         self.last = {}
 
     def build(self, inputs=None):
@@ -135,6 +139,9 @@ class MotionGeneratorModel(BaseModel):
             self._apply_adam('G', lr)
         self.global_step += 1
         self.last = dict(d_losses=d_losses.detach(), recon=recon.detach(), kl=kl.detach(), adv=adv.detach(), lr=float(lr), pred_seq=pred.detach())
+        if should_write_summary and self.train_writer is not None:
+            self._write_summaries(self.train_writer, step, self._summaries(self.loss_values(), self.last['pred_seq'], feed_dict)
+                                  + [[summary.scalar_value('lr', self.last['lr'])]])
         if should_write_log:
             v = self.loss_values()
             duration = time.time() - start_time
@@ -155,8 +162,43 @@ class MotionGeneratorModel(BaseModel):
             pred, kl, real = self._generate(kp, rs, ac, self._noise(feed_dict, 'eps_G', kp.shape[0]))
             d = self._loss_D(pred, real)
             recon, kl, adv = self._loss_G(pred, real, kl)
-        loss_g = float(recon.cpu()[0]) + float(kl.cpu()[0]) + float(adv.cpu()[0])
-        return float(d.cpu()[0]), loss_g, time.time() - start_time, batch_size
+        d_host = d.cpu().numpy()
+        recon_h, kl_h, adv_h = float(recon.cpu()[0]), float(kl.cpu()[0]), float(adv.cpu()[0])
+        loss_g = recon_h + kl_h + adv_h
+        duration = time.time() - start_time
+        if test_idx == 0 and self.test_writer is not None:
+            vals = dict(loss_D_real=float(d_host[1]), loss_D_fake=float(d_host[2]), loss_G_recon=recon_h, loss_G_kl=kl_h, loss_G_adv=adv_h)
+            self._write_summaries(self.test_writer, step, self._summaries(vals, pred, feed_dict))
+        return float(d_host[0]), loss_g, duration, batch_size
+
+    # ------------------------------------------------------------------------------------------------ summaries
+    def colors_tensor(self):
+        if self._colors_dev is None:
+            self._colors_dev = torch.tensor(self.colors, dtype=torch.float32, device=self.device)
+        return self._colors_dev
+
+    def _summaries(self, vals, pred_seq, feed_dict):
+        """The reference's merged summaries (:217-276) in add_summary order: [D_real, D_fake], [recon_loss, kl_loss, G_adv_loss], the image
+        summary (max_outputs=2): 'im' (only when the feed has an 'image'), 'first_pt' (128 x 128), 'predicted_pose_sequence' and
+        'real_pose_sequence' (32 frames of 64 x 64 along the width, then colorize_point_maps a second time over the 3-channel strip).
+        The second colourisation reads colors[0:3]: with K < 3 the reference cannot build it, and the two strips are left out."""
+        m, k = 2, self.n_points
+        colors = self.colors_tensor()
+        kp = feed_dict['keypoints']
+        b = kp.shape[0]
+        items = []
+        if feed_dict.get('image') is not None:
+            items.append(('im', feed_dict['image'], 'unit255'))
+        items.append(('first_pt', model_utils.render_point_maps(kp.reshape(b, k, 2)[:m], (128, 128), colors), 'identity'))
+        if k >= 3:
+            pred = pred_seq.reshape(b, N_FUTURE_FRAMES, k, 2)
+            real = feed_dict['real_seq'].reshape(b, N_FUTURE_FRAMES, k, 2)
+            items.append(('predicted_pose_sequence', ops.point_seq_strip_rgb(pred, 64, 64, colors, recolour=True, max_outputs=m), 'identity'))
+            items.append(('real_pose_sequence', ops.point_seq_strip_rgb(real, 64, 64, colors, recolour=True, max_outputs=m), 'identity'))
+        return [[summary.scalar_value('D_real', vals['loss_D_real']), summary.scalar_value('D_fake', vals['loss_D_fake'])],
+                [summary.scalar_value('recon_loss', vals['loss_G_recon']), summary.scalar_value('kl_loss', vals['loss_G_kl']),
+                 summary.scalar_value('G_adv_loss', vals['loss_G_adv'])],
+                summary.image_summary(items, max_outputs=m)]
 
     def collect_test_results(self, results, step):
         """reference collect_test_results (:119-135)."""

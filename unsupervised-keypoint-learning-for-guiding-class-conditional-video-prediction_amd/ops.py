@@ -1371,6 +1371,56 @@ def point_maps_rgb(mu, h, w, colors, inv_std=14.3, out=None):
     return out
 
 
+def point_seq_strip_rgb(mu, h, w, colors, recolour=True, inv_std=14.3, max_outputs=None):
+    """The reference's pose-sequence strip (motion_generator_model.py:225-248, 258-263) in one launch, forward only: mu [N,T,K,2] (x,y)
+    -> [N,h,T*w,3], frame t (= ``point_maps_rgb`` of mu[:, t], same bits) in columns [t*w, (t+1)*w).  ``recolour``: the summary's second
+    colorize_point_maps over the 3-channel strip, out[...,c] = max_{i<3} strip[...,i] * colors[i][c] (K >= 3).  ``max_outputs``: render
+    only the first images."""
+    _require_gpu(mu)
+    _require_gpu(colors)
+    if mu.dim() != 4 or mu.shape[3] != 2:
+        raise _lib.KpxError('point_seq_strip_rgb: mu must be [N,T,K,2] (got %s)' % (tuple(mu.shape),))
+    if max_outputs is not None:
+        mu = mu[:max_outputs]
+    mu = mu.contiguous()
+    colors = colors.contiguous()
+    n, t, k, _ = mu.shape
+    if mu.dtype != torch.float32 or colors.dtype != torch.float32 or tuple(colors.shape) != (k, 3) or colors.device != mu.device:
+        raise _lib.KpxError('point_seq_strip_rgb: mu [N,T,K,2] and colors [K,3], fp32 on one device (got %s %s, %s %s)'
+                            % (tuple(mu.shape), mu.dtype, tuple(colors.shape), colors.dtype))
+    if recolour and k < 3:
+        raise _lib.KpxError('point_seq_strip_rgb: the recolour reads colors[0:3] and needs K >= 3 (got K = %d)' % k)
+    out = torch.empty((n, h, t * w, 3), dtype=torch.float32, device=mu.device)
+    check(lib.kpx_point_seq_strip_rgb_f32(mu.data_ptr(), n, t, k, int(h), int(w), float(inv_std), colors.data_ptr(), 1 if recolour else 0,
+                                          out.data_ptr(), _stream()), 'kpx_point_seq_strip_rgb_f32')
+    return out
+
+
+SUMMARY_PREMAPS = {'identity': 0, 'x255': 1, 'unit255': 2, 'unit255_clip': 3}   # = KPX_PREMAP_* of include/kpx.h
+SUMMARY_SLICES = 64                                                               # = KPX_SUMMARY_SLICES
+
+
+def summary_image_u8(x, premap='identity', max_outputs=2):
+    """tf.summary.image's float -> uint8 conversion (TF 1.12 SummaryImageOp / NormalizeFloatImage) of the first ``max_outputs`` images of
+    x [N,H,W,C] fp32 (C in 1, 3, 4), after the pre-map ``premap``: 'identity' x, 'x255' x*255 (the mask), 'unit255' (x+1)/2*255 (the
+    input frames), 'unit255_clip' clip((x+1)/2*255, 0, 255) (the predictions).  -> uint8 [min(N, max_outputs),H,W,C] on x's device."""
+    _require_gpu(x)
+    if premap not in SUMMARY_PREMAPS:
+        raise _lib.KpxError('summary_image_u8: premap must be one of %s (got %r)' % (sorted(SUMMARY_PREMAPS), premap))
+    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[3] not in (1, 3, 4) or x.shape[0] < 1 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise _lib.KpxError('summary_image_u8: x must be a non-empty fp32 [N,H,W,C] tensor with C in (1, 3, 4) (got %s %s)'
+                            % (tuple(x.shape), x.dtype))
+    if int(max_outputs) < 1:
+        raise _lib.KpxError('summary_image_u8: max_outputs must be >= 1 (got %r)' % (max_outputs,))
+    x = x[:int(max_outputs)].contiguous()
+    n, h, w, c = x.shape
+    work = torch.empty(2 * SUMMARY_SLICES * n, dtype=torch.float32, device=x.device)
+    out = torch.empty((n, h, w, c), dtype=torch.uint8, device=x.device)
+    check(lib.kpx_summary_image_u8_f32(x.data_ptr(), n, h, w, c, SUMMARY_PREMAPS[premap], work.data_ptr(), out.data_ptr(), _stream()),
+          'kpx_summary_image_u8_f32')
+    return out
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
