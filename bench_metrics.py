@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Measure the frame metrics (kpx_frame_metrics_f32, evaluate.py --metrics) on one MI355X.
+
+1. The kernel alone on the BASELINE configs[4] batch (2 048 frame pairs of 128x128x3, the png8 form evaluate.py runs, and the plain fp32
+   form): device-event time of each launch after warm-up; median us, effective bytes/s of the two inputs (805 MB, more than the 256 MB
+   Infinity Cache) read once, and its fraction of the 6.29 TB/s measured copy rate.
+2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
+   one process; median ms of each and the overhead in %.
+
+    python bench_metrics.py [--launches 40] [--rollouts 10]
+
+Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+N_FRAMES, RES, B = 64 * 32, 128, 64
+COPY_RATE = 6.29e12                  # measured float4 copy rate of the MI355X (MI355X_MICROARCH: HBM)
+
+
+def kernel_leg(dev, launches, png8):
+    from kpx_amd import ops
+    g = torch.Generator(device=dev).manual_seed(1)
+    a = torch.rand((N_FRAMES, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    b = torch.rand((N_FRAMES, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    out = torch.empty((N_FRAMES, 3), dtype=torch.float32, device=dev)
+    for _ in range(3):
+        ops.frame_metrics(a, b, png8=png8, out=out)
+    torch.cuda.synchronize(dev)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
+    for e0, e1 in ev:
+        e0.record()
+        ops.frame_metrics(a, b, png8=png8, out=out)
+        e1.record()
+    torch.cuda.synchronize(dev)
+    us = [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
+    med = statistics.median(us)
+    nbytes = 2 * a.numel() * 4
+    assert bool(torch.isfinite(out).all())
+    return {'shape': [N_FRAMES, RES, RES, 3], 'png8': png8, 'input_mb': round(nbytes / 1e6, 1), 'launches': launches,
+            'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+            'gb_per_s': round(nbytes / (med * 1e-6) / 1e9, 1), 'frac_of_copy_rate': round(nbytes / (med * 1e-6) / COPY_RATE, 3)}
+
+
+def rollout_leg(dev, rollouts):
+    import kpx_amd
+    from kpx_amd import ops
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    real = torch.rand((N_FRAMES, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    out = torch.empty((N_FRAMES, 3), dtype=torch.float32, device=dev)
+    feed = {'image': im, 'action_code': act}
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    for _ in range(3):                                    # eager, capture, one replay
+        o = fm.run(None, feed, z=z)
+    ops.frame_metrics(o['pred_im_seq'].reshape(N_FRAMES, RES, RES, 3), real, png8=True, out=out)
+    torch.cuda.synchronize(dev)
+    ms = {False: [], True: []}
+    for _ in range(rollouts):
+        for score in (False, True):
+            t0 = time.perf_counter()
+            o = fm.run(None, feed, z=z)
+            if score:
+                ops.frame_metrics(o['pred_im_seq'].reshape(N_FRAMES, RES, RES, 3), real, png8=True, out=out)
+            torch.cuda.synchronize(dev)
+            ms[score].append((time.perf_counter() - t0) * 1e3)
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    return {'batch': B, 'frames': N_FRAMES, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 1,
+            'off_ms': round(off, 3), 'on_ms': round(on, 3), 'delta_ms': round(on - off, 3), 'overhead_pct': round(100 * (on - off) / off, 2),
+            'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--launches', type=int, default=40)
+    ap.add_argument('--rollouts', type=int, default=10)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_metrics.py needs the MI355X')
+    dev = torch.device('cuda:0')
+    res = {'kernel_png8': kernel_leg(dev, args.launches, True), 'kernel_f32': kernel_leg(dev, args.launches, False)}
+    torch.cuda.empty_cache()
+    res['rollout_c4'] = rollout_leg(dev, args.rollouts)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

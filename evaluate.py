@@ -2,7 +2,7 @@
 """Evaluation entry point with the reference's CLI (reference: evaluate.py:13-163):
 
     python evaluate.py --config configs/penn.yaml --checkpoint_stage1 S1.npz --checkpoint_stage2 S2.npz [--save_dir results/eval]
-                       [--synthetic N] [--colors_seed S] [--no-save]
+                       [--synthetic N] [--colors_seed S] [--no-save] [--metrics [--samples N]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -10,7 +10,13 @@ pred_points/ (:96-97, :107-109, :126-128) in the palette of ``random.Random(--co
 test subset of ``paths.data_dir`` is read through kpx_amd.data.SequenceDataLoader (the reference's data/sequence_dataloader.py);
 ``--synthetic N`` feeds N random images with random one-hot action codes instead.  Checkpoints: the ``.npz`` containers written
 by this repo or TensorFlow V2 bundle prefixes (TF variable names either way).
+
+``--metrics`` (data path only) scores every predicted frame against the real future frame -- SSIM and PSNR of the 8-bit frames the script
+writes (``kpx_amd.ops.frame_metrics``, one launch per rollout) -- and writes ``<save_dir>/metrics.npz`` (``ssim``, ``psnr``, ``mse``:
+[samples, draws, 32]) and ``<save_dir>/metrics.json`` (``summarise_metrics``).  ``--samples N`` runs the rollout N times per batch with
+fresh z; the PNGs come from draw 0.
 """
+import json
 import os
 import sys
 import time
@@ -38,6 +44,61 @@ def _save_img(file_path, img, rescale=False):
     Image.fromarray(img, mode=mode).save(file_path)
 
 
+METRICS_DEFINITION = (
+    'Per predicted frame against the real future frame, both as the 8-bit PNGs written to pred_seq/ and real_seq/ '
+    '(q = uint8(trunc(fl32(fl32(0.5 * fl32(x + 1)) * 255))), scored as q / 255 with dynamic range 1): '
+    'SSIM as TF 1.12 tf.image.ssim (11x11 Gaussian window, sigma 1.5, VALID, k1 = 0.01, k2 = 0.03; mean over positions, then channels), '
+    'MSE = mean (a - b)^2 over pixels and channels, PSNR = -10 log10(MSE) dB as tf.image.psnr (+inf for MSE = 0). '
+    'mean / per_frame: over samples and draws of z. best_of_draws / best_of_draws_per_frame: per sample the draw with the best mean over '
+    'its 32 frames, chosen per metric (highest SSIM, highest PSNR, lowest MSE; a tie goes to the lowest draw), then the mean over samples. '
+    'Non-finite values are null; n_nonfinite counts the frames with a non-finite metric.')
+
+
+def _json_num(v):
+    v = float(v)
+    return v if np.isfinite(v) else None
+
+
+def summarise_metrics(ssim, psnr, mse):
+    """metrics.json content from per-frame metrics of shape [S, N, T] (S samples, N draws of z, T predicted frames); numpy only."""
+    arrs = {'ssim': np.asarray(ssim, np.float64), 'psnr': np.asarray(psnr, np.float64), 'mse': np.asarray(mse, np.float64)}
+    shape = arrs['ssim'].shape
+    if len(shape) != 3 or any(a.shape != shape for a in arrs.values()):
+        raise ValueError('summarise_metrics: ssim, psnr and mse must share one [S, N, T] shape (got %s)'
+                         % [a.shape for a in arrs.values()])
+    s, n, t = shape
+    bad = ~(np.isfinite(arrs['ssim']) & np.isfinite(arrs['psnr']) & np.isfinite(arrs['mse']))
+    out = {'definition': METRICS_DEFINITION, 'n_samples': s, 'n_draws': n, 'n_nonfinite': int(bad.sum())}
+    for name, x in arrs.items():
+        lower_is_better = name == 'mse'
+        with np.errstate(invalid='ignore'):
+            draw_mean = x.mean(axis=2)                                           # [S, N]
+            key = np.where(np.isnan(draw_mean), np.inf if lower_is_better else -np.inf, draw_mean)
+            best = np.argmin(key, axis=1) if lower_is_better else np.argmax(key, axis=1)   # first extreme: ties go to the lowest draw
+            best_frames = x[np.arange(s), best]                                  # [S, T]
+            out[name] = {'mean': _json_num(x.mean()), 'per_frame': [_json_num(v) for v in x.mean(axis=(0, 1))],
+                         'best_of_draws': _json_num(best_frames.mean()),
+                         'best_of_draws_per_frame': [_json_num(v) for v in best_frames.mean(axis=0)],
+                         'best_draw': [int(i) for i in best]}
+    return out
+
+
+def _write_metrics(save_dir, scores, n_draws, n_frames):
+    """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them."""
+    host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
+    arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
+    ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
+    os.makedirs(save_dir, exist_ok=True)
+    np.savez(osp.join(save_dir, 'metrics.npz'), ssim=ssim, psnr=psnr, mse=mse)
+    res = summarise_metrics(ssim, psnr, mse)
+    with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
+        json.dump(res, f, indent=1, allow_nan=False)
+    fmt = lambda v, spec: 'n/a' if v is None else spec % v
+    print('metrics: %d samples x %d draws: SSIM %s (best of draws %s), PSNR %s dB (best of draws %s), MSE %s; %d non-finite frames'
+          % (res['n_samples'], res['n_draws'], fmt(res['ssim']['mean'], '%.4f'), fmt(res['ssim']['best_of_draws'], '%.4f'),
+             fmt(res['psnr']['mean'], '%.2f'), fmt(res['psnr']['best_of_draws'], '%.2f'), fmt(res['mse']['mean'], '%.3e'), res['n_nonfinite']))
+
+
 def _save_img_sequence(output_dir, img_seq, rescale=False):
     """reference :151-156"""
     os.makedirs(output_dir, exist_ok=True)
@@ -56,7 +117,13 @@ def main(argv=None):
     parser.add_argument('--batch', type=int, default=8)             # reference :27
     parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette (the reference draws it unseeded)')
     parser.add_argument('--no-save', action='store_true')
+    parser.add_argument('--metrics', action='store_true', help='score the predictions: <save_dir>/metrics.npz and metrics.json')
+    parser.add_argument('--samples', type=int, default=1, help='rollouts per batch with fresh z (PNGs from the first)')
     args = parser.parse_args(argv)
+    if args.metrics and args.synthetic:
+        parser.error('--metrics scores predictions against the real future frames, and --synthetic inputs have no ground truth')
+    if args.samples < 1:
+        parser.error('--samples must be >= 1 (got %d)' % args.samples)
     config = load_config(args.config)
     for p in (args.checkpoint_stage1, args.checkpoint_stage2):       # reference :34-38
         if not (osp.exists(p) or osp.exists(p + '.index')):                 # .npz file or TensorFlow bundle prefix
@@ -73,11 +140,23 @@ def main(argv=None):
     if not args.synthetic:                       # reference :43-51, :84-130: the test subset through the sequence loader
         loader = kpx_amd.data.SequenceDataLoader(config['paths']['data_dir'], 'test', n_points=config['model']['n_pts'], n_action=n_action,
                                                  random_order=False, randomness=False, with_image_seq=True)
+        scores, n_frames = [], 32
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
-            outputs = model.run(None, {'image': batch['image'], 'action_code': batch['action_code']})
             bsz = batch['image'].shape[0]
-            frames += bsz * 32
-            if not args.no_save:
+            if args.metrics:
+                real_seq = batch['real_im_seq']
+                n_frames = real_seq.shape[1]
+                real_flat = real_seq.reshape(bsz * n_frames, *real_seq.shape[2:])
+                score = torch.empty((args.samples, bsz * n_frames, 3), dtype=torch.float32, device=dev)
+                scores.append(score)
+            for draw in range(args.samples):
+                outputs = model.run(None, {'image': batch['image'], 'action_code': batch['action_code']})
+                frames += bsz * 32
+                if args.metrics:             # enqueued before the next run() overwrites the graph's output buffers
+                    pred = outputs['pred_im_seq']
+                    kpx_amd.ops.frame_metrics(pred.reshape(bsz * n_frames, *pred.shape[2:]), real_flat, png8=True, out=score[draw])
+                if draw > 0 or args.no_save:
+                    continue
                 o = {k: v.cpu().numpy() for k, v in outputs.items() if isinstance(v, torch.Tensor)}
                 real = batch['real_im_seq'].cpu().numpy()
                 for batch_idx in range(bsz):
@@ -93,6 +172,8 @@ def main(argv=None):
                     sample_idx += 1
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
+        if args.metrics:
+            _write_metrics(args.save_dir, scores, args.samples, n_frames)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 7
+#define KPX_ABI_VERSION 8
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -308,6 +308,16 @@ int kpx_point_seq_strip_rgb_f32(const float* mu, int N, int T, int K, int H, int
 #define KPX_SUMMARY_SLICES 64
 enum { KPX_PREMAP_IDENTITY = 0, KPX_PREMAP_X255 = 1, KPX_PREMAP_UNIT255 = 2, KPX_PREMAP_UNIT255_CLIP = 3 };
 int kpx_summary_image_u8_f32(const float* x, int N, int H, int W, int C, int premap, float* work, uint8_t* out, void* stream);
+
+/* ---- video-prediction frame metrics (evaluate.py --metrics): TF 1.12 tf.image.ssim and tf.image.psnr of frame pairs, DESIGN.md section 2.
+ * a, b fp32 NHWC [N,H,W,C] contiguous, C in {1,3}, H and W in [11,1024], dynamic range L > 0 (finite) -> out fp32 [N,3] = (ssim, mse, psnr).
+ *   SSIM: separable 11-tap Gaussian window (sigma 1.5), VALID, c1 = (0.01 L)^2, c2 = (0.03 L)^2, mean of lum * cs over positions per channel,
+ *   then over channels; moments in fp64.  mse = mean (a - b)^2 over H*W*C; psnr = 20 log10(L) - 10 log10(mse) (+inf for mse == 0).
+ *   png8 = 1: both inputs quantised as evaluate.py writes PNGs, q = clamp(uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))), 0, 255) (NaN -> 0),
+ *   and scored as q / 255 with L = 1 (the argument L is then not used beyond its check).
+ * One launch, one workgroup per frame; frame n's result is bitwise the same for every N and position in the batch and from run to run.
+ * No allocation, copy or synchronisation (capturable).  Added in ABI version 8. */
+int kpx_frame_metrics_f32(const float* a, const float* b, int N, int H, int W, int C, float L, int png8, float* out, void* stream);
 
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */

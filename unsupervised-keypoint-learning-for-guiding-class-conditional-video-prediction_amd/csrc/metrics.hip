@@ -1,0 +1,204 @@
+// Video-prediction frame metrics: SSIM (TF 1.12 tf.image.ssim: 11-tap Gaussian window, sigma 1.5, VALID, k1 = 0.01, k2 = 0.03,
+// compensation 1) and MSE / PSNR (tf.image.psnr) of frame pairs a[n], b[n] (fp32 NHWC, C in {1,3}).  DESIGN.md section 2 has the definition.
+//
+// One workgroup per frame.  The lanes cover (output column, channel) of a vertical strip of the frame (one strip at 128 x 128 x 3: 118 * 3 =
+// 354 lanes in 6 waves) and walk down its rows:
+//   - each input row of both images is staged in LDS (double-buffered; 16-byte loads when rows are 16-byte aligned), with D rows in flight
+//     in registers ahead of the one being filtered;
+//   - a lane filters its four moments (a, b, a*b, a^2 + b^2) horizontally from LDS in fp64 and pushes them into an 11-deep ring held in
+//     registers (the row loop is unrolled by 11 so that every ring index is a constant);
+//   - from row 10 on, the vertical filter over the ring gives mu_a, mu_b, S_ab, S_s of one output position, whose lum * cs is accumulated;
+//   - (a - b)^2 of the staged row is accumulated in the same pass.
+// fp64 moments: S_s - (mu_a^2 + mu_b^2) cancels against c2 = 9e-4 * L^2 on flat content, where fp32 sums miss 1e-5 in SSIM.
+// The per-lane sums are reduced in a fixed order (wave butterflies, then waves in order): frame n's result depends on frame n alone.
+// png8: both inputs are first quantised as evaluate.py writes PNGs, q = uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))) clamped to [0, 255],
+// and scored as q / 255 with L = 1 -- computed exactly as q with L = 255 (the same quantities up to fp64 rounding), mse scaled by 1/255^2.
+#include "kpx_common.h"
+#include <cmath>
+
+namespace {
+
+constexpr int FM_TAPS = 11;
+constexpr int FM_MAX_THREADS = 512;
+constexpr int FM_PREFETCH = 3;                                        // staged rows in flight (registers) ahead of the filtered row
+constexpr int FM_MAX_LF = FM_MAX_THREADS + 10 * 3 + 8;                // floats of one staged image row: strip columns + halo, rounded to 4
+
+struct FmParams {
+    double w[FM_TAPS];                // separable Gaussian window
+    double c1, c2;                    // (k1 L)^2, (k2 L)^2
+    double npos;                      // (H - 10) (W - 10) C
+    double npix;                      // H W C
+    double mse_scale;                 // 1, or 1 / 255^2 for png8
+    double psnr_l;                    // 20 log10(L) of the reported scale
+};
+
+__device__ __forceinline__ float fm_png8(float x) {
+    float v = kpx_mul_rn(kpx_mul_rn(0.5f, kpx_add_rn(x, 1.0f)), 255.0f);
+    v = fminf(fmaxf(v, 0.0f), 255.0f);                                 // NaN -> 0
+    return truncf(v);
+}
+
+// lum * cs of one position and channel, in TF's order of operations.  Not contracted: for a == b the numerator and the denominator are
+// the same roundings, so the term is exactly 1.
+__device__ __forceinline__ double fm_ssim_term(double ma, double mb, double sab, double ss, double c1, double c2) {
+#pragma clang fp contract(off)
+    const double p = ma * mb, q = ma * ma, s = mb * mb;
+    const double num0 = p + p, den0 = q + s;
+    const double lum_n = num0 + c1, lum_d = den0 + c1;
+    const double cs_n = ((sab + sab) - num0) + c2, cs_d = (ss - den0) + c2;
+    return (lum_n * cs_n) / (lum_d * cs_d);
+}
+
+template <bool VEC>
+__device__ __forceinline__ f32x4 fm_load(const float* __restrict__ src, int j, int lf) {
+    f32x4 v;
+    if (VEC) {
+        v = *reinterpret_cast<const f32x4*>(src + j);
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = j + e < lf ? src[j + e] : 0.0f;
+    }
+    return v;
+}
+
+template <int C, bool VEC, bool PNG8>
+__global__ __launch_bounds__(FM_MAX_THREADS) void frame_metrics_kernel(const float* __restrict__ a, const float* __restrict__ b, int H, int W,
+                                                                       int SC, FmParams p, float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float stage[2][2][FM_MAX_LF];   // [buffer][image][staged floats]
+    __shared__ double red[2][FM_MAX_THREADS / KPX_WAVE];
+    const int n = blockIdx.x, tid = threadIdx.x, T = blockDim.x;
+    const int Wo = W - 10;
+    const int x = tid / C, c = tid - x * C;
+    const size_t row_floats = (size_t)W * C;
+    double ssim_acc = 0.0, mse_acc = 0.0;
+
+    for (int x0 = 0; x0 < Wo; x0 += SC) {
+        const int sc = min(SC, Wo - x0);                              // output columns of this strip
+        const int lf = (sc + 10) * C;                                  // staged floats per image row
+        const int own = x0 + sc == Wo ? lf : sc * C;                   // floats this strip adds to the MSE (the last one takes the halo)
+        const int slots = (lf + 3) >> 2;                               // 4-float slots per image row; 2 * slots <= T
+        const bool loader = tid < 2 * slots;
+        const int img = tid < slots ? 0 : 1;
+        const int j4 = 4 * (tid - img * slots);
+        const float* src = (img ? b : a) + (size_t)n * H * row_floats + (size_t)x0 * C;
+        const bool active = x < sc;
+
+        auto put = [&](int buf, f32x4 v) {
+            if (PNG8) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fm_png8(v[e]);
+            }
+            *reinterpret_cast<f32x4*>(&stage[buf][img][j4]) = v;
+        };
+        f32x4 g[FM_PREFETCH];                                          // g[i] holds row r + 1 + i at the top of iteration r
+        if (loader) {
+            put(0, fm_load<VEC>(src, j4, lf));
+#pragma unroll
+            for (int i = 0; i < FM_PREFETCH; ++i)
+                if (1 + i < H) g[i] = fm_load<VEC>(src + (size_t)(1 + i) * row_floats, j4, lf);
+        }
+        __syncthreads();
+
+        double h[FM_TAPS][4];                                          // ring: horizontal moments of rows r-10..r, slot = row % 11
+        for (int r0 = 0; r0 < H; r0 += FM_TAPS) {
+#pragma unroll
+            for (int k = 0; k < FM_TAPS; ++k) {
+                const int r = r0 + k;
+                if (r >= H) continue;                                  // (wave-uniform; a break would keep the loop from unrolling)
+                if (loader && r + 1 < H) {                             // stage row r + 1 (its buffer was last read in iteration r - 1)
+                    put((r + 1) & 1, g[0]);
+#pragma unroll
+                    for (int i = 0; i + 1 < FM_PREFETCH; ++i) g[i] = g[i + 1];
+                    if (r + 1 + FM_PREFETCH < H) g[FM_PREFETCH - 1] = fm_load<VEC>(src + (size_t)(r + 1 + FM_PREFETCH) * row_floats, j4, lf);
+                }
+                const float* sa = stage[r & 1][0];
+                const float* sb = stage[r & 1][1];
+                for (int j = tid; j < own; j += T) {
+                    const double d = (double)sa[j] - (double)sb[j];
+                    mse_acc = fma(d, d, mse_acc);
+                }
+                if (active) {
+                    double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+#pragma unroll
+                    for (int i = 0; i < FM_TAPS; ++i) {
+                        const double da = sa[(x + i) * C + c], db = sb[(x + i) * C + c];
+                        const double w = p.w[i];
+                        m0 = fma(w, da, m0);
+                        m1 = fma(w, db, m1);
+                        m2 = fma(w, da * db, m2);
+                        m3 = fma(w, fma(da, da, db * db), m3);
+                    }
+                    h[k][0] = m0; h[k][1] = m1; h[k][2] = m2; h[k][3] = m3;
+                    if (r >= FM_TAPS - 1) {
+                        double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
+#pragma unroll
+                        for (int i = 0; i < FM_TAPS; ++i) {                // row r - 10 + i sits in slot (k + 1 + i) % 11
+                            const int s = (k + 1 + i) % FM_TAPS;
+                            const double w = p.w[i];
+                            v0 = fma(w, h[s][0], v0);
+                            v1 = fma(w, h[s][1], v1);
+                            v2 = fma(w, h[s][2], v2);
+                            v3 = fma(w, h[s][3], v3);
+                        }
+                        ssim_acc += fm_ssim_term(v0, v1, v2, v3, p.c1, p.c2);
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+
+    ssim_acc = kpx_wave_sum_d(ssim_acc);
+    mse_acc = kpx_wave_sum_d(mse_acc);
+    const int wave = tid / KPX_WAVE, nwaves = T / KPX_WAVE;
+    if ((tid & (KPX_WAVE - 1)) == 0) { red[0][wave] = ssim_acc; red[1][wave] = mse_acc; }
+    __syncthreads();
+    if (tid == 0) {
+        double s = red[0][0], m = red[1][0];
+        for (int i = 1; i < nwaves; ++i) { s += red[0][i]; m += red[1][i]; }
+        const double ssim = s / p.npos;                                 // exactly 1 when every term is
+        const double mse = m / p.npix * p.mse_scale;
+        const double psnr = p.psnr_l - 10.0 * log10(mse);               // +inf for mse == 0
+        out[3 * (size_t)n + 0] = (float)ssim;
+        out[3 * (size_t)n + 1] = (float)mse;
+        out[3 * (size_t)n + 2] = (float)psnr;
+    }
+}
+
+template <int C, bool PNG8>
+int fm_launch(const float* a, const float* b, int N, int H, int W, bool vec, int T, int SC, const FmParams& p, float* out, hipStream_t s) {
+    if (vec)
+        hipLaunchKernelGGL((frame_metrics_kernel<C, true, PNG8>), dim3(N), dim3(T), 0, s, a, b, H, W, SC, p, out);
+    else
+        hipLaunchKernelGGL((frame_metrics_kernel<C, false, PNG8>), dim3(N), dim3(T), 0, s, a, b, H, W, SC, p, out);
+    return kpx_launch_status();
+}
+
+}  // namespace
+
+extern "C" int kpx_frame_metrics_f32(const float* a, const float* b, int N, int H, int W, int C, float L, int png8, float* out, void* stream) {
+    if (!a || !b || !out || N < 1 || H < 11 || H > 1024 || W < 11 || W > 1024 || !(C == 1 || C == 3) || !(png8 == 0 || png8 == 1) ||
+        !(L > 0.0f) || !std::isfinite(L))
+        return KPX_EINVAL;
+    FmParams p;
+    double ws = 0.0;
+    for (int i = 0; i < FM_TAPS; ++i) ws += p.w[i] = std::exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+    for (int i = 0; i < FM_TAPS; ++i) p.w[i] /= ws;
+    const double l = png8 ? 255.0 : (double)L;                        // png8 scores q (integers) at L = 255, i.e. q / 255 at L = 1
+    p.c1 = (0.01 * l) * (0.01 * l);
+    p.c2 = (0.03 * l) * (0.03 * l);
+    p.npos = (double)(H - 10) * (W - 10) * C;
+    p.npix = (double)H * W * C;
+    p.mse_scale = png8 ? 1.0 / (255.0 * 255.0) : 1.0;
+    p.psnr_l = png8 ? 0.0 : 20.0 * std::log10((double)L);
+    // workgroup: one lane per (output column, channel) of a strip, up to FM_MAX_THREADS; strips of SC columns (a multiple of 4, so that
+    // every strip starts on a 16-byte boundary when the rows do)
+    const int Wo = W - 10;
+    int T = (Wo * C + KPX_WAVE - 1) / KPX_WAVE * KPX_WAVE;
+    T = T > FM_MAX_THREADS ? FM_MAX_THREADS : T;
+    const int SC = (T / C) & ~3;
+    const bool vec = (W * C) % 4 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0;
+    hipStream_t s = kpx_stream(stream);
+    if (C == 1) return png8 ? fm_launch<1, true>(a, b, N, H, W, vec, T, SC, p, out, s) : fm_launch<1, false>(a, b, N, H, W, vec, T, SC, p, out, s);
+    return png8 ? fm_launch<3, true>(a, b, N, H, W, vec, T, SC, p, out, s) : fm_launch<3, false>(a, b, N, H, W, vec, T, SC, p, out, s);
+}

@@ -1421,6 +1421,33 @@ def summary_image_u8(x, premap='identity', max_outputs=2):
     return out
 
 
+def frame_metrics(a, b, max_val=1.0, png8=False, out=None):
+    """Per-frame SSIM, MSE and PSNR (TF 1.12 tf.image.ssim / tf.image.psnr) of a against b, both contiguous fp32
+    [N,H,W,C] on one device, C in (1, 3), H and W in [11, 1024], dynamic range ``max_val`` > 0 -> fp32 [N,3] = (ssim, mse, psnr) on that
+    device, in one launch.  ``png8``: score the 8-bit frames evaluate.py writes (each value quantised as ``_save_img(rescale=True)``,
+    scored as q / 255 with max_val 1).  ``out``: a contiguous fp32 [N,3] tensor to write into."""
+    for t in (a, b):
+        _require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.KpxError('frame_metrics: a and b must be contiguous fp32 tensors (got %s, contiguous=%s)' % (t.dtype, t.is_contiguous()))
+    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise _lib.KpxError('frame_metrics: a and b must be [N,H,W,C] of one shape on one device (got %s on %s, %s on %s)'
+                            % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    n, h, w, c = a.shape
+    if n < 1 or not (11 <= h <= 1024 and 11 <= w <= 1024) or c not in (1, 3):
+        raise _lib.KpxError('frame_metrics: needs N >= 1, H and W in [11, 1024] and C in (1, 3) (got %s)' % (tuple(a.shape),))
+    L = float(max_val)
+    if not (0.0 < L < float('inf')):
+        raise _lib.KpxError('frame_metrics: max_val must be a finite value > 0 (got %r)' % (max_val,))
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.float32, device=a.device)
+    elif tuple(out.shape) != (n, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a.device:
+        raise _lib.KpxError('frame_metrics: out must be a contiguous fp32 [%d,3] tensor on %s' % (n, a.device))
+    check(lib.kpx_frame_metrics_f32(a.data_ptr(), b.data_ptr(), n, h, w, c, L, 1 if png8 else 0, out.data_ptr(), _stream()),
+          'kpx_frame_metrics_f32')
+    return out
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
