@@ -195,8 +195,8 @@ def test_f43_launch_policy_follows_the_float64_arbiter_findings():
 
 
 def test_f43_decision_keeps_the_kernel_choice_on_its_corner_cases(monkeypatch):
-    """ops._wino43_plan, the one F(4x4,3x3) decision of _wino_pretransformed and conv3x3_wino43_ex: the launches to try in order, [] = not
-    F(4x4,3x3).  Eligibility is the library's host-side answer for an aligned fake address."""
+    """ops._wino43_plan, the one F(4x4,3x3) decision of conv3x3_same (with and without the mask / pool options: vgg=): the launches to try in
+    order, [] = not F(4x4,3x3).  Eligibility is the library's host-side answer for an aligned fake address."""
     from kpx_amd import ops
     monkeypatch.setattr(ops, 'WINO43', True)
     monkeypatch.setattr(ops, 'WINO43B', True)
@@ -215,7 +215,7 @@ def test_f43_decision_keeps_the_kernel_choice_on_its_corner_cases(monkeypatch):
     # ... on 16x16 images or with Nn % 64 != 0: F(4x4,3x3) without the fused sums
     assert plan(4, 16, 16, 64, 64, 64, a, 1, both, bn_src=True) == plain
     assert plan(4, 32, 32, 64, 96, 64, a, 1, both, bn_src=True) == plain
-    # K = 20 in a 20-wide buffer: the bf16x3 kernel takes it, the fp32-MFMA kernel does not -- and conv3x3_wino43_ex never runs without it
+    # K = 20 in a 20-wide buffer: the bf16x3 kernel takes it, the fp32-MFMA kernel does not -- and the mask / pool options never run without it
     assert plan(4, 32, 32, 20, 64, 20, a, 0, both) == [('wino43b', False)]
     assert plan(4, 32, 32, 20, 64, 20, a, 0, both, vgg=True) == []
     assert plan(4, 32, 32, 64, 64, 64, a, 1, both, vgg=True) == plain
@@ -227,6 +227,48 @@ def test_f43_decision_keeps_the_kernel_choice_on_its_corner_cases(monkeypatch):
     assert plan(8, 32, 64, 64, 64, 64, a, 0, both) == [('wino43', False)]
     monkeypatch.setattr(ops, 'WINO43', False)
     assert plan(8, 32, 64, 64, 64, 64, a, 0, both) == []
+
+
+def test_conv3x3_same_launches_nothing_for_an_option_no_candidate_implements(monkeypatch):
+    """ops.conv3x3_same answers None -- and has launched NOTHING -- when the launch asks for an epilogue option that none of its candidate
+    kernels implements: the caller (vgg.py) then makes the plain launch and runs the separate kernel.  Every launch entry of the library
+    raises here, so a launch (on the way to a refusal, too) fails the test."""
+    import ctypes
+    from kpx_amd import ops, _lib
+
+    def launched(*args):
+        raise AssertionError('a kernel launch was attempted')
+    entries = [name for name, (res, args) in _lib.SIGNATURES.items()
+               if res is ctypes.c_int and args and args[-1] is ctypes.c_void_p and not name.endswith('_eligible')]
+    assert {'kpx_conv3x3_bf16s', 'kpx_conv3x3_bf16s_bnbwd', 'kpx_conv3x3_wino43_f32', 'kpx_conv3x3_wino43b_f32', 'kpx_conv3x3_wino_f32',
+            'kpx_conv3x3_c16_f32', 'kpx_conv2d_fwd_f32', 'kpx_conv3x3_bf16s_prepare_f32', 'kpx_wino43_filter_transform_batch_f32'} <= set(entries)
+    for name in entries:
+        monkeypatch.setattr(ops.lib, name, launched)
+    monkeypatch.setattr(ops, '_stream', launched)
+    calls, uses, uses16 = _lib.abi_calls[0], dict(ops.conv_kernel_uses), ops.conv_kernel_uses_bf16s[0]
+    n, h, c = 2, 32, 64
+    w = torch.zeros(3, 3, c, c)
+    x32, y32, m32 = (torch.zeros(n, h, h, c) for _ in range(3))
+    x16, y16, m16 = (torch.zeros(n, h, h, c, dtype=torch.bfloat16) for _ in range(3))
+    pool32 = torch.zeros(n, h // 2, h // 2, c)
+    for wino43 in (True, False):
+        monkeypatch.setattr(ops, 'WINO43', wino43)
+        # bf16 storage: the kernel has the mask, not the pool -- in either direction, whatever the output type
+        assert ops.conv3x3_same(x16, c, c, w, None, y16, c, c, ops.ACT_RELU, False, pool_out=pool32) is None
+        assert ops.conv3x3_same(x16, c, c, w, None, y32, c, c, ops.ACT_RELU, False, pool_out=pool32) is None
+        assert ops.conv3x3_same(x16, c, c, w, None, y16, c, c, ops.ACT_NONE, True, mask=m16, pool_out=pool32) is None
+        # fp32: only the F(4x4,3x3) plan has the options -- none without the filter's F(4x4,3x3) form (never made with WINO43 off; this
+        # filter was never registered), and F(2x2,3x3) / the 16-channel kernel are no candidates
+        assert ops.conv3x3_same(x32, c, c, w, None, y32, c, c, ops.ACT_NONE, True, mask=m32) is None
+        assert ops.conv3x3_same(x32, c, c, w, None, y32, c, c, ops.ACT_RELU, False, pool_out=pool32) is None
+        assert ops.conv3x3_same(x32, c, c, w[..., :16], None, y32, c, 16, ops.ACT_RELU, False, pool_out=pool32[..., :16]) is None
+        # an fp32 input with a bf16 output belongs to the image kernels of the bf16 configuration, with or without options
+        assert ops.conv3x3_same(x32, c, c, w, None, y16, c, c, ops.ACT_RELU, False, mask=m16) is None
+    # a REGISTERED filter with WINO43 switched off afterwards: its F(4x4,3x3) forms exist, the plan still refuses
+    monkeypatch.setitem(ops._filter_forms, ('wino43', w.data_ptr(), 1), (torch.zeros(1), None, None, (c, c)))
+    monkeypatch.setattr(ops, 'WINO43', False)
+    assert ops.conv3x3_same(x32, c, c, w, None, y32, c, c, ops.ACT_NONE, True, mask=m32) is None
+    assert (_lib.abi_calls[0], ops.conv_kernel_uses, ops.conv_kernel_uses_bf16s[0]) == (calls, uses, uses16)
 
 
 # ------------------------------------------------------------------------------------------------ bench.py supervisor (N > 1 cannot hang)

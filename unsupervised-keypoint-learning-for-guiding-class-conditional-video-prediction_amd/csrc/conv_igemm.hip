@@ -365,6 +365,16 @@ static int conv_splitk_plan(long M, int Cout, long nchunks_total) {
     return (int)(S < 1 ? 1 : S);
 }
 
+// The second launch of a split-K convolution: the g.ksplit partial slabs in g.ws -> y, with the bias / activation / multiplier epilogue
+// (g.io16 is 0 wherever the fp32 kernels of this file made the slabs: bf16 tensors only reach conv_gemm3.hip)
+static int launch_splitk_reduce(const ConvGeom& g, hipStream_t s) {
+    const size_t npix = (size_t)g.N * g.Ho * g.Wo;
+    size_t nb = (npix * (g.Cout / 4) + 255) / 256; if (nb > 2048) nb = 2048;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const float*)g.ws, g.ws_slab, g.ksplit, npix, g.Cout,
+                       g.bias, g.act, g.y, g.ldy, g.mul_y, g.ld_mul, g.mul_act, g.io16);
+    return kpx_launch_status();
+}
+
 template <bool BT, bool VEC, bool MERGE, bool TAIL>
 static int launch_gather_conv_v(ConvGeom g, hipStream_t s) {
     if (g.ncls <= 0) { g.ncls = 1; g.cls[0] = ConvClass{g.Ha, g.Wa, g.oy0, g.ox0, g.Tr, g.Tq, g.iy0, g.ix0, g.wr0, g.wq0, 0, 0}; }
@@ -380,13 +390,8 @@ static int launch_gather_conv_v(ConvGeom g, hipStream_t s) {
         const dim3 nblk((unsigned)(g.mt * g.nt), (unsigned)g.ncls, (unsigned)g.ksplit);
         if (BNs == 128) hipLaunchKernelGGL((conv_igemm_kernel<128, 128, 2, 4, BT, VEC, MERGE, TAIL>), nblk, dim3(512), 0, s, g);
         else hipLaunchKernelGGL((conv_igemm_kernel<128, 64, 4, 2, BT, VEC, MERGE, TAIL>), nblk, dim3(512), 0, s, g);
-        int rc = kpx_launch_status();
-        if (rc) return rc;
-        const size_t npix = (size_t)g.N * g.Ho * g.Wo;
-        size_t nb = (npix * (g.Cout / 4) + 255) / 256; if (nb > 2048) nb = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const float*)g.ws, g.ws_slab, g.ksplit, npix, g.Cout,
-                           g.bias, g.act, g.y, g.ldy, g.mul_y, g.ld_mul, g.mul_act);
-        return kpx_launch_status();
+        const int rc = kpx_launch_status();
+        return rc ? rc : launch_splitk_reduce(g, s);
     }
     // N tile: smallest padded width, ties -> wider tile
     int BN = 128;
@@ -442,12 +447,7 @@ template <bool BT>
 static int launch_gather_conv(const ConvGeom& g, hipStream_t s) {
     if (kpx_gemm3_eligible(&g)) {
         int rc = kpx_gemm3_launch(g, BT ? 1 : 0, g.terms == 1 ? 1 : 3, s);
-        if (rc || g.ksplit <= 1) return rc;
-        const size_t npix = (size_t)g.N * g.Ho * g.Wo;
-        size_t nb = (npix * (g.Cout / 4) + 255) / 256; if (nb > 2048) nb = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const float*)g.ws, g.ws_slab, g.ksplit, npix, g.Cout,
-                           g.bias, g.act, g.y, g.ldy, g.mul_y, g.ld_mul, g.mul_act, g.io16);
-        return kpx_launch_status();
+        return rc || g.ksplit <= 1 ? rc : launch_splitk_reduce(g, s);
     }
     if (g.io16) return KPX_EINVAL;                       // bf16 tensors: only the kernel above reads them
     if (g.merge) return launch_gather_conv_v<false, false, true, true>(g, s);
@@ -645,7 +645,7 @@ extern "C" int kpx_conv2d_dgrad_act_f32(const float* dy, int N, int Ho, int Wo, 
                       workspace, workspace_bytes, stream);
 }
 
-static inline void launch_wgrad_reduce(const float* ws, float* dw, size_t n, int S, hipStream_t s);
+static int finish_wgrad(int rc, const void* ws, float* dw, size_t n, int S, hipStream_t s);      // (defined with the weight-gradient reduce kernels)
 // bf16 configuration, image-input layers (the images stay fp32; what the layer produces / receives is bf16).  KPX_EINVAL for shapes the
 // LDS-resident image kernels (conv_rgb.hip, conv_wsmall.hip) do not take: the caller then converts and uses the fp32 entries.
 //   forward:  x fp32 [N, Hi, Wi, Cin <= 4] contiguous -> y bf16 (pixel stride ldy elements)
@@ -677,10 +677,8 @@ extern "C" int kpx_conv_image_wgrad_bf16(const float* x, int N, int Hi, int Wi, 
     const size_t slab = (size_t)KH * KW * Cin * Cout;
     if (Ss < 1 || (Ss > 1 && (!workspace || workspace_bytes < (size_t)Ss * slab * 4))) return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
-    int rc = kpx_wsmall_launch(x, N, Hi, Wi, Cin, ldx, (const float*)dy, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l, Ss > 1 ? (float*)workspace : dw, Ss, s, 1);
-    if (rc) return rc;
-    if (Ss > 1) { launch_wgrad_reduce((const float*)workspace, dw, slab, Ss, s); rc = kpx_launch_status(); }
-    return rc;
+    const int rc = kpx_wsmall_launch(x, N, Hi, Wi, Cin, ldx, (const float*)dy, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l, Ss > 1 ? (float*)workspace : dw, Ss, s, 1);
+    return finish_wgrad(rc, workspace, dw, slab, Ss, s);
 }
 
 // bf16 configuration: dy bf16, dx bf16 (dx_f32 = 0) or fp32 (the gradient towards an fp32 tensor); y_in (optional, with act_in): the bf16
@@ -1135,6 +1133,14 @@ static inline void launch_wgrad_reduce(const float* ws, float* dw, size_t n, int
     }
 }
 
+// The tail of every weight-gradient launch.  rc: the status of the kernel that wrote dw itself (S == 1) or S partial slabs of n floats into
+// the workspace ws, which the fixed-order reduce then sums into dw.
+static int finish_wgrad(int rc, const void* ws, float* dw, size_t n, int S, hipStream_t s) {
+    if (rc || S <= 1) return rc;
+    launch_wgrad_reduce((const float*)ws, dw, n, S, s);
+    return kpx_launch_status();
+}
+
 // ------------------------------------------------------------------------------------------ wgrad, small channel counts
 // High-resolution layers with <= 64 input and <= 32 output channels (pose_encoder tail, translator head, encoder conv_2):
 // the generic kernel above gives every filter tap its own workgroups, so x and dy are re-read KH*KW times and most of each
@@ -1441,10 +1447,7 @@ extern "C" int kpx_conv2d_wgrad_bf16(const void* x, int N, int Hi, int Wi, int C
     g.vecA = 1; g.vecB = 1; g.terms = 1;
     if (!kpx_wgrad3_eligible(&g)) return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
-    int rc = kpx_wgrad3_launch(g, bm, 1, s);
-    if (rc) return rc;
-    if (g.S > 1) { launch_wgrad_reduce((const float*)workspace, dw, g.slab, g.S, s); rc = kpx_launch_status(); }
-    return rc;
+    return finish_wgrad(kpx_wgrad3_launch(g, bm, 1, s), workspace, dw, g.slab, g.S, s);
 }
 
 extern "C" size_t kpx_conv2d_wgrad_workspace_bytes(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
@@ -1488,31 +1491,26 @@ extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int C
         const size_t slab = (size_t)KH * KW * Cin * Cout;
         if (Ss >= 1 && (Ss == 1 || (workspace && workspace_bytes >= (size_t)Ss * slab * 4))) {
             hipStream_t s = kpx_stream(stream);
-            int rc = kpx_wsmall_launch(x, N, Hi, Wi, Cin, ldx, dy, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l, Ss > 1 ? (float*)workspace : dw, Ss, s);
-            if (rc) return rc;
-            if (Ss > 1) { launch_wgrad_reduce((const float*)workspace, dw, slab, Ss, s); rc = kpx_launch_status(); }
-            return rc;
+            const int rc = kpx_wsmall_launch(x, N, Hi, Wi, Cin, ldx, dy, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l, Ss > 1 ? (float*)workspace : dw, Ss, s);
+            return finish_wgrad(rc, workspace, dw, slab, Ss, s);
         }
     }
     // (the bf16x3 weight gradient of conv_gemm3.hip runs where the generic fp32 kernel would, and on the strided layers: measured ahead of the
     //  specialised fp32 kernels it loses -- 18.65 vs 17.9 ms per step in round 3)
-    const int g3_first = 0;
-    if (g3_first < 2 && KH == 3 && KW == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && Ho == Hi && Wo == Wi && ldx % 4 == 0 && lddy % 4 == 0 &&
+    if (KH == 3 && KW == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && Ho == Hi && Wo == Wi && ldx % 4 == 0 && lddy % 4 == 0 &&
         ldx >= ((Cin + 3) & ~3) && aligned16(x) && aligned16(dy) &&
         (size_t)N * Hi * Wi * (size_t)(ldx > lddy ? ldx : lddy) * 4 < 0x60000000ull) {       // (the kernel addresses x / dy with 32-bit byte offsets)
         const int Sw = kpx_wino_wgrad_splits(N, Hi, Wi, Cin, Cout);
         const size_t slab = (size_t)9 * Cin * Cout;
         if (Sw >= 1 && (Sw == 1 || (workspace && workspace_bytes >= (size_t)Sw * slab * 4))) {
             hipStream_t s = kpx_stream(stream);
-            int rc = kpx_wino_wgrad3x3(x, N, Hi, Wi, Cin, ldx, dy, Cout, lddy, Sw > 1 ? (float*)workspace : dw, Sw, s);
-            if (rc) return rc;
-            if (Sw > 1) { launch_wgrad_reduce((const float*)workspace, dw, slab, Sw, s); rc = kpx_launch_status(); }
-            return rc;
+            const int rc = kpx_wino_wgrad3x3(x, N, Hi, Wi, Cin, ldx, dy, Cout, lddy, Sw > 1 ? (float*)workspace : dw, Sw, s);
+            return finish_wgrad(rc, workspace, dw, slab, Sw, s);
         }
     }
     {
         int S2, cpb;
-        if (!g3_first && stride == 1 && ldx == Cin && lddy % 4 == 0 && aligned16(dy) && wgrad_rows_merged_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb)) {
+        if (stride == 1 && ldx == Cin && lddy % 4 == 0 && aligned16(dy) && wgrad_rows_merged_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb)) {
             WgradRowsGeom r{};
             r.x = x; r.dy = dy;
             r.N = N; r.Hi = Hi; r.Wi = Wi; r.Cin = Cin; r.ldx = ldx;
@@ -1524,16 +1522,13 @@ extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int C
             r.out = S2 > 1 ? (float*)workspace : dw;
             hipStream_t s = kpx_stream(stream);
             hipLaunchKernelGGL((conv_wgrad_rows_merged_kernel<0>), dim3((unsigned)S2), dim3(256), 0, s, r);
-            int rc = kpx_launch_status();
-            if (rc) return rc;
-            if (S2 > 1) { launch_wgrad_reduce((const float*)workspace, dw, r.slab, S2, s); rc = kpx_launch_status(); }
-            return rc;
+            return finish_wgrad(kpx_launch_status(), workspace, dw, r.slab, S2, s);
         }
     }
     {
         int S2, cpb, CT;
         const bool vec = (ldx % 4 == 0) && (lddy % 4 == 0) && (Cin % 4 == 0) && aligned16(x) && aligned16(dy);
-        if (!g3_first && stride == 1 && vec && wgrad_rows_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb, &CT)) {
+        if (stride == 1 && vec && wgrad_rows_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb, &CT)) {
             WgradRowsGeom r{};
             r.x = x; r.dy = dy;
             r.N = N; r.Hi = Hi; r.Wi = Wi; r.Cin = Cin; r.ldx = ldx;
@@ -1547,13 +1542,7 @@ extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int C
             const dim3 grid((unsigned)(S2 * r.ct));
             if (CT == 2) hipLaunchKernelGGL((conv_wgrad_rows_kernel<2>), grid, dim3(256), 0, s, r);
             else hipLaunchKernelGGL((conv_wgrad_rows_kernel<1>), grid, dim3(256), 0, s, r);
-            int rc = kpx_launch_status();
-            if (rc) return rc;
-            if (S2 > 1) {
-                launch_wgrad_reduce((const float*)workspace, dw, r.slab, S2, s);
-                rc = kpx_launch_status();
-            }
-            return rc;
+            return finish_wgrad(kpx_launch_status(), workspace, dw, r.slab, S2, s);
         }
     }
     WgradGeom g{};
@@ -1576,7 +1565,7 @@ extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int C
     // (strided layers: the bf16x3 kernel below beats the fp32 tap-rows kernel -- encoder conv_3 at N = 64: 0.152 vs 0.198 ms; the stride-1
     //  layers that reach this point are faster on tap-rows / rows, and the 3x3 stride-1 layers on the Winograd weight gradient)
     const bool g3_strided = stride > 1 && g.vecA && g.vecB && kpx_wgrad3_eligible(&g);
-    if (!g3_first && !g3_strided && g.vecA && g.vecB && Cin % 4 == 0 && Cout % 4 == 0 && Wo % 32 == 0 && !wgrad_merge(Cin, ldx, KW)) {
+    if (!g3_strided && g.vecA && g.vecB && Cin % 4 == 0 && Cout % 4 == 0 && Wo % 32 == 0 && !wgrad_merge(Cin, ldx, KW)) {
         // chunk-aligned split: same S as the generic plan, but in units of 32-pixel row chunks
         WgradTapGeom r{};
         r.x = x; r.dy = dy;
@@ -1592,10 +1581,7 @@ extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int C
         const dim3 grid((unsigned)(r.S * KH * KW * r.ct * r.kt));
         if (bm == 128) hipLaunchKernelGGL((conv_wgrad_tap_rows_kernel<128, 128, 2, 4>), grid, dim3(512), 0, s, r);
         else hipLaunchKernelGGL((conv_wgrad_tap_rows_kernel<64, 64, 2, 2>), grid, dim3(256), 0, s, r);
-        int rc = kpx_launch_status();
-        if (rc) return rc;
-        if (r.S > 1) { launch_wgrad_reduce((const float*)workspace, dw, r.slab, r.S, s); rc = kpx_launch_status(); }
-        return rc;
+        return finish_wgrad(kpx_launch_status(), workspace, dw, r.slab, r.S, s);
     }
     int taps = KH * KW;
     if (wgrad_merge(Cin, ldx, KW)) {     // image inputs (Cin = 3): one tap per filter row, KW*Cin merged channels
@@ -1605,22 +1591,12 @@ extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int C
     hipStream_t s = kpx_stream(stream);
     const dim3 grid((unsigned)(g.S * taps * g.ct * g.kt));
     const bool vec = g.vecA && g.vecB && !g.merge;
-    if (vec && kpx_wgrad3_eligible(&g)) {                // bf16x3 (fp32-equivalent) weight gradient on the bf16 matrix pipe (conv_gemm3.hip)
-        int rc = kpx_wgrad3_launch(g, bm, g.terms == 1 ? 1 : 3, s);
-        if (rc) return rc;
-        if (g.S > 1) { launch_wgrad_reduce((const float*)workspace, dw, g.slab, g.S, s); rc = kpx_launch_status(); }
-        return rc;
-    }
+    if (vec && kpx_wgrad3_eligible(&g))                  // bf16x3 (fp32-equivalent) weight gradient on the bf16 matrix pipe (conv_gemm3.hip)
+        return finish_wgrad(kpx_wgrad3_launch(g, bm, g.terms == 1 ? 1 : 3, s), workspace, dw, g.slab, g.S, s);
     if (g.merge) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, true>), grid, dim3(256), 0, s, g);
     else if (bm == 128 && vec) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 4, true, false>), grid, dim3(512), 0, s, g);
     else if (bm == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 4, false, false>), grid, dim3(512), 0, s, g);
     else if (vec) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, true, false>), grid, dim3(256), 0, s, g);
     else hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, false>), grid, dim3(256), 0, s, g);
-    int rc = kpx_launch_status();
-    if (rc) return rc;
-    if (g.S > 1) {
-        launch_wgrad_reduce((const float*)workspace, dw, g.slab, g.S, s);
-        rc = kpx_launch_status();
-    }
-    return rc;
+    return finish_wgrad(kpx_launch_status(), workspace, dw, g.slab, g.S, s);
 }

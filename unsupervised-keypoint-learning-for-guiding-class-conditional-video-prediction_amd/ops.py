@@ -8,7 +8,11 @@ Weight / bias / gamma / beta gradients are written by the kernels straight into 
 flat gradient bucket (``*_grad_out``), so the RCCL all-reduce and the fused Adam step run on one contiguous buffer
 without a gather pass.
 """
+import collections as _collections
 import os as _os
+import struct as _struct
+import weakref as _weakref
+from fractions import Fraction
 
 import torch
 
@@ -30,6 +34,10 @@ def _stream():
     if _raw_stream is not None and _cur_device is not None:
         return _raw_stream(_cur_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
 
 
 def _require_gpu(t):
@@ -79,6 +87,20 @@ class _Scratch:
 
 
 scratch = _Scratch()
+
+
+def _workspace(key, nbytes, device):
+    """The (workspace, workspace_bytes) arguments of an entry whose *_workspace_bytes query answered ``nbytes``: the scratch buffer ``key``
+    of the current stream, or (None, 0) where the launch needs none."""
+    return (scratch.get(key, nbytes, device).data_ptr() if nbytes else None), nbytes
+
+
+def _took(rc, entry):
+    """Whether ``entry``, which answers KPX_EINVAL (-1) for a launch it does not take, took this one; any other failure raises."""
+    if rc == -1:
+        return False
+    check(rc, entry)
+    return True
 
 # Weight gradients are off the backward critical path (only the optimiser consumes them), so they are launched on a second
 # HIP stream where they fill the ramp-up / tail gaps of the dgrad chain on the main stream.  join_side_stream() is called
@@ -263,26 +285,44 @@ def _slice_f32(x, ldx, cin):
     return out
 
 
+# What conv3x3_same() and the kernel families under it answer for a launch they made (None: not theirs, nothing ran).  stats: None, or
+# (slab, tiles per image) when the epilogue wrote per-tile sums (want_stats / bn_src).  Tiles per image is a Fraction for every kernel: the
+# bf16 kernel packs G images into one tile on its small layers (1/G), the others have whole tiles per image.
+Launched = _collections.namedtuple('Launched', 'stats')
+
+
+def _bf16s_gathered(inp, ld_in, k):
+    """The gathered channel count the bf16-storage kernels run a K-channel launch on, or 0 when the buffer is too narrow for it.
+    Ragged channel counts (the 158-channel joint embedding in its 160-wide buffer) run on the rounded-up counts -- the prepared filters are
+    zero there, so the extra gathered channels (zero-filled / finite by the producer's contract) contribute nothing."""
+    if k % 32 == 0 or k in (8, 16):
+        return k
+    k0, k = k, 8 if k < 8 else 16 if k < 16 else (k + 31) // 32 * 32
+    if ld_in < k:
+        return 0
+    # CONTRACT of the rounded-up gather: channels k0..k of the caller's buffer are multiplied by zero filter rows, so they must be FINITE
+    # (0 * inf = nan).  Every producer on the path zero-fills its pad channels (JointEmbeddingFn, the concat buffers); KPX_DEBUG_FINITE=1
+    # checks it on every call (a device synchronisation: diagnostics only).
+    if DEBUG_FINITE and not bool(torch.isfinite(inp.reshape(-1, inp.shape[-1])[:, k0:k].float()).all()):
+        raise _lib.KpxError('bf16 3x3 conv: non-finite values in the pad channels %d..%d of a %d-wide buffer' % (k0, k, inp.shape[-1]))
+    return k
+
+
 def _bf16s_bnbwd(dy, lddy, k, w, dx, lddx, nn, bn_y, beta):
-    """(slab, tiles per image) or False: data gradient + the backward sums of the batch norm whose ReLU'd output ``bn_y`` the convolution read."""
+    """Data gradient + the backward sums of the batch norm whose ReLU'd output ``bn_y`` the convolution read (csrc/conv_bf16s.hip)."""
     n, h, wd = dy.shape[0], dy.shape[1], dy.shape[2]
-    if not (k % 32 == 0 or k in (8, 16)):
-        k = 8 if k < 8 else 16 if k < 16 else (k + 31) // 32 * 32            # (as _bf16s_conv: the prepared filters are zero there)
-        if lddy < k:
-            return False
-    if (bn_y.dtype != BF16 or not bn_y.is_contiguous() or bn_y.shape[3] != nn or nn % 8 or lddx % 8
+    k = _bf16s_gathered(dy, lddy, k)
+    if (not k or bn_y.dtype != BF16 or not bn_y.is_contiguous() or bn_y.shape[3] != nn or nn % 8 or lddx % 8
             or not lib.kpx_conv3x3_bf16s_eligible(n, h, wd, k, nn, lddy, dy.data_ptr())):
-        return False
+        return None
     wf = _bf16s_prepared(w, True)
     tiles = lib.kpx_conv3x3_bf16s_stats_tiles(n, h, wd, k, nn)
     slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=dy.device)
     rc = lib.kpx_conv3x3_bf16s_bnbwd(dy.data_ptr(), n, h, wd, k, lddy, wf.data_ptr(), dx.data_ptr(), nn, lddx, bn_y.data_ptr(), nn, beta.data_ptr(), slab.data_ptr(), _stream())
-    if rc == -1:
-        return False
-    check(rc, 'kpx_conv3x3_bf16s_bnbwd')
+    if not _took(rc, 'kpx_conv3x3_bf16s_bnbwd'):
+        return None
     conv_kernel_uses_bf16s[0] += 1
-    from fractions import Fraction
-    return slab, Fraction(tiles, n)
+    return Launched((slab, Fraction(tiles, n)))
 
 
 conv_kernel_uses_bf16s = [0]
@@ -303,58 +343,38 @@ def _bf16s_prepared(w, dgrad):
 
 
 def _bf16s_conv(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=False, mask=None):
-    """3x3 stride-1 SAME convolution on bf16 tensors (csrc/conv_bf16s.hip); False when the shape is not one the kernel takes.
-    With want_stats returns (slab, tiles per image as a Fraction)."""
+    """3x3 stride-1 SAME convolution on bf16 tensors (csrc/conv_bf16s.hip), either direction; mask (bf16, with a bf16 output): zero the
+    output where mask <= 0."""
     n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
     out_f32 = out.dtype == torch.float32
-    if inp.dtype != BF16:
-        return False
-    # ragged channel counts (the 158-channel joint embedding in its 160-wide buffer): the kernel runs on the rounded-up counts -- the
-    # prepared filters are zero there, so the extra gathered channels (zero-filled / finite by the producer's contract) contribute nothing
-    # and the extra produced channels come out as zeros
-    if not (k % 32 == 0 or k in (8, 16)):
-        k0 = k
-        k = 8 if k < 8 else 16 if k < 16 else (k + 31) // 32 * 32
-        if ld_in < k:
-            return False
-        # CONTRACT of the rounded-up gather: channels k0..k of the caller's buffer are multiplied by zero filter rows, so they must be FINITE
-        # (0 * inf = nan).  Every producer on the path zero-fills its pad channels (JointEmbeddingFn, the concat buffers); KPX_DEBUG_FINITE=1
-        # checks it on every call (a device synchronisation: diagnostics only).
-        if DEBUG_FINITE and not bool(torch.isfinite(inp.reshape(-1, inp.shape[-1])[:, k0:k].float()).all()):
-            raise _lib.KpxError('bf16 3x3 conv: non-finite values in the pad channels %d..%d of a %d-wide buffer' % (k0, k, inp.shape[-1]))
+    k = _bf16s_gathered(inp, ld_in, k)
+    if not k:
+        return None
     g = 4 if out_f32 else 8
     if nn % g:
-        nn = (nn + g - 1) // g * g
+        nn = (nn + g - 1) // g * g           # (the extra produced channels come out as zeros)
         if ld_out < nn:
-            return False
+            return None
     if ld_out % g or not lib.kpx_conv3x3_bf16s_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr()):
-        return False
+        return None
     if out.data_ptr() % 16 or (mask is not None and (out_f32 or mask.dtype != BF16 or mask.data_ptr() % 16)):
-        return False
+        return None
     wf = _bf16s_prepared(w, dgrad)
     slab = None
     if want_stats:
         tiles = lib.kpx_conv3x3_bf16s_stats_tiles(n, h, wd, k, nn)
         slab = torch.empty(tiles * 2 * nn, dtype=torch.float32, device=inp.device)
-    check(lib.kpx_conv3x3_bf16s(inp.data_ptr(), n, h, wd, k, ld_in, wf.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                out.data_ptr(), nn, ld_out, 1 if out_f32 else 0, act, mask.data_ptr() if mask is not None else None,
-                                mask.stride(2) if mask is not None else 0, slab.data_ptr() if slab is not None else None, _stream()), 'kpx_conv3x3_bf16s')
+    check(lib.kpx_conv3x3_bf16s(inp.data_ptr(), n, h, wd, k, ld_in, wf.data_ptr(), _ptr(bias), out.data_ptr(), nn, ld_out, 1 if out_f32 else 0, act,
+                                _ptr(mask), mask.stride(2) if mask is not None else 0, _ptr(slab), _stream()), 'kpx_conv3x3_bf16s')
     conv_kernel_uses_bf16s[0] += 1
-    if want_stats:
-        from fractions import Fraction
-        return slab, Fraction(tiles, n)
-    return True
+    return Launched((slab, Fraction(tiles, n)) if want_stats else None)
 
 
 # ----------------------------------------------------------------------------------------------- derived filter forms
 # U = G g G^T (and the bf16 kernel's fragment order) is a function of the filter only.  Constant filters (VGG19) are transformed once;
 # the trainable 3x3 filters of a VariableStore are transformed together in ONE launch per form (the batched transform entries) the first
 # time a convolution needs them after the store changed (optimiser update / restore), instead of once per convolution call.
-import collections as _collections
-import struct as _struct
-import weakref as _weakref
-
-conv_kernel_uses = {'wino43': 0, 'wino43b': 0}      # diagnostics / tests: launches of the F(4x4,3x3) kernels (fp32-MFMA form / bf16x3 form; 'wino43' counts both)
+conv_kernel_uses ={'wino43': 0, 'wino43b': 0}      # diagnostics / tests: launches of the F(4x4,3x3) kernels (fp32-MFMA form / bf16x3 form; 'wino43' counts both)
 
 # F(4x4,3x3) (csrc/conv_wino43.hip) does 2.25x fewer multiplies than F(2x2,3x3) at ~6x its rounding error (2-3e-6 rel-L2 per layer, still
 # inside the 1e-5 bar of one layer).  Where it runs is a PER-LAYER ATTRIBUTE and a direction, from the measured effect on a whole train
@@ -369,7 +389,7 @@ conv_kernel_uses = {'wino43': 0, 'wino43b': 0}      # diagnostics / tests: launc
 # (Round 4 measured the alternative -- F(4x4,3x3) on every forward layer: -0.13..-0.2 ms per step for a generated frame 3.6e-5 instead of
 #  1.7e-5 from the oracle's; the margin was kept and the experiment switches are gone.)  KPX_WINO43=0: F(2x2,3x3) everywhere (tests).
 WINO43 = _os.environ.get('KPX_WINO43', '1') != '0'
-DEBUG_FINITE = _os.environ.get('KPX_DEBUG_FINITE', '0') == '1'      # assert the finite-pad-channel contract of the rounded-up bf16 gathers (_bf16s_conv)
+DEBUG_FINITE = _os.environ.get('KPX_DEBUG_FINITE', '0') == '1'      # assert the finite-pad-channel contract of the rounded-up bf16 gathers (_bf16s_gathered)
 # launches of at most this many F(4x4,3x3) workgroups stay on F(2x2,3x3).  Round 2 set 128 from a kernel measured ALONE (128 workgroups: 0.187 vs
 # 0.158 ms -- one F(4x4) workgroup owns its CU); inside the step, where the other streams fill the idle CUs, F(4x4,3x3) wins on those layers too:
 # 23.73-23.83 ms per step at 0 / 32 / 64 against 24.01-24.16 at 128 (three repetitions each, B=32) -- so no threshold
@@ -380,10 +400,6 @@ WINO43_NMIN = 33                   # produced channels from which a layer takes 
 # statistics, K % 4 == 0: _wino43_plan).  KPX_WINO43B=0: the fp32-MFMA F(4x4,3x3) kernel everywhere (A/B, tests).
 WINO43B = _os.environ.get('KPX_WINO43B', '1') != '0'
 WINO43B_MAX_CHANNELS = 512         # gathered x produced channels up to which the bf16x3 form is prepared (its U is 1.5x the fp32 U: L2 traffic)
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _kn(cin, cout, dgrad):
@@ -435,13 +451,15 @@ def _cached_u(form, w, dgrad):
 
 
 class FilterBank:
-    wino_needed_in_bf16 = False      # set by the first lazy Winograd refresh inside the bf16 configuration (ensure_fresh)
+    # set by the first lazy Winograd refresh inside the bf16 configuration (ensure_fresh); class-level and sticky: ADVICE.md item 4 proposes a flag per bank
+    wino_needed_in_bf16 = False
 
     def __init__(self, named_filters, device, attrs=None):
         """named_filters: iterable of (name, [3,3,Cin,Cout] tensor views whose storage never moves); attrs: {name: {'f43_fwd': bool}}."""
         attrs = attrs or {}
         self.version = 0            # bumped by whoever writes the filters (Adam step, restore)
-        self.synced = -1
+        self.synced = {'wino': -1, 'bf16s': -1}     # form group -> the version its forms were last made from
+        self._wino_fresh_ev = None  # (event, raw stream) of the last lazy Winograd refresh: see ensure_fresh
         self.filters = [(n, w) for n, w in named_filters if w.dim() == 4 and w.shape[0] == 3 and w.shape[1] == 3]
         self.device = device
         self.f43_fwd = [attrs.get(n, {}).get('f43_fwd', True) for n, _ in self.filters]
@@ -487,16 +505,16 @@ class FilterBank:
             if form == 'bf16s' and FilterBank.wino_needed_in_bf16:
                 self.ensure_fresh('wino')                # an earlier step fell back to an fp32 Winograd kernel: refresh that form before the fork too
         if form == 'bf16s':
-            if getattr(self, 'synced16', -1) != self.version:
+            if self.synced['bf16s'] != self.version:
                 if 'bf16s' not in self.tables:
                     self._build('bf16s')
                 self._refresh('bf16s')
-                self.synced16 = self.version
+                self.synced['bf16s'] = self.version
             return
-        if self.synced != self.version:
+        if self.synced['wino'] != self.version:
             for f in _WINO_FORMS:
                 self._refresh(f)
-            self.synced = self.version
+            self.synced['wino'] = self.version
             # A LAZY refresh (an fp32 3x3 fall-back inside the bf16 configuration, whose pre-fork ensure_fresh() only refreshes the bf16
             # fragments) runs on whichever stream reaches it first: later readers on OTHER streams must wait for these launches
             self._wino_fresh_ev = None
@@ -505,14 +523,11 @@ class FilterBank:
                 ev.record(torch.cuda.current_stream())
                 self._wino_fresh_ev = (ev, torch.cuda.current_stream().cuda_stream)
                 FilterBank.wino_needed_in_bf16 = True      # from now on the model's pre-fork refresh covers the Winograd forms too
-        elif getattr(self, '_wino_fresh_ev', None) is not None and torch.cuda.current_stream().cuda_stream != self._wino_fresh_ev[1]:
+        elif self._wino_fresh_ev is not None and torch.cuda.current_stream().cuda_stream != self._wino_fresh_ev[1]:
             torch.cuda.current_stream().wait_event(self._wino_fresh_ev[0])
 
     def keys(self):
         return [(w.data_ptr(), dgrad) for _, w in self.filters for dgrad in (0, 1)]
-
-    def mode_key(self):
-        return _compute_dtype[0]
 
 
 def register_constant_filter(w, name='', f43_fwd=True):
@@ -543,7 +558,7 @@ def _wino43_plan(n, h, wd, k, nn, ld_in, in_ptr, dgrad, forms, want_stats=False,
     """The F(4x4,3x3) decision of one launch: [(form, fused bn sums), ...], the launches to try in this order until a kernel takes the
     options (the entries return KPX_EINVAL on a mix they do not take), or [] = not F(4x4,3x3).  forms: the filter's cached forms ('wino43',
     'wino43b'); want_stats: the forward's statistics strips; bn_src: a data gradient towards a ReLU'd batch norm's output; vgg: VGG19's mask /
-    pool options (conv3x3_wino43_ex: the fp32 kernel must take the launch and Nn % 64 == 0)."""
+    pool options (conv3x3_same(mask= / pool_out=): the fp32 kernel must take the launch and Nn % 64 == 0)."""
     if not (WINO43 and 'wino43' in forms):
         return []
     wgs = (n // 2 if wd == 16 else n * (h // 16) * (wd // 32)) * ((nn + 63) // 64)
@@ -564,7 +579,7 @@ def _wino43_plan(n, h, wd, k, nn, ld_in, in_ptr, dgrad, forms, want_stats=False,
 
 
 def _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, want_stats=False, bn_src=None, mask=None, pool=None):
-    """Make the first launch of ``plan`` that its kernel takes: (slab, tiles per image) when it wrote sums, True, or False if none ran."""
+    """Make the first launch of ``plan`` that its kernel takes; None if none ran."""
     n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
     for form, bn in plan:
         entry = 'kpx_conv3x3_wino43b_f32' if form == 'wino43b' else 'kpx_conv3x3_wino43_f32'
@@ -574,35 +589,39 @@ def _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, want_sta
                                  ld_out, ACT_NONE if bn else act, _ptr(mask), mask.shape[3] if mask is not None else 0, _ptr(pool),
                                  pool.shape[3] if pool is not None else 0, _ptr(slab), bn_src[0].data_ptr() if bn else None,
                                  bn_src[0].shape[3] if bn else 0, bn_src[1].data_ptr() if bn else None, _stream())
-        if rc != -1:
-            check(rc, entry)
+        if _took(rc, entry):
             conv_kernel_uses['wino43'] += 1
             if form == 'wino43b':
                 conv_kernel_uses['wino43b'] += 1
-            return (slab, tiles // n) if slab is not None else True
-    return False
+            return Launched((slab, Fraction(tiles, n)) if slab is not None else None)
+    return None
 
 
 def _f43_forms(w, dgrad):
     return {form: ent for form in ('wino43', 'wino43b') if (ent := _cached_u(form, w, dgrad)) is not None}
 
 
-def _wino_pretransformed(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=False, bn_src=None):
-    """Run a fused Winograd kernel on the cached forms of ``w``; False when there is none for this filter or the shape is not eligible.
-    want_stats: also have the epilogue write the per-tile batch-norm sums of the output; bn_src = (bn_y, beta): the data gradient towards a
-    ReLU'd batch norm's output, whose backward sums the epilogue reduces where it can.  Returns (slab, tiles per image) when it wrote sums."""
-    ent = _cached_u('wino', w, dgrad)
-    if ent is None:
-        return False
+def _wino_pretransformed(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=False, bn_src=None, mask=None, pool_out=None):
+    """Run a fused Winograd kernel on the cached forms of ``w``: the F(4x4,3x3) plan, then F(2x2,3x3); None when there is no form for this
+    filter or the shape is not eligible.  want_stats: also have the epilogue write the per-tile batch-norm sums of the output; bn_src =
+    (bn_y, beta): the data gradient towards a ReLU'd batch norm's output, whose backward sums the epilogue reduces where it can.
+    VGG19's epilogue options, which only the F(4x4,3x3) kernels implement (nothing runs when their plan is empty or refused): ``mask`` --
+    zero the output where mask <= 0 (ReLU backward of the tensor the data gradient belongs to), ``pool_out`` -- also write the 2x2 max-pool
+    of the activated output."""
     n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
-    if not lib.kpx_conv3x3_wino_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr()):
-        return False
-    if ent[1] is not None:
-        ent[1].ensure_fresh('wino')
+    vgg = mask is not None or pool_out is not None
+    ent = _cached_u('wino', w, dgrad)
+    if not vgg and (ent is None or not lib.kpx_conv3x3_wino_eligible(n, h, wd, k, nn, ld_in, inp.data_ptr())):
+        return None
     forms = _f43_forms(w, dgrad)
-    plan = _wino43_plan(n, h, wd, k, nn, ld_in, inp.data_ptr(), dgrad, forms, want_stats=want_stats, bn_src=bn_src is not None)
-    r = _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, want_stats=want_stats, bn_src=bn_src)
-    if r:
+    plan = _wino43_plan(n, h, wd, k, nn, ld_in, inp.data_ptr(), dgrad, forms, want_stats=want_stats, bn_src=bn_src is not None, vgg=vgg)
+    if vgg and not plan:
+        return None
+    bank = (forms['wino43'] if vgg else ent)[1]
+    if bank is not None:
+        bank.ensure_fresh('wino')
+    r = _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, want_stats=want_stats, bn_src=bn_src, mask=mask, pool=pool_out)
+    if r is not None or vgg:
         return r
     # F(2x2,3x3): sums per 16x16-pixel tile where the images are whole tiles (8x8 images are packed four to a workgroup)
     bn = bn_src is not None and dgrad and h % 16 == 0 and wd % 16 == 0
@@ -612,78 +631,88 @@ def _wino_pretransformed(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, wa
     check(lib.kpx_conv3x3_wino_f32(inp.data_ptr(), n, h, wd, k, ld_in, ent[0].data_ptr(), None if bn else _ptr(bias), out.data_ptr(), nn, ld_out,
                                    ACT_NONE if bn else act, _ptr(slab), bn_src[0].data_ptr() if bn else None, bn_src[0].shape[3] if bn else 0,
                                    bn_src[1].data_ptr() if bn else None, _stream()), 'kpx_conv3x3_wino_f32')
-    return (slab, tiles // n) if stats else True
+    return Launched((slab, Fraction(tiles, n)) if stats else None)
 
 
-def conv3x3_wino43_ex(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, mask=None, pool_out=None):
-    """The F(4x4,3x3) kernel with VGG19's epilogue options: ``mask`` -- zero the output where mask <= 0 (ReLU backward of the tensor the
-    data gradient belongs to), ``pool_out`` -- also write the 2x2 max-pool of the activated output.  True if it ran; False when the
-    layer / launch is not one the kernel takes (the caller then uses the plain path and the separate kernels)."""
-    forms = _f43_forms(w, dgrad)
+def conv3x3_same(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, *, want_stats=False, bn_src=None, mask=None, pool_out=None):
+    """Run one 3x3 stride-1 SAME launch (output size = input size) on a specialised kernel: THE ladder of the 3x3 kernel families, for either
+    direction (forward: inp = x, K = Cin gathered, Nn = Cout produced; dgrad: inp = dy, K = Cout, Nn = Cin, bias None, ACT_NONE) and either
+    storage type.  Returns Launched, or None when no specialised kernel takes the launch -- NOTHING has run then and the caller uses the
+    generic entries of its storage type.  The options narrow the candidates to the kernels that implement them: want_stats / bn_src are
+    served where a kernel can (Launched.stats says whether), mask / pool_out (see _wino_pretransformed) are all-or-nothing."""
+    if act == ACT_TANH:
+        return None                  # (no specialised kernel has the tanh epilogue)
     n, h, wd = inp.shape[0], inp.shape[1], inp.shape[2]
-    plan = _wino43_plan(n, h, wd, k, nn, ld_in, inp.data_ptr(), dgrad, forms, vgg=True)
-    if not plan:
-        return False
-    if forms['wino43'][1] is not None:
-        forms['wino43'][1].ensure_fresh('wino')
-    return _wino43_run(plan, forms, inp, ld_in, k, bias, out, ld_out, nn, act, mask=mask, pool=pool_out)
+    if inp.dtype == BF16:
+        # bf16 storage (csrc/conv_bf16s.hip), fp32 or bf16 output
+        if pool_out is not None:
+            return None
+        if dgrad and bn_src is not None and mask is None and out.dtype == BF16:
+            # towards a ReLU'd batch norm's output: the epilogue gates the gradient and reduces that batch norm's backward sums
+            r = _bf16s_bnbwd(inp, ld_in, k, w, out, ld_out, nn, bn_src[0], bn_src[1])
+            if r is not None:
+                return r
+        return _bf16s_conv(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=want_stats, mask=mask)
+    if out.dtype != torch.float32:
+        return None                  # (fp32 in, bf16 out: the image-input layers of the bf16 configuration)
+    if mask is not None or pool_out is not None:
+        return _wino_pretransformed(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, mask=mask, pool_out=pool_out)
+    if nn == 16 and not (dgrad and bn_src is not None) and lib.kpx_conv3x3_c16_eligible(n, h, wd, k, nn, ld_in, ld_out, inp.data_ptr()):
+        # exactly 16 produced channels: 16x16x4 MFMA blocks, no cout padding (csrc/conv_c16.hip); it has the statistics, not the bn sums
+        tiles = (h // 16) * (wd // 16)
+        slab = torch.empty(n * tiles * 2 * 16, dtype=torch.float32, device=inp.device) if want_stats else None
+        check(lib.kpx_conv3x3_c16_f32(inp.data_ptr(), n, h, wd, k, ld_in, w.data_ptr(), 1 if dgrad else 0, _ptr(bias), out.data_ptr(), ld_out, act,
+                                      _ptr(slab), _stream()), 'kpx_conv3x3_c16_f32')
+        return Launched((slab, Fraction(tiles)) if want_stats else None)
+    if not dgrad and nn <= 4 and k <= 128 and n * h * wd >= 65536:
+        return None                  # (few produced channels over a large image: VALU kernel inside the library)
+    return _wino_pretransformed(inp, ld_in, k, w, bias, out, ld_out, nn, act, dgrad, want_stats=want_stats, bn_src=bn_src)
 
 
 # ----------------------------------------------------------------------------------------------- raw launchers
+def _is_3x3_same(kh, kw, stride, pad_t, pad_l, hi, wi, ho, wo):
+    """The launches conv3x3_same() is asked about: 3x3, stride 1, pad 1 / 1, output size = input size."""
+    return kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and ho == hi and wo == wi
+
+
 def conv_fwd_raw(x, ldx, cin, w, bias, y, ldy, stride, pad_t, pad_l, act, want_stats=False):
     """Returns None, or (tile-statistics slab, tiles per image) when ``want_stats`` and the layer ran on the kernel that provides them."""
     n, hi, wi = x.shape[0], x.shape[1], x.shape[2]
+    ho, wo = y.shape[1], y.shape[2]
     kh, kw, _, cout = w.shape
+    same3 = _is_3x3_same(kh, kw, stride, pad_t, pad_l, hi, wi, ho, wo)
+    yf, ldyf = y, ldy
     if x.dtype == BF16 or y.dtype == BF16:
-        # bf16 configuration: the bf16-storage kernel, or (shapes it does not take, image-input layers) the fp32 kernel between conversions
-        if (x.dtype == BF16 and kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and act != ACT_TANH and y.shape[1] == hi and y.shape[2] == wi):
-            r = _bf16s_conv(x, ldx, cin, w, bias, y, ldy, cout, act, False, want_stats=want_stats)
-            if r:
-                return r if isinstance(r, tuple) else None
-        if x.dtype == torch.float32 and y.dtype == BF16 and cin <= 4 and ldx == cin:
-            # image-input layers: the LDS-resident image kernel writes bf16
-            rc = lib.kpx_conv_image_fwd_bf16(x.data_ptr(), n, hi, wi, cin, w.data_ptr(), kh, kw, bias.data_ptr() if bias is not None else None,
-                                             y.data_ptr(), y.shape[1], y.shape[2], cout, ldy, stride, pad_t, pad_l, act, _stream())
-            if rc != -1:
-                check(rc, 'kpx_conv_image_fwd_bf16')
-                return None
-        if x.dtype == BF16 and act != ACT_TANH:
-            # strided / 4x4 / 1x1 layers: the gather kernel of the bf16 matrix pipe on bf16 tensors
-            nbytes = lib.kpx_conv2d_fwd_workspace_bytes(n, y.shape[1], y.shape[2], cin, cout, kh, kw)
-            ws = scratch.get('splitk', nbytes, x.device) if nbytes else None
-            rc = lib.kpx_conv2d_fwd_bf16(x.data_ptr(), n, hi, wi, cin, ldx, w.data_ptr(), kh, kw, bias.data_ptr() if bias is not None else None,
-                                         y.data_ptr(), 1 if y.dtype == torch.float32 else 0, y.shape[1], y.shape[2], cout, ldy, stride, pad_t, pad_l, act,
-                                         ws.data_ptr() if ws is not None else None, nbytes, _stream())
-            if rc != -1:
-                check(rc, 'kpx_conv2d_fwd_bf16')
-                return None
+        # bf16 configuration: the bf16-storage kernel, or (shapes it does not take, image-input layers) the fp32 ladder below between conversions
+        if same3 and (r := conv3x3_same(x, ldx, cin, w, bias, y, ldy, cout, act, False, want_stats=want_stats)) is not None:
+            return r.stats
+        # image-input layers: the LDS-resident image kernel writes bf16
+        if x.dtype == torch.float32 and cin <= 4 and ldx == cin and _took(lib.kpx_conv_image_fwd_bf16(
+                x.data_ptr(), n, hi, wi, cin, w.data_ptr(), kh, kw, _ptr(bias), y.data_ptr(), ho, wo, cout, ldy, stride, pad_t, pad_l, act, _stream()),
+                'kpx_conv_image_fwd_bf16'):
+            return None
+        # strided / 4x4 / 1x1 layers: the gather kernel of the bf16 matrix pipe on bf16 tensors
+        if x.dtype == BF16 and act != ACT_TANH and _took(lib.kpx_conv2d_fwd_bf16(
+                x.data_ptr(), n, hi, wi, cin, ldx, w.data_ptr(), kh, kw, _ptr(bias), y.data_ptr(), 1 if y.dtype == torch.float32 else 0, ho, wo, cout, ldy,
+                stride, pad_t, pad_l, act, *_workspace('splitk', lib.kpx_conv2d_fwd_workspace_bytes(n, ho, wo, cin, cout, kh, kw), x.device), _stream()),
+                'kpx_conv2d_fwd_bf16'):
+            return None
+        # the fp32 detour: convert, run the fp32 ladder (without the statistics), convert back
+        want_stats = False
         if x.dtype == BF16:
             fallback_uses['conv_fwd'] += 1
             x, ldx = _slice_f32(x, ldx, cin), cin
-        yf = y if y.dtype == torch.float32 else torch.empty((n, y.shape[1], y.shape[2], cout), dtype=torch.float32, device=x.device)
-        conv_fwd_raw(x, ldx, cin, w, bias, yf, ldy if yf is y else cout, stride, pad_t, pad_l, act)
-        if yf is not y:
-            cast_channels_raw(yf.data_ptr(), cout, y.data_ptr(), ldy, n * y.shape[1] * y.shape[2], cout, 0)
-        return None
-    if (kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and act != ACT_TANH and cout == 16 and y.shape[1] == hi and y.shape[2] == wi
-            and lib.kpx_conv3x3_c16_eligible(n, hi, wi, cin, cout, ldx, ldy, x.data_ptr())):
-        # exactly 16 produced channels: 16x16x4 MFMA blocks, no cout padding (csrc/conv_c16.hip)
-        slab = torch.empty(n * (hi // 16) * (wi // 16) * 2 * 16, dtype=torch.float32, device=x.device) if want_stats else None
-        check(lib.kpx_conv3x3_c16_f32(x.data_ptr(), n, hi, wi, cin, ldx, w.data_ptr(), 0, bias.data_ptr() if bias is not None else None,
-                                      y.data_ptr(), ldy, act, slab.data_ptr() if slab is not None else None, _stream()), 'kpx_conv3x3_c16_f32')
-        return (slab, (hi // 16) * (wi // 16)) if want_stats else None
-    if (kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and act != ACT_TANH and y.shape[1] == hi and y.shape[2] == wi
-            and not (cout <= 4 and cin <= 128 and n * hi * wi >= 65536)):        # (few produced channels over a large image: VALU kernel inside the library)
-        r = _wino_pretransformed(x, ldx, cin, w, bias, y, ldy, cout, act, False, want_stats=want_stats)
-        if r:
-            return r if isinstance(r, tuple) else None
-    nbytes = lib.kpx_conv2d_fwd_workspace_bytes(n, y.shape[1], y.shape[2], cin, cout, kh, kw)
-    ws = scratch.get('splitk', nbytes, x.device) if nbytes else None
-    check(lib.kpx_conv2d_fwd_f32(x.data_ptr(), n, hi, wi, cin, ldx, w.data_ptr(), kh, kw,
-                                 bias.data_ptr() if bias is not None else None,
-                                 y.data_ptr(), y.shape[1], y.shape[2], cout, ldy, stride, pad_t, pad_l, act, _arith(),
-                                 ws.data_ptr() if ws is not None else None, nbytes, _stream()),
-          'kpx_conv2d_fwd_f32')
+        if y.dtype == BF16:
+            yf, ldyf = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device), cout
+    # the fp32 ladder: the specialised 3x3 kernels, then the library's own (include/kpx.h)
+    r = conv3x3_same(x, ldx, cin, w, bias, yf, ldyf, cout, act, False, want_stats=want_stats) if same3 else None
+    if r is None:
+        check(lib.kpx_conv2d_fwd_f32(x.data_ptr(), n, hi, wi, cin, ldx, w.data_ptr(), kh, kw, _ptr(bias), yf.data_ptr(), ho, wo, cout, ldyf, stride, pad_t, pad_l, act,
+                                     _arith(), *_workspace('splitk', lib.kpx_conv2d_fwd_workspace_bytes(n, ho, wo, cin, cout, kh, kw), x.device), _stream()),
+              'kpx_conv2d_fwd_f32')
+    if yf is not y:
+        cast_channels_raw(yf.data_ptr(), cout, y.data_ptr(), ldy, n * ho * wo, cout, 0)
+    return r.stats if r is not None else None
 
 
 def conv_dgrad_raw(dy, lddy, w, dx, lddx, cin, stride, pad_t, pad_l, bn_src=None, mul=None):
@@ -692,109 +721,78 @@ def conv_dgrad_raw(dy, lddy, w, dx, lddx, cin, stride, pad_t, pad_l, bn_src=None
     mul = (y_in, act): dx is the gradient of the ACTIVATED tensor y_in (the convolution's input); its activation backward is applied in the
     data-gradient epilogue (kpx_conv2d_dgrad_act_f32) -- the producer of y_in then skips its own pass."""
     n, ho, wo = dy.shape[0], dy.shape[1], dy.shape[2]
+    hi, wi = dx.shape[1], dx.shape[2]
     kh, kw, _, cout = w.shape
+    # (mul= never reaches the specialised kernels: the fused activation backward is an epilogue of the gather kernels only)
+    same3 = mul is None and _is_3x3_same(kh, kw, stride, pad_t, pad_l, hi, wi, ho, wo)
+    dxf, lddxf = dx, lddx
     if dy.dtype == BF16 or dx.dtype == BF16:
-        if dy.dtype == BF16 and mul is None and kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and dx.shape[1] == ho and dx.shape[2] == wo:
-            if bn_src is not None and dx.dtype == BF16:
-                # towards a ReLU'd batch norm's output: the epilogue gates the gradient and reduces that batch norm's backward sums
-                r = _bf16s_bnbwd(dy, lddy, cout, w, dx, lddx, cin, bn_src[0], bn_src[1])
-                if r:
-                    return r
-            if _bf16s_conv(dy, lddy, cout, w, None, dx, lddx, cin, ACT_NONE, True):
-                return None
-        if dy.dtype == BF16 and (mul is None or mul[0].dtype == BF16):
-            nbytes = lib.kpx_conv2d_dgrad_workspace_bytes(n, dx.shape[1], dx.shape[2], cin, cout, kh, kw, stride)
-            ws = scratch.get('splitk', nbytes, dy.device) if nbytes else None
-            rc = lib.kpx_conv2d_dgrad_bf16(dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw, dx.data_ptr(), 1 if dx.dtype == torch.float32 else 0,
-                                           dx.shape[1], dx.shape[2], cin, lddx, stride, pad_t, pad_l,
-                                           mul[0].data_ptr() if mul is not None else None, mul[0].shape[3] if mul is not None else 0, mul[1] if mul is not None else 0,
-                                           ws.data_ptr() if ws is not None else None, nbytes, _stream())
-            if rc != -1:
-                check(rc, 'kpx_conv2d_dgrad_bf16')
-                return None
-        if dy.dtype == BF16 and dx.dtype == torch.float32 and cin <= 4 and mul is None:
-            # gradient towards an image: the image kernel reads the bf16 gradient
-            rc = lib.kpx_conv_image_dgrad_bf16(dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw, dx.data_ptr(), dx.shape[1], dx.shape[2], cin, lddx,
-                                               stride, pad_t, pad_l, _stream())
-            if rc != -1:
-                check(rc, 'kpx_conv_image_dgrad_bf16')
-                return None
+        # bf16 configuration: as in conv_fwd_raw
+        if same3 and (r := conv3x3_same(dy, lddy, cout, w, None, dx, lddx, cin, ACT_NONE, True, bn_src=bn_src)) is not None:
+            return r.stats
+        if dy.dtype == BF16 and (mul is None or mul[0].dtype == BF16) and _took(lib.kpx_conv2d_dgrad_bf16(
+                dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw, dx.data_ptr(), 1 if dx.dtype == torch.float32 else 0, hi, wi, cin, lddx,
+                stride, pad_t, pad_l, *((mul[0].data_ptr(), mul[0].shape[3], mul[1]) if mul is not None else (None, 0, 0)),
+                *_workspace('splitk', lib.kpx_conv2d_dgrad_workspace_bytes(n, hi, wi, cin, cout, kh, kw, stride), dy.device), _stream()), 'kpx_conv2d_dgrad_bf16'):
+            return None
+        # gradient towards an image: the image kernel reads the bf16 gradient
+        if dy.dtype == BF16 and dx.dtype == torch.float32 and cin <= 4 and mul is None and _took(lib.kpx_conv_image_dgrad_bf16(
+                dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw, dx.data_ptr(), hi, wi, cin, lddx, stride, pad_t, pad_l, _stream()),
+                'kpx_conv_image_dgrad_bf16'):
+            return None
+        # the fp32 detour: convert, run the fp32 ladder (without the bn sums), convert back
+        bn_src = None
         if dy.dtype == BF16:
             fallback_uses['conv_dgrad'] += 1
             dy, lddy = _slice_f32(dy, lddy, cout), cout
-        dxf = dx if dx.dtype == torch.float32 else torch.empty((n, dx.shape[1], dx.shape[2], cin), dtype=torch.float32, device=dy.device)
+        if dx.dtype == BF16:
+            dxf, lddxf = torch.empty((n, hi, wi, cin), dtype=torch.float32, device=dy.device), cin
         if mul is not None and mul[0].dtype == BF16:
             mul = (cast(mul[0], torch.float32), mul[1])
-        conv_dgrad_raw(dy, lddy, w, dxf, lddx if dxf is dx else cin, cin, stride, pad_t, pad_l, mul=mul)
-        if dxf is not dx:
-            cast_channels_raw(dxf.data_ptr(), cin, dx.data_ptr(), lddx, n * dx.shape[1] * dx.shape[2], cin, 0)
-        return None
-    if mul is not None:
-        y_in, act_in = mul
-        nbytes = lib.kpx_conv2d_dgrad_workspace_bytes(n, dx.shape[1], dx.shape[2], cin, cout, kh, kw, stride)
-        ws = scratch.get('splitk', nbytes, dy.device) if nbytes else None
-        check(lib.kpx_conv2d_dgrad_act_f32(dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw,
-                                           dx.data_ptr(), dx.shape[1], dx.shape[2], cin, lddx, stride, pad_t, pad_l, _arith(),
-                                           y_in.data_ptr(), y_in.shape[3], act_in,
-                                           ws.data_ptr() if ws is not None else None, nbytes, _stream()), 'kpx_conv2d_dgrad_act_f32')
-        return
-    if (kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and cin == 16 and bn_src is None and dx.shape[1] == ho and dx.shape[2] == wo
-            and lib.kpx_conv3x3_c16_eligible(n, ho, wo, cout, cin, lddy, lddx, dy.data_ptr())):
-        check(lib.kpx_conv3x3_c16_f32(dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), 1, None, dx.data_ptr(), lddx, ACT_NONE, None, _stream()),
-              'kpx_conv3x3_c16_f32')
-        return
-    if kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and dx.shape[1] == ho and dx.shape[2] == wo:
-        r = _wino_pretransformed(dy, lddy, cout, w, None, dx, lddx, cin, ACT_NONE, True, bn_src=bn_src)
-        if r:
-            return r if isinstance(r, tuple) else None
-    nbytes = lib.kpx_conv2d_dgrad_workspace_bytes(n, dx.shape[1], dx.shape[2], cin, cout, kh, kw, stride)
-    ws = scratch.get('splitk', nbytes, dy.device) if nbytes else None
-    check(lib.kpx_conv2d_dgrad_f32(dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw,
-                                   dx.data_ptr(), dx.shape[1], dx.shape[2], cin, lddx, stride, pad_t, pad_l, _arith(),
-                                   ws.data_ptr() if ws is not None else None, nbytes, _stream()),
-          'kpx_conv2d_dgrad_f32')
+    # the fp32 ladder: the specialised 3x3 kernels, then the library's own (include/kpx.h), with the activation backward of ``mul``
+    r = conv3x3_same(dy, lddy, cout, w, None, dxf, lddxf, cin, ACT_NONE, True, bn_src=bn_src) if same3 else None
+    if r is None:
+        ws = _workspace('splitk', lib.kpx_conv2d_dgrad_workspace_bytes(n, hi, wi, cin, cout, kh, kw, stride), dy.device)
+        geom = (dy.data_ptr(), n, ho, wo, cout, lddy, w.data_ptr(), kh, kw, dxf.data_ptr(), hi, wi, cin, lddxf, stride, pad_t, pad_l, _arith())
+        if mul is not None:
+            check(lib.kpx_conv2d_dgrad_act_f32(*geom, mul[0].data_ptr(), mul[0].shape[3], mul[1], *ws, _stream()), 'kpx_conv2d_dgrad_act_f32')
+        else:
+            check(lib.kpx_conv2d_dgrad_f32(*geom, *ws, _stream()), 'kpx_conv2d_dgrad_f32')
+    if dxf is not dx:
+        cast_channels_raw(dxf.data_ptr(), cin, dx.data_ptr(), lddx, n * hi * wi, cin, 0)
+    return r.stats if r is not None else None
 
 
 def conv_wgrad_raw(x, ldx, cin, dy, lddy, dw, stride, pad_t, pad_l):
     n, hi, wi = x.shape[0], x.shape[1], x.shape[2]
     ho, wo = dy.shape[1], dy.shape[2]
     kh, kw, _, cout = dw.shape
-    if (x.dtype == BF16 and dy.dtype == BF16 and kh == 3 and kw == 3 and stride == 1 and pad_t == 1 and pad_l == 1 and ho == hi and wo == wi
-            and lib.kpx_conv3x3_wgrad_bf16_eligible(n, hi, wi, cin, ldx, cout, lddy, x.data_ptr(), dy.data_ptr())):
-        nbytes = lib.kpx_conv3x3_wgrad_bf16_workspace_bytes(n, hi, wi, cin, cout)
-        ws = scratch.get('wgrad', nbytes, x.device)
-        check(lib.kpx_conv3x3_wgrad_bf16(x.data_ptr(), n, hi, wi, cin, ldx, dy.data_ptr(), cout, lddy, dw.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-              'kpx_conv3x3_wgrad_bf16')
-        return
+
+    def generic(entry, *arith):
+        """A gather entry of either storage type: they share the geometry arguments and the workspace query."""
+        return getattr(lib, entry)(x.data_ptr(), n, hi, wi, cin, ldx, dy.data_ptr(), ho, wo, cout, lddy, dw.data_ptr(), kh, kw, stride, pad_t, pad_l, *arith,
+                                   *_workspace('wgrad', lib.kpx_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw), x.device), _stream())
+
     if x.dtype == BF16 and dy.dtype == BF16:
-        nbytes = lib.kpx_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw)
-        ws = scratch.get('wgrad', nbytes, x.device) if nbytes else None
-        rc = lib.kpx_conv2d_wgrad_bf16(x.data_ptr(), n, hi, wi, cin, ldx, dy.data_ptr(), ho, wo, cout, lddy, dw.data_ptr(), kh, kw, stride, pad_t, pad_l,
-                                       ws.data_ptr() if ws is not None else None, nbytes, _stream())
-        if rc != -1:
-            check(rc, 'kpx_conv2d_wgrad_bf16')
+        if (_is_3x3_same(kh, kw, stride, pad_t, pad_l, hi, wi, ho, wo)
+                and lib.kpx_conv3x3_wgrad_bf16_eligible(n, hi, wi, cin, ldx, cout, lddy, x.data_ptr(), dy.data_ptr())):
+            check(lib.kpx_conv3x3_wgrad_bf16(x.data_ptr(), n, hi, wi, cin, ldx, dy.data_ptr(), cout, lddy, dw.data_ptr(),
+                                             *_workspace('wgrad', lib.kpx_conv3x3_wgrad_bf16_workspace_bytes(n, hi, wi, cin, cout), x.device), _stream()),
+                  'kpx_conv3x3_wgrad_bf16')
             return
-    if x.dtype == torch.float32 and dy.dtype == BF16 and cin <= 4:
-        # image-input layers: fp32 image, bf16 gradient
-        nbytes = lib.kpx_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw)
-        ws = scratch.get('wgrad', nbytes, x.device) if nbytes else None
-        rc = lib.kpx_conv_image_wgrad_bf16(x.data_ptr(), n, hi, wi, cin, ldx, dy.data_ptr(), ho, wo, cout, lddy, dw.data_ptr(), kh, kw, stride, pad_t, pad_l,
-                                           ws.data_ptr() if ws is not None else None, nbytes, _stream())
-        if rc != -1:
-            check(rc, 'kpx_conv_image_wgrad_bf16')
+        if _took(generic('kpx_conv2d_wgrad_bf16'), 'kpx_conv2d_wgrad_bf16'):
             return
+    # image-input layers: fp32 image, bf16 gradient
+    if x.dtype == torch.float32 and dy.dtype == BF16 and cin <= 4 and _took(generic('kpx_conv_image_wgrad_bf16'), 'kpx_conv_image_wgrad_bf16'):
+        return
+    # the fp32 detour of the bf16 configuration: convert, then the fp32 entry (its own ladder: include/kpx.h)
     if x.dtype == BF16 or dy.dtype == BF16:
         fallback_uses['conv_wgrad'] += 1
         if x.dtype == BF16:
             x, ldx = _slice_f32(x, ldx, cin), cin
         if dy.dtype == BF16:
             dy, lddy = _slice_f32(dy, lddy, cout), cout
-    nbytes = lib.kpx_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, kh, kw)
-    ws = scratch.get('wgrad', nbytes, x.device) if nbytes else None
-    check(lib.kpx_conv2d_wgrad_f32(x.data_ptr(), n, hi, wi, cin, ldx, dy.data_ptr(), ho, wo, cout, lddy,
-                                   dw.data_ptr(), kh, kw, stride, pad_t, pad_l, _arith(),
-                                   ws.data_ptr() if ws is not None else None, nbytes, _stream()),
-          'kpx_conv2d_wgrad_f32')
+    check(generic('kpx_conv2d_wgrad_f32', _arith()), 'kpx_conv2d_wgrad_f32')
 
 
 def chan_sum_raw(x, ldx, pixels, c, out):
@@ -993,8 +991,7 @@ def _whole_tiles_per_group(n, groups, tiles_per_image):
     """True when every statistics tile of a producing convolution lies inside ONE batch-norm group.  The bf16 3x3 kernel packs G images into a
     tile on 8x8 / narrow 16x16 layers (tiles per image = 1/G, a Fraction): with n / groups not a multiple of G a tile would straddle two
     groups, and int(ng * tpi) would silently drop or misattribute images."""
-    from fractions import Fraction
-    return n % groups == 0 and (Fraction(tiles_per_image) * (n // groups)).denominator == 1
+    return n % groups == 0 and (tiles_per_image * (n // groups)).denominator == 1
 
 
 class BatchNormFn(torch.autograd.Function):
@@ -1269,7 +1266,7 @@ class KeypointHeadProjFn(torch.autograd.Function):
         xs_y = torch.empty((bsz, h, c), dtype=torch.float32, device=dev)
         xs_x = torch.empty((bsz, wd, c), dtype=torch.float32, device=dev)
         sc = scratch.get('kpproj', lib.kpx_keypoint_head_proj_scratch_bytes(bsz, h, wd, c, k), dev)
-        check(lib.kpx_keypoint_head_proj_fwd_f32(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, bsz, h, wd, c, k,
+        check(lib.kpx_keypoint_head_proj_fwd_f32(x.data_ptr(), w.data_ptr(), _ptr(b), bsz, h, wd, c, k,
                                                  mu.data_ptr(), py.data_ptr(), px.data_ptr(), xs_y.data_ptr(), xs_x.data_ptr(),
                                                  sc.data_ptr(), _stream()), 'kpx_keypoint_head_proj_fwd_f32')
         ctx.dims = (bsz, h, wd, c, k)
@@ -1301,9 +1298,7 @@ class KeypointHeadProjFn(torch.autograd.Function):
             acc = 0
         sc = scratch.get('kpproj', lib.kpx_keypoint_head_proj_scratch_bytes(bsz, h, wd, c, k), dev)
         check(lib.kpx_keypoint_head_proj_bwd_f32(dmu.data_ptr(), mu.data_ptr(), py.data_ptr(), px.data_ptr(), xs_y.data_ptr(), xs_x.data_ptr(),
-                                                 w.data_ptr(), bsz, h, wd, c, k, dx.data_ptr() if dx is not None else None,
-                                                 dw_buf.data_ptr() if dw_buf is not None else None,
-                                                 db_buf.data_ptr() if db_buf is not None else None, acc, sc.data_ptr(), _stream()),
+                                                 w.data_ptr(), bsz, h, wd, c, k, _ptr(dx), _ptr(dw_buf), _ptr(db_buf), acc, sc.data_ptr(), _stream()),
               'kpx_keypoint_head_proj_bwd_f32')
         if direct:
             return dx, None, None, None, None
@@ -1685,10 +1680,9 @@ class LstmLayerFn(torch.autograd.Function):
         hs = torch.empty((t, bsz, units), dtype=torch.float32, device=dev)
         zero = torch.zeros((bsz, units), dtype=torch.float32, device=dev)
         width = n_in + units
-        nbytes = lib.kpx_conv2d_fwd_workspace_bytes(bsz, 1, 1, width, 4 * units, 1, 1)
-        ws = scratch.get('splitk', nbytes, dev) if nbytes else None
         check(lib.kpx_lstm_layer_fwd_f32(x.data_ptr(), t, bsz, n_in, kernel.data_ptr(), bias.data_ptr(), units, xin.data_ptr(), gates.data_ptr(),
-                                         cs.data_ptr(), hs.data_ptr(), zero.data_ptr(), ws.data_ptr() if ws is not None else None, nbytes, _stream()),
+                                         cs.data_ptr(), hs.data_ptr(), zero.data_ptr(),
+                                         *_workspace('splitk', lib.kpx_conv2d_fwd_workspace_bytes(bsz, 1, 1, width, 4 * units, 1, 1), dev), _stream()),
               'kpx_lstm_layer_fwd_f32')
         ctx.save_for_backward(xin, gates, cs, kernel)
         ctx.w_grad_out, ctx.b_grad_out, ctx.n_in = w_grad_out, b_grad_out, n_in
@@ -1707,11 +1701,10 @@ class LstmLayerFn(torch.autograd.Function):
         dh = torch.empty((bsz, units), dtype=torch.float32, device=dev)
         dc0 = torch.zeros((bsz, units), dtype=torch.float32, device=dev)
         dc1 = torch.empty((bsz, units), dtype=torch.float32, device=dev)
-        nbytes = lib.kpx_conv2d_dgrad_workspace_bytes(bsz, 1, 1, width, 4 * units, 1, 1, 1)
-        ws = scratch.get('splitk', nbytes, dev) if nbytes else None
         check(lib.kpx_lstm_layer_bwd_f32(dhs.data_ptr(), t, bsz, n_in, kernel.data_ptr(), units, gates.data_ptr(), cs.data_ptr(), dgates.data_ptr(),
-                                         dx.data_ptr() if dx is not None else None, dxin.data_ptr(), dh.data_ptr(), dc0.data_ptr(), dc1.data_ptr(),
-                                         ws.data_ptr() if ws is not None else None, nbytes, _stream()), 'kpx_lstm_layer_bwd_f32')
+                                         _ptr(dx), dxin.data_ptr(), dh.data_ptr(), dc0.data_ptr(), dc1.data_ptr(),
+                                         *_workspace('splitk', lib.kpx_conv2d_dgrad_workspace_bytes(bsz, 1, 1, width, 4 * units, 1, 1, 1), dev), _stream()),
+              'kpx_lstm_layer_bwd_f32')
         dw = db = None
         if ctx.needs_input_grad[1]:
             direct = ctx.w_grad_out is not None and _claim_grad(ctx.w_grad_out)
@@ -1756,8 +1749,7 @@ class VaeSampleKlFn(torch.autograd.Function):
         dlogit = torch.empty_like(logit)
         dz = dz.contiguous() if dz is not None else None
         dkl = dkl.contiguous() if dkl is not None else None
-        check(lib.kpx_vae_sample_kl_bwd_f32(logit.data_ptr(), eps.data_ptr(), dz.data_ptr() if dz is not None else None,
-                                            dkl.data_ptr() if dkl is not None else None, 1.0 if dkl is not None else 0.0,
+        check(lib.kpx_vae_sample_kl_bwd_f32(logit.data_ptr(), eps.data_ptr(), _ptr(dz), _ptr(dkl), 1.0 if dkl is not None else 0.0,
                                             dlogit.data_ptr(), bsz, v, _stream()), 'kpx_vae_sample_kl_bwd_f32')
         return dlogit, None
 

@@ -109,9 +109,10 @@ def _vgg_forward(vgg, images):
             cout = wgt.shape[3]
             y = torch.empty((nn_, hh, ww, cout), dtype=ops.act_dtype(), device=dev)
             pooled = None
-            if FUSE_POOL_FWD and y.dtype == torch.float32 and 'P' in VGG_SEQ[pos + 1:pos + 3] and hh % 2 == 0 and ww % 2 == 0:      # conv -> ('F' ->) pool: pool in the epilogue
+            # conv -> ('F' ->) pool: pool in the epilogue (the guard only spares a buffer no kernel would fill: fp32 outputs of even size)
+            if FUSE_POOL_FWD and y.dtype == torch.float32 and 'P' in VGG_SEQ[pos + 1:pos + 3] and hh % 2 == 0 and ww % 2 == 0:
                 pooled = torch.empty((nn_, hh // 2, ww // 2, cout), dtype=torch.float32, device=dev)
-                if not ops.conv3x3_wino43_ex(x, cc, cc, wgt, b, y, cout, cout, ops.ACT_RELU, False, pool_out=pooled):
+                if ops.conv3x3_same(x, cc, cc, wgt, b, y, cout, cout, ops.ACT_RELU, False, pool_out=pooled) is None:
                     pooled = None
             if pooled is None:
                 ops.conv_fwd_raw(x, cc, cc, wgt, b, y, cout, 1, 1, 1, ops.ACT_RELU)
@@ -120,7 +121,6 @@ def _vgg_forward(vgg, images):
     return feats, tape
 
 
-import os as _os
 FUSE_FEAT_BWD = True      # feature gradient (pool bwd + L1 bwd + ReLU bwd) in one pass
 FUSE_POOL_FWD = True      # 2x2 max-pool written by the producing conv's epilogue
 FUSE_RELU_BWD = True      # ReLU backward applied in the epilogue of the data gradient above it
@@ -200,11 +200,8 @@ class _PerceptualLossFn(torch.autograd.Function):
                     ops.act_bwd_raw_(d, yp, ops.ACT_RELU)             # d is ours: in place
                 dx = torch.empty(xp.shape, dtype=xp.dtype, device=xp.device)
                 # x is the ReLU output of the conv below (not a pooled tensor, not the image): its ReLU backward rides in this epilogue
-                if (FUSE_RELU_BWD and d.dtype == ops.BF16 and id(x) in conv_outputs and id(x) not in feat_ids
-                        and ops._bf16s_conv(d, wgt.shape[3], wgt.shape[3], wgt, None, dx, xp.shape[3], xp.shape[3], ops.ACT_NONE, True, mask=xp)):
-                    done.add(id(x))
-                elif (FUSE_RELU_BWD and d.dtype == torch.float32 and id(x) in conv_outputs and id(x) not in feat_ids
-                        and ops.conv3x3_wino43_ex(d, wgt.shape[3], wgt.shape[3], wgt, None, dx, xp.shape[3], xp.shape[3], ops.ACT_NONE, True, mask=xp)):
+                if (FUSE_RELU_BWD and id(x) in conv_outputs and id(x) not in feat_ids
+                        and ops.conv3x3_same(d, wgt.shape[3], wgt.shape[3], wgt, None, dx, xp.shape[3], xp.shape[3], ops.ACT_NONE, True, mask=xp) is not None):
                     done.add(id(x))
                 else:
                     ops.conv_dgrad_raw(d, wgt.shape[3], wgt, dx, xp.shape[3], xp.shape[3], 1, 1, 1)
