@@ -1,5 +1,7 @@
 """Throughput of the image-pair input pipeline (kpx_amd.data) on Penn-Action-sized synthetic JPEG frames (480x270):
-pairs/s of the threaded decode + augment + pinned H2D + on-device conversion, alone and feeding the train step."""
+pairs/s of the threaded decode + augment + pinned H2D + on-device conversion -- or, with --resident, of the HIP augmentation on frames
+kept in HBM -- alone and feeding the train step, next to the same train-step loop on ONE fixed device batch of the same process.
+Every window is warmed up and at least a second long.  KPX_DTYPE=bf16 selects the bf16 configuration as everywhere."""
 import argparse, io, os, sys, tempfile, time
 import numpy as np
 import torch
@@ -20,30 +22,57 @@ def make_dataset(root, videos=8, frames=40, w=480, h=270):
         f.write(''.join('%04d 0\n' % v for v in range(videos)))
 
 
+def timed(step, batch, batches, min_seconds=1.0):
+    """pairs/s of ``step(i)`` over a window of at least ``batches`` calls and ``min_seconds`` (the caller has warmed up)."""
+    n = 0
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    while True:
+        for _ in range(batches): step(n); n += 1
+        torch.cuda.synchronize(); dt = time.perf_counter() - t0
+        if dt >= min_seconds: return batch * n / dt
+
+
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument('--batch', type=int, default=32); ap.add_argument('--batches', type=int, default=40)
     ap.add_argument('--threads', type=int, default=12); ap.add_argument('--train', action='store_true')
+    ap.add_argument('--resident', action='store_true', help='frames decoded once into HBM, augmentation in HIP (batches(resident=True))')
+    ap.add_argument('--frames', type=int, default=40, help='frames per synthetic video (8 videos)')
     a = ap.parse_args()
     import kpx_amd
     dev = torch.device('cuda', 0)
     with tempfile.TemporaryDirectory() as root:
-        make_dataset(root)
-        it = iter(kpx_amd.ImagePairDataLoader(root, 'train', random_order=True, randomness=True).batches(a.batch, dev, num_preprocess_threads=a.threads))
+        make_dataset(root, frames=a.frames)
+        loader = kpx_amd.ImagePairDataLoader(root, 'train', random_order=True, randomness=True)
+        if a.resident:
+            store = loader.resident_frames(dev)
+            print('resident store: %d frames, %d bytes (%.1f MiB) ingested in %.2f s (%.0f frames/s, header scan + decode + copy)'
+                  % (len(store.index.offsets), store.index.total_bytes, store.index.total_bytes / 2.0 ** 20, store.ingest_seconds,
+                     len(store.index.offsets) / store.ingest_seconds))
+            what = 'resident path'
+        else:
+            what = 'CPU pipeline, %d threads' % a.threads
+        it = iter(loader.batches(a.batch, dev, num_preprocess_threads=a.threads, resident=a.resident))
         for _ in range(3): next(it)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        for _ in range(a.batches): b = next(it)
-        torch.cuda.synchronize(); dt = time.perf_counter() - t0
-        print('input pipeline alone: %.0f pairs/s (%d threads, batch %d)' % (a.batch * a.batches / dt, a.threads, a.batch))
+        print('input pipeline alone (%s): %.0f pairs/s (batch %d)' % (what, timed(lambda i: next(it), a.batch, a.batches), a.batch))
         if a.train:
             cfg = {'training': {'lr': {'start_val': 1e-4, 'step': 20000, 'decay': 0.95}, 'batch_size': a.batch}, 'model': {'n_pts': 15},
                    'paths': {'log_dir': '/tmp/kpx_bench', 'vggnet': None}}
             vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(seed=19), device=dev)
             model = kpx_amd.DetectorTranslatorModel(cfg, device=dev, vgg=vgg, image_size=128); model.build()
-            for i in range(3): model.train_step(None, next(it), i, a.batch)
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            for i in range(a.batches): model.train_step(None, next(it), 3 + i, a.batch)
-            torch.cuda.synchronize(); dt = time.perf_counter() - t0
-            print('train step fed by the pipeline: %.0f pairs/s' % (a.batch * a.batches / dt))
+            fixed = {k: v.clone() for k, v in next(it).items()}
+            steps = [0]
+
+            def fed(i):
+                model.train_step(None, next(it), steps[0], a.batch); steps[0] += 1
+
+            def on_fixed(i):
+                model.train_step(None, fixed, steps[0], a.batch); steps[0] += 1
+            for i in range(3): fed(i)
+            for rep in range(2):                       # alternated: the spread between the repetitions is the noise of this session
+                for i in range(3): on_fixed(i)
+                print('train step on one fixed device batch [%d]: %.0f pairs/s' % (rep, timed(on_fixed, a.batch, a.batches)))
+                for i in range(3): fed(i)
+                print('train step fed by the pipeline (%s) [%d]: %.0f pairs/s' % (what, rep, timed(fed, a.batch, a.batches)))
 
 
 if __name__ == '__main__':

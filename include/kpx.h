@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 8
+#define KPX_ABI_VERSION 9
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -458,6 +458,46 @@ int kpx_maxpool2_fwd_bf16(const void* x, int N, int H, int W, int C, void* y, vo
 int kpx_vgg_feat_bwd_bf16(const void* f, size_t half, const float* gscale_dev, float gscale_host, const void* dy_pooled,
                           int B, int H, int W, int C, void* d, void* stream);
 int kpx_l1_pair_fwd_bf16(const void* f, size_t half, float* loss_out, void* scratch, void* stream);
+
+/* ---- The image-pair augmentation on frames resident in HBM (ABI 9): what ImagePairDataLoader.render does with PIL
+ *      (data/image_pair_dataloader.py:71-165: rotate, resize to short side 128, crop, flip; utils/data.py:8-35: one of ten filters),
+ *      byte for byte, from a table of per-frame decisions the host draws (kpx_amd/resident.py).
+ *
+ *   frames     one flat uint8 buffer of decoded RGB frames in HWC order; frame_off[i] = byte offset of frame i (a multiple of 16)
+ *   rows       [n_rows][KPX_AUG_ROW_INTS] int32, one row per output frame:
+ *                0 frame number      1 w   2 h (size of the source frame)      3 x0   4 y0 (crop origin in the RESIZED frame)
+ *                5 flags (KPX_AUG_FLIP | KPX_AUG_ROTATE | KPX_AUG_IDENTITY = the enhancer's factor is 1.0: the tile passes unchanged)
+ *                6 filter id: -1 none, 0..5 the ImageFilter kernels of `kernels`, 6..9 Sharpness / Brightness / Color / Contrast
+ *                7 the enhancer's factor (the bits of the float32 nearest to filt_val * 0.1)
+ *                8..13 a0..a5: Pillow's 16.16 fixed-point NEAREST rotation, xin = (a2 + a1*y + a0*x) >> 16, yin = (a5 + a4*y + a3*x) >> 16
+ *                14 / 15 offset into resize_tabs and entry stride of the horizontal pass (w -> resized width), 16 / 17 of the vertical pass
+ *                18.. unused (the loader records the resized size there)
+ *   resize_tabs  int32; a table of a pass is n_out entries of `stride` ints: first input index, tap count, the taps' 22-bit coefficients
+ *                (a pass Pillow skips, n_in == n_out, is the table {i, 1, 1 << 22})
+ *   kernels    [6][KPX_AUG_KERNEL_FLOATS] float32: size (3 or 5), float32(offset) + 0.5f, size*size coefficients float32(k / scale)
+ *   band_rows_cap  rows of the horizontally resized frame one 16-row band of the tile may need (LDS: cap * 384 bytes)
+ *   tiles      uint8 [n_rows][128][128][3], lsum int32 [n_rows][KPX_AUG_BANDS] (luminance sums): written by geometry, read by filter
+ *   out        float32 [n_rows][128][128][3] in [-1,1] (the arithmetic of kpx_u8_to_unit_f32)
+ *
+ * The kernels trust the table: the HOST rejects, before the launch, a frame number outside the store, a crop window outside the resized
+ * frame, a filter id outside -1..9, a frame side above KPX_AUG_MAX_SIDE, a pass with more than KPX_AUG_MAX_TAPS taps or with
+ * 255 * sum|k| >= 2^31, and a band that needs more than KPX_AUG_MAX_BAND_ROWS rows (kpx_amd.resident.check_rows).  With those bounds
+ * no 32-bit sum overflows (rotation: |a1*y + a0*x + a2| < 2^29). */
+#define KPX_AUG_ROW_INTS 24
+#define KPX_AUG_FLIP 1
+#define KPX_AUG_ROTATE 2
+#define KPX_AUG_IDENTITY 4
+#define KPX_AUG_BAND 16
+#define KPX_AUG_BANDS 8
+#define KPX_AUG_KERNEL_FLOATS 32
+#define KPX_AUG_MAX_SIDE 2048
+#define KPX_AUG_MAX_TAPS 32
+#define KPX_AUG_MAX_BAND_ROWS 160
+#define KPX_AUG_MAX_ROWS 32768
+int kpx_augment_geometry_u8(const unsigned char* frames, const int64_t* frame_off, const int32_t* rows, int n_rows,
+                            const int32_t* resize_tabs, int band_rows_cap, unsigned char* tiles, int32_t* lsum, void* stream);
+int kpx_augment_filter_f32(const unsigned char* tiles, const int32_t* lsum, const int32_t* rows, int n_rows, const float* kernels,
+                           float* out, void* stream);
 
 #ifdef __cplusplus
 }

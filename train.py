@@ -8,7 +8,8 @@ Both modes are built: ``detector_translator`` (stage 1, the BASELINE.json hot pa
 sequence VAE-GAN over the pseudo labels written by make_pseudo_labels.py).  Without ``--synthetic`` the frames come from ``paths.data_dir`` through kpx_amd.data.ImagePairDataLoader (the
 reference's data/image_pair_dataloader.py + tf.data pipeline: threaded PIL augmentation, uint8 batches in pinned memory, async
 copy + on-device conversion); ``--synthetic`` feeds Penn-shaped random pairs with the same output contract (float32 NHWC in
-[-1,1], keys image / future_image).
+[-1,1], keys image / future_image).  ``--resident-data`` (detector_translator) decodes every frame of both subsets once into HBM and augments on the
+GPU (kpx_amd.resident): the same batches bit for bit, without the per-step JPEG decoding.
 """
 import logging
 import os
@@ -95,6 +96,9 @@ def main(argv=None):
     parser.add_argument('--mode', type=str, choices=['detector_translator', 'motion_generator'], help='which mode to train')
     parser.add_argument('--config', type=str, help='path of the configuration file')
     parser.add_argument('--synthetic', action='store_true', help='synthetic Penn-shaped pairs instead of the JPEG pipeline')
+    parser.add_argument('--resident-data', action='store_true',
+                        help='detector_translator: decode every frame once, keep the frames in HBM and augment with HIP kernels '
+                             '(ImagePairDataLoader.batches(resident=True)); the same batches as without the flag')
     parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
     parser.add_argument('--steps', type=int, default=None, help='override training.n_steps')
     parser.add_argument('--ckpt-format', choices=['npz', 'tf', 'bundle'], default=os.environ.get('KPX_CKPT_FORMAT', 'npz'),
@@ -107,6 +111,8 @@ def main(argv=None):
     parser.add_argument('--colors_seed', type=int, default=0,
                         help='seed of the key-point palette of the image summaries (the reference draws it from the unseeded random module)')
     args = parser.parse_args(argv)
+    if args.resident_data and (args.mode != 'detector_translator' or args.synthetic):
+        parser.error('--resident-data keeps JPEG frames in HBM: the motion_generator mode reads key-point files and --synthetic reads no frames')
     logging.basicConfig(level=logging.INFO, format='%(message)s')
 
     config = load_config(args.config)
@@ -141,10 +147,10 @@ def main(argv=None):
         import numpy as np
         random.seed(1000 + rank); np.random.seed(1000 + rank)          # different sample streams per data-parallel rank
         train_it = iter(kpx_amd.ImagePairDataLoader(data_dir, 'train', random_order=True, randomness=True)
-                        .batches(batch_size, dev, repeat=True, shuffle=True))
+                        .batches(batch_size, dev, repeat=True, shuffle=True, resident=args.resident_data))
         if os.path.exists(os.path.join(str(data_dir), 'test_set.txt')):
             test_loader = kpx_amd.ImagePairDataLoader(data_dir, 'test', random_order=False, randomness=False)
-            test_it = lambda: iter(test_loader.batches(batch_size, dev, repeat=False, shuffle=False))
+            test_it = lambda: iter(test_loader.batches(batch_size, dev, repeat=False, shuffle=False, resident=args.resident_data))
     n_steps = args.steps if args.steps is not None else train_config['n_steps']
     model.initialize_loggers(paths_config['log_dir'], None)
     print('training start')

@@ -56,6 +56,13 @@ __device__ __forceinline__ float kpx_sub_rn(float a, float b) {
     return a - b;
 }
 
+// uint8 -> [-1,1] with the loaders' arithmetic (kpx_u8_to_unit_f32, the augmentation's last stage): numpy's float64 division, tf.data's
+// float32 cast, then map_fn in float32 (v * 2 is exact, so the subtraction is the only rounding whether or not it is contracted).
+__device__ __forceinline__ float kpx_u8_to_unit(unsigned char u) {
+    const float v = (float)((double)u / 255.0);
+    return __fsub_rn(__fmul_rn(v, 2.0f), 1.0f);
+}
+
 // d(act)/d(pre-activation) from the ACTIVATED value y (relu / leaky relu keep the sign of their argument)
 __device__ __forceinline__ float kpx_act_grad_from_y(float y, int act) {
     return act == KPX_ACT_RELU ? (y > 0.f ? 1.f : 0.f) : act == KPX_ACT_LRELU ? (y > 0.f ? 1.f : 0.01f) : 1.f;

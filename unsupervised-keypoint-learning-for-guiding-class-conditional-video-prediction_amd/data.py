@@ -17,7 +17,9 @@ What is different from the reference's tf.data graph:
   reference's arithmetic (float32(u8 / 255.0) * 2 - 1), double-buffered so the next batch's copy overlaps the current step
   (the reference: ``dataset.prefetch(1)`` + feed_dict);
 * ``shuffle(2000)`` of the reference acts on an i.i.d. stream when ``random_order`` is set (a no-op in distribution); for
-  sequential order a plan-level shuffle buffer of the same size is kept, so nothing bigger than indices is buffered.
+  sequential order a plan-level shuffle buffer of the same size is kept, so nothing bigger than indices is buffered;
+* ``batches(..., resident=True)`` (kpx_amd/resident.py): the subset's frames are decoded ONCE into HBM and every batch is produced there by
+  two HIP launches that repeat ``render``'s PIL arithmetic byte for byte, from the same ``PairPlan``s -- no JPEG decoding per step.
 """
 import os
 import os.path as osp
@@ -67,6 +69,8 @@ class ImagePairDataLoader(object):
             self._images = f.read().splitlines()
         self._total = len(self._images)
         self._n_files = {}
+        self._frames = None            # resident.FrameIndex once attached: plan() reads frame sizes and counts from it
+        self._store = None             # resident.ResidentFrames, built by the first batches(..., resident=True)
         print(subset + 'set : ', self._total)
 
     # ---- reference surface
@@ -105,8 +109,9 @@ class ImagePairDataLoader(object):
     def plan(self, idx):
         video = self._images[idx].split()[0]
         n_files = self._n_files.get(video)
+        frames = self._frames
         if n_files is None:
-            n_files = self._n_files[video] = len(os.listdir(osp.join(self._data_dir, video)))
+            n_files = self._n_files[video] = frames.count(video) if frames is not None else len(os.listdir(osp.join(self._data_dir, video)))
         rng = self._rng
         im_idx, fu_idx = 0, 10                                                       # :75-76
         if self._random_order:
@@ -116,8 +121,11 @@ class ImagePairDataLoader(object):
         angle = crop = flip = filt = filt_val = None
         if self._randomness:
             angle = rng.randrange(-10, 11)                                           # :93
-            with Image.open(self._frame_path(video, im_idx)) as im:                  # header only: the crop range needs the size
-                w, h = im.size
+            if frames is not None:
+                w, h = frames.size(video)                                            # the store has read every header already
+            else:
+                with Image.open(self._frame_path(video, im_idx)) as im:              # header only: the crop range needs the size
+                    w, h = im.size
             rw, rh, _ = _resized_size(w, h)
             crop = rng.randint(0, int((rw if w > h else rh) - IMAGE_SIZE))            # :113 / :143 (int(w/ratio - 128))
             flip = rng.randint(0, 1)
@@ -151,12 +159,38 @@ class ImagePairDataLoader(object):
         return tuple(np.asarray(f) for f in frames)
 
     # ---- batches on the device
-    def batches(self, batch_size, device, repeat=True, shuffle=False, num_preprocess_threads=8, prefetch=2):
+    def batches(self, batch_size, device, repeat=True, shuffle=False, num_preprocess_threads=8, prefetch=2, resident=False,
+                max_resident_bytes=64 << 30):
         """The reference's get_dataset(batch_size, repeat, shuffle, num_preprocess_threads, prefetch) as an iterator of
-        {'image','future_image'} float32 tensors [B,128,128,3] in [-1,1] living on ``device``.  (The reference maps with 12
-        threads; 6-8 decode threads already deliver ~1400 pairs/s of 480x270 JPEGs and leave the GIL to the thread that
-        enqueues the train step -- measured with bench_input.py: 890-926 pairs/s fed vs 926 synthetic.)"""
+        {'image','future_image'} float32 tensors [B,128,128,3] in [-1,1] living on ``device``.
+
+        ``resident=False``: JPEG decode + PIL augmentation on ``num_preprocess_threads`` host threads (the reference maps with 12).
+        ``resident=True``: every frame of the subset is decoded once into HBM (at most ``max_resident_bytes``; built on first use, kept
+        on the loader) and each batch is two HIP launches (kpx_amd.resident) -- the same batches bit for bit, from the same draws of
+        ``rng`` / ``np_rng``; needs a GPU ``device``.  What either path delivers, alone and feeding the train step: bench_input.py,
+        DESIGN.md section 5a."""
+        if resident:
+            from .resident import ResidentBatcher
+            return ResidentBatcher(self, batch_size, device, repeat, shuffle, max_resident_bytes)
         return _DeviceBatcher(self, batch_size, device, repeat, shuffle, num_preprocess_threads, prefetch)
+
+    # ---- resident frames (kpx_amd.resident)
+    def attach_frames(self, frames):
+        """plan() takes frame sizes and frame counts from ``frames`` (a resident.FrameIndex) from now on."""
+        self._frames = frames
+        self._n_files = {}
+
+    def resident_frames(self, device, max_bytes=64 << 30):
+        """The loader's frame store on ``device``, decoded on first use."""
+        import torch
+        from .resident import ResidentFrames
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if self._store is None or self._store.device != device:
+            self._store = ResidentFrames(self._data_dir, self._images, device, max_bytes)
+            self.attach_frames(self._store.index)
+        return self._store
 
 
 def _u8_to_unit_numpy(u8):
