@@ -19,15 +19,9 @@
 //   * wavefront (wm, wn) owns P pixel blocks x Q cout blocks: P + Q fragment reads per P*Q MFMAs.
 // Epilogue options: bias, activation, a ReLU mask (data gradient towards an activated tensor: VGG19), per-workgroup batch-norm sums of the
 // fp32 accumulators (consumed by kpx_bn_train_fwd: no statistics pass over the activation).
-#include "kpx_common.h"
+#include "kpx_bf16.h"
 #include "kpx_env.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-#define S16_OOB 0x7ffffff0
 #define S16_PIX 80                       // bytes of one patch pixel in LDS: 32 channels + one 16-B pad slot
 
 struct S16Geom {
@@ -81,14 +75,6 @@ __global__ __launch_bounds__(256) void conv_bf16s_prepare_batch_kernel(const S16
         d.Wf[idx] = *reinterpret_cast<const unsigned short*>(&b);
     }
 }
-
-__device__ __forceinline__ unsigned s16_pack2(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 p = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, p);
-}
-__device__ __forceinline__ float s16_lo(unsigned v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float s16_hi(unsigned v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
 
 // outstanding vector-memory operations allowed to remain (s_waitcnt takes an immediate)
 __device__ __forceinline__ void s16_wait_vmcnt(int n) {
@@ -194,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(const S16Geom g, 
             const int pos = a_pos[i], u = (pos >> 24) & 3;
             const int n = n0 + ((pos >> 16) & 255), iy = oy0 - 1 + (pos & 255), ix = ox0 - 1 + ((pos >> 8) & 255);
             const bool ok = pos >= 0 && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W && n < g.N;
-            a_voff[i] = ok ? (int)((((size_t)n * g.H + iy) * g.W + ix) * g.ldx * 2 + u * 16) : S16_OOB;
+            a_voff[i] = ok ? (int)((((size_t)n * g.H + iy) * g.W + ix) * g.ldx * 2 + u * 16) : KPX_BUF_OOB;
             if (ok && u * 8 < ktail) a_tail |= 1u << i;
         }
     };
@@ -233,7 +219,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(const S16Geom g, 
             if (i >= APW) continue;
             const int piece = wave + 8 * i;
             if (piece < APIECES) {
-                const int vo = (last && !((a_tail >> i) & 1u)) ? S16_OOB : a_voff[i];
+                const int vo = (last && !((a_tail >> i) & 1u)) ? KPX_BUF_OOB : a_voff[i];
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_x, (lds_ptr_t)(Asm + buf * ABYTES + piece * 1024), 16, vo, kc * 64, 0, 0);
             }
         }
@@ -394,7 +380,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(const S16Geom g, 
                         const u32x2 yy = ch < g.Nn ? *reinterpret_cast<const u32x2*>(yo + ch) : u32x2{0u, 0u};
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const float yv = (j & 1) ? s16_hi(yy[j >> 1]) : s16_lo(yy[j >> 1]);
+                            const float yv = (j & 1) ? kpx_bf_hi(yy[j >> 1]) : kpx_bf_lo(yy[j >> 1]);
                             const int e = 4 * gq + j;
                             const float v = yv > 0.f ? acc[p][q][e] : 0.f;
                             acc[p][q][e] = v;
@@ -474,8 +460,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_bf16s_kernel(const S16Geom g, 
                 for (int k = 0; k < 4; k += 2) {
                     // groups k, k+1 (channels 8k + 4lh .. and 8(k+1) + 4lh ..): after the half exchange lanes 0-31 hold channels 8k .. 8k+7,
                     // lanes 32-63 channels 8(k+1) .. 8(k+1)+7 of their pixel
-                    unsigned a0 = s16_pack2(v[4 * k], v[4 * k + 1]), a1 = s16_pack2(v[4 * k + 2], v[4 * k + 3]);
-                    unsigned b0 = s16_pack2(v[4 * k + 4], v[4 * k + 5]), b1 = s16_pack2(v[4 * k + 6], v[4 * k + 7]);
+                    unsigned a0 = kpx_pack2(v[4 * k], v[4 * k + 1]), a1 = kpx_pack2(v[4 * k + 2], v[4 * k + 3]);
+                    unsigned b0 = kpx_pack2(v[4 * k + 4], v[4 * k + 5]), b1 = kpx_pack2(v[4 * k + 6], v[4 * k + 7]);
                     auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
                     auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
                     u32x4 o = {r0[0], r1[0], r0[1], r1[1]};

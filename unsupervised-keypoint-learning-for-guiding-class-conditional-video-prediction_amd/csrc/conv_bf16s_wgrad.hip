@@ -16,17 +16,11 @@
 //     channel blocks of a pixel are XOR-swizzled with the pixel index (on the SOURCE side of the LDS-DMA, the LDS image stays lane-linear);
 //   * the K range (all pixels) is split over workgroups into partial slabs [splits][9][Cin][Cout] fp32 (the WS wavefronts of a block are summed
 //     through LDS first), summed in a fixed tree by wgrad16_reduce_kernel (bitwise reproducible, no float atomics).
-#include "kpx_common.h"
+#include "kpx_bf16.h"
 #include "kpx_env.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-#define W16_OOB 0x7ffffff0
 
 struct W16Geom {
     const void* x; const void* dy; float* out;
@@ -55,7 +49,6 @@ __device__ __forceinline__ void w16_dma16(const w16_i32x4 rsrc, const void* lds,
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(l), "v"(voffset), "s"(rsrc) : "memory");       // (m0 is a reserved register to hipcc: it cannot be named as a clobber, and nothing else in this kernel uses it)
 }
 
-template <int V> struct w16_ic { static constexpr int value = V; };
 // XOR swizzle of the 64-B channel block `cb` of pixel q, for NBLK blocks per pixel (see the header)
 template <int NBLK>
 __device__ __forceinline__ int w16_swz(int cb, int q) { return NBLK == 4 ? (cb ^ (q & 3)) : NBLK == 2 ? (cb ^ ((q >> 1) & 1)) : cb; }
@@ -118,13 +111,13 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_bf16_kernel(const W16Geo
             if (wave + 8 * i < XPIECES) {
                 const int iy = y0 - 1 + x_pr[i], ix = x0 - 1 + x_pc[i];
                 const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-                w16_dma16(rs_x, Xs + buf * XBYTES + (wave + 8 * i) * 1024, ok ? base_x + x_rel[i] : W16_OOB);
+                w16_dma16(rs_x, Xs + buf * XBYTES + (wave + 8 * i) * 1024, ok ? base_x + x_rel[i] : KPX_BUF_OOB);
             }
         }
 #pragma unroll
         for (int i = 0; i < YPW; ++i) {
             if (wave + 8 * i < YPIECES)
-                w16_dma16(rs_y, Ys + buf * YBYTES + (wave + 8 * i) * 1024, y_rel[i] >= 0 ? base_y + y_rel[i] : W16_OOB);
+                w16_dma16(rs_y, Ys + buf * YBYTES + (wave + 8 * i) * 1024, y_rel[i] >= 0 ? base_y + y_rel[i] : KPX_BUF_OOB);
         }
     };
 
@@ -221,7 +214,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_wgrad_bf16_kernel(const W16Geo
         for (int h = 0; h < NRUN; ++h) {
             const int u0 = __builtin_amdgcn_readfirstlane(wsi * KSTEPS + h * RL);
             const int colh = TW == 32 ? u0 / TR : 0, row0 = TW == 32 ? u0 - colh * TR : u0;
-            run(w16_ic<RL>{}, row0, colh * 16);
+            run(kpx_ic<RL>{}, row0, colh * 16);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();

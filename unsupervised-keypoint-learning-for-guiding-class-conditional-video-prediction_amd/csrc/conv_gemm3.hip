@@ -2,55 +2,19 @@
 // Winograd kernels cannot take (strided, 4x4, 1x1: the discriminator, the encoders' stride-2 layers, the key-point head), through the same
 // geometry (conv_geom.h) and the same C entry points as the fp32 kernel of conv_igemm.hip (kpx_conv2d_fwd_f32 / kpx_conv2d_dgrad_f32).
 //
-// Arithmetic.  Every fp32 operand is split EXACTLY into three bf16 terms while its tile is staged in LDS:
-//     a = a0 + a1 + a2,   a0 = trunc16(a),  a1 = trunc16(a - a0),  a2 = a - a0 - a1
-// (a - a0 has at most 16 significant bits and a - a0 - a1 at most 8, so both subtractions are exact and a2 is a bf16 number: no bit of
-// the fp32 value is lost).  The product a*b = sum_ij ai*bj is accumulated with the six terms of weight >= 2^-16,
-//     a0*b0 + (a0*b1 + a1*b0) + (a1*b1 + a0*b2 + a2*b0),
-// on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; each bf16 x bf16 product is exact in fp32.  The dropped terms (a1*b2, a2*b1, a2*b2)
-// are below 2^-23 |a*b| -- smaller than the rounding of one fp32 accumulation.  Measured against a float64 convolution the result is as
-// close as the v_mfma_f32_32x32x2_f32 kernel's (tests/test_ops_gpu.py::test_gemm3_*): this is the fp32 configuration's arithmetic, not the
-// bf16 mode.  Six bf16 MFMAs cost 6 x 32 = 192 cycles per 32x32x16 block against 8 x 64 = 512 for the fp32 MFMA, and -- unlike the fp32
-// MFMA, which holds its SIMD's issue port -- the bf16 MFMA lets the splitting VALU work and the LDS traffic issue beside it.
-// TERMS = 1 keeps only a0*b0: the bf16 configuration's arithmetic (BASELINE configs[2]) from the same kernel.
+// Arithmetic (kpx_bf16.h has the derivation): every fp32 operand is split exactly into three bf16 terms while its tile is staged in LDS, six
+// bf16 MFMAs per product.  TERMS = 1 keeps only a0*b0: the bf16 configuration's arithmetic (BASELINE configs[2]) from the same kernel.
 //
 // One workgroup = 8 wavefronts (WM x WN) = BM x BN outputs as 32x32 accumulators; K chunks of 32 channels.
 // LDS per stage: TERMS planes of A [BM][32] bf16 and of B [BN][32] bf16 (k contiguous: one ds_read_b128 = one MFMA operand of a lane) at a
 // row pitch of 80 bytes (conflict-free reads and writes, see G3_PITCH).
-#include "conv_geom.h"
+#include "kpx_internal.h"
+#include "kpx_bf16.h"
 #include "kpx_env.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned g3_bits(float v) { return __builtin_bit_cast(unsigned, v); }
-__device__ __forceinline__ float g3_float(unsigned v) { return __builtin_bit_cast(float, v); }
-// {hi16(b), hi16(a)}: two truncated bf16 values in one dword, a in the low half
-__device__ __forceinline__ unsigned g3_pack_hi(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
-// exact three-way split of two floats; p[t] = packed (term t of a, term t of b)
-template <int TERMS>
-__device__ __forceinline__ void g3_split2(float a, float b, unsigned* p) {
-    const unsigned ua = g3_bits(a), ub = g3_bits(b);
-    p[0] = g3_pack_hi(ua, ub);
-    if (TERMS > 1) {
-        const float ra = a - g3_float(ua & 0xffff0000u), rb = b - g3_float(ub & 0xffff0000u);
-        const unsigned va = g3_bits(ra), vb = g3_bits(rb);
-        p[1] = g3_pack_hi(va, vb);
-        if (TERMS > 2) {
-            const float sa = ra - g3_float(va & 0xffff0000u), sb = rb - g3_float(vb & 0xffff0000u);
-            p[2] = g3_pack_hi(g3_bits(sa), g3_bits(sb));
-        }
-    }
-}
-
-template <int V> struct g3_ic { static constexpr int value = V; };
 
 #define G3_PITCH 80            // bytes of one LDS row (32 bf16 + 16 pad): 80 = 5 x 16 and 5 is odd, so sixteen consecutive rows start in sixteen
                                // different 16-B slots of the 256-B bank window -- ds_read_b128 fragment reads, the 8-lane ds_write_b128 groups and
                                // the 16-lane ds_write_b64 groups of the transposing B store are all conflict-free without an XOR swizzle
-#define G3_OOB 0x7ffffff0      // voffset beyond any buffer: the load returns zeros (out-of-image taps, channel tails, chunks past the end)
 
 // IO16 (bf16 configuration, TERMS == 1): the gathered tensor is bf16 in HBM -- a staging unit is ONE 16-byte load of eight channels and
 // goes to LDS as it is; the produced tensor is bf16 when g.io16 says so.
@@ -165,7 +129,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3_kernel(const ConvG
 #pragma unroll
         for (int i = 0; i < RA; ++i) {
             const bool va = live & (((a_vm[i] >> tapbit) & 1u) != 0) & (c0 + a_k[i] < g.Cin);       // (bitwise: no short-circuit branches)
-            const int av = va ? a_voff[i] + a_off : G3_OOB;
+            const int av = va ? a_voff[i] + a_off : KPX_BUF_OOB;
             ra[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, av, 0, 0));
             if (!IO16) ra[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_a, av + 16, 0, 0));
         }
@@ -173,14 +137,14 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3_kernel(const ConvG
         for (int i = 0; i < RB; ++i) {
             if (BT) {
                 const bool vb = live & b_ok[i] & (c0 + b_k[i] < g.Cin);
-                const int bv = vb ? b_voff[i] + b_off : G3_OOB;
+                const int bv = vb ? b_voff[i] + b_off : KPX_BUF_OOB;
                 rb[i][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, bv, 0, 0));
                 if (KU == 8) rb[i][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, bv + 16, 0, 0));
             } else {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const bool vb = live & b_ok[i] & (c0 + b_k[i] + j < g.Cin);
-                    const int bv = vb ? b_voff[i] + b_off + j * g.ldw * 4 : G3_OOB;
+                    const int bv = vb ? b_voff[i] + b_off + j * g.ldw * 4 : KPX_BUF_OOB;
                     if (CW == 4) rb[i][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, bv, 0, 0));
                     else {
                         // (two dword loads: hipcc of ROCm 7.2 lowers __builtin_amdgcn_raw_buffer_load_b64 to ONE buffer_load_dword and
@@ -207,8 +171,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3_kernel(const ConvG
             unsigned char* const Ab = Asm + a_st[i];
             if (IO16) { *reinterpret_cast<u32x4*>(Ab) = __builtin_bit_cast(u32x4, ra[i][0]); continue; }
             unsigned p[4][3];
-            g3_split2<TERMS>(ra[i][0][0], ra[i][0][1], p[0]); g3_split2<TERMS>(ra[i][0][2], ra[i][0][3], p[1]);
-            g3_split2<TERMS>(ra[i][1][0], ra[i][1][1], p[2]); g3_split2<TERMS>(ra[i][1][2], ra[i][1][3], p[3]);
+            kpx_split2<TERMS>(ra[i][0][0], ra[i][0][1], p[0]); kpx_split2<TERMS>(ra[i][0][2], ra[i][0][3], p[1]);
+            kpx_split2<TERMS>(ra[i][1][0], ra[i][1][1], p[2]); kpx_split2<TERMS>(ra[i][1][2], ra[i][1][3], p[3]);
 #pragma unroll
             for (int tm = 0; tm < TERMS; ++tm) *reinterpret_cast<u32x4*>(Ab + tm * APL) = u32x4{p[0][tm], p[1][tm], p[2][tm], p[3][tm]};
         }
@@ -217,9 +181,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3_kernel(const ConvG
             unsigned char* const Bb = Bsm + b_st[i];
             if (BT) {
                 unsigned p[4][3];
-                g3_split2<TERMS>(rb[i][0][0], rb[i][0][1], p[0]); g3_split2<TERMS>(rb[i][0][2], rb[i][0][3], p[1]);
+                kpx_split2<TERMS>(rb[i][0][0], rb[i][0][1], p[0]); kpx_split2<TERMS>(rb[i][0][2], rb[i][0][3], p[1]);
                 if (KU == 8) {
-                    g3_split2<TERMS>(rb[i][1][0], rb[i][1][1], p[2]); g3_split2<TERMS>(rb[i][1][2], rb[i][1][3], p[3]);
+                    kpx_split2<TERMS>(rb[i][1][0], rb[i][1][1], p[2]); kpx_split2<TERMS>(rb[i][1][2], rb[i][1][3], p[3]);
 #pragma unroll
                     for (int tm = 0; tm < TERMS; ++tm) *reinterpret_cast<u32x4*>(Bb + tm * BPL) = u32x4{p[0][tm], p[1][tm], p[2][tm], p[3][tm]};
                 } else {
@@ -231,7 +195,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3_kernel(const ConvG
 #pragma unroll
                 for (int c = 0; c < CW; ++c) {
                     unsigned p[3];
-                    g3_split2<TERMS>(rb[i][0][c], rb[i][1][c], p);
+                    kpx_split2<TERMS>(rb[i][0][c], rb[i][1][c], p);
 #pragma unroll
                     for (int tm = 0; tm < TERMS; ++tm) *reinterpret_cast<unsigned*>(Bb + tm * BPL + c * G3_PITCH) = p[tm];
                 }
@@ -335,7 +299,7 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_gemm3_kernel(const ConvG
                     else if (g.act == KPX_ACT_LRELU) v = v > 0.f ? v : 0.01f * v;
                     else if (g.act == KPX_ACT_TANH) v = tanhf(v);
                     if (g.mul_y) {
-                        const float my = (g.io16 & 4) ? g3_float((unsigned)reinterpret_cast<const unsigned short*>(g.mul_y)[(size_t)pix * g.ld_mul + col] << 16)
+                        const float my = (g.io16 & 4) ? kpx_float((unsigned)reinterpret_cast<const unsigned short*>(g.mul_y)[(size_t)pix * g.ld_mul + col] << 16)
                                                       : g.mul_y[(size_t)pix * g.ld_mul + col];
                         v *= kpx_act_grad_from_y(my, g.mul_act);
                     }
@@ -425,7 +389,7 @@ extern "C" __attribute__((visibility("hidden"))) int kpx_gemm3_launch(ConvGeom g
 // operands are pixel-major in HBM (channels contiguous) while an MFMA fragment wants 8 consecutive K = pixels per lane, so BOTH are staged
 // like the forward kernel's n-contiguous weights: a unit = 2 pixels x 4 channels (two 16-B loads), transposed in registers -- each channel
 // becomes one bf16 pair per term, written to LDS row `channel` of the operand's plane (pitch G3_PITCH: conflict-free).  Workgroup =
-// (split, tap, Cin tile, Cout tile) as in conv_wgrad_kernel (conv_igemm.hip), partial slabs reduced in fixed order by wgrad_reduce_kernel.
+// (split, tap, Cin tile, Cout tile) as in conv_wgrad_kernel (conv_wgrad.hip), partial slabs reduced in fixed order by wgrad_reduce_kernel.
 template <int BM, int WM, int WN, int TERMS, bool IO16 = false>
 __global__ __launch_bounds__(WM * WN * 64, 2) void conv_wgrad3_kernel(const WgradGeom g) {
     static_assert(!IO16 || TERMS == 1, "bf16 tensors carry one term");
@@ -496,9 +460,9 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_wgrad3_kernel(const Wgra
         for (int j = 0; j < 2; ++j) {
             const int ih = pho[j] * g.stride + r - g.pad_t, iw = pwo[j] * g.stride + q - g.pad_l;
             const bool va = a_cok & (p0 + j < pend) & ((unsigned)ih < (unsigned)g.Hi) & ((unsigned)iw < (unsigned)g.Wi);
-            const int av = va ? (((pn[j] * g.Hi + ih) * g.Wi + iw) * g.ldx + ac) * ESZ : G3_OOB;
+            const int av = va ? (((pn[j] * g.Hi + ih) * g.Wi + iw) * g.ldx + ac) * ESZ : KPX_BUF_OOB;
             const bool vb = b_cok & (p0 + j < pend);
-            const int bv = vb ? ((p0 + j) * g.lddy + bc) * ESZ : G3_OOB;
+            const int bv = vb ? ((p0 + j) * g.lddy + bc) * ESZ : KPX_BUF_OOB;
             if (IO16) {                                    // one operand per thread: ra[j] = eight bf16 channels of pixel j
                 ra[j] = __builtin_bit_cast(f32x4, isB16 ? __builtin_amdgcn_raw_buffer_load_b128(rs_b, bv, 0, 0) : __builtin_amdgcn_raw_buffer_load_b128(rs_a, av, 0, 0));
             } else {
@@ -531,8 +495,8 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void conv_wgrad3_kernel(const Wgra
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             unsigned pa[3], pb[3];
-            g3_split2<TERMS>(ra[0][c], ra[1][c], pa);
-            g3_split2<TERMS>(rb[0][c], rb[1][c], pb);
+            kpx_split2<TERMS>(ra[0][c], ra[1][c], pa);
+            kpx_split2<TERMS>(rb[0][c], rb[1][c], pb);
 #pragma unroll
             for (int tm = 0; tm < TERMS; ++tm) {
                 *reinterpret_cast<unsigned*>(Ab + tm * APL + c * G3_PITCH) = pa[tm];
@@ -610,7 +574,7 @@ extern "C" __attribute__((visibility("hidden"))) int kpx_wgrad3_eligible(const W
     if (g->io16 && g->terms != 1) return 0;
     return 1;
 }
-// bm: the square channel tile conv_igemm.hip planned the grid for (128 or 64); the grid is g.S * taps * g.ct * g.kt workgroups.
+// bm: the square channel tile conv_wgrad.hip planned the grid for (128 or 64); the grid is g.S * taps * g.ct * g.kt workgroups.
 extern "C" __attribute__((visibility("hidden"))) int kpx_wgrad3_launch(WgradGeom g, int bm, int terms, hipStream_t s) {
     const dim3 grid((unsigned)(g.S * g.KH * g.KW * g.ct * g.kt));
     if (g.io16) {

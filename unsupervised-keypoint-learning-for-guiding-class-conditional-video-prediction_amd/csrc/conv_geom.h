@@ -1,4 +1,4 @@
-// Geometry of the "gather convolution" shared by the fp32 implicit-GEMM kernels (conv_igemm.hip) and the bf16x3 kernels (conv_gemm3.hip):
+// Geometry of the "gather convolution" shared by the fp32 implicit-GEMM kernels (conv_igemm.hip, conv_wgrad.hip) and the bf16x3 kernels (conv_gemm3.hip):
 //   out[n, a*osy+oy0, b*osx+ox0, j] = act( bias[j] + sum_{tr,tq,c} in[n, a*isy+tr*ity+iy0, b*isx+tq*itx+ix0, c] * B[tap(tr,tq)][c][j] )
 // forward: in = x, B = HWIO weights; dgrad: in = dy, B = the same weights read transposed, one class per stride parity of dx pixels.
 #pragma once

@@ -4,7 +4,7 @@
 // the complete filter in LDS once and runs the K = KH*KW*Cin contraction out of LDS with v_mfma_f32_32x32x2_f32:
 // the KW*Cin floats of a filter row are contiguous in NHWC, so k runs over (row, kk < KW*Cin) and the A operand of pixel (y, x) is
 // patch[(y + r) * PWC + x * Cin + kk].  4 wavefronts x 2 M-tiles of 32 pixels (two output rows) x Cout/32 N-tiles.
-#include "kpx_common.h"
+#include "kpx_internal.h"
 #include "kpx_env.h"
 
 struct RgbGeom {

@@ -12,7 +12,7 @@
 // The same kernel serves dgrad with filters transformed from the flipped / transposed weights.  The filter transform is its own
 // entry point (kpx_wino_filter_transform[_batch]_f32): constant filters (VGG19) are transformed once, trainable ones once per
 // optimiser update in ONE launch, instead of once per convolution call.
-#include "kpx_common.h"
+#include "kpx_internal.h"
 #include "kpx_env.h"
 #include <stdlib.h>
 #include <type_traits>

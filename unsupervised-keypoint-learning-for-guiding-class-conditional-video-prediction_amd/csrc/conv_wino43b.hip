@@ -6,7 +6,7 @@
 //   Y = A^T [ (G g G^T) (.) (B^T d B) ] A      as in conv_wino43.hip (points 0, +-1, +-2, inf), but
 //   U = G g G^T (fp64, rounded once to fp32) is stored PRE-SPLIT as u = u0 + u1 + u2 (three bf16 planes, exact: trunc16 twice, the rest fits)
 //   V = B^T d B (fp32 VALU) is split the same way in registers right after the input transform, and each point-wise product is
-//   v.u ~ v1u1 + v0u2 + v2u0 + v0u1 + v1u0 + v0u0  (smallest first, fp32 accumulate; the dropped terms are < 2^-23 |vu|: conv_gemm3.hip).
+//   v.u ~ v1u1 + v0u2 + v2u0 + v0u1 + v1u0 + v0u0  (smallest first, fp32 accumulate; the dropped terms are < 2^-23 |vu|: kpx_bf16.h).
 // Cost per 32 x 32 x 16 block: 6 x 32 cycles instead of 8 x 64 of v_mfma_f32_32x32x2_f32, and -- the point of the exercise, DESIGN.md 4.1 --
 // a bf16 MFMA lets the other instructions of its SIMD issue beside it.
 //
@@ -34,16 +34,11 @@
 //     both passes, every thread owns (tile, 4 couts), reads its 36 values as ds_read_b128 and finishes the 4 x 4 output pixels in one go.
 // STATS / mask / pool epilogue options are those of conv_wino43_kernel (same statistics strips: kpx_conv3x3_wino43_stats_tiles); PACK: two 16 x 16
 // images side by side in one 16 x 32 region (VGG19 conv4_*, the 16 x 16 data gradients of the encoders), each with its own zero halo in the patch.
-#include "kpx_common.h"
+#include "kpx_bf16.h"
 #include "kpx_env.h"
 #include "wino43_options.h"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-#define W4B_OOB 0x7ffffff0                 // voffset beyond any buffer: the load returns / lands as zeros
 #define W4B_ROWSLOTS 146                   // 16-B slots per patch row: pixel column c at slot 4 c + (c >> 2) (four channel quads per pixel, one skew slot per
                                            // four pixels), 34 columns = 144 slots, padded to 146 so that four rows are 8 (mod 16) slots
 #define W4B_ROWSLOTS_PACK 154              // PACK (two 16 x 16 images side by side): image A's 18 patch columns at slots 0..75 of a row, image B's at 76..151 (tile
@@ -87,28 +82,18 @@ struct Wino43bGeom {
     const float* bn_beta;
 };
 
-__device__ __forceinline__ unsigned w4b_bits(float v) { return __builtin_bit_cast(unsigned, v); }
-__device__ __forceinline__ float w4b_float(unsigned v) { return __builtin_bit_cast(float, v); }
-// {hi16(b), hi16(a)}: two truncated bf16 values in one dword, a in the low half
-__device__ __forceinline__ unsigned w4b_pack_hi(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
-// exact three-way split of eight floats into the three A-operand fragments of one point (element e of a fragment = channel e of the lane's octet)
+// exact three-way split (kpx_bf16.h) of eight floats into the three A-operand fragments of one point (element e of a fragment = channel e of the lane's octet)
 __device__ __forceinline__ void w4b_split8(const float* __restrict__ v, u32x4* __restrict__ f) {
 #if defined(W4B_EXP) && (W4B_EXP & 1)      // timing experiment (numerically meaningless): no split arithmetic
 #pragma unroll
-    for (int m = 0; m < 4; ++m) { f[0][m] = w4b_bits(v[2 * m]); f[1][m] = w4b_bits(v[2 * m + 1]); f[2][m] = w4b_bits(v[m]); }
+    for (int m = 0; m < 4; ++m) { f[0][m] = kpx_bits(v[2 * m]); f[1][m] = kpx_bits(v[2 * m + 1]); f[2][m] = kpx_bits(v[m]); }
     return;
 #endif
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-        const float a = v[2 * m], b = v[2 * m + 1];
-        const unsigned a0 = w4b_bits(a), b0 = w4b_bits(b);
-        f[0][m] = w4b_pack_hi(a0, b0);
-        const float ra = a - w4b_float(a0 & 0xffff0000u), rb = b - w4b_float(b0 & 0xffff0000u);
-        const unsigned a1 = w4b_bits(ra), b1 = w4b_bits(rb);
-        f[1][m] = w4b_pack_hi(a1, b1);
-        const float sa = ra - w4b_float(a1 & 0xffff0000u), sb = rb - w4b_float(b1 & 0xffff0000u);
-        f[2][m] = w4b_pack_hi(w4b_bits(sa), w4b_bits(sb));
+        unsigned p[3];
+        kpx_split2<3>(v[2 * m], v[2 * m + 1], p);
+        f[0][m] = p[0]; f[1][m] = p[1]; f[2][m] = p[2];
     }
 }
 
@@ -260,12 +245,12 @@ __device__ __forceinline__ void w4b_kloop(const int rh, const int ch, const Wino
         const int col = 4 * grp + (r17 >> 2), q = r17 & 3;
         const int iy = oy0 - 1 + row, ix = ox0 - 1 + col;
         const bool ok = r17 < 16 && rs < (PACK ? 76 : 144) && row < 18 && col < (PACK ? 18 : 34) && (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-        dv[i] = ok ? (((half * g.H + iy) * g.W + ix) * g.ldx + q * 4) * 4 : W4B_OOB;
+        dv[i] = ok ? (((half * g.H + iy) * g.W + ix) * g.ldx + q * 4) * 4 : KPX_BUF_OOB;
         if ((KS - 1) * 16 + q * 4 < g.Cin) dtail |= 1u << i;
     }
     auto dma_piece = [&](int s, int buf, int i) {        // piece i of K step s -> raw buffer buf (past the last K step: zeros into the idle buffer)
         unsigned char* const dst = smem + buf * W4B_RAW_BYTES + wave * 11 * 1024;
-        const int vo = (s >= KS || (s == KS - 1 && !((dtail >> i) & 1u))) ? W4B_OOB : dv[i];
+        const int vo = (s >= KS || (s == KS - 1 && !((dtail >> i) & 1u))) ? KPX_BUF_OOB : dv[i];
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsx, (lds_ptr_t)(dst + i * 1024), 16, vo, s * 64, 0, 0);
     };
     auto dma = [&](int s, int buf) {                     // K step s -> raw buffer buf
@@ -321,11 +306,11 @@ __device__ __forceinline__ void w4b_kloop(const int rh, const int ch, const Wino
     auto split_op = [&](const int idx, float (&x)[8], unsigned (&h)[8], u32x4* f) {
         const int lvl = idx < 4 ? 0 : idx < 12 ? 1 : idx < 20 ? 2 : idx < 24 ? 3 : idx < 32 ? 4 : idx < 40 ? 5 : 6;
         const int k = idx - (lvl == 0 ? 0 : lvl == 1 ? 4 : lvl == 2 ? 12 : lvl == 3 ? 20 : lvl == 4 ? 24 : lvl == 5 ? 32 : 40);
-        if (lvl == 0 || lvl == 3 || lvl == 6) f[lvl / 3][k] = w4b_pack_hi(w4b_bits(x[2 * k]), w4b_bits(x[2 * k + 1]));
+        if (lvl == 0 || lvl == 3 || lvl == 6) f[lvl / 3][k] = kpx_pack_hi(kpx_bits(x[2 * k]), kpx_bits(x[2 * k + 1]));
 #if defined(W4B_EXP) && (W4B_EXP & 32)
-        else if (lvl == 1 || lvl == 4) h[k] = w4b_bits(x[k]) & hmask;
+        else if (lvl == 1 || lvl == 4) h[k] = kpx_bits(x[k]) & hmask;
 #else
-        else if (lvl == 1 || lvl == 4) h[k] = w4b_bits(x[k]) & 0xffff0000u;
+        else if (lvl == 1 || lvl == 4) h[k] = kpx_bits(x[k]) & 0xffff0000u;
 #endif
         else asm("v_sub_f32 %0, %1, %2" : "=v"(x[k]) : "v"(x[k]), "v"(h[k]));      // (asm: never SLP-packed; exact -- the difference fits)
     };

@@ -12,7 +12,7 @@
 // patch[row*stride + ky][ (x + k)*stride + kx ][c] (consecutive lanes = consecutive (kx, c) = consecutive floats), a B operand one
 // ds_read_b32 of dy.  Persistent workgroups (a contiguous range of tiles each) write one partial slab in HWIO order; the fixed-order
 // wgrad_reduce kernel sums the slabs (bitwise reproducible, no atomics).
-#include "kpx_common.h"
+#include "kpx_internal.h"
 #include "kpx_env.h"
 #include <type_traits>
 

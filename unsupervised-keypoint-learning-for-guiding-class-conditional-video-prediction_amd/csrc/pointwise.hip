@@ -3,7 +3,7 @@
 // All are streaming kernels: 16-B per-lane accesses along the contiguous channel axis, grid-stride loops capped
 // at 2048 blocks, per-channel reductions accumulated in fp64 and finished by a second tiny kernel (no atomics,
 // bitwise reproducible).
-#include "kpx_common.h"
+#include "kpx_bf16.h"
 
 #define KPX_MAX_BLOCKS 2048
 #define KPX_RED_BLOCKS 1024
@@ -896,26 +896,19 @@ extern "C" int kpx_maxpool2_bwd_f32(const float* dy, const float* x, int N, int 
 // fp64 through the same block partials and fixed-order finalize kernels as the fp32 entries (statistics, moving averages, gamma / beta
 // gradients stay fp32).  Every entry wants C, the pixel strides multiples of 8 and 16-byte aligned pointers (KPX_EINVAL otherwise) unless
 // it says otherwise.
-typedef unsigned int pw_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short bf16_t;
 
 __device__ __forceinline__ float pw_bf(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
 __device__ __forceinline__ unsigned short pw_to_bf(float v) { const __bf16 b = (__bf16)v; return __builtin_bit_cast(unsigned short, b); }
 __device__ __forceinline__ void pw_ld8(const bf16_t* p, float* v) {
-    const pw_u32x4 r = *reinterpret_cast<const pw_u32x4*>(p);
+    const u32x4 r = *reinterpret_cast<const u32x4*>(p);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { v[2 * j] = __builtin_bit_cast(float, r[j] << 16); v[2 * j + 1] = __builtin_bit_cast(float, r[j] & 0xffff0000u); }
-}
-__device__ __forceinline__ unsigned pw_pack2(float a, float b) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    const bf16x2 p = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, p);
+    for (int j = 0; j < 4; ++j) { v[2 * j] = kpx_bf_lo(r[j]); v[2 * j + 1] = kpx_bf_hi(r[j]); }
 }
 __device__ __forceinline__ void pw_st8(bf16_t* p, const float* v) {
-    const pw_u32x4 r = {pw_pack2(v[0], v[1]), pw_pack2(v[2], v[3]), pw_pack2(v[4], v[5]), pw_pack2(v[6], v[7])};
-    *reinterpret_cast<pw_u32x4*>(p) = r;
+    const u32x4 r = {kpx_pack2(v[0], v[1]), kpx_pack2(v[2], v[3]), kpx_pack2(v[4], v[5]), kpx_pack2(v[6], v[7])};
+    *reinterpret_cast<u32x4*>(p) = r;
 }
-static inline bool pw_al16(const void* a, const void* b = nullptr, const void* c = nullptr) { return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0; }
 
 // ---- casts / copies between channel slices: dst[p][0:C] = src[p][0:C] (any C; vector path when everything is 8-aligned)
 template <typename TS, typename TD>
@@ -969,7 +962,7 @@ extern "C" int kpx_cast_channels(const void* src, int ldsrc, void* dst, int ldds
         return kpx_launch_status();
     }
     const int sa = kind == 0 ? 4 : 2, da = kind == 1 ? 4 : 2;
-    const int vec = (C % 8 == 0) && (((size_t)ldsrc * sa) % 16 == 0) && (((size_t)lddst * da) % 16 == 0) && pw_al16(src, dst);
+    const int vec = (C % 8 == 0) && (((size_t)ldsrc * sa) % 16 == 0) && (((size_t)lddst * da) % 16 == 0) && kpx_aligned16(src, dst);
     const unsigned nb = grid_for(vec ? P * (C / 8) : P * C);
     hipStream_t s = kpx_stream(stream);
     if (kind == 0) hipLaunchKernelGGL((cast_channels_kernel<float, bf16_t>), dim3(nb), dim3(256), 0, s, (const float*)src, ldsrc, (bf16_t*)dst, lddst, P, C, vec);
@@ -1058,7 +1051,7 @@ static int launch_chan_reduce_bf16(int mode, bool dyf32, RedArgs a, int* nb_out,
 }
 // bias gradient of a bf16 gradient tensor: sum over pixels, fp32 out (same scratch as kpx_chan_sum_f32)
 extern "C" int kpx_chan_sum_bf16(const void* x, size_t P, int C, int ldx, float* sum_out, void* scratch, void* stream) {
-    if (!x || !sum_out || !scratch || C <= 0 || C % 8 || ldx % 8 || ldx < C || P == 0 || !pw_al16(x)) return KPX_EINVAL;
+    if (!x || !sum_out || !scratch || C <= 0 || C % 8 || ldx % 8 || ldx < C || P == 0 || !kpx_aligned16(x)) return KPX_EINVAL;
     RedArgs a{}; a.x = (const float*)x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch;
     int nb; int rc = launch_chan_reduce_bf16(0, false, a, &nb, kpx_stream(stream), 1);
     if (rc) return rc;
@@ -1103,7 +1096,7 @@ extern "C" int kpx_bn_train_fwd_bf16(const void* x, size_t P, int groups, int C,
                                      float eps, const float* gamma, const float* beta, float* mean, float* invstd,
                                      float* moving_mean, float* moving_var, float decay, void* y, int ldy, int y_f32, int act, void* scratch, void* stream) {
     if (!x || !y || !gamma || !beta || !mean || !invstd || !scratch || groups <= 0 || groups > 65535 || C <= 0 || C % 8 || ldx % 8 || ldy % 8 || ldx < C || ldy < C ||
-        act < 0 || act > 1 || P == 0 || !pw_al16(x, y))
+        act < 0 || act > 1 || P == 0 || !kpx_aligned16(x, y))
         return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
     RedArgs a{}; a.x = (const float*)x; a.ldx = ldx; a.P = P; a.C = C; a.part = (double*)scratch;
@@ -1170,7 +1163,7 @@ extern "C" int kpx_bn_train_bwd_bf16(const void* dy, int lddy, int dy_f32, const
                                      void* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
                                      const float* tile_stats, size_t tiles_per_group, void* scratch, void* stream) {
     if (!dy || !x || !mean || !invstd || !gamma || !beta || !dx || !dgamma || !dbeta || !scratch || groups <= 0 || groups > 65535 || C <= 0 || C % 8 ||
-        ldx % 8 || lddy % 8 || lddx % 8 || ldx < C || lddy < C || lddx < C || act < 0 || act > 1 || P == 0 || !pw_al16(dy, x, dx) ||
+        ldx % 8 || lddy % 8 || lddx % 8 || ldx < C || lddy < C || lddx < C || act < 0 || act > 1 || P == 0 || !kpx_aligned16(dy, x, dx) ||
         (tile_stats && (act != KPX_ACT_RELU || tiles_per_group == 0)))
         return KPX_EINVAL;
     hipStream_t s = kpx_stream(stream);
@@ -1196,7 +1189,7 @@ __global__ __launch_bounds__(256) void act_bwd_bf16_kernel(const bf16_t* dy, con
     }
 }
 extern "C" int kpx_act_bwd_bf16(const void* dy, const void* y, void* dz, size_t n, int act, void* stream) {
-    if (!dy || !y || !dz || n % 8 || !pw_al16(dy, y, dz)) return KPX_EINVAL;
+    if (!dy || !y || !dz || n % 8 || !kpx_aligned16(dy, y, dz)) return KPX_EINVAL;
     if (n == 0) return 0;
     hipLaunchKernelGGL(act_bwd_bf16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, kpx_stream(stream), (const bf16_t*)dy, (const bf16_t*)y, (bf16_t*)dz, n / 8, act);
     return kpx_launch_status();
@@ -1229,7 +1222,7 @@ __global__ __launch_bounds__(256) void resize2x_fwd_bf16_kernel(const bf16_t* __
     }
 }
 extern "C" int kpx_resize2x_fwd_bf16(const void* x, int N, int H, int W, int C, int ldx, void* y, int ldy, void* stream) {
-    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || ldx % 8 || ldy % 8 || ldx < C || ldy < C || !pw_al16(x, y) || (size_t)N * H * W * (C / 8) >= 0x7fffffffu) return KPX_EINVAL;
+    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || ldx % 8 || ldy % 8 || ldx < C || ldy < C || !kpx_aligned16(x, y) || (size_t)N * H * W * (C / 8) >= 0x7fffffffu) return KPX_EINVAL;
     size_t nb = ((size_t)N * H * W * (C / 8) + 255) / 256; if (nb > 16384) nb = 16384;
     hipLaunchKernelGGL(resize2x_fwd_bf16_kernel, dim3((unsigned)nb), dim3(256), 0, kpx_stream(stream), (const bf16_t*)x, N, H, W, C, ldx, (bf16_t*)y, ldy);
     return kpx_launch_status();
@@ -1268,7 +1261,7 @@ __global__ __launch_bounds__(256) void resize2x_bwd_bf16_kernel(const bf16_t* __
     }
 }
 extern "C" int kpx_resize2x_bwd_bf16(const void* dy, int N, int H, int W, int C, int lddy, void* dx, int lddx, void* stream) {
-    if (!dy || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || lddy % 8 || lddx % 8 || lddy < C || lddx < C || !pw_al16(dy, dx)) return KPX_EINVAL;
+    if (!dy || !dx || N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || lddy % 8 || lddx % 8 || lddy < C || lddx < C || !kpx_aligned16(dy, dx)) return KPX_EINVAL;
     hipLaunchKernelGGL(resize2x_bwd_bf16_kernel, dim3(grid_for((size_t)N * H * W * (C / 8))), dim3(256), 0, kpx_stream(stream), (const bf16_t*)dy, N, H, W, C, lddy, (bf16_t*)dx, lddx);
     return kpx_launch_status();
 }
@@ -1295,7 +1288,7 @@ __global__ __launch_bounds__(256) void maxpool2_fwd_bf16_kernel(const bf16_t* __
     }
 }
 extern "C" int kpx_maxpool2_fwd_bf16(const void* x, int N, int H, int W, int C, void* y, void* stream) {
-    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8 || !pw_al16(x, y)) return KPX_EINVAL;
+    if (!x || !y || N <= 0 || H <= 0 || W <= 0 || H % 2 || W % 2 || C <= 0 || C % 8 || !kpx_aligned16(x, y)) return KPX_EINVAL;
     hipLaunchKernelGGL(maxpool2_fwd_bf16_kernel, dim3(grid_for((size_t)N * (H / 2) * (W / 2) * (C / 8))), dim3(256), 0, kpx_stream(stream), (const bf16_t*)x, N, H, W, C, (bf16_t*)y);
     return kpx_launch_status();
 }
@@ -1349,7 +1342,7 @@ __global__ __launch_bounds__(256) void vgg_feat_bwd_bf16_kernel(const bf16_t* __
 }
 extern "C" int kpx_vgg_feat_bwd_bf16(const void* f, size_t half, const float* gscale_dev, float gscale_host, const void* dy_pooled,
                                      int B, int H, int W, int C, void* d, void* stream) {
-    if (!f || !d || half == 0 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || half != (size_t)B * H * W * C || (dy_pooled && (H % 2 || W % 2)) || !pw_al16(f, d, dy_pooled))
+    if (!f || !d || half == 0 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || half != (size_t)B * H * W * C || (dy_pooled && (H % 2 || W % 2)) || !kpx_aligned16(f, d, dy_pooled))
         return KPX_EINVAL;
     const size_t items = dy_pooled ? (size_t)B * (H / 2) * (W / 2) * (C / 8) : half / 8;
     hipLaunchKernelGGL(vgg_feat_bwd_bf16_kernel, dim3(grid_for(items)), dim3(256), 0, kpx_stream(stream), (const bf16_t*)f, half, gscale_dev, gscale_host, (const bf16_t*)dy_pooled, B, H, W, C, (bf16_t*)d);
@@ -1379,7 +1372,7 @@ __global__ void l1_pair_finalize_bf16_kernel(const double* part, int nb, double 
     if (threadIdx.x == 0) *out = (float)(s / count);
 }
 extern "C" int kpx_l1_pair_fwd_bf16(const void* f, size_t half, float* loss_out, void* scratch, void* stream) {
-    if (!f || !loss_out || !scratch || half == 0 || half % 8 || !pw_al16(f)) return KPX_EINVAL;
+    if (!f || !loss_out || !scratch || half == 0 || half % 8 || !kpx_aligned16(f)) return KPX_EINVAL;
     size_t nb = (half / 8 + 255) / 256;
     if (nb < 1) nb = 1;
     if (nb > 1024) nb = 1024;

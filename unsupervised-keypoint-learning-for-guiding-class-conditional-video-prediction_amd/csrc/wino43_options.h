@@ -6,9 +6,7 @@
 //   mask_y / pool_y: VGG19's fused ReLU backward / 2x2 max-pool (no tile_stats).
 // The bn and mask / pool forms need Nn % 64 == 0 and 16-B aligned rows everywhere.
 #pragma once
-#include "kpx_common.h"
-
-static inline bool kpx_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+#include "kpx_bf16.h"
 
 static inline bool wino43_options_valid(const float* in, int H, int W, int K, int ldin, const void* U, const float* bias,
                                         const float* out, int Nn, int ldout, int act, const float* mask_y, int ld_mask,
