@@ -2,7 +2,7 @@
 """Evaluation entry point with the reference's CLI (reference: evaluate.py:13-163):
 
     python evaluate.py --config configs/penn.yaml --checkpoint_stage1 S1.npz --checkpoint_stage2 S2.npz [--save_dir results/eval]
-                       [--synthetic N] [--colors_seed S] [--no-save] [--metrics [--samples N]]
+                       [--synthetic N] [--colors_seed S] [--no-save] [--metrics [--samples N] [--vgg-metrics [--synthetic-vgg]]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -15,6 +15,11 @@ by this repo or TensorFlow V2 bundle prefixes (TF variable names either way).
 writes (``kpx_amd.ops.frame_metrics``, one launch per rollout) -- and writes ``<save_dir>/metrics.npz`` (``ssim``, ``psnr``, ``mse``:
 [samples, draws, 32]) and ``<save_dir>/metrics.json`` (``summarise_metrics``).  ``--samples N`` runs the rollout N times per batch with
 fresh z; the PNGs come from draw 0.
+
+``--vgg-metrics`` (with ``--metrics``) adds the VGG19 feature-space scores of the same 8-bit frames (``kpx_amd.FeatureScorer``: the
+network of ``paths.vggnet`` -- ``--synthetic-vgg`` for He-normal weights --, the real frames' features computed once per batch and reused
+by every draw): ``vgg_cos`` and ``vgg_l1`` [samples, draws, 32] and their per-layer parts ``vgg_cos_layers`` / ``vgg_l1_layers``
+[samples, draws, 32, 5] in metrics.npz, ``vgg_cos`` / ``vgg_l1`` blocks in metrics.json.  DESIGN.md section 2 has the definition.
 """
 import json
 import os
@@ -54,23 +59,44 @@ METRICS_DEFINITION = (
     'Non-finite values are null; n_nonfinite counts the frames with a non-finite metric.')
 
 
+VGG_FEATURE_LAYERS = ['conv1_2', 'conv2_2', 'conv3_4', 'conv4_4', 'conv5_4']      # = kpx_amd.vgg.FEATURE_LAYERS
+VGG_METRICS_DEFINITION = (
+    'vgg_cos / vgg_l1: the same 8-bit frames q through the VGG19 of this project (input q on the 0..255 scale, BGR, minus VGG_MEAN; features '
+    'conv1_2, conv2_2, conv3_4, conv4_4, conv5_4 as listed in vgg_layers). Per layer and spatial position over the C channels '
+    'saa = sum a^2, sbb = sum b^2, dot = sum a b; the position scores 1 if saa == 0 and sbb == 0, 0 if exactly one of them is 0, else '
+    'min(1, dot / sqrt(saa sbb)); cos_layer = mean over positions, l1_layer = mean |a - b| over positions and channels (the perceptual '
+    'L1 term of stage-1 training, per frame). vgg_cos = mean of cos_layer over the five layers, in [0, 1], higher is better (best draw: '
+    'highest); vgg_l1 = mean of l1_layer over the five layers, lower is better (best draw: lowest). Defined on this VGG19 and these layers: '
+    'not numerically comparable with published VGG16- or LPIPS-weight figures.')
+LOWER_IS_BETTER = ('mse', 'vgg_l1')
+
+
 def _json_num(v):
     v = float(v)
     return v if np.isfinite(v) else None
 
 
-def summarise_metrics(ssim, psnr, mse):
-    """metrics.json content from per-frame metrics of shape [S, N, T] (S samples, N draws of z, T predicted frames); numpy only."""
+def summarise_metrics(ssim, psnr, mse, extras=None):
+    """metrics.json content from per-frame metrics of shape [S, N, T] (S samples, N draws of z, T predicted frames); numpy only.
+    ``extras``: further per-frame metrics by name ({'vgg_cos': [S, N, T], 'vgg_l1': [S, N, T]}), summarised like the three (the names in
+    LOWER_IS_BETTER pick their lowest draw) and counted in n_nonfinite; without them the result is that of the three alone."""
     arrs = {'ssim': np.asarray(ssim, np.float64), 'psnr': np.asarray(psnr, np.float64), 'mse': np.asarray(mse, np.float64)}
+    for name, x in (extras or {}).items():
+        if name in arrs:
+            raise ValueError('summarise_metrics: extras may not replace %r' % name)
+        arrs[name] = np.asarray(x, np.float64)
     shape = arrs['ssim'].shape
     if len(shape) != 3 or any(a.shape != shape for a in arrs.values()):
-        raise ValueError('summarise_metrics: ssim, psnr and mse must share one [S, N, T] shape (got %s)'
-                         % [a.shape for a in arrs.values()])
+        raise ValueError('summarise_metrics: %s must share one [S, N, T] shape (got %s)'
+                         % (', '.join(arrs) if extras else 'ssim, psnr and mse', [a.shape for a in arrs.values()]))
     s, n, t = shape
-    bad = ~(np.isfinite(arrs['ssim']) & np.isfinite(arrs['psnr']) & np.isfinite(arrs['mse']))
+    bad = ~np.logical_and.reduce([np.isfinite(a) for a in arrs.values()])
     out = {'definition': METRICS_DEFINITION, 'n_samples': s, 'n_draws': n, 'n_nonfinite': int(bad.sum())}
+    if extras:
+        out['definition'] = METRICS_DEFINITION + ' ' + VGG_METRICS_DEFINITION
+        out['vgg_layers'] = list(VGG_FEATURE_LAYERS)
     for name, x in arrs.items():
-        lower_is_better = name == 'mse'
+        lower_is_better = name in LOWER_IS_BETTER
         with np.errstate(invalid='ignore'):
             draw_mean = x.mean(axis=2)                                           # [S, N]
             key = np.where(np.isnan(draw_mean), np.inf if lower_is_better else -np.inf, draw_mean)
@@ -83,20 +109,37 @@ def summarise_metrics(ssim, psnr, mse):
     return out
 
 
-def _write_metrics(save_dir, scores, n_draws, n_frames):
-    """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them."""
+def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None):
+    """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
+    vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer)."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
+    arrays, extras = {'ssim': ssim, 'psnr': psnr, 'mse': mse}, None
+    if vgg_scores is not None:
+        nl = len(VGG_FEATURE_LAYERS)
+        host = torch.cat(vgg_scores, dim=1).cpu().numpy() if vgg_scores else np.zeros((n_draws, 0, nl, 2), np.float32)
+        layers = host.reshape(n_draws, -1, n_frames, nl, 2).transpose(1, 0, 2, 3, 4)    # [S, N, T, 5, 2]
+        arrays['vgg_cos_layers'] = np.ascontiguousarray(layers[..., 0])
+        arrays['vgg_l1_layers'] = np.ascontiguousarray(layers[..., 1])
+        # the mean over the five layers, in fp64, stored as the fp32 the other metrics are
+        extras = {'vgg_cos': arrays['vgg_cos_layers'].astype(np.float64).mean(axis=-1).astype(np.float32),
+                  'vgg_l1': arrays['vgg_l1_layers'].astype(np.float64).mean(axis=-1).astype(np.float32)}
+        arrays.update(extras)
     os.makedirs(save_dir, exist_ok=True)
-    np.savez(osp.join(save_dir, 'metrics.npz'), ssim=ssim, psnr=psnr, mse=mse)
-    res = summarise_metrics(ssim, psnr, mse)
+    np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
+    res = summarise_metrics(ssim, psnr, mse, extras=extras)
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
-    print('metrics: %d samples x %d draws: SSIM %s (best of draws %s), PSNR %s dB (best of draws %s), MSE %s; %d non-finite frames'
-          % (res['n_samples'], res['n_draws'], fmt(res['ssim']['mean'], '%.4f'), fmt(res['ssim']['best_of_draws'], '%.4f'),
-             fmt(res['psnr']['mean'], '%.2f'), fmt(res['psnr']['best_of_draws'], '%.2f'), fmt(res['mse']['mean'], '%.3e'), res['n_nonfinite']))
+    line = ('metrics: %d samples x %d draws: SSIM %s (best of draws %s), PSNR %s dB (best of draws %s), MSE %s'
+            % (res['n_samples'], res['n_draws'], fmt(res['ssim']['mean'], '%.4f'), fmt(res['ssim']['best_of_draws'], '%.4f'),
+               fmt(res['psnr']['mean'], '%.2f'), fmt(res['psnr']['best_of_draws'], '%.2f'), fmt(res['mse']['mean'], '%.3e')))
+    if extras is not None:
+        line += (', VGG cos %s (best of draws %s), VGG L1 %s (best of draws %s)'
+                 % (fmt(res['vgg_cos']['mean'], '%.4f'), fmt(res['vgg_cos']['best_of_draws'], '%.4f'),
+                    fmt(res['vgg_l1']['mean'], '%.4f'), fmt(res['vgg_l1']['best_of_draws'], '%.4f')))
+    print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
 
 
 def _save_img_sequence(output_dir, img_seq, rescale=False):
@@ -119,7 +162,12 @@ def main(argv=None):
     parser.add_argument('--no-save', action='store_true')
     parser.add_argument('--metrics', action='store_true', help='score the predictions: <save_dir>/metrics.npz and metrics.json')
     parser.add_argument('--samples', type=int, default=1, help='rollouts per batch with fresh z (PNGs from the first)')
+    parser.add_argument('--vgg-metrics', action='store_true',
+                        help='with --metrics: VGG19 feature-space cosine similarity and perceptual L1 per predicted frame (paths.vggnet)')
+    parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
     args = parser.parse_args(argv)
+    if args.vgg_metrics and not args.metrics:
+        parser.error('--vgg-metrics adds to the scores of --metrics and needs it')
     if args.metrics and args.synthetic:
         parser.error('--metrics scores predictions against the real future frames, and --synthetic inputs have no ground truth')
     if args.samples < 1:
@@ -128,8 +176,14 @@ def main(argv=None):
     for p in (args.checkpoint_stage1, args.checkpoint_stage2):       # reference :34-38
         if not (osp.exists(p) or osp.exists(p + '.index')):                 # .npz file or TensorFlow bundle prefix
             raise Exception('checkpoint not found at %s' % p)
+    vggnet = config.get('paths', {}).get('vggnet')
+    if args.vgg_metrics and not args.synthetic_vgg and not os.path.exists(str(vggnet)):      # as train.py
+        raise Exception('file of pretrained vgg19 does not exist at: %s (pass --synthetic-vgg for benchmarking)' % vggnet)
     import kpx_amd
     dev = torch.device('cuda', 0)
+    vgg = None
+    if args.vgg_metrics:
+        vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev) if args.synthetic_vgg else kpx_amd.Vgg19(vggnet, device=dev)
     model = kpx_amd.FinalModel(config, device=dev, point_maps=not args.no_save, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
@@ -141,6 +195,7 @@ def main(argv=None):
         loader = kpx_amd.data.SequenceDataLoader(config['paths']['data_dir'], 'test', n_points=config['model']['n_pts'], n_action=n_action,
                                                  random_order=False, randomness=False, with_image_seq=True)
         scores, n_frames = [], 32
+        vgg_scores = [] if args.vgg_metrics else None
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
             if args.metrics:
@@ -149,12 +204,19 @@ def main(argv=None):
                 real_flat = real_seq.reshape(bsz * n_frames, *real_seq.shape[2:])
                 score = torch.empty((args.samples, bsz * n_frames, 3), dtype=torch.float32, device=dev)
                 scores.append(score)
+                if args.vgg_metrics:         # the real frames' features once per batch, reused by every draw
+                    scorer = kpx_amd.FeatureScorer(vgg, real_flat)
+                    vgg_score = torch.empty((args.samples, bsz * n_frames, len(VGG_FEATURE_LAYERS), 2), dtype=torch.float32, device=dev)
+                    vgg_scores.append(vgg_score)
             for draw in range(args.samples):
                 outputs = model.run(None, {'image': batch['image'], 'action_code': batch['action_code']})
                 frames += bsz * 32
                 if args.metrics:             # enqueued before the next run() overwrites the graph's output buffers
                     pred = outputs['pred_im_seq']
-                    kpx_amd.ops.frame_metrics(pred.reshape(bsz * n_frames, *pred.shape[2:]), real_flat, png8=True, out=score[draw])
+                    pred_flat = pred.reshape(bsz * n_frames, *pred.shape[2:])
+                    kpx_amd.ops.frame_metrics(pred_flat, real_flat, png8=True, out=score[draw])
+                    if args.vgg_metrics:
+                        scorer(pred_flat, out=vgg_score[draw])
                 if draw > 0 or args.no_save:
                     continue
                 o = {k: v.cpu().numpy() for k, v in outputs.items() if isinstance(v, torch.Tensor)}
@@ -173,7 +235,7 @@ def main(argv=None):
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
         if args.metrics:
-            _write_metrics(args.save_dir, scores, args.samples, n_frames)
+            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

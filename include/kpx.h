@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 9
+#define KPX_ABI_VERSION 10
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -319,6 +319,18 @@ int kpx_summary_image_u8_f32(const float* x, int N, int H, int W, int C, int pre
  * No allocation, copy or synchronisation (capturable).  Added in ABI version 8. */
 int kpx_frame_metrics_f32(const float* a, const float* b, int N, int H, int W, int C, float L, int png8, float* out, void* stream);
 
+/* ---- VGG feature-space metrics (evaluate.py --vgg-metrics), DESIGN.md section 2: per frame pair of one layer's features fa, fb (fp32 NHWC
+ * [N,H,W,C] contiguous on 16-byte aligned pointers, C % 4 == 0, 4 <= C <= 512, H and W in [1,1024], N >= 1) -> out fp32 [N,2] =
+ * (cos_layer, l1_layer).  Per position over the C channels saa = sum a^2, sbb = sum b^2, dot = sum a b (fp32); its cosine is 1 where
+ * saa == 0 and sbb == 0, 0 where exactly one of them is 0, else min(1, dot / sqrt(saa sbb)) in fp64; cos_layer = mean over positions,
+ * l1_layer = mean |a - b| over positions and channels, both summed in fp64: identical inputs score exactly (1, 0).
+ * Two launches: per-slab fp64 partials into `work` (kpx_feature_pair_metrics_workspace_bytes, 8-byte aligned; the slab count depends on
+ * (H, W, C) alone), then a fixed-order fold per frame.  No atomics: frame n's result is bitwise the same for every N, every position in the
+ * batch and every run.  No allocation, copy or synchronisation (capturable).  KPX_EINVAL before any device call for anything else.
+ * Added in ABI version 10. */
+size_t kpx_feature_pair_metrics_workspace_bytes(int N, int H, int W, int C);
+int kpx_feature_pair_metrics_f32(const float* fa, const float* fb, int N, int H, int W, int C, float* work, float* out, void* stream);
+
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */
 int kpx_head_blend_fwd_f32(const float* im, const float* raw4, size_t P, float* final_out, float* crude_out, float* mask_out, void* stream);
@@ -328,6 +340,9 @@ int kpx_head_blend_bwd_f32(const float* dfinal, const float* im, const float* ra
  *      (detector_translator_model.py:262-263, vgg.py:16-19). */
 int kpx_vgg_prep_fwd_f32(const float* rgb, size_t P, float* bgr, void* stream);
 int kpx_vgg_prep_bwd_f32(const float* dbgr, size_t P, float* drgb, void* stream);
+/* The same transform of the 8-bit frame evaluate.py writes: q = clamp(uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))), 0, 255) (NaN -> 0) as
+ * kpx_frame_metrics_f32's png8, bgr = q - mean on the 0..255 scale (no round trip through [-1,1]).  Added in ABI version 10. */
+int kpx_vgg_prep_png8_f32(const float* rgb, size_t P, float* bgr, void* stream);
 
 /* ---- tf.nn.max_pool 2x2 s2 SAME (vgg.py:45-46). */
 int kpx_maxpool2_fwd_f32(const float* x, int N, int H, int W, int C, float* y, void* stream);

@@ -13,6 +13,14 @@
 // The per-lane sums are reduced in a fixed order (wave butterflies, then waves in order): frame n's result depends on frame n alone.
 // png8: both inputs are first quantised as evaluate.py writes PNGs, q = uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))) clamped to [0, 255],
 // and scored as q / 255 with L = 1 -- computed exactly as q with L = 255 (the same quantities up to fp64 rounding), mse scaled by 1/255^2.
+//
+// VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics): per frame pair of one VGG19 layer's features fa, fb
+// (fp32 NHWC, C a multiple of 4), the mean over positions of the channel cosine and the mean of |a - b|.  G = the largest power of two
+// <= min(C / 4, 64) lanes share one position, each with 16-byte loads of both sides (a wave reads 64 / G consecutive positions: one
+// contiguous run); the three channel sums of a position are fp32 lane partials folded by a butterfly inside the group, the ratio and every
+// sum across positions are fp64.  A frame is cut into S slabs of positions, S a function of (H, W, C) alone: one workgroup per (slab, frame)
+// writes its two fp64 partials to `work`, a second launch folds a frame's slabs in order.  No atomics; frame n depends on frame n alone.
+// kpx_vgg_prep_png8_f32 is the VGG input of those frames: q - mean, BGR, of the same 8-bit quantisation.
 #include "kpx_common.h"
 #include <cmath>
 
@@ -174,7 +182,141 @@ int fm_launch(const float* a, const float* b, int N, int H, int W, bool vec, int
     return kpx_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------- VGG feature-space metrics
+constexpr int FP_THREADS = 256;
+constexpr int FP_SLAB_BYTES = 32768;                                  // of one side per workgroup: 8 passes of 256 lanes x 16 bytes
+constexpr int FP_MAX_SLABS = 128;
+
+int fp_slabs(int H, int W, int C) {
+    const long long bytes = (long long)H * W * C * 4;                  // >= 16; a slab never holds less than one position (C * 4 <= 2048)
+    const long long s = (bytes + FP_SLAB_BYTES - 1) / FP_SLAB_BYTES;
+    return (int)(s > FP_MAX_SLABS ? FP_MAX_SLABS : s);
+}
+
+// cosine of one position from its channel sums: 1 where both sides are zero, 0 where one is, else min(1, dot / sqrt(saa sbb)) in fp64.
+// saa == sbb == dot (identical sides) gives exactly 1: the product of two floats and its root are exact in fp64.  NaN stays NaN.
+__device__ __forceinline__ double fp_cos(float saa, float sbb, float dot) {
+    if (saa == 0.0f && sbb == 0.0f) return 1.0;
+    if (saa == 0.0f || sbb == 0.0f) return 0.0;
+    const double c = (double)dot / sqrt((double)saa * (double)sbb);
+    return c > 1.0 ? 1.0 : c;
+}
+
+template <int G>
+__global__ __launch_bounds__(FP_THREADS) void feature_pair_kernel(const float* __restrict__ fa, const float* __restrict__ fb, int N, int P, int C4,
+                                                                   int S, double* __restrict__ work) {
+    constexpr int PPB = FP_THREADS / G;                                // positions per pass of the workgroup
+    __shared__ double red[2][FP_THREADS / KPX_WAVE];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const int l = tid % G, g = tid / G;
+    const int p0 = (int)((long long)P * s / S), p1 = (int)((long long)P * (s + 1) / S);
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const f32x4* an = reinterpret_cast<const f32x4*>(fa) + (size_t)n * P * C4;
+        const f32x4* bn = reinterpret_cast<const f32x4*>(fb) + (size_t)n * P * C4;
+        double cos_acc = 0.0, l1_acc = 0.0;
+        for (int pb = p0; pb < p1; pb += PPB) {                        // uniform over the workgroup: every lane takes part in the butterflies
+            const int p = pb + g;
+            const bool valid = p < p1;
+            float saa = 0.0f, sbb = 0.0f, dot = 0.0f, l1 = 0.0f;
+            if (valid) {
+                const f32x4* pa = an + (size_t)p * C4;
+                const f32x4* pq = bn + (size_t)p * C4;
+                for (int j = l; j < C4; j += G) {                      // at most 2 rounds (C4 < 2 G, or G = 64 and C4 <= 128): 8 elements per lane
+                    const f32x4 va = pa[j], vb = pq[j];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        saa = fmaf(va[e], va[e], saa);
+                        sbb = fmaf(vb[e], vb[e], sbb);
+                        dot = fmaf(va[e], vb[e], dot);
+                        l1 += fabsf(va[e] - vb[e]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int o = G / 2; o > 0; o >>= 1) {
+                saa += __shfl_xor(saa, o, 64);
+                sbb += __shfl_xor(sbb, o, 64);
+                dot += __shfl_xor(dot, o, 64);
+            }
+            if (valid) {
+                l1_acc += (double)l1;
+                if (l == 0) cos_acc += fp_cos(saa, sbb, dot);
+            }
+        }
+        cos_acc = kpx_wave_sum_d(cos_acc);
+        l1_acc = kpx_wave_sum_d(l1_acc);
+        if ((tid & (KPX_WAVE - 1)) == 0) { red[0][tid / KPX_WAVE] = cos_acc; red[1][tid / KPX_WAVE] = l1_acc; }
+        __syncthreads();
+        if (tid == 0) {
+            double c = red[0][0], d = red[1][0];
+            for (int i = 1; i < FP_THREADS / KPX_WAVE; ++i) { c += red[0][i]; d += red[1][i]; }
+            double* o = work + ((size_t)n * S + s) * 2;
+            o[0] = c;
+            o[1] = d;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(KPX_WAVE) void feature_pair_finalize_kernel(const double* __restrict__ work, int N, int S, double npos, double nelem,
+                                                                         float* __restrict__ out) {
+    const int n = blockIdx.x * KPX_WAVE + threadIdx.x;
+    if (n >= N) return;
+    const double* w = work + (size_t)n * S * 2;
+    double c = w[0], d = w[1];
+    for (int i = 1; i < S; ++i) { c += w[2 * i]; d += w[2 * i + 1]; }
+    out[2 * (size_t)n + 0] = (float)(c / npos);                        // exactly 1 when every position's cosine is
+    out[2 * (size_t)n + 1] = (float)(d / nelem);
+}
+
+template <int G>
+void fp_launch(const float* fa, const float* fb, int N, int P, int C4, int S, double* work, hipStream_t s) {
+    hipLaunchKernelGGL((feature_pair_kernel<G>), dim3(S, N > 65535 ? 65535 : N), dim3(FP_THREADS), 0, s, fa, fb, N, P, C4, S, work);
+}
+
+__global__ __launch_bounds__(256) void vgg_prep_png8_kernel(const float* __restrict__ rgb, size_t P, float* __restrict__ bgr) {
+    for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (size_t)gridDim.x * 256) {
+        const float r = fm_png8(rgb[p * 3 + 0]), g = fm_png8(rgb[p * 3 + 1]), b = fm_png8(rgb[p * 3 + 2]);
+        bgr[p * 3 + 0] = b - 103.939f; bgr[p * 3 + 1] = g - 116.779f; bgr[p * 3 + 2] = r - 123.68f;
+    }
+}
+
 }  // namespace
+
+extern "C" size_t kpx_feature_pair_metrics_workspace_bytes(int N, int H, int W, int C) {
+    if (N < 1 || H < 1 || H > 1024 || W < 1 || W > 1024 || C < 4 || C > 512 || C % 4) return 0;
+    return (size_t)N * fp_slabs(H, W, C) * 2 * sizeof(double);
+}
+
+extern "C" int kpx_feature_pair_metrics_f32(const float* fa, const float* fb, int N, int H, int W, int C, float* work, float* out, void* stream) {
+    if (!fa || !fb || !work || !out || N < 1 || H < 1 || H > 1024 || W < 1 || W > 1024 || C < 4 || C > 512 || C % 4 ||
+        ((((uintptr_t)fa) | ((uintptr_t)fb)) & 15) || (((uintptr_t)work) & 7) || (((uintptr_t)out) & 3))
+        return KPX_EINVAL;
+    const int P = H * W, C4 = C / 4, S = fp_slabs(H, W, C);
+    double* wk = reinterpret_cast<double*>(work);
+    hipStream_t s = kpx_stream(stream);
+    const int lanes = C4 > 64 ? 64 : C4;                               // lanes of one position: the largest power of two <= min(C / 4, 64)
+    if (lanes >= 64) fp_launch<64>(fa, fb, N, P, C4, S, wk, s);
+    else if (lanes >= 32) fp_launch<32>(fa, fb, N, P, C4, S, wk, s);
+    else if (lanes >= 16) fp_launch<16>(fa, fb, N, P, C4, S, wk, s);
+    else if (lanes >= 8) fp_launch<8>(fa, fb, N, P, C4, S, wk, s);
+    else if (lanes >= 4) fp_launch<4>(fa, fb, N, P, C4, S, wk, s);
+    else if (lanes >= 2) fp_launch<2>(fa, fb, N, P, C4, S, wk, s);
+    else fp_launch<1>(fa, fb, N, P, C4, S, wk, s);
+    int rc = kpx_launch_status();
+    if (rc) return rc;
+    hipLaunchKernelGGL(feature_pair_finalize_kernel, dim3((N + KPX_WAVE - 1) / KPX_WAVE), dim3(KPX_WAVE), 0, s, (const double*)wk, N, S,
+                       (double)P, (double)P * C, out);
+    return kpx_launch_status();
+}
+
+extern "C" int kpx_vgg_prep_png8_f32(const float* rgb, size_t P, float* bgr, void* stream) {
+    if (!rgb || !bgr) return KPX_EINVAL;
+    if (P == 0) return 0;
+    const size_t blocks = (P + 255) / 256;
+    hipLaunchKernelGGL(vgg_prep_png8_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, kpx_stream(stream), rgb, P, bgr);
+    return kpx_launch_status();
+}
 
 extern "C" int kpx_frame_metrics_f32(const float* a, const float* b, int N, int H, int W, int C, float L, int png8, float* out, void* stream) {
     if (!a || !b || !out || N < 1 || H < 11 || H > 1024 || W < 11 || W > 1024 || !(C == 1 || C == 3) || !(png8 == 0 || png8 == 1) ||

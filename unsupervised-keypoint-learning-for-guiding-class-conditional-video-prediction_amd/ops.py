@@ -1443,6 +1443,35 @@ def frame_metrics(a, b, max_val=1.0, png8=False, out=None):
     return out
 
 
+def feature_pair_metrics(fa, fb, out=None):
+    """Per-frame VGG feature-space metrics of one layer's features fa against fb, both contiguous fp32 [N,H,W,C] on
+    one device at 16-byte aligned addresses, C a multiple of 4 in [4, 512], H and W in [1, 1024] -> fp32 [N,2] = (cos_layer, l1_layer): the
+    mean over positions of the channel cosine (1 where both sides are zero, 0 where one is) and the mean of |a - b|.  ``out``: a contiguous
+    fp32 [N,2] tensor to write into.  Two launches on the current stream; frame n's result is bitwise independent of the batch."""
+    for t in (fa, fb):
+        _require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.KpxError('feature_pair_metrics: fa and fb must be contiguous fp32 tensors (got %s, contiguous=%s)'
+                                % (t.dtype, t.is_contiguous()))
+    if fa.dim() != 4 or tuple(fa.shape) != tuple(fb.shape) or fa.device != fb.device:
+        raise _lib.KpxError('feature_pair_metrics: fa and fb must be [N,H,W,C] of one shape on one device (got %s on %s, %s on %s)'
+                            % (tuple(fa.shape), fa.device, tuple(fb.shape), fb.device))
+    n, h, w, c = fa.shape
+    if n < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c % 4 or not 4 <= c <= 512:
+        raise _lib.KpxError('feature_pair_metrics: needs N >= 1, H and W in [1, 1024] and C a multiple of 4 in [4, 512] (got %s)'
+                            % (tuple(fa.shape),))
+    if fa.data_ptr() % 16 or fb.data_ptr() % 16:
+        raise _lib.KpxError('feature_pair_metrics: fa and fb must start on 16-byte boundaries')
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.float32, device=fa.device)
+    elif tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != fa.device:
+        raise _lib.KpxError('feature_pair_metrics: out must be a contiguous fp32 [%d,2] tensor on %s' % (n, fa.device))
+    work = scratch.get('feature_pair', lib.kpx_feature_pair_metrics_workspace_bytes(n, h, w, c), fa.device)
+    check(lib.kpx_feature_pair_metrics_f32(fa.data_ptr(), fb.data_ptr(), n, h, w, c, work.data_ptr(), out.data_ptr(), _stream()),
+          'kpx_feature_pair_metrics_f32')
+    return out
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4

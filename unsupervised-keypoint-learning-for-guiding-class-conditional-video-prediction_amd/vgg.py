@@ -60,10 +60,11 @@ class Vgg19:
                 keys += ops.register_constant_filter(self.params[name][0], 'vgg/' + name)     # tf.constant filters (vgg.py:57-61): Winograd form once
         weakref.finalize(self, ops.release_filters, keys)
 
-    def build(self, rgb01):
+    def build(self, rgb01, png8=False):
         """Forward only: images in [-1,1] (the (x+1)/2*255, BGR, mean shift of :262-263 / vgg.py:16-19 is fused into the
-        first kernel) -> [conv1_2, conv2_2, conv3_4, conv4_4, conv5_4]."""
-        feats, _ = _vgg_forward(self, rgb01.contiguous())
+        first kernel) -> [conv1_2, conv2_2, conv3_4, conv4_4, conv5_4].  ``png8``: the features of the 8-bit frames evaluate.py writes
+        (each value quantised as ``_save_img(rescale=True)``, fed on the 0..255 scale)."""
+        feats, _ = _vgg_forward(self, rgb01.contiguous(), png8=png8)
         return feats
 
     def perceptual_loss(self, gt_image, pred_image):
@@ -71,12 +72,16 @@ class Vgg19:
         return _PerceptualLossFn.apply(pred_image, gt_image, self)
 
 
-def _vgg_forward(vgg, images):
-    """images [N,H,W,3] in [-1,1] -> (features, tape) where tape records (kind, name, input, output)."""
+def _vgg_forward(vgg, images, png8=False):
+    """images [N,H,W,3] in [-1,1] -> (features, tape) where tape records (kind, name, input, output).  ``png8``: the network's input is
+    q - mean of the 8-bit quantisation q of the images (kpx_vgg_prep_png8_f32) instead of (x+1)/2*255 - mean."""
     n, h, w, _ = images.shape
     dev = images.device
     x = torch.empty_like(images)
-    check(lib.kpx_vgg_prep_fwd_f32(images.data_ptr(), n * h * w, x.data_ptr(), ops._stream()), 'kpx_vgg_prep_fwd_f32')
+    if png8:
+        check(lib.kpx_vgg_prep_png8_f32(images.data_ptr(), n * h * w, x.data_ptr(), ops._stream()), 'kpx_vgg_prep_png8_f32')
+    else:
+        check(lib.kpx_vgg_prep_fwd_f32(images.data_ptr(), n * h * w, x.data_ptr(), ops._stream()), 'kpx_vgg_prep_fwd_f32')
     feats, tape = [], []
     pooled = None                                        # max-pool of the last conv's output, when its epilogue already wrote it
     for pos, item in enumerate(VGG_SEQ):
@@ -119,6 +124,57 @@ def _vgg_forward(vgg, images):
             tape.append(('conv', item, x, y))
             x = y
     return feats, tape
+
+
+FEATURE_LAYERS = ['conv1_2', 'conv2_2', 'conv3_4', 'conv4_4', 'conv5_4']      # the features Vgg19.build returns, in order
+FEATURE_CHUNK = 64        # frames per VGG forward of FeatureScorer (the stage-1 step runs the network on 64 frames of 128 x 128 too)
+
+
+class FeatureScorer:
+    """VGG feature-space metrics of predicted frames against real ones (evaluate.py --vgg-metrics).
+
+    ``real_frames`` [N,H,W,3] fp32 in [-1,1]: their features (of the 8-bit frames, ``png8``) are computed once, FEATURE_CHUNK frames per VGG
+    forward, and kept, so every draw of z scores against the same tensors -- about 8 MB per 128 x 128 frame.  ``scorer(pred_frames, out=)``
+    -> fp32 [N,5,2] on the device: per frame and layer of FEATURE_LAYERS (cos_layer, l1_layer) of ``ops.feature_pair_metrics``; vgg_cos and
+    vgg_l1 are their means over the five layers.  fp32 activations only."""
+
+    def __init__(self, vgg, real_frames):
+        if ops.act_dtype() != torch.float32:
+            raise ops._lib.KpxError('FeatureScorer: the VGG feature metrics are defined on fp32 activations; the bf16 configuration is not built')
+        self._check(real_frames, None)
+        self.vgg = vgg
+        self.shape = tuple(real_frames.shape)
+        self.chunk = max(1, int(FEATURE_CHUNK))
+        self.real = [vgg.build(real_frames[i:i + self.chunk], png8=True) for i in range(0, self.shape[0], self.chunk)]
+
+    @staticmethod
+    def _check(frames, shape):
+        ops._require_gpu(frames)
+        if frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1 or frames.dtype != torch.float32 or not frames.is_contiguous():
+            raise ops._lib.KpxError('FeatureScorer: frames must be a contiguous non-empty fp32 [N,H,W,3] tensor (got %s %s)'
+                                    % (tuple(frames.shape), frames.dtype))
+        if shape is not None and tuple(frames.shape) != shape:
+            raise ops._lib.KpxError('FeatureScorer: predicted frames %s do not match the real frames %s' % (tuple(frames.shape), shape))
+
+    def __call__(self, pred_frames, out=None):
+        if ops.act_dtype() != torch.float32:
+            raise ops._lib.KpxError('FeatureScorer: the VGG feature metrics are defined on fp32 activations; the bf16 configuration is not built')
+        self._check(pred_frames, self.shape)
+        n, dev = self.shape[0], pred_frames.device
+        nl = len(FEATURE_LAYERS)
+        if out is None:
+            out = torch.empty((n, nl, 2), dtype=torch.float32, device=dev)
+        elif tuple(out.shape) != (n, nl, 2) or out.dtype != torch.float32 or out.device != dev:
+            raise ops._lib.KpxError('FeatureScorer: out must be an fp32 [%d,%d,2] tensor on %s' % (n, nl, dev))
+        per_layer = torch.empty((nl, n, 2), dtype=torch.float32, device=dev)       # what the kernel writes: [N,2] per layer
+        for k, real in enumerate(self.real):
+            i0 = k * self.chunk
+            i1 = min(n, i0 + self.chunk)
+            feats = self.vgg.build(pred_frames[i0:i1], png8=True)
+            for layer, (fp, fr) in enumerate(zip(feats, real)):
+                ops.feature_pair_metrics(fp, fr, out=per_layer[layer, i0:i1])
+        out.copy_(per_layer.permute(1, 0, 2))                                        # [N,5,2]: a few KB of glue
+        return out
 
 
 FUSE_FEAT_BWD = True      # feature gradient (pool bwd + L1 bwd + ReLU bwd) in one pass
