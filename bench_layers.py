@@ -9,16 +9,20 @@ forward / dgrad / wgrad of every distinct layer, weighted by how often the step 
 translator's 4-channel head and D_logit produce fp32) -- each layer on the kernel `ops` picks for it there, fraction against the bf16 peak.
 """
 import argparse
+import ctypes
 import os
+import re
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-from kpx_amd import ops  # noqa: E402
+from kpx_amd import _lib, ops  # noqa: E402
 
 PEAK = 157.3
+with open(os.path.join(ROOT, 'include', 'kpx.h')) as _h:                # enum KpxWgradFamily, in the header's order
+    WGRAD_FAMILIES = re.findall(r'KPX_WGRAD_(\w+)', _h.read().split('enum KpxWgradFamily {')[1].split('}')[0])
 
 
 def layers(B, K=15):
@@ -121,10 +125,16 @@ def main():
             ops.release_filters(keys)
         name = name + (' [F43 ' + ('f' if f43_f else '-') + ('d' if f43_d else '-') + ']' if (f43_f or f43_d) else '')
         tw = timeit(lambda: ops.conv_wgrad_raw(x, ld, ci, dy, co, dw, s, pad_t, pad_t)) if ww else 0.0
+        fam = ''
+        if ww and x.dtype == dy.dtype == torch.float32:          # (the fp32 entry's plan: bf16 tensors go to the bf16 entries first)
+            got = [ctypes.c_int(), ctypes.c_int(), ctypes.c_size_t()]
+            _lib.check(_lib.lib.kpx_conv2d_wgrad_plan(x.data_ptr(), n, h, h, ci, ld, dy.data_ptr(), ho, ho, co, co, k, k, s, pad_t, pad_t, ops._arith(),
+                                                      *map(ctypes.byref, got)), 'kpx_conv2d_wgrad_plan')
+            fam = '  wgrad: %s x %d' % (WGRAD_FAMILIES[got[0].value].lower(), got[1].value)
         tot['fwd'] += wf * tf; tot['dgrad'] += wd * td; tot['wgrad'] += ww * tw
         flops_tot += flops * (wf + wd + ww)
         f = lambda t: flops / (t * 1e-3) / 1e12 if t else 0.0
-        print('%-36s %5d %4d %5d %5d %d %d | %9.3f %6.1f | %9.3f %6.1f | %9.3f %6.1f' % (name, n, h, ci, co, k, s, tf, f(tf), td, f(td), tw, f(tw)))
+        print('%-36s %5d %4d %5d %5d %d %d | %9.3f %6.1f | %9.3f %6.1f | %9.3f %6.1f%s' % (name, n, h, ci, co, k, s, tf, f(tf), td, f(td), tw, f(tw), fam))
     t = sum(tot.values())
     print('weighted per-step totals: fwd %.2f ms, dgrad %.2f ms, wgrad %.2f ms, all %.2f ms; %.1f TF = %.1f%% of the %s MFMA peak%s'
           % (tot['fwd'], tot['dgrad'], tot['wgrad'], t, flops_tot / (t * 1e-3) / 1e12, 100 * flops_tot / (t * 1e-3) / 1e12 / peak, 'bf16' if b16 else 'fp32',

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 10
+#define KPX_ABI_VERSION 11
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -137,12 +137,32 @@ int kpx_conv2d_dgrad_act_f32(const float* dy, int N, int Ho, int Wo, int Cout, i
                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* dw[r,q,c,k] = sum_{n,oh,ow} x[n, oh*s+r-pad_t, ow*s+q-pad_l, c] * dy[n,oh,ow,k].
- * `workspace` holds split-K partial slabs; query its size with kpx_conv2d_wgrad_workspace_bytes. */
+ * `workspace` holds split-K partial slabs; query its size with kpx_conv2d_wgrad_workspace_bytes, which covers every call of the three
+ * weight-gradient entries (this one, kpx_conv2d_wgrad_bf16, kpx_conv_image_wgrad_bf16) for a layer of that shape.  One plan per call chooses
+ * the kernel family and the number of slabs; a workspace smaller than that plan needs is refused with KPX_EINVAL before any device call
+ * (no other family is tried in its place). */
 size_t kpx_conv2d_wgrad_workspace_bytes(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW);
 int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int Cin, int ldx,
                          const float* dy, int Ho, int Wo, int Cout, int lddy,
                          float* dw_hwio, int KH, int KW, int stride, int pad_t, int pad_l, int arith,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* The plan kpx_conv2d_wgrad_f32 makes for the same arguments, a host question (no device call; KPX_EINVAL for arguments the entry refuses):
+ * the kernel family in the order the families are asked, the number of partial slabs (1: the kernel writes dw itself) and the workspace
+ * that call needs -- never more than kpx_conv2d_wgrad_workspace_bytes answers for the shape.  For tests and per-layer benchmarks. */
+enum KpxWgradFamily {
+    KPX_WGRAD_WSMALL = 0,       /* conv_wsmall.hip: tiny filters over very many pixels, the whole gradient in one workgroup's accumulators */
+    KPX_WGRAD_WINO,             /* conv_wino.hip: F(2x2,3x3) weight gradient of the stride-1 3x3 SAME layers */
+    KPX_WGRAD_ROWS_MERGED,      /* conv_wgrad_rows_merged_kernel: image inputs at high resolution, one tap per filter row */
+    KPX_WGRAD_ROWS,             /* conv_wgrad_rows_kernel: few channels at high resolution, all taps from one LDS halo */
+    KPX_WGRAD_GEMM3,            /* conv_gemm3.hip: bf16 matrix pipe (bf16x3 or bf16 operands); strided layers, and what TAP_ROWS does not take */
+    KPX_WGRAD_TAP_ROWS,         /* conv_wgrad_tap_rows_kernel: Wo a multiple of 32, wave-uniform row chunks */
+    KPX_WGRAD_GENERIC           /* conv_wgrad_kernel: any shape */
+};
+int kpx_conv2d_wgrad_plan(const float* x, int N, int Hi, int Wi, int Cin, int ldx,
+                          const float* dy, int Ho, int Wo, int Cout, int lddy,
+                          int KH, int KW, int stride, int pad_t, int pad_l, int arith,
+                          int* family, int* splits, size_t* workspace_bytes);
 
 /* dz = dy * act'(y) (y = the activated conv output; dz may alias dy): relu / leaky_relu(0.01) / tanh backward
  * (tf.nn.relu vgg.py:54, tf.nn.leaky_relu networks/__init__.py:145,148, tf.tanh layers.py:28 in stage-2 training). */

@@ -52,15 +52,15 @@ CONV_CASES = [
     (2, 4, 4, 256, 1, 3, 1, 1, 0),         # D_logit-shaped: wave-per-pixel small-Cout kernel
     (2, 6, 6, 512, 4, 3, 1, 0, 1),         # small-Cout kernel, Cout=4, relu
     (2, 20, 20, 3, 64, 3, 1, 0, 1),        # VGG conv1_1 shape (row-merged Cin=3)
-    (4, 128, 128, 16, 16, 3, 1, 0, 0),     # multi-tap small-channel wgrad kernel (pose conv_7_1); fwd + dgrad on the 16-cout kernel
+    (4, 128, 128, 16, 16, 3, 1, 0, 0),     # pose conv_7_1: fwd + dgrad on the 16-cout kernel; wgrad on the tiny-filter 16 -> 16 variant (conv_wsmall.hip)
     (3, 48, 80, 32, 16, 3, 1, 0, 2),       # 16-cout kernel: two chunks, lrelu, non-square
-    (4, 128, 128, 64, 16, 3, 1, 0, 1),     # same, two 32-channel input tiles per wave (pose conv_7_0)
-    (16, 64, 64, 128, 32, 3, 1, 0, 0),     # same, two channel tiles of 64 (pose conv_5_0)
+    (4, 128, 128, 64, 16, 3, 1, 0, 1),     # same, two 32-channel input tiles per wave (pose conv_7_0); Winograd weight gradient
+    (16, 64, 64, 128, 32, 3, 1, 0, 0),     # same, two channel tiles of 64 (pose conv_5_0); Winograd weight gradient
     (4, 128, 128, 64, 4, 3, 1, 0, 0),      # same, translator crude+mask head (forward: VALU kernel for few produced channels)
     (5, 128, 128, 32, 3, 3, 1, 0, 1),      # few-channel forward kernel, Cout = 3, relu, ragged tile count
     (3, 160, 144, 16, 4, 3, 1, 1, 2),      # same with an explicit pad (output 162 x 146), lrelu
-    (2, 64, 64, 256, 128, 3, 1, 0, 0),     # 8-wave 128x128 wgrad tiles
-    (4, 128, 128, 3, 32, 7, 1, 0, 0),      # row-merged multi-tap wgrad (encoder conv_1 at full resolution)
+    (2, 64, 64, 256, 128, 3, 1, 0, 0),     # Winograd weight gradient, 64 x 64 blocks, 4 x 2 of them (256 -> 128 channels)
+    (4, 128, 128, 3, 32, 7, 1, 0, 0),      # encoder conv_1 at full resolution: wgrad on the tiny-filter 7x7 image-input variant (conv_wsmall.hip)
     (8, 8, 8, 512, 512, 3, 1, 0, 1),       # split-K forward/dgrad (VGG conv5 shape), relu epilogue in the reduce
     (16, 10, 10, 256, 512, 4, 2, 1, 2),    # split-K with stride-2 parity classes (img_discr conv_4 geometry)
     (2, 32, 48, 48, 96, 3, 1, 0, 2),       # fused Winograd F(2x2,3x3): non-square, 3 chunks of 16 channels, lrelu
@@ -71,7 +71,7 @@ CONV_CASES = [
     (8, 32, 64, 64, 128, 3, 1, 0, 0),      # Winograd weight gradient (64-channel tiles, non-square image, 64 splits)
     (16, 32, 32, 128, 16, 3, 1, 0, 0),     # Winograd weight gradient, 64 x 32 blocks with the 16 output channels masked (pose conv_7_0)
     (16, 32, 32, 32, 160, 3, 1, 0, 1),     # Winograd weight gradient, 32 x 64 blocks, Cout = 160 overhangs the last block
-    (8, 64, 64, 64, 4, 3, 1, 0, 0),        # translator head shape: Winograd with 4 produced channels (fwd), 4 gathered channels (dgrad), wgrad 64 x 32 block
+    (8, 64, 64, 64, 4, 3, 1, 0, 0),        # translator head shape: Winograd with 4 produced channels (fwd), 4 gathered channels (dgrad), wgrad on the tiny-filter 64 -> 4 variant
     (32, 64, 64, 128, 128, 3, 1, 0, 1),    # THE bench / roofline shape (translator conv_3_1 at B=32): 64-cout Winograd workgroups, 16 chunks, fwd + dgrad
     (64, 32, 32, 24, 64, 3, 1, 0, 2),      # 64-cout Winograd workgroups with a 3-chunk K loop (only the un-pipelined tail iterations run)
     (128, 8, 8, 64, 512, 3, 1, 0, 0),      # 64-cout Winograd workgroups on packed 8x8 images (VGG conv5 at a large batch)
@@ -88,7 +88,24 @@ CONV_CASES = [
     (5, 96, 72, 64, 4, 3, 1, 0, 0),        # 64 -> 4 head variant on a non-square image (tile tails in both directions)
     (2, 128, 128, 32, 32, 3, 1, 0, 1),     # 32 -> 32 variant (encoder conv_2): 18 row blocks x 2 column blocks on six wavefronts
     (5, 100, 72, 32, 24, 3, 1, 0, 0),      # same, ragged tiles, 24 of 32 output channels
+    # the two high-resolution row kernels of conv_wgrad.hip, which take what the tiny-filter variants and the Winograd weight gradient leave
+    (4, 128, 128, 3, 16, 3, 1, 0, 0),      # row-merged multi-tap wgrad (conv_wgrad_rows_merged_kernel): image input, 3x3, 65 536 pixels
+    (4, 128, 128, 16, 32, 3, 1, 0, 0),     # multi-tap small-channel wgrad (conv_wgrad_rows_kernel): 16 -> 32, one 32-channel block per wave
+    (1, 32, 32, 128, 128, 3, 1, 0, 0),     # wgrad on the 8-wave 128x128 tiles of conv_wgrad_tap_rows_kernel (too few pixels for the Winograd weight gradient), two slabs
 ]
+
+# One row per weight-gradient kernel family (enum KpxWgradFamily), the cheapest CONV_CASES row of each; test_wgrad_plan_cpu.py holds the
+# plan of every one to its name.  GENERIC-MERGED: conv_wgrad_kernel's row-merged variant in a single slab (no workspace at all).
+WGRAD_FAMILY_ROWS = {
+    'WSMALL': (2, 128, 128, 16, 16, 3, 1, 0, 1),
+    'WINO': (16, 32, 32, 128, 16, 3, 1, 0, 0),
+    'ROWS_MERGED': (4, 128, 128, 3, 16, 3, 1, 0, 0),
+    'ROWS': (4, 128, 128, 16, 32, 3, 1, 0, 0),
+    'TAP_ROWS': (1, 32, 32, 64, 4, 3, 1, 0, 0),
+    'GEMM3': (3, 48, 80, 32, 16, 3, 1, 0, 2),
+    'GENERIC': (2, 32, 32, 16, 15, 1, 1, 0, 0),
+    'GENERIC-MERGED': (2, 20, 20, 3, 64, 3, 1, 0, 1),
+}
 
 
 @pytest.mark.parametrize('n,h,w,cin,cout,k,s,pad,act', CONV_CASES)
@@ -122,6 +139,47 @@ def test_conv_fwd_dgrad_wgrad(kpx, dev, n, h, w, cin, cout, k, s, pad, act, gtol
     assert rel_l2(t2n(xg.grad), t2n(xo.grad)) < gtol
     assert rel_l2(t2n(wg.grad), t2n(wo.grad)) < gtol
     assert rel_l2(t2n(bg.grad), t2n(bo.grad)) < gtol
+
+
+@pytest.mark.parametrize('family', sorted(WGRAD_FAMILY_ROWS))
+def test_wgrad_entry_stays_inside_the_planned_workspace(kpx, dev, family):
+    """kpx_conv2d_wgrad_f32 called directly with a workspace of exactly the bytes kpx_conv2d_wgrad_plan names (none where the plan has one
+    slab), followed by a guard of two slabs (a mistake in the split count is off by whole slabs): the guard keeps its bits, dw has the bits
+    ops.conv_wgrad_raw gets with the query-sized scratch (the reduce is fixed-order), and is within 1e-5 rel-L2 of the oracle's."""
+    import ctypes
+    from kpx_amd._lib import lib
+    n, h, w, cin, cout, k, s, pad, _ = WGRAD_FAMILY_ROWS[family]
+    assert WGRAD_FAMILY_ROWS[family] in CONV_CASES
+    pt, _, ho = kpx.ops.same_pad(h + 2 * pad, k, s)
+    pl, _, wo = kpx.ops.same_pad(w + 2 * pad, k, s)
+    pad_t, pad_l = pad + pt, pad + pl
+    rs = np.random.RandomState(cin * 7 + cout)
+    x = rs.randn(n, h, w, cin).astype(np.float32)
+    gy = rs.randn(n, ho, wo, cout).astype(np.float32)
+    wo_ = torch.zeros(k, k, cin, cout, requires_grad=True)
+    zo = R.conv(torch.from_numpy(x), wo_, None, s, pad)
+    assert tuple(zo.shape) == gy.shape
+    zo.backward(torch.from_numpy(gy))
+    xg, dyg = torch.from_numpy(x).to(dev), torch.from_numpy(gy).to(dev)
+    geom = (xg.data_ptr(), n, h, w, cin, cin, dyg.data_ptr(), ho, wo, cout, cout)
+    fam, splits, need = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_size_t(0)
+    arith = kpx.ops._arith()
+    assert lib.kpx_conv2d_wgrad_plan(*geom, k, k, s, pad_t, pad_l, arith, ctypes.byref(fam), ctypes.byref(splits), ctypes.byref(need)) == 0
+    slab = k * k * cin * cout
+    assert need.value == (splits.value * slab * 4 if splits.value > 1 else 0)
+    assert need.value <= lib.kpx_conv2d_wgrad_workspace_bytes(n, ho, wo, cin, cout, k, k)
+    pattern = 0x5A5AA5A5                                      # a fixed bit pattern, as int32
+    buf = torch.full((need.value // 4 + 2 * slab,), pattern, dtype=torch.int32, device=dev)
+    dw = torch.full((k, k, cin, cout), float('nan'), dtype=torch.float32, device=dev)
+    rc = lib.kpx_conv2d_wgrad_f32(*geom, dw.data_ptr(), k, k, s, pad_t, pad_l, arith, buf.data_ptr() if need.value else None, need.value, None)
+    torch.cuda.synchronize()
+    assert rc == 0
+    assert bool((buf[need.value // 4:] == pattern).all())
+    via_ops = torch.full_like(dw, float('nan'))
+    kpx.ops.conv_wgrad_raw(xg, cin, cin, dyg, cout, via_ops, s, pad_t, pad_l)
+    torch.cuda.synchronize()
+    assert torch.equal(dw.view(torch.int32), via_ops.view(torch.int32))
+    assert rel_l2(t2n(dw), t2n(wo_.grad)) < 1e-5
 
 
 def test_conv_reads_and_writes_channel_slices(kpx, dev):

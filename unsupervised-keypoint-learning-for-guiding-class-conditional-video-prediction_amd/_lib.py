@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/kpx.h one to one (tests/test_abi.py checks header vs this table)
-ABI_VERSION = 10       # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
+ABI_VERSION = 11       # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
 SIGNATURES = {
     'kpx_abi_version': (c_int, []),
     'kpx_reload_env': (c_int, []),
@@ -44,6 +44,8 @@ SIGNATURES = {
     'kpx_conv2d_wgrad_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'kpx_conv2d_wgrad_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int,
                                      P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P]),
+    'kpx_conv2d_wgrad_plan': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     'kpx_wino_u_bytes': (c_size_t, [c_int, c_int]),
     'kpx_wino_filter_transform_f32': (c_int, [P, c_int, c_int, c_int, P, P]),
     'kpx_wino_filter_transform_batch_f32': (c_int, [P, c_int, P]),

@@ -570,7 +570,7 @@ extern "C" __attribute__((visibility("hidden"))) int kpx_wgrad3_eligible(const W
     const KpxEnv* e = kpx_env();
     if (e->no_gemm3 || g->merge || !g->vecA || !g->vecB) return 0;
     if (g->Cin % 4 != 0 || g->Cout % 4 != 0 || g->Cin < 16 || g->Cout < 16) return 0;
-    if ((size_t)g->N * g->Hi * g->Wi * g->ldx * 4 >= 0x7fffffffu || (size_t)g->P * g->lddy * 4 >= 0x7fffffffu) return 0;     // 32-bit buffer offsets
+    if (!kpx_offsets_fit((size_t)g->N * g->Hi * g->Wi, g->ldx, 0x7fffffffu) || !kpx_offsets_fit(g->P, g->lddy, 0x7fffffffu)) return 0;
     if (g->io16 && g->terms != 1) return 0;
     return 1;
 }

@@ -7,9 +7,10 @@
 //   conv_wgrad_rows_kernel         small channel counts at high resolution: all taps of a row chunk from one LDS halo
 //   conv_wgrad_rows_merged_kernel  the same for image inputs (Cin = 3)
 // All of them split the pixel range over workgroups into partial slabs, summed in a fixed order by the reduce kernels below (finish_wgrad).
-// The entries hand a layer to conv_wsmall.hip, conv_wino.hip or conv_gemm3.hip first where those take it (kpx_internal.h).
+// wgrad_plan() below chooses among these four, conv_wsmall.hip, conv_wino.hip and conv_gemm3.hip (kpx_internal.h), for the entries and the host queries alike.
 #include "kpx_internal.h"
 #include "kpx_bf16.h"
+#include <cassert>
 
 // 16 zero bytes in the code object: invalid 16-B units are loaded from here.  Each translation unit that needs it has its own; the host
 // side of the library already has conv_igemm.hip's shadow symbol of that name, so this one is defined for the device only.
@@ -684,197 +685,193 @@ static int wgrad_splits(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW
     return (int)S;
 }
 
-// bf16 configuration: x and dy bf16 (pixel strides multiples of 8 elements), dw fp32; the bf16-pipe weight-gradient kernel of conv_gemm3.hip
-// with the generic split plan (workspace: kpx_conv2d_wgrad_workspace_bytes).  KPX_EINVAL for shapes it does not take.
-extern "C" int kpx_conv2d_wgrad_bf16(const void* x, int N, int Hi, int Wi, int Cin, int ldx, const void* dy, int Ho, int Wo, int Cout, int lddy,
-                                     float* dw, int KH, int KW, int stride, int pad_t, int pad_l, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !dy || !dw || N <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || KH <= 0 || KW <= 0 || stride <= 0 ||
-        ldx < Cin || lddy < Cout || ldx % 8 || lddy % 8 || !kpx_aligned16(x) || !kpx_aligned16(dy))
-        return KPX_EINVAL;
-    WgradGeom g{};
-    g.x = (const float*)x; g.dy = (const float*)dy; g.io16 = 1;
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Cin = Cin; g.ldx = ldx;
-    g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.lddy = lddy;
-    g.KH = KH; g.KW = KW; g.stride = stride; g.pad_t = pad_t; g.pad_l = pad_l;
-    g.P = N * Ho * Wo;
-    g.S = wgrad_splits(N, Ho, Wo, Cin, Cout, KH, KW);
-    g.slab = (size_t)KH * KW * Cin * Cout;
-    if (g.S > 1 && (!workspace || workspace_bytes < (size_t)g.S * g.slab * 4)) return KPX_EINVAL;
-    g.pps = ((g.P + g.S - 1) / g.S + 31) / 32 * 32;
-    g.out = g.S > 1 ? (float*)workspace : dw;
-    int bm, bn;
-    wgrad_tiles(Cin, Cout, bm, bn);
-    g.ct = (Cin + bm - 1) / bm; g.kt = (Cout + bn - 1) / bn;
-    g.vecA = 1; g.vecB = 1; g.terms = 1;
-    if (!kpx_wgrad3_eligible(&g)) return KPX_EINVAL;
-    hipStream_t s = kpx_stream(stream);
-    return finish_wgrad(kpx_wgrad3_launch(g, bm, 1, s), workspace, dw, g.slab, g.S, s);
+// The plan: ONE decision, read by the three entries, by kpx_conv2d_wgrad_plan and by kpx_conv2d_wgrad_workspace_bytes: which kernel family takes a call,
+// in how many partial slabs, and the few numbers its launch needs.  The families are asked in the order of enum KpxWgradFamily.
+enum { WG_F32, WG_BF16, WG_IMAGE16 };       // operand types: x and dy fp32 / both bf16 / fp32 image with a bf16 gradient
+// an entry's arguments: the leading fields of WgradGeom, x to pad_l (x, dy: bf16 tensors behind the float* type; the plan reads their alignment only)
+struct WgradCall : WgradGeom { int arith, types; };
+
+struct WgradPlan {
+    int family = -1;                        // KPX_WGRAD_*; -1: no kernel for these operand types takes the call
+    int S; size_t need;                     // partial slabs (1: the kernel writes dw itself) and the workspace bytes they take
+    int cpb, CT, bm;                        // 32-pixel row chunks per workgroup (the three row kernels), 32-channel blocks per wavefront (rows), square channel tile
+    WgradGeom g;                            // the call and its slab size; from the generic split plan on, the kernel arguments of gemm3 / generic
+};
+
+static bool wgrad_args_ok(const WgradCall& c) {
+    if (!c.x || !c.dy || c.N <= 0 || c.Hi <= 0 || c.Wi <= 0 || c.Cin <= 0 || c.Cout <= 0 || c.Ho <= 0 || c.Wo <= 0 || c.KH <= 0 || c.KW <= 0 ||
+        c.stride <= 0 || c.ldx < c.Cin || c.lddy < c.Cout || c.arith < 0 || c.arith > 1)
+        return false;
+    if (c.types == WG_BF16) return c.ldx % 8 == 0 && c.lddy % 8 == 0 && kpx_aligned16(c.x, c.dy);
+    return c.types != WG_IMAGE16 || c.Cin <= 4;             // (image-input layers only)
 }
 
-extern "C" size_t kpx_conv2d_wgrad_workspace_bytes(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
-    const int S = wgrad_splits(N, Ho, Wo, Cin, Cout, KH, KW);
-    size_t need = S > 1 ? (size_t)S * KH * KW * Cin * Cout * 4 : 0;
-    if (KH == 3 && KW == 3) {                      // Winograd wgrad (stride / padding unknown here: upper bound)
-        const int Sw = kpx_wino_wgrad_splits(N, Ho, Wo, Cin, Cout);
-        const size_t nw = (size_t)Sw * 9 * Cin * Cout * 4;
-        if (Sw > 1 && nw > need) need = nw;
+// The fields that the kernel arguments of the three row-chunk kernels share
+template <class G>
+static G wgrad_fill(const WgradPlan& p) {
+    const WgradGeom& c = p.g;
+    G g{};
+    g.x = c.x; g.dy = c.dy; g.out = c.out;
+    g.N = c.N; g.Hi = c.Hi; g.Wi = c.Wi; g.Cin = c.Cin; g.ldx = c.ldx;
+    g.Ho = c.Ho; g.Wo = c.Wo; g.Cout = c.Cout; g.lddy = c.lddy;
+    g.KH = c.KH; g.KW = c.KW; g.pad_t = c.pad_t; g.pad_l = c.pad_l;
+    g.total_chunks = c.N * c.Ho * (c.Wo / 32); g.cpb = p.cpb; g.ct = c.ct; g.slab = c.slab;
+    return g;
+}
+
+// An entry's call ends at the first family that takes it.  The workspace query (c.x == nullptr) does not know the operands' layout, which
+// can close any family to a call: for it every layout condition holds and the walk goes on to the end, `need` the largest it met.
+static WgradPlan wgrad_plan(const WgradCall& c) {
+    WgradPlan p{};
+    WgradGeom& g = p.g = c;
+    g.slab = (size_t)c.KH * c.KW * c.Cin * c.Cout;
+    const bool any = !c.x;
+    auto take = [&](int family, int S) {
+        p.family = family; p.S = S;
+        if (S > 1 && (size_t)S * g.slab * 4 > p.need) p.need = (size_t)S * g.slab * 4;
+        return !any;
+    };
+    g.vecA = any || (c.ldx % 4 == 0 && kpx_aligned16(c.x)); g.vecB = any || (c.lddy % 4 == 0 && kpx_aligned16(c.dy));     // 16-B loads of x / dy
+    const bool vec = g.vecA && g.vecB;
+    const size_t px_in = (size_t)c.N * c.Hi * c.Wi, px_out = (size_t)c.N * c.Ho * c.Wo;
+    int S, bn;
+
+    // tiny filters over very many pixels (image-input layers, 16 -> 16 at full resolution, the 64 -> 4 head): conv_wsmall.hip, 16-B staging
+    // units (dy always, x when it has a multiple of 4 channels) and 32-bit byte offsets at the PIXEL STRIDES (a channel slice has ldx > Cin)
+    if (c.types != WG_BF16 && kpx_offsets_fit(px_in, c.ldx, 0x60000000ull) && kpx_offsets_fit(px_out, c.lddy, 0x60000000ull) &&
+        (any || (c.Cout % 4 == 0 && g.vecB)) && (c.Cin % 4 != 0 || g.vecA)) {     // (any: the query has always counted this family for every Cout)
+        S = kpx_wsmall_splits(c.N, c.Hi, c.Wi, c.Cin, c.Ho, c.Wo, c.Cout, c.KH, c.KW, c.stride);
+        if (S >= 1 && take(KPX_WGRAD_WSMALL, S)) return p;
     }
-    for (int st = 1; st <= 2; ++st) {             // tiny-filter family (conv_wsmall.hip); the stride is unknown here: both
-        const int Ss = kpx_wsmall_splits(N, Ho * st, Wo * st, Cin, Ho, Wo, Cout, KH, KW, st);
-        const size_t ns = (size_t)Ss * KH * KW * Cin * Cout * 4;
-        if (Ss > 1 && ns > need) need = ns;
+    if (c.types == WG_IMAGE16) return p;                    // (the caller converts dy and uses the fp32 entry)
+    if (c.types == WG_F32 && c.stride == 1) {
+        // (the bf16x3 weight gradient of conv_gemm3.hip runs where the generic fp32 kernel would, and on the strided layers: measured ahead of the
+        //  specialised fp32 kernels it loses -- 18.65 vs 17.9 ms per step in round 3)
+        if (c.KH == 3 && c.KW == 3 && c.pad_t == 1 && c.pad_l == 1 && c.Ho == c.Hi && c.Wo == c.Wi && vec && (any || c.ldx >= ((c.Cin + 3) & ~3)) &&
+            kpx_offsets_fit(px_in, c.ldx > c.lddy ? c.ldx : c.lddy, 0x60000000ull)) {
+            S = kpx_wino_wgrad_splits(c.N, c.Hi, c.Wi, c.Cin, c.Cout);
+            if (S >= 1 && take(KPX_WGRAD_WINO, S)) return p;
+        }
+        g.ct = 1;
+        if (c.ldx == c.Cin && g.vecB && wgrad_rows_merged_plan(c.N, c.Ho, c.Wo, c.Cin, c.Cout, c.KH, c.KW, &S, &p.cpb) && take(KPX_WGRAD_ROWS_MERGED, S))
+            return p;
+        if (vec && c.Cin % 4 == 0 && wgrad_rows_plan(c.N, c.Ho, c.Wo, c.Cin, c.Cout, c.KH, c.KW, &S, &p.cpb, &p.CT)) {
+            g.ct = (c.Cin + 32 * p.CT - 1) / (32 * p.CT);
+            if (take(KPX_WGRAD_ROWS, S)) return p;
+        }
     }
-    int S2, cpb, CT;
-    if (wgrad_rows_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb, &CT)) {
-        const size_t n2 = (size_t)S2 * KH * KW * Cin * Cout * 4;
-        if (n2 > need) need = n2;
+    // the generic split plan: conv_wgrad_kernel, and the two families that run on its grid
+    wgrad_tiles(c.Cin, c.Cout, p.bm, bn);
+    g.ct = (c.Cin + p.bm - 1) / p.bm; g.kt = (c.Cout + bn - 1) / bn; g.P = (int)px_out;
+    g.S = S = wgrad_splits(c.N, c.Ho, c.Wo, c.Cin, c.Cout, c.KH, c.KW);
+    g.pps = ((g.P + S - 1) / S + 31) / 32 * 32;
+    g.io16 = c.types == WG_BF16;
+    g.terms = g.io16 || c.arith == KPX_ARITH_BF16 ? 1 : 3;
+    const bool tap = c.types == WG_F32 && vec && c.Cin % 4 == 0 && c.Cout % 4 == 0 && c.Wo % 32 == 0;
+    // (strided layers: the bf16x3 kernel beats the fp32 tap-rows kernel -- encoder conv_3 at N = 64: 0.152 vs 0.198 ms; the stride-1
+    //  layers that reach this point are faster on tap-rows / rows, and the 3x3 stride-1 layers on the Winograd weight gradient)
+    if (kpx_wgrad3_eligible(&g) && (c.stride > 1 || !tap) && take(KPX_WGRAD_GEMM3, S)) return p;
+    if (c.types == WG_BF16) return p;
+    if (tap) {
+        // chunk-aligned split: the generic plan's S in units of 32-pixel row chunks, which never comes out larger
+        const int chunks = c.N * c.Ho * (c.Wo / 32);
+        p.cpb = (chunks + S - 1) / S;
+        const int St = (chunks + p.cpb - 1) / p.cpb;
+        assert(St <= S);
+        if (take(KPX_WGRAD_TAP_ROWS, St)) return p;
     }
-    if (wgrad_rows_merged_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb)) {
-        const size_t n2 = (size_t)S2 * KH * KW * Cin * Cout * 4;
-        if (n2 > need) need = n2;
+    if (wgrad_merge(c.Cin, c.ldx, c.KW)) {                  // image inputs (Cin = 3, never a tap-rows layer): one tap per filter row, KW*Cin merged channels
+        g.merge = c.Cin; g.Cin = c.KW * c.Cin; g.KW = 1; g.vecA = 0;
+        g.ct = (g.Cin + p.bm - 1) / p.bm;
     }
-    return need;
+    take(KPX_WGRAD_GENERIC, S);
+    return p;
+}
+
+// Every entry: validate, plan, ONE workspace check (below the plan's need: refused, no other family is tried), fill the family's kernel arguments and launch, reduce.
+static int wgrad_run(const WgradCall& c, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!dw || !wgrad_args_ok(c)) return KPX_EINVAL;
+    WgradPlan p = wgrad_plan(c);
+    if (p.family < 0 || p.need > (workspace ? workspace_bytes : 0)) return KPX_EINVAL;
+    float* const out = p.g.out = p.S > 1 ? (float*)workspace : dw;       // the slabs where the plan has them
+    hipStream_t s = kpx_stream(stream);
+    int rc = 0;                             // (of the launches made in other files; the kernels launched here are asked after the switch)
+    switch (p.family) {
+        case KPX_WGRAD_WSMALL:
+            rc = kpx_wsmall_launch(c.x, c.N, c.Hi, c.Wi, c.Cin, c.ldx, c.dy, c.Ho, c.Wo, c.Cout, c.lddy, c.KH, c.KW, c.stride, c.pad_t, c.pad_l, out, p.S, s,
+                                   c.types == WG_IMAGE16);
+            break;
+        case KPX_WGRAD_WINO:
+            rc = kpx_wino_wgrad3x3(c.x, c.N, c.Hi, c.Wi, c.Cin, c.ldx, c.dy, c.Cout, c.lddy, out, p.S, s);
+            break;
+        case KPX_WGRAD_ROWS_MERGED:
+        case KPX_WGRAD_ROWS: {
+            const WgradRowsGeom r = wgrad_fill<WgradRowsGeom>(p);
+            const dim3 grid((unsigned)(p.S * r.ct));
+            if (p.family == KPX_WGRAD_ROWS_MERGED) hipLaunchKernelGGL((conv_wgrad_rows_merged_kernel<0>), grid, dim3(256), 0, s, r);
+            else if (p.CT == 2) hipLaunchKernelGGL((conv_wgrad_rows_kernel<2>), grid, dim3(256), 0, s, r);
+            else hipLaunchKernelGGL((conv_wgrad_rows_kernel<1>), grid, dim3(256), 0, s, r);
+            break;
+        }
+        case KPX_WGRAD_TAP_ROWS: {
+            WgradTapGeom r = wgrad_fill<WgradTapGeom>(p);
+            r.stride = c.stride; r.S = p.S; r.kt = p.g.kt;
+            const dim3 grid((unsigned)(r.S * r.KH * r.KW * r.ct * r.kt));
+            if (p.bm == 128) hipLaunchKernelGGL((conv_wgrad_tap_rows_kernel<128, 128, 2, 4>), grid, dim3(512), 0, s, r);
+            else hipLaunchKernelGGL((conv_wgrad_tap_rows_kernel<64, 64, 2, 2>), grid, dim3(256), 0, s, r);
+            break;
+        }
+        default: {
+            const WgradGeom& g = p.g;
+            const dim3 grid((unsigned)(g.S * g.KH * g.KW * g.ct * g.kt));
+            const bool vec = g.vecA && g.vecB;
+            if (p.family == KPX_WGRAD_GEMM3) rc = kpx_wgrad3_launch(g, p.bm, g.terms, s);       // bf16x3 (fp32-equivalent) or bf16 operands on the bf16 matrix pipe
+            else if (g.merge) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, true>), grid, dim3(256), 0, s, g);
+            else if (p.bm == 128 && vec) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 4, true, false>), grid, dim3(512), 0, s, g);
+            else if (p.bm == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 4, false, false>), grid, dim3(512), 0, s, g);
+            else if (vec) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, true, false>), grid, dim3(256), 0, s, g);
+            else hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, false>), grid, dim3(256), 0, s, g);
+        }
+    }
+    return finish_wgrad(rc ? rc : kpx_launch_status(), workspace, dw, p.g.slab, p.S, s);
 }
 
 extern "C" int kpx_conv2d_wgrad_f32(const float* x, int N, int Hi, int Wi, int Cin, int ldx,
                                     const float* dy, int Ho, int Wo, int Cout, int lddy,
                                     float* dw, int KH, int KW, int stride, int pad_t, int pad_l, int arith,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !dy || !dw || N <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 ||
-        KH <= 0 || KW <= 0 || stride <= 0 || ldx < Cin || lddy < Cout || arith < 0 || arith > 1)
-        return KPX_EINVAL;
-    {   // tiny filters over very many pixels (image-input layers, 16 -> 16 at full resolution, the 64 -> 4 head): conv_wsmall.hip
-        // (16-B staging units: dy always, x when it has a multiple of 4 channels)
-        // the kernel addresses x and dy with 32-bit byte offsets at their PIXEL STRIDES (a channel slice of a wider buffer has ldx > Cin)
-        const bool off32_ok = (size_t)N * Hi * Wi * (size_t)ldx * 4 < 0x60000000ull && (size_t)N * Ho * Wo * (size_t)lddy * 4 < 0x60000000ull;
-        const bool units_ok = off32_ok && Cout % 4 == 0 && lddy % 4 == 0 && kpx_aligned16(dy) && (Cin % 4 != 0 || (ldx % 4 == 0 && kpx_aligned16(x)));
-        const int Ss = units_ok ? kpx_wsmall_splits(N, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride) : 0;
-        const size_t slab = (size_t)KH * KW * Cin * Cout;
-        if (Ss >= 1 && (Ss == 1 || (workspace && workspace_bytes >= (size_t)Ss * slab * 4))) {
-            hipStream_t s = kpx_stream(stream);
-            const int rc = kpx_wsmall_launch(x, N, Hi, Wi, Cin, ldx, dy, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l, Ss > 1 ? (float*)workspace : dw, Ss, s);
-            return finish_wgrad(rc, workspace, dw, slab, Ss, s);
-        }
-    }
-    // (the bf16x3 weight gradient of conv_gemm3.hip runs where the generic fp32 kernel would, and on the strided layers: measured ahead of the
-    //  specialised fp32 kernels it loses -- 18.65 vs 17.9 ms per step in round 3)
-    if (KH == 3 && KW == 3 && stride == 1 && pad_t == 1 && pad_l == 1 && Ho == Hi && Wo == Wi && ldx % 4 == 0 && lddy % 4 == 0 &&
-        ldx >= ((Cin + 3) & ~3) && kpx_aligned16(x) && kpx_aligned16(dy) &&
-        (size_t)N * Hi * Wi * (size_t)(ldx > lddy ? ldx : lddy) * 4 < 0x60000000ull) {       // (the kernel addresses x / dy with 32-bit byte offsets)
-        const int Sw = kpx_wino_wgrad_splits(N, Hi, Wi, Cin, Cout);
-        const size_t slab = (size_t)9 * Cin * Cout;
-        if (Sw >= 1 && (Sw == 1 || (workspace && workspace_bytes >= (size_t)Sw * slab * 4))) {
-            hipStream_t s = kpx_stream(stream);
-            const int rc = kpx_wino_wgrad3x3(x, N, Hi, Wi, Cin, ldx, dy, Cout, lddy, Sw > 1 ? (float*)workspace : dw, Sw, s);
-            return finish_wgrad(rc, workspace, dw, slab, Sw, s);
-        }
-    }
-    {
-        int S2, cpb;
-        if (stride == 1 && ldx == Cin && lddy % 4 == 0 && kpx_aligned16(dy) && wgrad_rows_merged_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb)) {
-            WgradRowsGeom r{};
-            r.x = x; r.dy = dy;
-            r.N = N; r.Hi = Hi; r.Wi = Wi; r.Cin = Cin; r.ldx = ldx;
-            r.Ho = Ho; r.Wo = Wo; r.Cout = Cout; r.lddy = lddy;
-            r.KH = KH; r.KW = KW; r.pad_t = pad_t; r.pad_l = pad_l;
-            r.total_chunks = N * Ho * (Wo / 32); r.cpb = cpb; r.ct = 1;
-            r.slab = (size_t)KH * KW * Cin * Cout;
-            if (S2 > 1 && (!workspace || workspace_bytes < (size_t)S2 * r.slab * 4)) return KPX_EINVAL;
-            r.out = S2 > 1 ? (float*)workspace : dw;
-            hipStream_t s = kpx_stream(stream);
-            hipLaunchKernelGGL((conv_wgrad_rows_merged_kernel<0>), dim3((unsigned)S2), dim3(256), 0, s, r);
-            return finish_wgrad(kpx_launch_status(), workspace, dw, r.slab, S2, s);
-        }
-    }
-    {
-        int S2, cpb, CT;
-        const bool vec = (ldx % 4 == 0) && (lddy % 4 == 0) && (Cin % 4 == 0) && kpx_aligned16(x) && kpx_aligned16(dy);
-        if (stride == 1 && vec && wgrad_rows_plan(N, Ho, Wo, Cin, Cout, KH, KW, &S2, &cpb, &CT)) {
-            WgradRowsGeom r{};
-            r.x = x; r.dy = dy;
-            r.N = N; r.Hi = Hi; r.Wi = Wi; r.Cin = Cin; r.ldx = ldx;
-            r.Ho = Ho; r.Wo = Wo; r.Cout = Cout; r.lddy = lddy;
-            r.KH = KH; r.KW = KW; r.pad_t = pad_t; r.pad_l = pad_l;
-            r.total_chunks = N * Ho * (Wo / 32); r.cpb = cpb; r.ct = (Cin + 32 * CT - 1) / (32 * CT);
-            r.slab = (size_t)KH * KW * Cin * Cout;
-            if (S2 > 1 && (!workspace || workspace_bytes < (size_t)S2 * r.slab * 4)) return KPX_EINVAL;
-            r.out = S2 > 1 ? (float*)workspace : dw;
-            hipStream_t s = kpx_stream(stream);
-            const dim3 grid((unsigned)(S2 * r.ct));
-            if (CT == 2) hipLaunchKernelGGL((conv_wgrad_rows_kernel<2>), grid, dim3(256), 0, s, r);
-            else hipLaunchKernelGGL((conv_wgrad_rows_kernel<1>), grid, dim3(256), 0, s, r);
-            return finish_wgrad(kpx_launch_status(), workspace, dw, r.slab, S2, s);
-        }
-    }
-    WgradGeom g{};
-    g.x = x; g.dy = dy;
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Cin = Cin; g.ldx = ldx;
-    g.Ho = Ho; g.Wo = Wo; g.Cout = Cout; g.lddy = lddy;
-    g.KH = KH; g.KW = KW; g.stride = stride; g.pad_t = pad_t; g.pad_l = pad_l;
-    g.P = N * Ho * Wo;
-    g.S = wgrad_splits(N, Ho, Wo, Cin, Cout, KH, KW);
-    g.slab = (size_t)KH * KW * Cin * Cout;
-    if (g.S > 1 && (!workspace || workspace_bytes < (size_t)g.S * g.slab * 4)) return KPX_EINVAL;
-    g.pps = ((g.P + g.S - 1) / g.S + 31) / 32 * 32;
-    g.out = g.S > 1 ? (float*)workspace : dw;
-    int bm, bn;
-    wgrad_tiles(Cin, Cout, bm, bn);
-    g.ct = (Cin + bm - 1) / bm; g.kt = (Cout + bn - 1) / bn;
-    g.vecA = (ldx % 4 == 0) && kpx_aligned16(x);
-    g.vecB = (lddy % 4 == 0) && kpx_aligned16(dy);
-    g.terms = arith == KPX_ARITH_BF16 ? 1 : 3;
-    // (strided layers: the bf16x3 kernel below beats the fp32 tap-rows kernel -- encoder conv_3 at N = 64: 0.152 vs 0.198 ms; the stride-1
-    //  layers that reach this point are faster on tap-rows / rows, and the 3x3 stride-1 layers on the Winograd weight gradient)
-    const bool g3_strided = stride > 1 && g.vecA && g.vecB && kpx_wgrad3_eligible(&g);
-    if (!g3_strided && g.vecA && g.vecB && Cin % 4 == 0 && Cout % 4 == 0 && Wo % 32 == 0 && !wgrad_merge(Cin, ldx, KW)) {
-        // chunk-aligned split: same S as the generic plan, but in units of 32-pixel row chunks
-        WgradTapGeom r{};
-        r.x = x; r.dy = dy;
-        r.N = N; r.Hi = Hi; r.Wi = Wi; r.Cin = Cin; r.ldx = ldx;
-        r.Ho = Ho; r.Wo = Wo; r.Cout = Cout; r.lddy = lddy;
-        r.KH = KH; r.KW = KW; r.stride = stride; r.pad_t = pad_t; r.pad_l = pad_l;
-        r.total_chunks = N * Ho * (Wo / 32);
-        r.cpb = (r.total_chunks + g.S - 1) / g.S;
-        r.S = (r.total_chunks + r.cpb - 1) / r.cpb;             // <= g.S, so the workspace query still covers it
-        r.ct = g.ct; r.kt = g.kt; r.slab = g.slab;
-        r.out = r.S > 1 ? (float*)workspace : dw;
-        hipStream_t s = kpx_stream(stream);
-        const dim3 grid((unsigned)(r.S * KH * KW * r.ct * r.kt));
-        if (bm == 128) hipLaunchKernelGGL((conv_wgrad_tap_rows_kernel<128, 128, 2, 4>), grid, dim3(512), 0, s, r);
-        else hipLaunchKernelGGL((conv_wgrad_tap_rows_kernel<64, 64, 2, 2>), grid, dim3(256), 0, s, r);
-        return finish_wgrad(kpx_launch_status(), workspace, dw, r.slab, r.S, s);
-    }
-    int taps = KH * KW;
-    if (wgrad_merge(Cin, ldx, KW)) {     // image inputs (Cin = 3): one tap per filter row, KW*Cin merged channels
-        g.merge = Cin; g.Cin = KW * Cin; g.KW = 1; g.vecA = 0; taps = KH;
-        g.ct = (g.Cin + bm - 1) / bm;
-    }
-    hipStream_t s = kpx_stream(stream);
-    const dim3 grid((unsigned)(g.S * taps * g.ct * g.kt));
-    const bool vec = g.vecA && g.vecB && !g.merge;
-    if (vec && kpx_wgrad3_eligible(&g))                  // bf16x3 (fp32-equivalent) weight gradient on the bf16 matrix pipe (conv_gemm3.hip)
-        return finish_wgrad(kpx_wgrad3_launch(g, bm, g.terms == 1 ? 1 : 3, s), workspace, dw, g.slab, g.S, s);
-    if (g.merge) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, true>), grid, dim3(256), 0, s, g);
-    else if (bm == 128 && vec) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 4, true, false>), grid, dim3(512), 0, s, g);
-    else if (bm == 128) hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 2, 4, false, false>), grid, dim3(512), 0, s, g);
-    else if (vec) hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, true, false>), grid, dim3(256), 0, s, g);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 2, 2, false, false>), grid, dim3(256), 0, s, g);
-    return finish_wgrad(kpx_launch_status(), workspace, dw, g.slab, g.S, s);
+    return wgrad_run({{x, dy, nullptr, N, Hi, Wi, Cin, ldx, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l}, arith, WG_F32}, dw, workspace, workspace_bytes, stream);
+}
+
+// bf16 configuration: x and dy bf16 (pixel strides multiples of 8 elements), dw fp32; the bf16-pipe weight-gradient kernel of conv_gemm3.hip
+// with the generic split plan.  KPX_EINVAL for shapes it does not take.
+extern "C" int kpx_conv2d_wgrad_bf16(const void* x, int N, int Hi, int Wi, int Cin, int ldx, const void* dy, int Ho, int Wo, int Cout, int lddy,
+                                     float* dw, int KH, int KW, int stride, int pad_t, int pad_l, void* workspace, size_t workspace_bytes, void* stream) {
+    return wgrad_run({{(const float*)x, (const float*)dy, nullptr, N, Hi, Wi, Cin, ldx, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l}, 0, WG_BF16},
+                     dw, workspace, workspace_bytes, stream);
 }
 
 // bf16 configuration, image-input layers (conv_igemm.hip has their forward and data gradient): x fp32 image, dy bf16 (pixel stride lddy
-// elements, a multiple of 4) -> dw fp32 [KH, KW, Cin, Cout] (workspace: kpx_conv2d_wgrad_workspace_bytes).  KPX_EINVAL for shapes
-// conv_wsmall.hip does not take: the caller then converts and uses the fp32 entry.
+// elements, a multiple of 4) -> dw fp32 [KH, KW, Cin, Cout].  KPX_EINVAL for shapes conv_wsmall.hip does not take: the caller then converts
+// and uses the fp32 entry.
 extern "C" int kpx_conv_image_wgrad_bf16(const float* x, int N, int Hi, int Wi, int Cin, int ldx, const void* dy, int Ho, int Wo, int Cout, int lddy,
                                          float* dw, int KH, int KW, int stride, int pad_t, int pad_l, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !dy || !dw || N <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cin > 4 || Cout <= 0 || Ho <= 0 || Wo <= 0 || ldx < Cin || lddy < Cout)
-        return KPX_EINVAL;
-    const bool off32_ok = (size_t)N * Hi * Wi * (size_t)ldx * 4 < 0x60000000ull && (size_t)N * Ho * Wo * (size_t)lddy * 4 < 0x60000000ull;
-    if (!off32_ok || Cout % 4 || lddy % 4 || !kpx_aligned16(dy)) return KPX_EINVAL;
-    const int Ss = kpx_wsmall_splits(N, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride);
-    const size_t slab = (size_t)KH * KW * Cin * Cout;
-    if (Ss < 1 || (Ss > 1 && (!workspace || workspace_bytes < (size_t)Ss * slab * 4))) return KPX_EINVAL;
-    hipStream_t s = kpx_stream(stream);
-    const int rc = kpx_wsmall_launch(x, N, Hi, Wi, Cin, ldx, (const float*)dy, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l, Ss > 1 ? (float*)workspace : dw, Ss, s, 1);
-    return finish_wgrad(rc, workspace, dw, slab, Ss, s);
+    return wgrad_run({{x, (const float*)dy, nullptr, N, Hi, Wi, Cin, ldx, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l}, 0, WG_IMAGE16},
+                     dw, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kpx_conv2d_wgrad_plan(const float* x, int N, int Hi, int Wi, int Cin, int ldx, const float* dy, int Ho, int Wo, int Cout, int lddy,
+                                     int KH, int KW, int stride, int pad_t, int pad_l, int arith, int* family, int* splits, size_t* workspace_bytes) {
+    const WgradCall c{{x, dy, nullptr, N, Hi, Wi, Cin, ldx, Ho, Wo, Cout, lddy, KH, KW, stride, pad_t, pad_l}, arith, WG_F32};
+    if (!family || !splits || !workspace_bytes || !wgrad_args_ok(c)) return KPX_EINVAL;
+    const WgradPlan p = wgrad_plan(c);
+    *family = p.family; *splits = p.S; *workspace_bytes = p.need;
+    return 0;
+}
+
+// The workspace of any of the three entries for a layer of this shape.  Unknown here: the operands' layout and the stride (1, or 2 with
+// Hi = Ho * 2); 3x3 filters are asked with the SAME padding of the Winograd weight gradient.
+extern "C" size_t kpx_conv2d_wgrad_workspace_bytes(int N, int Ho, int Wo, int Cin, int Cout, int KH, int KW) {
+    auto need = [&](int st) { return wgrad_plan({{nullptr, nullptr, nullptr, N, Ho * st, Wo * st, Cin, Cin, Ho, Wo, Cout, Cout, KH, KW, st, 1, 1}, 0, WG_F32}).need; };
+    return std::max(need(1), need(2));
 }

@@ -230,7 +230,7 @@ static void wsmall_geom(int variant, int N, int Hi, int Wi, int ldx, int Ho, int
 extern "C" __attribute__((visibility("hidden"))) int kpx_wsmall_splits(int N, int Hi, int Wi, int Cin, int Ho, int Wo, int Cout, int KH, int KW, int stride) {
     const int variant = wsmall_variant(Cin, Cout, KH, KW, stride);
     if (!variant || (long)N * Ho * Wo < 32768) return 0;
-    if ((size_t)N * Hi * Wi * (size_t)((Cin + 3) & ~3) * 4 >= 0x60000000ull || (size_t)N * Ho * Wo * (size_t)((Cout + 3) & ~3) * 4 >= 0x60000000ull) return 0;   // 32-bit byte offsets in the kernel
+    if (!kpx_offsets_fit((size_t)N * Hi * Wi, (Cin + 3) & ~3, 0x60000000ull) || !kpx_offsets_fit((size_t)N * Ho * Wo, (Cout + 3) & ~3, 0x60000000ull)) return 0;
     WsmallGeom g{}; int lds, threads;
     wsmall_geom(variant, N, Hi, Wi, Cin, Ho, Wo, Cout, Cout, KH, KW, stride, 0, 0, Cin, &g, &lds, &threads);
     // persistent workgroups: as many as are resident at once (LDS and, at ~200 VGPRs, two wavefronts per SIMD), at least 2 tiles each

@@ -4,6 +4,9 @@
 #pragma once
 #include "conv_geom.h"
 
+// 32-bit byte offsets into an fp32 tensor: `pixels` pixels at a stride of `ld` floats end below `limit`, which each kernel family keeps as it was written.
+static inline bool kpx_offsets_fit(size_t pixels, size_t ld, size_t limit) { return pixels * ld * 4 < limit; }
+
 // conv_gemm3.hip: the gather convolution / weight gradient on the bf16 matrix pipe with fp32 operands split into three bf16 terms
 extern "C" __attribute__((visibility("hidden"))) int kpx_gemm3_eligible(const ConvGeom* g);
 extern "C" __attribute__((visibility("hidden"))) int kpx_gemm3_launch(ConvGeom g, int bt, int terms, hipStream_t s);
