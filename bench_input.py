@@ -1,7 +1,12 @@
 """Throughput of the image-pair input pipeline (kpx_amd.data) on Penn-Action-sized synthetic JPEG frames (480x270):
 pairs/s of the threaded decode + augment + pinned H2D + on-device conversion -- or, with --resident, of the HIP augmentation on frames
 kept in HBM -- alone and feeding the train step, next to the same train-step loop on ONE fixed device batch of the same process.
-Every window is warmed up and at least a second long.  KPX_DTYPE=bf16 selects the bf16 configuration as everywhere."""
+Every window is warmed up and at least a second long.  KPX_DTYPE=bf16 selects the bf16 configuration as everywhere.
+
+--motion measures stage 2 instead (kpx_amd.data.SequenceDataLoader, K = 40 pseudo labels on 480x270 videos of 40 / 70 / 100 frames, the
+motion generator at the reference's size): sequences/s at batch 16 and 64 of the loader alone -- the host threads, or with --resident
+the key-point kernel on labels kept in HBM -- of the train step on one fixed device batch, and of the train step fed by the loader.
+Run it once without and once with --resident in the same session to compare the two loaders."""
 import argparse, io, os, sys, tempfile, time
 import numpy as np
 import torch
@@ -22,6 +27,69 @@ def make_dataset(root, videos=8, frames=40, w=480, h=270):
         f.write(''.join('%04d 0\n' % v for v in range(videos)))
 
 
+def make_motion_dataset(root, videos=12, lengths=(40, 70, 100), k=40, n_action=9, w=480, h=270):
+    """Penn-shaped stage-2 data: frames/NNNN/*.jpg (eight distinct pictures per video, repeated), pseudo_labels/NNNN.npy float32 [len, k, 2];
+    40 / 70 / 100 frames give SequenceDataLoader's gap 1 / 2 / 3."""
+    rs = np.random.RandomState(0)
+    os.makedirs(os.path.join(root, 'pseudo_labels'))
+    lines = []
+    for v in range(videos):
+        n, name = lengths[v % len(lengths)], 'frames/%04d' % (v + 1)
+        os.makedirs(os.path.join(root, name))
+        low = rs.rand(h // 16 + 2, w // 16 + 2, 3)
+        bg = np.asarray(Image.fromarray((low * 255).astype(np.uint8)).resize((w, h), Image.BILINEAR)).astype(np.float32)
+        jpegs = []
+        for i in range(8):
+            buf = io.BytesIO()
+            Image.fromarray(np.clip(bg + rs.randn(h, w, 3) * 6 + 4 * i, 0, 255).astype(np.uint8)).save(buf, format='JPEG', quality=90)
+            jpegs.append(buf.getvalue())
+        for i in range(n):
+            with open(os.path.join(root, name, '%06d.jpg' % (i + 1)), 'wb') as f:
+                f.write(jpegs[i % 8])
+        np.save(os.path.join(root, 'pseudo_labels', '%04d.npy' % (v + 1)), (rs.rand(n, k, 2) * 1.6 - 0.8).astype(np.float32))
+        lines.append('%s %d\n' % (name, v % n_action))
+    with open(os.path.join(root, 'train_set.txt'), 'w') as f:
+        f.write(''.join(lines))
+
+
+def motion(a):
+    """The --motion mode: every figure in sequences/s, batch 16 then 64."""
+    import kpx_amd
+    dev = torch.device('cuda', 0)
+    k, n_action = 40, 9
+    what = 'resident labels' if a.resident else 'CPU pipeline, %d threads' % a.threads
+    with tempfile.TemporaryDirectory() as root:
+        make_motion_dataset(root, k=k, n_action=n_action)
+        for b in (16, 64):
+            loader = kpx_amd.SequenceDataLoader(root, 'train', n_points=k, n_action=n_action, random_order=True, randomness=True)
+            if a.resident:
+                t0 = time.perf_counter()
+                store = loader.resident_labels(dev)
+                torch.cuda.synchronize()
+                print('resident label store: %d videos, %d bytes read and copied in %.3f s'
+                      % (len(store.index.names), store.index.labels.nbytes, time.perf_counter() - t0))
+            it = iter(loader.batches(b, dev, repeat=True, num_preprocess_threads=a.threads, resident=a.resident))
+            for _ in range(3): next(it)
+            print('stage-2 loader alone (%s): %.0f sequences/s (batch %d)' % (what, timed(lambda i: next(it), b, a.batches), b))
+            cfg = {'training': {'lr': {'start_val': 1e-4, 'step': 20000, 'decay': 0.95}, 'batch_size': b},
+                   'model': {'n_pts': k, 'n_action': n_action, 'cell_info': [1024, 1024], 'vae_dim': 64}, 'paths': {'log_dir': '/tmp/kpx_motion'}}
+            model = kpx_amd.MotionGeneratorModel(cfg, device=dev); model.build()
+            fixed = {key: v.clone() for key, v in next(it).items() if key != 'image'}
+            steps = [0]
+
+            def fed(i):
+                model.train_step(None, next(it), steps[0], b); steps[0] += 1
+
+            def on_fixed(i):
+                model.train_step(None, fixed, steps[0], b); steps[0] += 1
+            for i in range(3): fed(i)
+            for rep in range(2):                       # alternated: the spread between the repetitions is the noise of this session
+                for i in range(3): on_fixed(i)
+                print('stage-2 train step on one fixed device batch [%d]: %.0f sequences/s (batch %d)' % (rep, timed(on_fixed, b, a.batches), b))
+                for i in range(3): fed(i)
+                print('stage-2 train step fed by the loader (%s) [%d]: %.0f sequences/s (batch %d)' % (what, rep, timed(fed, b, a.batches), b))
+
+
 def timed(step, batch, batches, min_seconds=1.0):
     """pairs/s of ``step(i)`` over a window of at least ``batches`` calls and ``min_seconds`` (the caller has warmed up)."""
     n = 0
@@ -37,7 +105,11 @@ def main():
     ap.add_argument('--threads', type=int, default=12); ap.add_argument('--train', action='store_true')
     ap.add_argument('--resident', action='store_true', help='frames decoded once into HBM, augmentation in HIP (batches(resident=True))')
     ap.add_argument('--frames', type=int, default=40, help='frames per synthetic video (8 videos)')
+    ap.add_argument('--motion', action='store_true', help='stage 2: the sequence loader and the motion generator step (batch 16 and 64); '
+                                                          'with --resident the key-point labels are kept in HBM')
     a = ap.parse_args()
+    if a.motion:
+        return motion(a)
     import kpx_amd
     dev = torch.device('cuda', 0)
     with tempfile.TemporaryDirectory() as root:

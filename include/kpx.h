@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 11
+#define KPX_ABI_VERSION 12
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -533,6 +533,40 @@ int kpx_augment_geometry_u8(const unsigned char* frames, const int64_t* frame_of
                             const int32_t* resize_tabs, int band_rows_cap, unsigned char* tiles, int32_t* lsum, void* stream);
 int kpx_augment_filter_f32(const unsigned char* tiles, const int32_t* lsum, const int32_t* rows, int n_rows, const float* kernels,
                            float* out, void* stream);
+
+/* ---- The key-point half of the sequence loader on pseudo labels resident in HBM (ABI 12): what SequenceDataLoader.render does to the
+ *      key points with numpy (data/sequence_dataloader.py:105-198: gather 33 sets, rotate, flip, scale; the one-hot action code),
+ *      bit for bit, from a table of per-sample decisions the host draws (kpx_amd/resident.py).  One launch per batch.
+ *
+ *   labels     one flat float32 buffer: every stored video's pseudo-label array [len_v][n_points][2], one after the other
+ *   label_off  label_off[v] = element offset of video v's array in `labels`
+ *   rows       [n_rows][KPX_SEQ_ROW_INTS] int32, one row per sample:
+ *                0 video number      1 im_idx (label row of the start frame)
+ *                2 gap: >= 1 reads the rows im_idx + gap * i, i = 0..32, and computes in float32; 0 is the short-video form, rows
+ *                  im_idx .. im_idx + 16 with every odd entry the float32 mean of its neighbours, then float64 arithmetic rounded once
+ *                3 flags (KPX_SEQ_ROTATE | KPX_SEQ_FLIP | KPX_SEQ_SCALE): an operation whose flag is set is PERFORMED, also for angle 0 and
+ *                  scale 1.0 (the host does, and it decides signs of zero); none set: the gathered values pass through
+ *                4 the angle's index into `trig` (angle + 15)
+ *                5 / 6 low and high 32 bits of the scale, a double (randint(70, 120) / 100.0 on the host)
+ *                7 action index: action_code[row] is its one-hot vector
+ *   trig       [KPX_SEQ_ANGLES][2] double: cos and sin of radians(-angle), angle = -15..15, from the host's libm
+ *   keypoints  float32 [n_rows][n_points][2] (set 0), real_seq float32 [n_rows][32][n_points][2] (sets 1..32),
+ *   action_code float32 [n_rows][n_action]
+ *
+ * No product or sum is fused and nothing but the halving of the short form divides.  The kernel trusts the table: the HOST rejects, before
+ * the launch, a video number outside the store, im_idx + 32 * gap (or im_idx + 16) beyond the video's label rows, an angle index outside
+ * 0..30, an action index outside 0..n_action-1 and more than KPX_SEQ_MAX_ROWS rows (kpx_amd.resident.SequencePlanner.check_rows). */
+#define KPX_SEQ_ROW_INTS 8
+#define KPX_SEQ_ROTATE 1
+#define KPX_SEQ_FLIP 2
+#define KPX_SEQ_SCALE 4
+#define KPX_SEQ_LEN 33
+#define KPX_SEQ_ANGLES 31
+#define KPX_SEQ_MAX_ROWS 4096
+#define KPX_SEQ_MAX_POINTS 256
+#define KPX_SEQ_MAX_ACTIONS 256
+int kpx_keypoint_seq_augment_f32(const float* labels, const int64_t* label_off, const int32_t* rows, int n_rows, int n_points,
+                                 int n_action, const double* trig, float* keypoints, float* real_seq, float* action_code, void* stream);
 
 #ifdef __cplusplus
 }

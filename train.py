@@ -9,7 +9,9 @@ sequence VAE-GAN over the pseudo labels written by make_pseudo_labels.py).  With
 reference's data/image_pair_dataloader.py + tf.data pipeline: threaded PIL augmentation, uint8 batches in pinned memory, async
 copy + on-device conversion); ``--synthetic`` feeds Penn-shaped random pairs with the same output contract (float32 NHWC in
 [-1,1], keys image / future_image).  ``--resident-data`` (detector_translator) decodes every frame of both subsets once into HBM and augments on the
-GPU (kpx_amd.resident): the same batches bit for bit, without the per-step JPEG decoding.
+GPU (kpx_amd.resident): the same batches bit for bit, without the per-step JPEG decoding.  ``--resident-labels`` (motion_generator) keeps
+every video's pseudo labels in HBM and builds each key-point batch with one HIP launch: the same batches bit for bit, with no file read,
+PIL call or numpy work per step; the start frames, which only the image summary shows, are rendered for its two samples alone.
 """
 import logging
 import os
@@ -59,10 +61,17 @@ def _train_motion_generator(args, config, dev, rank, world):
         random.seed(1000 + rank); np.random.seed(1000 + rank)
         mk = lambda subset, train: kpx_amd.SequenceDataLoader(paths_config['data_dir'], subset, n_points=k, n_action=a,
                                                               random_order=train, randomness=train)
-        train_it = mk('train', True).batches(batch_size, dev, repeat=True)
+        train_it = mk('train', True).batches(batch_size, dev, repeat=True, resident=args.resident_labels)
         if os.path.exists(os.path.join(str(paths_config['data_dir']), 'test_set.txt')):
             test_loader = mk('test', False)
-            test_batches = lambda: test_loader.batches(batch_size, dev, repeat=False)
+            test_batches = lambda: test_loader.batches(batch_size, dev, repeat=False, resident=args.resident_labels)
+
+    def test_feeds(it):
+        """The batches of one test pass; the resident iterator has no 'image', so the batch the summary is written from gets its two."""
+        for i, f in enumerate(it):
+            if i == 0 and args.resident_labels:
+                f = dict(f, image=it.start_images(2))
+            yield f
 
     def synthetic(seed):
         rs = np.random.RandomState(seed)
@@ -73,12 +82,15 @@ def _train_motion_generator(args, config, dev, rank, world):
     print('training start')
     for step in range(model.global_step, n_steps):
         feed = next(train_it) if train_it is not None else synthetic(step * world + rank)
+        should_write_summary = _should_write_summary(train_config, step, rank)
+        if args.resident_labels and should_write_summary:
+            feed = dict(feed, image=train_it.start_images(2))
         model.train_step(None, feed, step, batch_size, should_write_log=step % train_config['log_interval'] == 0 and rank == 0,
-                         should_write_summary=_should_write_summary(train_config, step, rank))
+                         should_write_summary=should_write_summary)
         if step % train_config['checkpoint_interval'] == 0 and rank == 0:
             model.save_checkpoint(None, step, fmt=args.ckpt_format)
         if step % train_config['test_interval'] == 0 and rank == 0:
-            feeds = test_batches() if test_batches is not None else [synthetic(10 ** 6)]
+            feeds = test_feeds(test_batches()) if test_batches is not None else [synthetic(10 ** 6)]
             model.collect_test_results([model.test_step(None, f, step, i, f['keypoints'].shape[0]) for i, f in enumerate(feeds)], step)
     model.close_loggers()
     if world > 1:
@@ -99,6 +111,9 @@ def main(argv=None):
     parser.add_argument('--resident-data', action='store_true',
                         help='detector_translator: decode every frame once, keep the frames in HBM and augment with HIP kernels '
                              '(ImagePairDataLoader.batches(resident=True)); the same batches as without the flag')
+    parser.add_argument('--resident-labels', action='store_true',
+                        help='motion_generator: keep the pseudo labels of every listed video in HBM and build each key-point batch with '
+                             'one HIP launch (SequenceDataLoader.batches(resident=True)); the same batches and summaries as without the flag')
     parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
     parser.add_argument('--steps', type=int, default=None, help='override training.n_steps')
     parser.add_argument('--ckpt-format', choices=['npz', 'tf', 'bundle'], default=os.environ.get('KPX_CKPT_FORMAT', 'npz'),
@@ -113,6 +128,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.resident_data and (args.mode != 'detector_translator' or args.synthetic):
         parser.error('--resident-data keeps JPEG frames in HBM: the motion_generator mode reads key-point files and --synthetic reads no frames')
+    if args.resident_labels and (args.mode != 'motion_generator' or args.synthetic):
+        parser.error('--resident-labels keeps pseudo labels in HBM: the detector_translator mode reads frames (see --resident-data) and '
+                     '--synthetic reads no label files')
     logging.basicConfig(level=logging.INFO, format='%(message)s')
 
     config = load_config(args.config)

@@ -19,7 +19,10 @@ What is different from the reference's tf.data graph:
 * ``shuffle(2000)`` of the reference acts on an i.i.d. stream when ``random_order`` is set (a no-op in distribution); for
   sequential order a plan-level shuffle buffer of the same size is kept, so nothing bigger than indices is buffered;
 * ``batches(..., resident=True)`` (kpx_amd/resident.py): the subset's frames are decoded ONCE into HBM and every batch is produced there by
-  two HIP launches that repeat ``render``'s PIL arithmetic byte for byte, from the same ``PairPlan``s -- no JPEG decoding per step.
+  two HIP launches that repeat ``render``'s PIL arithmetic byte for byte, from the same ``PairPlan``s -- no JPEG decoding per step;
+* ``SequenceDataLoader.batches(..., resident=True)`` likewise keeps stage 2's pseudo labels in HBM: one HIP launch per batch repeats
+  ``render``'s numpy arithmetic on the key points bit for bit, and the start frame -- which the motion generator never reads -- is rendered
+  only on request (``start_images``), for the samples an image summary shows.
 """
 import os
 import os.path as osp
@@ -410,6 +413,13 @@ class SequenceDataLoader(_ListedVideos):
         self._with_image_seq, self._random_order, self._randomness = with_image_seq, random_order, randomness
         self._rng = rng if rng is not None else _random
         self._np_rng = np_rng if np_rng is not None else np.random
+        self._labels = None            # resident.LabelIndex once attached: plan() reads frame counts from it
+        self._label_store = None       # resident.ResidentLabels, built by the first batches(..., resident=True)
+
+    def _n_frames(self, video):
+        if self._labels is not None:
+            return self._labels.count(video)
+        return super(SequenceDataLoader, self)._n_frames(video)
 
     def get_sample_shape(self):
         d = {'image': [IMAGE_SIZE, IMAGE_SIZE, 3], 'keypoints': [self.n_points, 2],
@@ -451,13 +461,29 @@ class SequenceDataLoader(_ListedVideos):
             scale = rng.randint(70, 120) / 100.0
         return SeqPlan(idx, video, n, im_idx, angle, flip, scale)
 
+    def _start_frame(self, plan):
+        """-> (the start frame as ``render`` delivers it: rotated, centre-cropped to 128 x 128, flipped; resized size; crop box)"""
+        image = self._frame(plan.video, plan.im_idx)
+        if self._randomness:
+            image = image.rotate(plan.angle)
+        w, h = image.size
+        box, ratio = center_crop_box(w, h)
+        size = [int(w / ratio), int(h / ratio)]
+        image = image.resize(size).crop(box)
+        if self._randomness and plan.flip:
+            image = image.transpose(Image.FLIP_LEFT_RIGHT)
+        return image, size, box
+
+    def render_start_image(self, plan):
+        """-> uint8 [128,128,3]: ``render(plan)['image']`` alone, without reading the key points"""
+        return np.asarray(self._start_frame(plan)[0])
+
     def render(self, plan):
         """-> dict with uint8 'image' (and 'real_im_seq'), float 'keypoints' / 'real_seq' / 'action_code' (before the /255)."""
         video, n, im_idx = plan.video, plan.n_files, plan.im_idx
         action_idx = self._images[plan.index].split()[1]
         keypoints = np.load(osp.join(self._data_dir, video.replace('frames', 'pseudo_labels') + '.npy'))
         gap = int(n / N_SEQUENCE_LEN)
-        image = self._frame(video, im_idx)
         if gap >= 1:
             real_seq = keypoints[[im_idx + gap * i for i in range(N_SEQUENCE_LEN)], :, :]
         else:                                    # short video: every second entry is the mean of its neighbours (:126-136)
@@ -469,12 +495,8 @@ class SequenceDataLoader(_ListedVideos):
                 real_seq[i * 2 + 1] = (half[i] + half[i + 1]) / 2.0
             real_seq[-1] = half[-1]
         if self._randomness:
-            image = image.rotate(plan.angle)
             real_seq = rotate_keypoints(real_seq, plan.angle)
-        w, h = image.size
-        box, ratio = center_crop_box(w, h)
-        size = [int(w / ratio), int(h / ratio)]
-        image = image.resize(size).crop(box)
+        image, size, box = self._start_frame(plan)
         out = {}
         if self._with_image_seq:                 # the future frames start at frame gap (not im_idx + gap) and are never rotated / flipped (:152-171)
             n_future, twice = N_SEQUENCE_LEN - 1, False
@@ -488,7 +510,6 @@ class SequenceDataLoader(_ListedVideos):
                     seq.append(cur)
             out['real_im_seq'] = np.stack(seq)
         if self._randomness and plan.flip:
-            image = image.transpose(Image.FLIP_LEFT_RIGHT)
             real_seq[:, :, 0] *= -1
         label = np.zeros(self.n_action)
         label[int(action_idx)] = 1
@@ -505,9 +526,31 @@ class SequenceDataLoader(_ListedVideos):
                 s['real_im_seq'] = s['real_im_seq'] / 255.0
             yield s
 
-    def batches(self, batch_size, device, repeat=False, num_preprocess_threads=8):
-        """get_dataset(batch_size, ...) + map_fn: float32 tensors on ``device``; images in [-1,1] (converted on the GPU)."""
+    def batches(self, batch_size, device, repeat=False, num_preprocess_threads=8, resident=False):
+        """get_dataset(batch_size, ...) + map_fn: float32 tensors on ``device``; images in [-1,1] (converted on the GPU).
+
+        ``resident=True`` (kpx_amd.resident, needs a GPU ``device`` and a loader without ``with_image_seq``): the pseudo labels of every
+        listed video are kept in HBM (built on first use, kept on the loader) and each batch is one HIP launch -- the same 'keypoints',
+        'real_seq' and 'action_code' bit for bit, from the same draws of ``rng`` / ``np_rng``, and NO 'image': the iterator's
+        ``start_images(n)`` renders the start frames of the latest batch's first ``n`` samples for an image summary."""
+        if resident:
+            from .resident import ResidentSeqBatcher
+            return ResidentSeqBatcher(self, batch_size, device, repeat)
+        return self._host_batches(batch_size, device, repeat, num_preprocess_threads)
+
+    def resident_labels(self, device):
+        """The loader's label store on ``device``, read on first use; plan() takes frame counts from it from then on."""
         import torch
+        from .resident import ResidentLabels
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if self._label_store is None or self._label_store.device != device:
+            self._label_store = ResidentLabels(self._data_dir, self._images, self.n_points, self.n_action, device)
+            self._labels = self._label_store.index
+        return self._label_store
+
+    def _host_batches(self, batch_size, device, repeat, num_preprocess_threads):
         pool = ThreadPoolExecutor(max_workers=max(1, num_preprocess_threads))
         try:
             while True:

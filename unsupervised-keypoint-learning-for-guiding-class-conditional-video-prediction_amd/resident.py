@@ -14,6 +14,9 @@ Everything of Pillow's arithmetic that involves double precision is done HERE, i
 
 tests/test_resident_cpu.py applies these tables in numpy and compares with PIL itself; tests/test_resident_gpu.py compares the kernels'
 output with ``render``.  There is no fallback: ``resident=True`` on a CPU device raises ``KpxError``.
+
+The second half of the file is stage 2's counterpart (csrc/augment_seq.hip, ABI 12): ``SequenceDataLoader.batches(..., resident=True)`` keeps
+the pseudo labels of every listed video in HBM and produces the key-point batches of ``SequenceDataLoader.render`` with one launch each.
 """
 import math
 import os
@@ -23,7 +26,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 from PIL import Image
 
-from .data import IMAGE_SIZE, _KERNEL_FILTERS, _DeviceBatcher, _resized_size
+from .data import IMAGE_SIZE, _KERNEL_FILTERS, _DeviceBatcher, _resized_size, _to_device_unit
 
 # mirrors of include/kpx.h (tests/test_resident_cpu.py holds them equal to the header)
 ROW_INTS, FLIP, ROTATE, IDENTITY = 24, 1, 2, 4
@@ -453,3 +456,219 @@ class ResidentBatcher(object):
             self.copied[slot].record()
             both = self.store.augment(rows_dev, 2 * n).view(2, n, IMAGE_SIZE, IMAGE_SIZE, 3)
         return {'image': both[0], 'future_image': both[1]}
+
+
+# ================================================================================================ stage 2: resident key-point labels
+# csrc/augment_seq.hip, include/kpx.h ABI 12.  ``SequenceDataLoader.batches(..., resident=True)`` keeps every listed video's pseudo-label
+# array in one flat float32 device buffer and produces {'keypoints', 'real_seq', 'action_code'} with ONE launch per batch -- the floats
+# ``SequenceDataLoader.render`` + ``_collate`` produce, bit for bit.  The start frame, which the model never reads, is not produced;
+# ``start_images`` renders it on the host for the two samples an image summary shows.  Cosine, sine and the scale are Python floats
+# computed here (``seq_trig``; ``plan.scale``) and reach the kernel as doubles: the device runs no transcendental and no division.
+
+# mirrors of include/kpx.h (tests/test_resident_seq_cpu.py holds them equal to the header)
+SEQ_ROW_INTS, SEQ_ROTATE, SEQ_FLIP, SEQ_SCALE = 8, 1, 2, 4
+SEQ_LEN, SEQ_ANGLES, SEQ_MAX_ROWS, SEQ_MAX_POINTS, SEQ_MAX_ACTIONS = 33, 31, 4096, 256, 256
+S_VIDEO, S_IM_IDX, S_GAP, S_FLAGS, S_ANGLE, S_SCALE_LO, S_SCALE_HI, S_ACTION = range(8)
+SEQ_ANGLE_MIN = -15                # plan(): randrange(-15, 16); the angle's index into the trig table is angle - SEQ_ANGLE_MIN
+SEQ_SHORT = (SEQ_LEN - 1) // 2 + 1      # label rows the short-video form (gap 0) reads
+
+
+def seq_trig():
+    """float64 [SEQ_ANGLES, 2]: cos and sin of radians(-angle) for angle = -15..15, the expressions of data.rotate_keypoints."""
+    return np.array([[math.cos(math.radians(-a)), math.sin(math.radians(-a))] for a in range(SEQ_ANGLE_MIN, SEQ_ANGLE_MIN + SEQ_ANGLES)],
+                    np.float64)
+
+
+def label_path(data_dir, video):
+    return osp.join(data_dir, video.replace('frames', 'pseudo_labels') + '.npy')
+
+
+class LabelIndex(object):
+    """Which videos a label store holds: per video its frame count (what ``SequenceDataLoader._n_frames`` lists), its label rows and the
+    element offset of its array in the flat buffer ``labels``; per line of the listing its action index.  Host only."""
+
+    def __init__(self, names, counts, arrays, actions, n_points):
+        self.names, self.n_points = list(names), int(n_points)
+        if not 1 <= self.n_points <= SEQ_MAX_POINTS:
+            raise _error('n_points = %d, the key-point kernel takes 1..%d' % (self.n_points, SEQ_MAX_POINTS))
+        self._video = {name: i for i, name in enumerate(self.names)}
+        self.n_frames = np.array(counts, np.int64).reshape(-1)
+        for name, n, a in zip(self.names, self.n_frames, arrays):
+            if a.dtype != np.float32 or a.ndim != 3 or a.shape[1:] != (self.n_points, 2):
+                raise _error('%s: pseudo labels %s %s, expected float32 [len, %d, 2]' % (name, a.dtype, a.shape, self.n_points))
+            if a.shape[0] < n:
+                raise _error('%s: %d label rows for %d frame files' % (name, a.shape[0], n))
+        self.label_rows = np.array([a.shape[0] for a in arrays], np.int64).reshape(-1)
+        self.offsets = np.concatenate([[0], np.cumsum(self.label_rows * self.n_points * 2)[:-1]]).astype(np.int64)
+        self.labels = np.concatenate([a.reshape(-1) for a in arrays]) if arrays else np.zeros(0, np.float32)
+        self.actions = [int(a) for a in actions]
+
+    @classmethod
+    def scan(cls, data_dir, listing, n_points):
+        """From the files: one ``os.listdir`` and one ``np.load`` per distinct video, in listing order."""
+        names = []
+        for line in listing:
+            v = line.split()[0]
+            if v not in names:
+                names.append(v)
+        counts = [len(os.listdir(osp.join(data_dir, v))) for v in names]
+        arrays = [np.load(label_path(data_dir, v)) for v in names]
+        return cls(names, counts, arrays, [line.split()[1] for line in listing], n_points)
+
+    def video(self, name):
+        return self._video[name]
+
+    def count(self, name):
+        return int(self.n_frames[self._video[name]])
+
+    def array(self, name):
+        v = self._video[name]
+        o = int(self.offsets[v])
+        return self.labels[o:o + int(self.label_rows[v]) * self.n_points * 2].reshape(-1, self.n_points, 2)
+
+
+class SequencePlanner(object):
+    """Table rows (include/kpx.h: kpx_keypoint_seq_augment_f32) from ``SeqPlan``s or by hand, and their validation.  Host only."""
+
+    def __init__(self, index, n_action):
+        self.index, self.n_action = index, int(n_action)
+        if not 1 <= self.n_action <= SEQ_MAX_ACTIONS:
+            raise _error('n_action = %d, the key-point kernel takes 1..%d' % (self.n_action, SEQ_MAX_ACTIONS))
+
+    def row(self, video, im_idx, gap, action, angle=None, flip=0, scale=None):
+        """One table row.  ``angle`` None: no rotation, ``scale`` None: no scaling (the loader without ``randomness``); an angle of 0 and a
+        scale of 1.0 ARE performed, as ``render`` performs them."""
+        flags = (SEQ_ROTATE if angle is not None else 0) | (SEQ_FLIP if flip else 0) | (SEQ_SCALE if scale is not None else 0)
+        lo, hi = np.array([1.0 if scale is None else scale], np.float64).view(np.int32)        # little endian: low word first
+        return [self.index.video(video), im_idx, gap, flags, 0 if angle is None else angle - SEQ_ANGLE_MIN, int(lo), int(hi), action]
+
+    def rows_for_plans(self, plans):
+        """int32 [len(plans), SEQ_ROW_INTS]; a plan drawn without ``randomness`` (angle None) sets no flag."""
+        rows = [self.row(p.video, p.im_idx, int(p.n_files / SEQ_LEN), self.index.actions[p.index], p.angle, p.flip, p.scale) for p in plans]
+        return np.array(rows, np.int64).astype(np.int32).reshape(-1, SEQ_ROW_INTS)
+
+    def check_rows(self, rows):
+        """Raises ``KpxError`` for a row the kernel cannot take; it trusts the table and clamps nothing."""
+        rows = np.asarray(rows)
+        if rows.dtype != np.int32 or rows.ndim != 2 or rows.shape[1] != SEQ_ROW_INTS or not 0 < rows.shape[0] <= SEQ_MAX_ROWS:
+            raise _error('key-point rows: int32 [1..%d, %d] expected, got %s %s' % (SEQ_MAX_ROWS, SEQ_ROW_INTS, rows.dtype, rows.shape))
+        idx = self.index
+        video = rows[:, S_VIDEO].astype(np.int64)
+        if (video < 0).any() or (video >= len(idx.names)).any():
+            raise _error('key-point rows: video number outside the store (0..%d)' % (len(idx.names) - 1))
+        im_idx, gap = rows[:, S_IM_IDX].astype(np.int64), rows[:, S_GAP].astype(np.int64)
+        last = np.where(gap >= 1, im_idx + (SEQ_LEN - 1) * gap, im_idx + SEQ_SHORT - 1)
+        if (im_idx < 0).any() or (gap < 0).any() or (last >= idx.label_rows[video]).any():
+            raise _error("key-point rows: the sequence leaves its video's label rows")
+        if (rows[:, S_FLAGS] & ~(SEQ_ROTATE | SEQ_FLIP | SEQ_SCALE)).any():
+            raise _error('key-point rows: unknown flag')
+        if (rows[:, S_ANGLE] < 0).any() or (rows[:, S_ANGLE] >= SEQ_ANGLES).any():
+            raise _error('key-point rows: angle index outside 0..%d' % (SEQ_ANGLES - 1))
+        if (rows[:, S_ACTION] < 0).any() or (rows[:, S_ACTION] >= self.n_action).any():
+            raise _error('key-point rows: action index outside 0..%d' % (self.n_action - 1))
+        return rows
+
+
+class ResidentLabels(SequencePlanner):
+    """Every listed video's pseudo labels in ONE flat float32 device buffer, with the offsets and the trig table beside it."""
+
+    def __init__(self, data_dir, listing, n_points, n_action, device):
+        import torch
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _error('resident labels live in HBM: device %s is not a GPU (the package has no CPU fallback)' % device)
+        super(ResidentLabels, self).__init__(LabelIndex.scan(data_dir, listing, n_points), n_action)      # raises before anything is allocated
+        self.device = device
+        self.labels = torch.from_numpy(self.index.labels).to(device)
+        self.label_off = torch.from_numpy(self.index.offsets).to(device)
+        self.trig = torch.from_numpy(seq_trig()).to(device)
+
+    def augment(self, rows_dev, n_rows):
+        """The launch on the current stream: rows_dev = DEVICE int32 [>= n_rows, SEQ_ROW_INTS] (validated by the caller with
+        ``check_rows``) -> {'keypoints' [n,K,2], 'real_seq' [n,32,K,2], 'action_code' [n,A]} float32."""
+        import torch
+        from ._lib import lib, check
+        k, a = self.index.n_points, self.n_action
+        with torch.cuda.device(self.device):
+            out = {'keypoints': torch.empty((n_rows, k, 2), dtype=torch.float32, device=self.device),
+                   'real_seq': torch.empty((n_rows, SEQ_LEN - 1, k, 2), dtype=torch.float32, device=self.device),
+                   'action_code': torch.empty((n_rows, a), dtype=torch.float32, device=self.device)}
+            check(lib.kpx_keypoint_seq_augment_f32(self.labels.data_ptr(), self.label_off.data_ptr(), rows_dev.data_ptr(), n_rows, k, a,
+                                                   self.trig.data_ptr(), out['keypoints'].data_ptr(), out['real_seq'].data_ptr(),
+                                                   out['action_code'].data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+                  'kpx_keypoint_seq_augment_f32')
+        return out
+
+    def augment_rows(self, rows):
+        """Host rows (``row`` / ``rows_for_plans``) -> the batch: validation, upload, the launch."""
+        import torch
+        rows = self.check_rows(np.ascontiguousarray(rows))
+        return self.augment(torch.from_numpy(rows).to(self.device), rows.shape[0])
+
+
+class ResidentSeqBatcher(object):
+    """``SequenceDataLoader.batches(..., resident=True)``: the host iterator's batching (``batch_size`` plans of a pass, a short batch at
+    the end of every pass, passes repeated with ``repeat``) on a ``ResidentLabels`` store, from the same ``plans()``.  Per batch one pinned
+    int32 table goes to the device asynchronously and one launch is enqueued on the consumer's stream; the host never waits for the device."""
+    SLOTS = 4
+
+    def __init__(self, loader, batch_size, device, repeat):
+        import torch
+        self._torch = torch
+        self.loader, self.batch_size, self.repeat = loader, batch_size, repeat
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise _error('resident=True needs a GPU device, got %s (the package has no CPU fallback)' % self.device)
+        if loader._with_image_seq:
+            raise _error('resident=True yields key points only: a loader with_image_seq=True needs the host path')
+        if batch_size > SEQ_MAX_ROWS:
+            raise _error('batch_size %d, the key-point kernel takes %d rows' % (batch_size, SEQ_MAX_ROWS))
+        self.store = loader.resident_labels(self.device)
+        self.host = [torch.empty((batch_size, SEQ_ROW_INTS), dtype=torch.int32).pin_memory() for _ in range(self.SLOTS)]
+        self.copied = [None] * self.SLOTS          # per pinned slot: event after its last H2D copy
+        self._slot = 0
+        self._chunks = self._chunk_stream()
+        self._last = []
+
+    def _chunk_stream(self):
+        while True:
+            chunk = []
+            for plan in self.loader.plans():
+                chunk.append(plan)
+                if len(chunk) == self.batch_size:
+                    yield chunk
+                    chunk = []
+            if chunk:
+                yield chunk
+            if not self.repeat:
+                break
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        torch = self._torch
+        plans = next(self._chunks)
+        n = len(plans)
+        rows = self.store.check_rows(self.store.rows_for_plans(plans))
+        slot = self._slot
+        self._slot = (slot + 1) % self.SLOTS
+        if self.copied[slot] is not None:
+            self.copied[slot].synchronize()        # SLOTS batches ago: long complete
+        host = self.host[slot][:n]
+        host.numpy()[:] = rows
+        with torch.cuda.device(self.device):
+            rows_dev = host.to(self.device, non_blocking=True)
+            self.copied[slot] = torch.cuda.Event()
+            self.copied[slot].record()
+            out = self.store.augment(rows_dev, n)
+        self._last = plans
+        return out
+
+    def start_images(self, n):
+        """float32 [n, 128, 128, 3] in [-1, 1] on the device: the start frames of the first ``n`` samples of the batch most recently
+        yielded, rendered on the host by the PIL code of ``render`` (what the host feed's 'image' holds for those samples)."""
+        plans = self._last[:n]
+        if not plans:
+            raise _error('start_images: no batch has been yielded yet')
+        return _to_device_unit(np.stack([self.loader.render_start_image(p) for p in plans]), self.device)
