@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 12
+#define KPX_ABI_VERSION 13
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -350,6 +350,35 @@ int kpx_frame_metrics_f32(const float* a, const float* b, int N, int H, int W, i
  * Added in ABI version 10. */
 size_t kpx_feature_pair_metrics_workspace_bytes(int N, int H, int W, int C);
 int kpx_feature_pair_metrics_f32(const float* fa, const float* fb, int N, int H, int W, int C, float* work, float* out, void* stream);
+
+/* ---- motion metrics (evaluate.py --motion-metrics), DESIGN.md section 2: how far the D draws of z of one sample lie apart in the 8-bit
+ * frames, and the key-point error of each draw.  All three: no allocation, copy or synchronisation (capturable); no atomics; KPX_EINVAL
+ * before any device call for a null pointer (other than the optional outputs), a pointer that is not 4-byte aligned or an argument out of
+ * range.  Added in ABI version 13.
+ *
+ * kpx_draw_moments_add_f32: one draw into the accumulators.  Per value i < n, q = the 8-bit value of kpx_frame_metrics_f32's png8
+ *   (clamp(uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))), 0, 255), NaN -> 0): sum[i] += q, sumsq[i] += q * q (uint32, zeroed by the caller
+ *   before the first draw).  Exact for up to 4096 draws (65025 * 4096 < 2^32).  Element-wise; 16-byte accesses when x, sum and sumsq are all
+ *   16-byte aligned, 4-byte accesses otherwise -- the same bits either way.  n == 0 is a no-op.
+ *
+ * kpx_draw_diversity_f32: the accumulators of D draws of frames [N,H,W,C] (C in {1,3}, H and W in [1,1024], 2 <= D <= 4096, N >= 1).
+ *   Per value V = D * sumsq - sum^2 = sum over the pairs i < j of draws of (q_i - q_j)^2, in 64-bit integers; per frame S = sum of V (uint64,
+ *   exact: < 2^63 at the largest arguments).  div_mse[n] = fl32(double(S) / denom), denom = fl64(D (D - 1) / 2 * 65025) * fl64(H W C): the
+ *   mean over pairs of draws of the MSE between their 8-bit frames on the q / 255 scale.  std_map (uint8 [N,H,W], or NULL for none):
+ *   min(255, isqrt((4 * sum_c V) div (C * D^2))) = floor(2 sqrt(mean over channels of the population variance of q)), in 8-bit units, by an
+ *   exact integer square root.  One workgroup per frame; integer sums, so frame n's result does not depend on N, its position or the run.
+ *   Defined for accumulators that kpx_draw_moments_add_f32 filled with D draws (V >= 0); others wrap modulo 2^64.
+ *
+ * kpx_keypoint_draw_metrics_f32: pts fp32 [D,N,T,K,2] (the key points of D draws), real fp32 [N,T,K,2] (the labels), 1 <= D <= 4096,
+ *   N, T, K >= 1.  l2[d,n,t] = (1/K) sum_k |pts[d,n,t,k] - real[n,t,k]|_2 (fp32 [D,N,T]); div[n,t] = 2 / (D (D - 1) K) * sum_{i<j} sum_k
+ *   |pts[i,n,t,k] - pts[j,n,t,k]|_2 (fp32 [N,T], or NULL for none; must be NULL when D == 1).  Differences, squares, square roots and sums
+ *   in fp64, one chain per output in ascending (i, j, k), not contracted; the result rounded once to fp32.  Non-finite inputs propagate to
+ *   the outputs of their (d, n, t) / (n, t) alone. */
+int kpx_draw_moments_add_f32(const float* x, size_t n, uint32_t* sum, uint32_t* sumsq, void* stream);
+int kpx_draw_diversity_f32(const uint32_t* sum, const uint32_t* sumsq, int N, int H, int W, int C, int D, float* div_mse /*[N]*/,
+                           uint8_t* std_map /*[N,H,W] or NULL*/, void* stream);
+int kpx_keypoint_draw_metrics_f32(const float* pts /*[D,N,T,K,2]*/, const float* real /*[N,T,K,2]*/, int D, int N, int T, int K,
+                                  float* l2 /*[D,N,T]*/, float* div /*[N,T] or NULL*/, void* stream);
 
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */

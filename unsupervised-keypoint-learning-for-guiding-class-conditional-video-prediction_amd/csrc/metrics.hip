@@ -21,6 +21,15 @@
 // sum across positions are fp64.  A frame is cut into S slabs of positions, S a function of (H, W, C) alone: one workgroup per (slab, frame)
 // writes its two fp64 partials to `work`, a second launch folds a frame's slabs in order.  No atomics; frame n depends on frame n alone.
 // kpx_vgg_prep_png8_f32 is the VGG input of those frames: q - mean, BGR, of the same 8-bit quantisation.
+//
+// Motion metrics (evaluate.py --motion-metrics): how far the D draws of z of one sample lie apart, and the key-point error of each.
+//   - kpx_draw_moments_add_f32: per value of a rollout, sum += q and sumsq += q * q of its 8-bit value q (fm_png8), uint32, one call per
+//     draw: element-wise, 16 bytes per lane and array when the three pointers allow it.
+//   - kpx_draw_diversity_f32: V = D * sumsq - sum^2 = the sum over the D (D - 1) / 2 pairs of draws of (q_i - q_j)^2, an integer; one
+//     workgroup per frame sums V in uint64 (order-free, so exact and the same for every batch) and writes floor(2 sqrt(mean_c variance)) per
+//     pixel with an integer square root.
+//   - kpx_keypoint_draw_metrics_f32: one lane per (draw, sample, frame) for the error against the labels and one per (sample, frame) for the
+//     mean pairwise distance of the draws, each a single fp64 chain in a fixed order.
 #include "kpx_common.h"
 #include <cmath>
 
@@ -281,7 +290,153 @@ __global__ __launch_bounds__(256) void vgg_prep_png8_kernel(const float* __restr
     }
 }
 
+// ---------------------------------------------------------------------------------------------- motion metrics: draws of z
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int DM_THREADS = 256;
+constexpr int DM_MAX_BLOCKS = 4096;                                   // 16 workgroups per CU: grid-stride beyond that
+constexpr int DM_MAX_DRAWS = 4096;                                    // 255^2 * 4096 < 2^32: the accumulators cannot wrap
+
+template <bool VEC>
+__global__ __launch_bounds__(DM_THREADS) void draw_moments_add_kernel(const float* __restrict__ x, size_t n, uint32_t* __restrict__ sum,
+                                                                      uint32_t* __restrict__ sumsq) {
+    const size_t t0 = (size_t)blockIdx.x * DM_THREADS + threadIdx.x, stride = (size_t)gridDim.x * DM_THREADS;
+    const size_t nv = VEC ? n >> 2 : 0;                                // 16-byte groups; the rest (everything without VEC) is the scalar tail
+    for (size_t i = t0; i < nv; i += stride) {
+        const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+        u32x4 s = reinterpret_cast<const u32x4*>(sum)[i], ss = reinterpret_cast<const u32x4*>(sumsq)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t q = (uint32_t)fm_png8(v[e]);
+            s[e] += q;
+            ss[e] += q * q;
+        }
+        reinterpret_cast<u32x4*>(sum)[i] = s;
+        reinterpret_cast<u32x4*>(sumsq)[i] = ss;
+    }
+    for (size_t i = 4 * nv + t0; i < n; i += stride) {
+        const uint32_t q = (uint32_t)fm_png8(x[i]);
+        sum[i] += q;
+        sumsq[i] += q * q;
+    }
+}
+
+// floor(sqrt(m)), exactly: the fp64 estimate is off by at most one either way, the integer comparisons settle it (m < 2^62)
+__device__ __forceinline__ uint64_t dm_isqrt(uint64_t m) {
+    uint64_t r = (uint64_t)sqrt((double)m);
+    while (r * r > m) --r;
+    while ((r + 1) * (r + 1) <= m) ++r;
+    return r;
+}
+
+template <int C>
+__global__ __launch_bounds__(DM_THREADS) void draw_diversity_kernel(const uint32_t* __restrict__ sum, const uint32_t* __restrict__ sumsq, int P,
+                                                                    uint32_t D, double denom, float* __restrict__ div_mse,
+                                                                    uint8_t* __restrict__ std_map) {
+    __shared__ uint64_t red[DM_THREADS];
+    const int n = blockIdx.x, tid = threadIdx.x;
+    const uint32_t* s = sum + (size_t)n * P * C;
+    const uint32_t* ss = sumsq + (size_t)n * P * C;
+    const uint64_t per_pixel = (uint64_t)C * D * D;
+    uint64_t acc = 0;
+    for (int p = tid; p < P; p += DM_THREADS) {
+        uint64_t v = 0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const uint64_t a = s[(size_t)p * C + c];
+            v += (uint64_t)D * ss[(size_t)p * C + c] - a * a;
+        }
+        acc += v;
+        if (std_map) {
+            const uint64_t r = dm_isqrt(4 * v / per_pixel);
+            std_map[(size_t)n * P + p] = (uint8_t)(r > 255 ? 255 : r);
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int o = DM_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) div_mse[n] = (float)((double)red[0] / denom);
+}
+
+// |a - b| of two points in fp64, each operation rounded once (no fma: the float64 restatement has none)
+__device__ __forceinline__ double kd_dist(const float* __restrict__ a, const float* __restrict__ b) {
+#pragma clang fp contract(off)
+    const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1];
+    return sqrt(dx * dx + dy * dy);
+}
+
+__global__ __launch_bounds__(DM_THREADS) void keypoint_draw_metrics_kernel(const float* __restrict__ pts, const float* __restrict__ real, int D,
+                                                                           size_t NT, int K, float* __restrict__ l2, float* __restrict__ div) {
+    const size_t idx = (size_t)blockIdx.x * DM_THREADS + threadIdx.x;
+    const size_t roles = (size_t)D + (div ? 1 : 0);
+    if (idx >= roles * NT) return;
+    const size_t role = idx / NT, f = idx - role * NT;               // role < D: the error of draw `role`; role == D: the draws' diversity
+    const size_t frame = (size_t)K * 2;
+    if (role < (size_t)D) {
+        const float* p = pts + (role * NT + f) * frame;
+        const float* r = real + f * frame;
+        double acc = 0.0;
+        for (int k = 0; k < K; ++k) acc += kd_dist(p + 2 * k, r + 2 * k);
+        l2[role * NT + f] = (float)(acc / (double)K);
+        return;
+    }
+    double acc = 0.0;
+    for (int i = 0; i < D; ++i)
+        for (int j = i + 1; j < D; ++j) {
+            const float* a = pts + ((size_t)i * NT + f) * frame;
+            const float* b = pts + ((size_t)j * NT + f) * frame;
+            for (int k = 0; k < K; ++k) acc += kd_dist(a + 2 * k, b + 2 * k);
+        }
+    div[f] = (float)(acc * 2.0 / ((double)D * (double)(D - 1) * (double)K));
+}
+
 }  // namespace
+
+extern "C" int kpx_draw_moments_add_f32(const float* x, size_t n, uint32_t* sum, uint32_t* sumsq, void* stream) {
+    if (!x || !sum || !sumsq || ((((uintptr_t)x) | ((uintptr_t)sum) | ((uintptr_t)sumsq)) & 3)) return KPX_EINVAL;
+    if (n == 0) return 0;
+    const bool vec = ((((uintptr_t)x) | ((uintptr_t)sum) | ((uintptr_t)sumsq)) & 15) == 0;
+    const size_t items = vec ? (n + 3) >> 2 : n;                       // one per lane and pass (the tail of the 16-byte form has < 4 values)
+    const size_t blocks = (items + DM_THREADS - 1) / DM_THREADS;
+    const dim3 grid((unsigned)(blocks > DM_MAX_BLOCKS ? DM_MAX_BLOCKS : blocks));
+    hipStream_t s = kpx_stream(stream);
+    if (vec)
+        hipLaunchKernelGGL(draw_moments_add_kernel<true>, grid, dim3(DM_THREADS), 0, s, x, n, sum, sumsq);
+    else
+        hipLaunchKernelGGL(draw_moments_add_kernel<false>, grid, dim3(DM_THREADS), 0, s, x, n, sum, sumsq);
+    return kpx_launch_status();
+}
+
+extern "C" int kpx_draw_diversity_f32(const uint32_t* sum, const uint32_t* sumsq, int N, int H, int W, int C, int D, float* div_mse,
+                                      uint8_t* std_map, void* stream) {
+    if (!sum || !sumsq || !div_mse || N < 1 || H < 1 || H > 1024 || W < 1 || W > 1024 || !(C == 1 || C == 3) || D < 2 || D > DM_MAX_DRAWS ||
+        ((((uintptr_t)sum) | ((uintptr_t)sumsq) | ((uintptr_t)div_mse)) & 3))
+        return KPX_EINVAL;
+    const int P = H * W;
+    const double pairs = (double)((long long)D * (D - 1) / 2);
+    const double denom = (pairs * 65025.0) * (double)((long long)P * C);   // pairs * 255^2 is exact; at most one rounding in the product
+    hipStream_t s = kpx_stream(stream);
+    if (C == 1)
+        hipLaunchKernelGGL(draw_diversity_kernel<1>, dim3(N), dim3(DM_THREADS), 0, s, sum, sumsq, P, (uint32_t)D, denom, div_mse, std_map);
+    else
+        hipLaunchKernelGGL(draw_diversity_kernel<3>, dim3(N), dim3(DM_THREADS), 0, s, sum, sumsq, P, (uint32_t)D, denom, div_mse, std_map);
+    return kpx_launch_status();
+}
+
+extern "C" int kpx_keypoint_draw_metrics_f32(const float* pts, const float* real, int D, int N, int T, int K, float* l2, float* div,
+                                             void* stream) {
+    if (!pts || !real || !l2 || D < 1 || D > DM_MAX_DRAWS || N < 1 || T < 1 || K < 1 || (D == 1 && div) ||
+        ((((uintptr_t)pts) | ((uintptr_t)real) | ((uintptr_t)l2) | ((uintptr_t)div)) & 3))
+        return KPX_EINVAL;
+    const size_t NT = (size_t)N * T;
+    const size_t blocks = (((size_t)D + (div ? 1 : 0)) * NT + DM_THREADS - 1) / DM_THREADS;
+    if (blocks > 0x7fffffffULL) return KPX_EINVAL;
+    hipLaunchKernelGGL(keypoint_draw_metrics_kernel, dim3((unsigned)blocks), dim3(DM_THREADS), 0, kpx_stream(stream), pts, real, D, NT, K, l2, div);
+    return kpx_launch_status();
+}
 
 extern "C" size_t kpx_feature_pair_metrics_workspace_bytes(int N, int H, int W, int C) {
     if (N < 1 || H < 1 || H > 1024 || W < 1 || W > 1024 || C < 4 || C > 512 || C % 4) return 0;

@@ -1472,6 +1472,108 @@ def feature_pair_metrics(fa, fb, out=None):
     return out
 
 
+MAX_DRAWS = 4096                                                                  # draws of z the uint32 accumulators hold exactly
+
+
+def _draw_accumulators(what, sum, sumsq):
+    for t in (sum, sumsq):
+        if not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % t.device)
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.KpxError('%s: sum and sumsq must be contiguous int32 tensors (got %s, contiguous=%s)' % (what, t.dtype, t.is_contiguous()))
+    if sum.numel() != sumsq.numel() or sum.device != sumsq.device:
+        raise _lib.KpxError('%s: sum and sumsq must have one size on one device (got %d on %s, %d on %s)'
+                            % (what, sum.numel(), sum.device, sumsq.numel(), sumsq.device))
+
+
+def draw_moments_add(x, sum, sumsq):
+    """One draw of z into the accumulators of the draw diversity: per value of x (contiguous fp32, any shape), the
+    8-bit value q evaluate.py writes (as ``frame_metrics(png8=True)``): sum += q, sumsq += q * q.  ``sum`` / ``sumsq``: contiguous int32
+    tensors (the bits of uint32) of x's size on x's device, zeroed before the first draw; exact for up to 4096 draws.  One launch."""
+    _require_gpu(x)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise _lib.KpxError('draw_moments_add: x must be a contiguous fp32 tensor (got %s, contiguous=%s)' % (x.dtype, x.is_contiguous()))
+    _draw_accumulators('draw_moments_add', sum, sumsq)
+    if sum.numel() != x.numel() or sum.device != x.device:
+        raise _lib.KpxError('draw_moments_add: the accumulators must have the size and device of x (got %d on %s for %d on %s)'
+                            % (sum.numel(), sum.device, x.numel(), x.device))
+    if sum.data_ptr() == sumsq.data_ptr() and x.numel():
+        raise _lib.KpxError('draw_moments_add: sum and sumsq must be two buffers')
+    check(lib.kpx_draw_moments_add_f32(x.data_ptr(), x.numel(), sum.data_ptr(), sumsq.data_ptr(), _stream()), 'kpx_draw_moments_add_f32')
+
+
+def draw_diversity(sum, sumsq, draws, frame_shape, std_map=False, out=None):
+    """The diversity of ``draws`` draws of z from the accumulators ``draw_moments_add`` filled.  ``frame_shape`` =
+    (H, W, C) of one frame, C in (1, 3), H and W in [1, 1024]; the accumulators hold N = numel / (H W C) >= 1 frames; 2 <= draws <= 4096.
+    -> div_mse fp32 [N]: per frame the mean over pairs of draws of the MSE between their 8-bit frames (q / 255 scale), exact up to its one
+    rounding.  ``std_map``: also the per-pixel spread uint8 [N,H,W] = floor(2 * sqrt(mean over channels of the variance of q)), capped at
+    255 -> (div_mse, std_map); True allocates it, a contiguous uint8 [N,H,W] tensor is written into.  ``out``: a contiguous fp32 [N]
+    tensor for div_mse.  One launch."""
+    _draw_accumulators('draw_diversity', sum, sumsq)
+    try:
+        h, w, c = (int(v) for v in frame_shape)
+        d = int(draws)
+    except (TypeError, ValueError):
+        raise _lib.KpxError('draw_diversity: frame_shape must be (H, W, C) and draws an integer (got %r, %r)' % (frame_shape, draws))
+    if not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
+        raise _lib.KpxError('draw_diversity: needs H and W in [1, 1024] and C in (1, 3) (got %r)' % (tuple(frame_shape),))
+    if not 2 <= d <= MAX_DRAWS:
+        raise _lib.KpxError('draw_diversity: needs 2 <= draws <= %d (got %d)' % (MAX_DRAWS, d))
+    n = sum.numel() // (h * w * c)
+    if n < 1 or n * h * w * c != sum.numel():
+        raise _lib.KpxError('draw_diversity: the accumulators must hold N >= 1 frames of %d x %d x %d (got %d values)' % (h, w, c, sum.numel()))
+    dev = sum.device
+    if out is None:
+        out = torch.empty((n,), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (n,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise _lib.KpxError('draw_diversity: out must be a contiguous fp32 [%d] tensor on %s' % (n, dev))
+    smap = None
+    if isinstance(std_map, torch.Tensor):
+        smap = std_map
+        if tuple(smap.shape) != (n, h, w) or smap.dtype != torch.uint8 or not smap.is_contiguous() or smap.device != dev:
+            raise _lib.KpxError('draw_diversity: std_map must be a contiguous uint8 [%d,%d,%d] tensor on %s' % (n, h, w, dev))
+    elif std_map:
+        smap = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
+    check(lib.kpx_draw_diversity_f32(sum.data_ptr(), sumsq.data_ptr(), n, h, w, c, d, out.data_ptr(), _ptr(smap), _stream()),
+          'kpx_draw_diversity_f32')
+    return out if smap is None else (out, smap)
+
+
+def keypoint_draw_metrics(pts, real, diversity=True, out=None):
+    """Key-point error and diversity of D draws of z: pts contiguous fp32 [D,N,T,K,2], real contiguous fp32 [N,T,K,2]
+    (the labels) on one device, D <= 4096 -> (l2, div): l2 fp32 [D,N,T] = the mean over the K points of the Euclidean distance to the label,
+    div fp32 [N,T] = the mean over pairs of draws and points of the distance between the draws (None with ``diversity=False``; needs
+    D >= 2).  fp64 arithmetic in a fixed order, rounded once.  ``out``: (l2, div) tensors to write into.  One launch."""
+    for t in (pts, real):
+        _require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.KpxError('keypoint_draw_metrics: pts and real must be contiguous fp32 tensors (got %s, contiguous=%s)'
+                                % (t.dtype, t.is_contiguous()))
+    if pts.dim() != 5 or real.dim() != 4 or tuple(pts.shape[1:]) != tuple(real.shape) or pts.shape[4] != 2 or pts.device != real.device:
+        raise _lib.KpxError('keypoint_draw_metrics: pts must be [D,N,T,K,2] and real [N,T,K,2] on one device (got %s on %s, %s on %s)'
+                            % (tuple(pts.shape), pts.device, tuple(real.shape), real.device))
+    d, n, t, k, _ = pts.shape
+    if min(d, n, t, k) < 1 or d > MAX_DRAWS:
+        raise _lib.KpxError('keypoint_draw_metrics: needs 1 <= D <= %d and N, T, K >= 1 (got %s)' % (MAX_DRAWS, tuple(pts.shape)))
+    if diversity and d < 2:
+        raise _lib.KpxError('keypoint_draw_metrics: the diversity needs D >= 2 draws (got %d); pass diversity=False' % d)
+    l2, div = out if out is not None else (None, None)
+    if l2 is None:
+        l2 = torch.empty((d, n, t), dtype=torch.float32, device=pts.device)
+    if diversity and div is None:
+        div = torch.empty((n, t), dtype=torch.float32, device=pts.device)
+    for name, o, shape in (('l2', l2, (d, n, t)), ('div', div, (n, t))):
+        if o is None:
+            continue
+        if name == 'div' and not diversity:
+            raise _lib.KpxError('keypoint_draw_metrics: out has a div tensor but diversity=False')
+        if tuple(o.shape) != shape or o.dtype != torch.float32 or not o.is_contiguous() or o.device != pts.device:
+            raise _lib.KpxError('keypoint_draw_metrics: out %s must be a contiguous fp32 %s tensor on %s' % (name, list(shape), pts.device))
+    check(lib.kpx_keypoint_draw_metrics_f32(pts.data_ptr(), real.data_ptr(), d, n, t, k, l2.data_ptr(), _ptr(div), _stream()),
+          'kpx_keypoint_draw_metrics_f32')
+    return l2, div
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
