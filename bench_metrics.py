@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -25,6 +25,19 @@
 6. Four configs[4] rollouts (the draws of one batch) without and with what --motion-metrics adds -- per rollout the key-point copy and the
    accumulator update, per batch the zeroing, kpx_keypoint_draw_metrics_f32 and kpx_draw_diversity_f32 --, alternated in one process;
    median ms per rollout of each and the overhead in %.
+
+``--actions`` measures the class sweep (evaluate.py --actions) instead:
+
+7. kpx_sheet_paste_u8_f32 alone at the configs[4] size (B = 64 rollouts of 32 frames of 128x128x3, J = 8 frames into one row of a sheet of
+   10 x 9 cells): per pixel 12 bytes read and 3 written; device-event time of each launch after warm-up, the launches walking over the four
+   groups of 8 frames and the 10 rows (the 403 MB of frames and the 283 MB sheet do not stay in the 256 MB Infinity Cache); median us,
+   bytes/s and the fraction of the copy rate, beside kpx_draw_moments_add_f32 (the sibling stream) measured in the same process.  Then the
+   route the kernel replaces, in the same run: the same 8 frames of every sample gathered and copied to the host as fp32, quantised and
+   pasted with numpy, against the paste on the device plus the copy of the strip's bytes; wall-clock ms of each, medians of 5.
+8. A configs[4] sweep -- the batch's own rollout and one per class, 9 classes, at one z -- without what --actions adds, with its scores
+   alone (--no-save: the key-point copies, accumulator updates and score launches) and with the sheets too: the pastes of both sheets and
+   their two copies into page-locked host memory (not the PNG encoding, which is host work after the device is idle); the three alternated
+   in one process; median ms per rollout of each and the overheads in %; the two copies alone, page-locked and pageable.
 
 Prints one JSON line.
 """
@@ -268,15 +281,164 @@ def motion_rollout_leg(dev, rollouts):
             'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
 
 
+ACTION_CLASSES = 9
+SHEET_FRAMES = [3, 7, 11, 15, 19, 23, 27, 31]
+
+
+def actions_kernel_leg(dev, launches):
+    import numpy as np
+    from kpx_amd import ops
+    g = torch.Generator(device=dev).manual_seed(4)
+    j, rows, cols = len(SHEET_FRAMES), 1 + ACTION_CLASSES, 1 + len(SHEET_FRAMES)
+    src = torch.rand((B, 32, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    canvas = torch.zeros((B, rows * RES, cols * RES, 3), dtype=torch.uint8, device=dev)
+    turn = [0]
+
+    def paste():                                          # another group of 8 frames and another row each launch: nothing stays cached
+        t = turn[0] = turn[0] + 1
+        ops.sheet_paste(canvas, src, list(range(8 * (t % 4), 8 * (t % 4) + j)), t % rows, 1, 'unit')
+
+    us = _event_times(paste, launches, dev)
+    med = statistics.median(us)
+    pixels = B * j * RES * RES
+    nbytes = pixels * (12 + 3)
+    res = {'sheet_paste': {'src': list(src.shape), 'sheet_cells': [rows, cols], 'frames_per_launch': j, 'bytes_per_pixel': [12, 3],
+                           'mb': round(nbytes / 1e6, 1), 'launches': launches, 'median_us': round(med, 1), 'min_us': round(min(us), 1),
+                           'max_us': round(max(us), 1), 'gb_per_s': round(nbytes / (med * 1e-6) / 1e9, 1),
+                           'frac_of_copy_rate': round(nbytes / (med * 1e-6) / COPY_RATE, 3)}}
+    # the route the kernel replaces: the same frames to the host as fp32, quantised and pasted there -- against paste + copy of the bytes
+    strip = torch.zeros((B, RES, j * RES, 3), dtype=torch.uint8, device=dev)
+    idx = torch.tensor(SHEET_FRAMES, device=dev)
+    host_canvas = np.zeros((B, RES, j * RES, 3), np.uint8)
+
+    def host_route():
+        x = src.index_select(1, idx).cpu().numpy()
+        for k in range(j):
+            host_canvas[:, :, k * RES:(k + 1) * RES] = ((0.5 * (x[:, k] + 1.0)) * 255).astype(np.uint8)
+        return host_canvas
+
+    def device_route():
+        ops.sheet_paste(strip, src, SHEET_FRAMES, 0, 0, 'unit')
+        return strip.cpu().numpy()
+
+    ms = {'host': [], 'device': []}
+    same = None
+    for _ in range(6):                                    # the first pair warms both routes up and is dropped
+        for name, fn in (('host', host_route), ('device', device_route)):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            out = fn()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            if name == 'host':
+                same = out.copy()
+            else:
+                same = bool((same == out).all())          # values in [-1, 1): the two routes write the same bytes
+    host_ms, dev_ms = statistics.median(ms['host'][1:]), statistics.median(ms['device'][1:])
+    res['route'] = {'frames': [B, j, RES, RES, 3], 'fp32_to_host_mb': round(pixels * 12 / 1e6, 1), 'bytes_to_host_mb': round(pixels * 3 / 1e6, 1),
+                    'host_route_ms': round(host_ms, 2), 'device_route_ms': round(dev_ms, 2), 'host_over_device': round(host_ms / dev_ms, 2),
+                    'same_bytes': same, 'host_ms_all': [round(v, 2) for v in ms['host'][1:]], 'device_ms_all': [round(v, 2) for v in ms['device'][1:]]}
+    del src, canvas, strip
+    torch.cuda.empty_cache()
+    res['draw_moments_add'] = motion_kernel_leg(dev, launches)['draw_moments_add']
+    return res
+
+
+def actions_rollout_leg(dev, batches):
+    import kpx_amd
+    from kpx_amd import ops
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    a_n, cols = ACTION_CLASSES, 1 + len(SHEET_FRAMES)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    codes = [torch.eye(9, device=dev)[a:a + 1].expand(B, -1).contiguous() for a in range(a_n)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    real = torch.rand((B, 32, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    kp_real = torch.rand((B, 32, 15, 2), generator=g, device=dev) * 1.6 - 0.8
+    kp = torch.empty((1, a_n, B, 32, 15, 2), dtype=torch.float32, device=dev)
+    acc = torch.empty((2, N_FRAMES * RES * RES * 3), dtype=torch.int32, device=dev)
+    classes = torch.empty((B, (1 + a_n) * RES, cols * RES, 3), dtype=torch.uint8, device=dev)
+    points = torch.empty((B, a_n * RES, cols * RES, 3), dtype=torch.uint8, device=dev)
+    kp_l2 = torch.empty((a_n, B, 32), dtype=torch.float32, device=dev)
+    kp_div = torch.empty((B, 32), dtype=torch.float32, device=dev)
+    div_mse = torch.empty((N_FRAMES,), dtype=torch.float32, device=dev)
+    im1 = im.unsqueeze(1)
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256, point_maps=True)
+    fm.build()
+
+    pinned = [torch.empty(tuple(t.shape), dtype=torch.uint8, pin_memory=True) for t in (classes, points)]   # as evaluate.py keeps them
+
+    def batch(mode):                                      # 'off': the rollouts alone; 'scores': --no-save; 'on': sheets and scores
+        sheets, scores = mode == 'on', mode != 'off'
+        fm.run(None, {'image': im, 'action_code': act}, z=z)
+        if sheets:
+            ops.sheet_paste(classes, im1, [0], 0, 0, 'unit')
+            ops.sheet_paste(classes, real, SHEET_FRAMES, 0, 1, 'unit')
+        if scores:
+            ops.fill_raw_(acc, 0.0)
+        for a in range(a_n):
+            o = fm.run(None, {'image': im, 'action_code': codes[a]}, z=z)
+            pred = o['pred_im_seq'].contiguous()
+            if sheets:
+                ops.sheet_paste(classes, im1, [0], 1 + a, 0, 'unit')
+                ops.sheet_paste(classes, pred, SHEET_FRAMES, 1 + a, 1, 'unit')
+                ops.sheet_paste(points, o['current_points'].contiguous().unsqueeze(1), [0], a, 0, 'raw')
+                ops.sheet_paste(points, o['future_points'].contiguous(), SHEET_FRAMES, a, 1, 'raw')
+            if scores:
+                ops.flat_copy_tensor(o['fut_pt_raw'].contiguous(), kp[0, a].data_ptr())
+                ops.draw_moments_add(pred.reshape(N_FRAMES, RES, RES, 3), acc[0], acc[1])
+        if scores:
+            ops.keypoint_draw_metrics(kp[0], kp_real, out=(kp_l2, kp_div))
+            ops.draw_diversity(acc[0], acc[1], a_n, (RES, RES, 3), out=div_mse)
+        if sheets:
+            for host, t in zip(pinned, (classes, points)):
+                host.copy_(t)
+
+    for _ in range(3):                                    # eager, capture, one replay
+        fm.run(None, {'image': im, 'action_code': act}, z=z)
+    batch('on')
+    torch.cuda.synchronize(dev)
+    modes = ('off', 'scores', 'on')
+    ms = {m: [] for m in modes}
+    copy_ms = {'pinned': [], 'pageable': []}
+    for _ in range(batches):
+        for m in modes:
+            t0 = time.perf_counter()
+            batch(m)
+            torch.cuda.synchronize(dev)
+            ms[m].append((time.perf_counter() - t0) * 1e3 / (1 + a_n))
+        for kind in copy_ms:                              # the two copies of a sweep alone, on an idle device
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            if kind == 'pinned':
+                for host, t in zip(pinned, (classes, points)):
+                    host.copy_(t)
+            else:
+                classes.cpu(), points.cpu()
+            copy_ms[kind].append((time.perf_counter() - t0) * 1e3 / (1 + a_n))
+    assert bool(torch.isfinite(div_mse).all()) and bool(torch.isfinite(kp_l2).all()) and bool(torch.isfinite(kp_div).all())
+    assert bool((pinned[0] == classes.cpu()).all()) and bool((pinned[1] == points.cpu()).all())
+    off, scores, on = (statistics.median(ms[m]) for m in modes)
+    return {'batch': B, 'frames': N_FRAMES, 'classes': a_n, 'rollouts_per_sweep': 1 + a_n, 'sweeps_each': batches,
+            'graph_replay': len(fm._graphs) == 1, 'sheet_mb': [round(classes.numel() / 1e6, 1), round(points.numel() / 1e6, 1)],
+            'off_ms_per_rollout': round(off, 3), 'scores_only_ms_per_rollout': round(scores, 3), 'on_ms_per_rollout': round(on, 3),
+            'scores_only_delta_ms_per_rollout': round(scores - off, 3), 'scores_only_overhead_pct': round(100 * (scores - off) / off, 2),
+            'delta_ms_per_rollout': round(on - off, 3), 'overhead_pct': round(100 * (on - off) / off, 2),
+            'sheet_copies_alone_ms_per_rollout': {k: round(statistics.median(v), 3) for k, v in copy_ms.items()},
+            'off_ms_all': [round(v, 2) for v in ms['off']], 'scores_only_ms_all': [round(v, 2) for v in ms['scores']],
+            'on_ms_all': [round(v, 2) for v in ms['on']]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
     ap.add_argument('--rollouts', type=int, default=10)
     ap.add_argument('--vgg', action='store_true', help='measure the VGG feature-space metrics instead of the frame metrics')
     ap.add_argument('--motion', action='store_true', help='measure the motion metrics (draw diversity, key-point error) instead')
+    ap.add_argument('--actions', action='store_true', help='measure the class sweep (contact-sheet paste, sheets and class scores) instead')
     args = ap.parse_args()
-    if args.vgg and args.motion:
-        ap.error('--vgg and --motion are two measurements: pass one')
+    if args.vgg + args.motion + args.actions > 1:
+        ap.error('--vgg, --motion and --actions are three measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
@@ -284,6 +446,12 @@ def main():
         res = {'vgg_kernel': vgg_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()
         res['vgg_rollout_c4'] = vgg_rollout_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
+    if args.actions:
+        res = {'actions_kernels': actions_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['actions_rollout_c4'] = actions_rollout_leg(dev, args.rollouts)
         print(json.dumps(res))
         return
     if args.motion:

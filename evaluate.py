@@ -4,6 +4,7 @@
     python evaluate.py --config configs/penn.yaml --checkpoint_stage1 S1.npz --checkpoint_stage2 S2.npz [--save_dir results/eval]
                        [--synthetic N] [--colors_seed S] [--no-save]
                        [--metrics [--samples N] [--vgg-metrics [--synthetic-vgg]] [--motion-metrics]]
+                       [--actions all|i,j,k [--sheet-frames f,g,h]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -27,6 +28,16 @@ distance of each draw's predicted key points to the pseudo labels of the real fr
 ``--samples`` >= 2 how far the draws lie apart: ``kp_div`` [samples, 32] in key-point space and ``div_mse`` [samples, 32], the mean over
 pairs of draws of the MSE between their 8-bit frames (``draw_moments_add`` per draw, ``draw_diversity`` per batch: exact integers), plus
 per sample ``pred_std/``, the per-pixel spread of the draws as 8-bit grey PNGs.  Blocks of the same names in metrics.json.
+
+``--actions`` (data path and ``--synthetic``) rolls every source image out under each listed action class at ONE z: per batch and draw
+the script draws z itself, gives it to the batch's own rollout (the source of everything above) and to one further rollout per listed
+class, whose action code is that class's one-hot row, so the rows of a sheet differ by the class alone.  Per sample, from draw 0:
+``classes.png`` (a ``real`` row on the data path, then one row per class; columns: the input image, then the ``--sheet-frames`` frames,
+default 3,7,...,31) and ``classes_points.png`` (the colourised key points of the same cells), composed and quantised on the device
+(``kpx_amd.ops.sheet_paste``: only the bytes cross to the host), and ``<save_dir>/actions.json``.  With ``--metrics`` the classes at one z
+are scored as draws are: ``act_kp_l2`` [samples, classes, draws, 32], ``act_kp_div`` / ``act_div_mse`` [samples, draws, 32] (two or more
+classes), ``act_own``, ``act_rank`` and ``actions`` in metrics.npz, an ``actions`` block in metrics.json (``summarise_actions``): under
+which class does the rollout land closest to the real motion?  DESIGN.md section 2 has the definitions.
 """
 import json
 import os
@@ -141,11 +152,174 @@ def summarise_metrics(ssim, psnr, mse, extras=None, motion=None):
     return out
 
 
-def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None):
+ACTIONS_DEFINITION = (
+    'actions: every source image rolled out under each listed action class at the same z (one z per batch and draw, shared with the '
+    'batch\'s own rollout). kp_l2: per class, draw and frame the key-point error of --motion-metrics against the pseudo labels of the real '
+    'frames. score[s, a] = mean of kp_l2 over draws and frames (non-finite: +inf). A sample is ranked if its own class (the argmax of its '
+    'action code) is listed; its rank is the number of OTHER listed classes with score <= the score of the own class, so ties count against '
+    'the model: one that ignores the class has rank A - 1 and top1 0. top1 = share of ranked samples with rank 0, chance = 1 / A, '
+    'mean_rank over ranked samples, confusion[i][j] = ranked samples whose own class is actions[i] and whose lowest score is at actions[j] '
+    '(a tie goes to the lowest j). kp_div and div_mse (two or more classes): per draw the kp_div and div_mse of --motion-metrics with the '
+    'classes in the place of the draws; a model that ignores the class scores 0 in both. A network-free stand-in for action-recognition '
+    'accuracy, not that figure.')
+SHEET_FRAMES_DEFAULT = (3, 7, 11, 15, 19, 23, 27, 31)
+N_FUTURE_FRAMES = 32                                                              # = kpx_amd.final_model.N_FUTURE_FRAMES
+
+
+def action_ranks(actions, act_own, act_kp_l2):
+    """-> (score float64 [S, A], rank int32 [S]) of ACTIONS_DEFINITION from act_kp_l2 [S, A, D, T]; rank -1 where the own class is not listed."""
+    actions = [int(a) for a in actions]
+    own = np.asarray(act_own).reshape(-1).astype(np.int64)
+    l2 = np.asarray(act_kp_l2, np.float64)
+    if l2.ndim != 4 or l2.shape[:2] != (own.size, len(actions)) or not actions:
+        raise ValueError('action_ranks: act_kp_l2 must be [S, A, D, T] for S = %d samples and A = %d classes (got %s)'
+                         % (own.size, len(actions), l2.shape))
+    with np.errstate(invalid='ignore', over='ignore'):
+        score = l2.reshape(own.size, len(actions), -1).mean(axis=2) if l2.shape[2] * l2.shape[3] else np.full(l2.shape[:2], np.inf)
+    score = np.where(np.isfinite(score), score, np.inf)
+    rank = np.full(own.size, -1, np.int32)
+    for s in range(own.size):
+        if int(own[s]) in actions:
+            i = actions.index(int(own[s]))
+            rank[s] = int((score[s] <= score[s, i]).sum()) - 1
+    return score, rank
+
+
+def summarise_actions(actions, act_own, act_kp_l2, act_kp_div=None, act_div_mse=None):
+    """The ``actions`` block of metrics.json (ACTIONS_DEFINITION) from the arrays of metrics.npz: actions [A], act_own [S], act_kp_l2
+    [S, A, D, T] and, for two or more classes, act_kp_div and act_div_mse [S, D, T]; numpy only."""
+    actions = [int(a) for a in actions]
+    score, rank = action_ranks(actions, act_own, act_kp_l2)
+    own = np.asarray(act_own).reshape(-1).astype(np.int64)
+    ranked = rank >= 0
+    n_ranked, n_cls = int(ranked.sum()), len(actions)
+    confusion = [[0] * n_cls for _ in range(n_cls)]
+    for s in np.nonzero(ranked)[0]:
+        confusion[actions.index(int(own[s]))][int(np.argmin(score[s]))] += 1      # first minimum: a tie goes to the lowest list position
+    out = {'definition': ACTIONS_DEFINITION, 'actions': actions, 'n_ranked': n_ranked, 'chance': 1.0 / n_cls,
+           'top1': float((rank[ranked] == 0).mean()) if n_ranked else None,
+           'mean_rank': float(rank[ranked].astype(np.float64).mean()) if n_ranked else None, 'confusion': confusion}
+    parts = {'kp_l2': act_kp_l2}
+    if n_cls >= 2:
+        if act_kp_div is None or act_div_mse is None:
+            raise ValueError('summarise_actions: two or more classes come with act_kp_div and act_div_mse')
+        parts.update(kp_div=act_kp_div, div_mse=act_div_mse)
+    for name, x in parts.items():
+        x = np.asarray(x, np.float64)
+        x = x.reshape(-1, x.shape[-1])
+        with np.errstate(invalid='ignore', over='ignore'):
+            out[name] = {'mean': _json_num(x.mean()) if x.size else None,
+                         'per_frame': [_json_num(v) for v in x.mean(axis=0)] if x.shape[0] else [None] * x.shape[1]}
+    return out
+
+
+def _parse_index_list(text, what, limit):
+    """'i,j,k' -> [i, j, k], distinct and in [0, limit); a ValueError names what is wrong"""
+    try:
+        idx = [int(v) for v in text.split(',')] if text.strip() else []
+    except ValueError:
+        raise ValueError('%s takes integers separated by commas (got %r)' % (what, text))
+    if not idx:
+        raise ValueError('%s lists nothing' % what)
+    if len(set(idx)) != len(idx):
+        raise ValueError('%s lists an index twice (got %r)' % (what, text))
+    if min(idx) < 0 or max(idx) >= limit:
+        raise ValueError('%s takes indices in [0, %d) (got %r)' % (what, limit, text))
+    return idx
+
+
+_PINNED = {}
+
+
+def _sheet_to_host(canvas):
+    """The one copy of a sheet's bytes to the host, into page-locked memory kept per shape (DESIGN.md section 4.4 has the rates)."""
+    key = tuple(canvas.shape)
+    if key not in _PINNED:
+        _PINNED[key] = torch.empty(key, dtype=torch.uint8, pin_memory=True)
+    _PINNED[key].copy_(canvas)               # synchronous: the bytes are there when it returns
+    return _PINNED[key].numpy()
+
+
+class _ClassSweep:
+    """--actions for one batch: the further rollouts of each draw, their sheets (draw 0) and their scores."""
+
+    def __init__(self, kpx_amd, model, actions, n_action, sheet_frames, image, real_im_seq, save, samples, kp_real, dev):
+        self.ops, self.model, self.actions, self.sheet_frames, self.save = kpx_amd.ops, model, actions, sheet_frames, save
+        self.image = image.contiguous()
+        self.bsz = bsz = image.shape[0]
+        self.codes = torch.eye(n_action, dtype=torch.float32, device=dev)[actions]                    # [A, n_action] one-hot rows
+        self.real_row = 1 if real_im_seq is not None else 0
+        self.classes = self.points = None
+        if save:
+            h, w = image.shape[1:3]
+            cols = 1 + len(sheet_frames)
+            self.classes = torch.empty((bsz, (self.real_row + len(actions)) * h, cols * w, 3), dtype=torch.uint8, device=dev)
+            self.points = torch.empty((bsz, len(actions) * h, cols * w, 3), dtype=torch.uint8, device=dev)
+            if real_im_seq is not None:
+                self.ops.sheet_paste(self.classes, self.image.unsqueeze(1), [0], 0, 0, 'unit')
+                self.ops.sheet_paste(self.classes, real_im_seq.contiguous(), sheet_frames, 0, 1, 'unit')
+        self.kp_real = kp_real
+        if kp_real is not None:              # the key points of every sweep run [D, A, B, 32, K, 2]: [d] is contiguous, the whole a [D * A, ...] view
+            self.kp = torch.empty((samples, len(actions)) + tuple(kp_real.shape), dtype=torch.float32, device=dev)
+            self.kp_div, self.div_mse, self.moments = [], [], None
+
+    def run(self, draw, z):
+        """One rollout per listed class at z; -> the frames predicted"""
+        ops, n_cls = self.ops, len(self.actions)
+        for a in range(n_cls):
+            out = self.model.run(None, {'image': self.image, 'action_code': self.codes[a:a + 1].expand(self.bsz, -1).contiguous()}, z=z)
+            pred = out['pred_im_seq'].contiguous()      # consumed before the next run() overwrites the graph's output buffers
+            if self.save and draw == 0:
+                ops.sheet_paste(self.classes, self.image.unsqueeze(1), [0], self.real_row + a, 0, 'unit')
+                ops.sheet_paste(self.classes, pred, self.sheet_frames, self.real_row + a, 1, 'unit')
+                ops.sheet_paste(self.points, out['current_points'].contiguous().unsqueeze(1), [0], a, 0, 'raw')
+                ops.sheet_paste(self.points, out['future_points'].contiguous(), self.sheet_frames, a, 1, 'raw')
+            if self.kp_real is not None:
+                ops.flat_copy_tensor(out['fut_pt_raw'].contiguous(), self.kp[draw, a].data_ptr())
+                if n_cls >= 2:
+                    if a == 0:               # this draw's own pair of accumulators (not those of --motion-metrics)
+                        if self.moments is None:
+                            self.moments = torch.empty((2, pred.numel()), dtype=torch.int32, device=pred.device)
+                        ops.fill_raw_(self.moments, 0.0)
+                    ops.draw_moments_add(pred.reshape(-1, *pred.shape[2:]), self.moments[0], self.moments[1])
+        if self.kp_real is not None and n_cls >= 2:
+            self.kp_div.append(ops.keypoint_draw_metrics(self.kp[draw], self.kp_real)[1])
+            self.div_mse.append(ops.draw_diversity(self.moments[0], self.moments[1], n_cls, tuple(pred.shape[2:])))
+        return self.bsz * N_FUTURE_FRAMES * n_cls
+
+    def write_sheets(self, save_dir, first_sample):
+        from PIL import Image
+        for name, canvas in (('classes.png', self.classes), ('classes_points.png', self.points)):
+            host = _sheet_to_host(canvas)    # one copy per canvas: the bytes of the PNGs
+            for batch_idx in range(self.bsz):
+                d = osp.join(save_dir, '%04d' % (first_sample + batch_idx))
+                os.makedirs(d, exist_ok=True)
+                Image.fromarray(host[batch_idx]).save(osp.join(d, name))
+
+    def scores(self, action_scores):
+        """after the last draw: this batch's class scores, as device tensors"""
+        d, a = self.kp.shape[:2]
+        l2, _ = self.ops.keypoint_draw_metrics(self.kp.view((d * a,) + tuple(self.kp.shape[2:])), self.kp_real, diversity=False)
+        action_scores['kp_l2'].append(l2.view(d, a, self.bsz, -1))
+        if a >= 2:
+            action_scores['kp_div'].append(torch.stack(self.kp_div))                                   # [D, B, T]
+            action_scores['div_mse'].append(torch.stack(self.div_mse).view(d, self.bsz, -1))          # [D, B, T]
+
+
+def _write_actions_json(save_dir, actions, sheet_frames, real_row, cell):
+    os.makedirs(save_dir, exist_ok=True)
+    with open(osp.join(save_dir, 'actions.json'), 'w') as f:
+        json.dump({'actions': actions, 'sheet_frames': sheet_frames, 'rows': (['real'] if real_row else []) + actions, 'points_rows': actions,
+                   'cell': list(cell)}, f, indent=1)
+
+
+def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
-    per batch [B * T]}."""
+    per batch [B * T]}.
+    action_scores (--actions): {'actions': [A], 'own': per batch the action codes [B, n_action], 'kp_l2': per batch [draws, A, B, T]} and for
+    two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -169,9 +343,23 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
             if name in motion_scores:
                 motion[name] = host(motion_scores[name], (0,), 0).reshape(n_samples, n_frames)
         arrays.update(motion)
+    act = None
+    if action_scores is not None:
+        actions = action_scores['actions']
+        host = lambda ts, shape, dim: torch.cat(ts, dim=dim).cpu().numpy() if ts else np.zeros(shape, np.float32)
+        own = host(action_scores['own'], (0, 1), 0)
+        act = {'actions': np.asarray(actions, np.int32), 'act_own': own.argmax(axis=1).astype(np.int32),
+               'act_kp_l2': np.ascontiguousarray(host(action_scores['kp_l2'], (n_draws, len(actions), 0, n_frames), 2).transpose(2, 1, 0, 3))}
+        for name in ('kp_div', 'div_mse'):
+            if name in action_scores:
+                act['act_' + name] = np.ascontiguousarray(host(action_scores[name], (n_draws, 0, n_frames), 1).transpose(1, 0, 2))
+        act['act_rank'] = action_ranks(actions, act['act_own'], act['act_kp_l2'])[1]
+        arrays.update(act)
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
+    if act is not None:
+        res['actions'] = summarise_actions(actions, act['act_own'], act['act_kp_l2'], act.get('act_kp_div'), act.get('act_div_mse'))
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
@@ -186,6 +374,10 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         line += ', key-point L2 %s (best of draws %s)' % (fmt(res['kp_l2']['mean'], '%.4f'), fmt(res['kp_l2']['best_of_draws'], '%.4f'))
         if 'kp_div' in res:
             line += ', key-point diversity %s, draw diversity MSE %s' % (fmt(res['kp_div']['mean'], '%.4f'), fmt(res['div_mse']['mean'], '%.3e'))
+    if act is not None:
+        blk = res['actions']
+        line += ', class top-1 %s (chance %.4f), class diversity %s' % (fmt(blk['top1'], '%.4f'), blk['chance'],
+                                                                        fmt(blk['kp_div']['mean'], '%.4f') if 'kp_div' in blk else 'n/a')
     print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
 
 
@@ -214,7 +406,13 @@ def main(argv=None):
     parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
     parser.add_argument('--motion-metrics', action='store_true',
                         help='with --metrics: key-point error against the pseudo labels and, for --samples >= 2, the diversity of the draws')
+    parser.add_argument('--actions', type=str, default=None,
+                        help="'all' or i,j,k: also roll every image out under these action classes at the same z: classes.png, "
+                             'classes_points.png, actions.json and, with --metrics, the class scores')
+    parser.add_argument('--sheet-frames', type=str, default=None, help='with --actions: the predicted frames of a sheet (default 3,7,...,31)')
     args = parser.parse_args(argv)
+    if args.sheet_frames is not None and args.actions is None:
+        parser.error('--sheet-frames picks the frames of the sheets of --actions and needs it')
     if args.vgg_metrics and not args.metrics:
         parser.error('--vgg-metrics adds to the scores of --metrics and needs it')
     if args.motion_metrics and not args.metrics:
@@ -226,6 +424,21 @@ def main(argv=None):
     if args.samples < 1:
         parser.error('--samples must be >= 1 (got %d)' % args.samples)
     config = load_config(args.config)
+    actions = sheet_frames = None
+    if args.actions is not None:
+        n_cls_all = config['model'].get('n_action', 9)
+        try:
+            actions = list(range(n_cls_all)) if args.actions.strip() == 'all' else _parse_index_list(args.actions, '--actions', n_cls_all)
+            sheet_frames = list(SHEET_FRAMES_DEFAULT)
+            if args.sheet_frames is not None:
+                sheet_frames = _parse_index_list(args.sheet_frames, '--sheet-frames', N_FUTURE_FRAMES)
+                if sheet_frames != sorted(sheet_frames) or len(sheet_frames) > 63:
+                    raise ValueError('--sheet-frames takes at most 63 increasing frame indices (got %r)' % args.sheet_frames)
+        except ValueError as e:
+            parser.error(str(e))
+        if len(actions) * args.samples > MAX_MOTION_DRAWS:
+            parser.error('--actions scores classes x --samples as draws and holds at most %d of them (got %d x %d)'
+                         % (MAX_MOTION_DRAWS, len(actions), args.samples))
     for p in (args.checkpoint_stage1, args.checkpoint_stage2):       # reference :34-38
         if not (osp.exists(p) or osp.exists(p + '.index')):                 # .npz file or TensorFlow bundle prefix
             raise Exception('checkpoint not found at %s' % p)
@@ -249,7 +462,11 @@ def main(argv=None):
                                                  random_order=False, randomness=False, with_image_seq=True)
         scores, n_frames = [], 32
         vgg_scores = [] if args.vgg_metrics else None
-        motion_scores = None
+        motion_scores = action_scores = None
+        if actions and args.metrics:
+            action_scores = {'actions': actions, 'own': [], 'kp_l2': []}
+            if len(actions) >= 2:
+                action_scores.update(kp_div=[], div_mse=[])
         if args.motion_metrics:
             motion_scores = {'kp_l2': []} if args.samples < 2 else {'kp_l2': [], 'kp_div': [], 'div_mse': []}
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
@@ -270,8 +487,16 @@ def main(argv=None):
                     if args.samples >= 2:
                         moments = torch.empty((2, real_flat.numel()), dtype=torch.int32, device=dev)
                         kpx_amd.ops.fill_raw_(moments, 0.0)
+            sweep = None
+            if actions:
+                sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, batch['image'], batch['real_im_seq'], not args.no_save,
+                                    args.samples, batch['real_seq'].contiguous() if args.metrics else None, dev)
+                if args.metrics:
+                    action_scores['own'].append(batch['action_code'].clone())
             for draw in range(args.samples):
-                outputs = model.run(None, {'image': batch['image'], 'action_code': batch['action_code']})
+                # --actions: one z per batch and draw, drawn here, for the batch's own rollout and for every class of the sweep
+                z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None
+                outputs = model.run(None, {'image': batch['image'], 'action_code': batch['action_code']}, z=z)
                 frames += bsz * 32
                 if args.metrics:             # enqueued before the next run() overwrites the graph's output buffers
                     pred = outputs['pred_im_seq']
@@ -296,32 +521,41 @@ def main(argv=None):
                                     for batch_idx in range(bsz):
                                         _save_img_sequence(osp.join(args.save_dir, '%04d' % (sample_idx - bsz + batch_idx), 'pred_std'),
                                                            spread[batch_idx], raw=True)
-                if draw > 0 or args.no_save:
-                    continue
-                o = {k: v.cpu().numpy() for k, v in outputs.items() if isinstance(v, torch.Tensor)}
-                real = batch['real_im_seq'].cpu().numpy()
-                for batch_idx in range(bsz):
-                    d = osp.join(args.save_dir, '%04d' % sample_idx)
-                    os.makedirs(d, exist_ok=True)
-                    _save_img(osp.join(d, 'input_im.png'), o['im'][batch_idx], rescale=True)
-                    _save_img(osp.join(d, 'current_points.png'), o['current_points'][batch_idx], rescale=False)
-                    _save_img_sequence(osp.join(d, 'real_seq'), real[batch_idx], rescale=True)
-                    _save_img_sequence(osp.join(d, 'pred_seq'), o['pred_im_seq'][batch_idx], rescale=True)
-                    _save_img_sequence(osp.join(d, 'mask'), o['mask'][batch_idx], rescale=False)
-                    _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
-                    _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
-                    sample_idx += 1
+                if draw == 0 and not args.no_save:
+                    o = {k: v.cpu().numpy() for k, v in outputs.items() if isinstance(v, torch.Tensor)}
+                    real = batch['real_im_seq'].cpu().numpy()
+                    for batch_idx in range(bsz):
+                        d = osp.join(args.save_dir, '%04d' % sample_idx)
+                        os.makedirs(d, exist_ok=True)
+                        _save_img(osp.join(d, 'input_im.png'), o['im'][batch_idx], rescale=True)
+                        _save_img(osp.join(d, 'current_points.png'), o['current_points'][batch_idx], rescale=False)
+                        _save_img_sequence(osp.join(d, 'real_seq'), real[batch_idx], rescale=True)
+                        _save_img_sequence(osp.join(d, 'pred_seq'), o['pred_im_seq'][batch_idx], rescale=True)
+                        _save_img_sequence(osp.join(d, 'mask'), o['mask'][batch_idx], rescale=False)
+                        _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
+                        _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
+                        sample_idx += 1
+                if sweep is not None:        # after everything that reads this draw's own rollout: the sweep replays the same graph
+                    frames += sweep.run(draw, z)
+                    if draw == 0 and not args.no_save:
+                        sweep.write_sheets(args.save_dir, sample_idx - bsz)
+                    if draw == args.samples - 1 and args.metrics:
+                        sweep.scores(action_scores)
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
+        if actions and not args.no_save:
+            _write_actions_json(args.save_dir, actions, sheet_frames, True, (model.image_size, model.image_size))
         if args.metrics:
-            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores)
+            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)
         rs = np.random.RandomState(start)
         im = (rs.randint(0, 256, size=(bsz, 128, 128, 3)).astype(np.float32) / 255.0 * 2.0 - 1.0)
         act = np.eye(n_action, dtype=np.float32)[rs.randint(0, n_action, size=bsz)]
-        outputs = model.run(None, {'image': torch.from_numpy(im).to(dev), 'action_code': torch.from_numpy(act).to(dev)})
+        image = torch.from_numpy(im).to(dev)
+        z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None       # --actions: shared with the sweep below
+        outputs = model.run(None, {'image': image, 'action_code': torch.from_numpy(act).to(dev)}, z=z)
         frames += bsz * 32
         if not args.no_save:
             o = {k: v.cpu().numpy() for k, v in outputs.items() if isinstance(v, torch.Tensor)}
@@ -335,6 +569,13 @@ def main(argv=None):
                 _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                 _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                 sample_idx += 1
+        if actions:
+            sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, image, None, not args.no_save, 1, None, dev)
+            frames += sweep.run(0, z)
+            if not args.no_save:
+                sweep.write_sheets(args.save_dir, sample_idx - bsz)
+    if actions and not args.no_save:
+        _write_actions_json(args.save_dir, actions, sheet_frames, False, (model.image_size, model.image_size))
     torch.cuda.synchronize()
     print('iteration through synthetic set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
 

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 13
+#define KPX_ABI_VERSION 14
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -379,6 +379,26 @@ int kpx_draw_diversity_f32(const uint32_t* sum, const uint32_t* sumsq, int N, in
                            uint8_t* std_map /*[N,H,W] or NULL*/, void* stream);
 int kpx_keypoint_draw_metrics_f32(const float* pts /*[D,N,T,K,2]*/, const float* real /*[N,T,K,2]*/, int D, int N, int T, int K,
                                   float* l2 /*[D,N,T]*/, float* div /*[N,T] or NULL*/, void* stream);
+
+/* ---- contact sheets (evaluate.py --actions), DESIGN.md section 4.4: frames of a rollout quantised to the bytes evaluate.py writes and
+ * pasted into an 8-bit RGB sheet of rows x cols cells of H x W pixels, on the device.
+ *   src fp32 [B,F,H,W,C] contiguous, C in {1,3} (C = 1 is written to the three channels); canvas uint8 [B, rows*H, cols*W, 3] contiguous.
+ *   frames: J ints on the HOST (the one pointer of this ABI that is not device memory), each in [0,F), any order, repeats allowed; they
+ *   are read before the call returns and travel by value in the launch arguments (no device index buffer: capturable).
+ *   For every b < B and j < J: canvas[b, row*H + y, (col + j)*W + x, :] = q(src[b, frames[j], y, x, :]); nothing else is written.
+ *   premap: KPX_SHEET_UNIT q = clamp(uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))), 0, 255) -- kpx_frame_metrics_f32's png8, the bytes of
+ *           _save_img(rescale=True); KPX_SHEET_RAW q = clamp(uint8(trunc(fl(x * 255))), 0, 255), the bytes of _save_img(rescale=False) for
+ *           x in [0,1].  NaN -> 0 in both.
+ *   Limits: B >= 1, F >= 1, H and W in [1,1024], rows and cols in [1,64], 1 <= J <= KPX_SHEET_MAX_FRAMES, 0 <= row < rows, col >= 0,
+ *   col + J <= cols.  KPX_EINVAL before any device call for anything else, a null pointer, a src that is not 4-byte aligned or an unknown
+ *   premap.
+ * One launch: 16 source values per lane (four 16-byte loads, 16-byte stores) when W % 16 == 0 and src and canvas are 16-byte aligned, 4 per
+ * lane (one 16-byte load, 4-byte stores) when W % 4 == 0, src is 16-byte and canvas 4-byte aligned, one value per lane otherwise -- the
+ * same bytes on every path.  No allocation, copy or synchronisation.  Added in ABI version 14. */
+#define KPX_SHEET_MAX_FRAMES 64
+enum { KPX_SHEET_UNIT = 0, KPX_SHEET_RAW = 1 };
+int kpx_sheet_paste_u8_f32(const float* src /*[B,F,H,W,C]*/, int B, int F, int H, int W, int C, const int* frames /*host [J]*/, int J,
+                           uint8_t* canvas /*[B,rows*H,cols*W,3]*/, int rows, int cols, int row, int col, int premap, void* stream);
 
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */

@@ -56,6 +56,20 @@ __device__ __forceinline__ float kpx_sub_rn(float a, float b) {
     return a - b;
 }
 
+// The 8-bit values evaluate.py writes, as floats in [0, 255] (the one definition: frame and motion metrics, the VGG input, the contact
+// sheets).  unit: _save_img(rescale=True) of x in [-1, 1], q = uint8(trunc(fl(fl(0.5 * fl(x + 1)) * 255))); raw: _save_img(rescale=False) of
+// x in [0, 1], q = uint8(trunc(fl(x * 255))).  Both clamped to [0, 255], NaN -> 0.
+__device__ __forceinline__ float kpx_png8_unit(float x) {
+    float v = kpx_mul_rn(kpx_mul_rn(0.5f, kpx_add_rn(x, 1.0f)), 255.0f);
+    v = fminf(fmaxf(v, 0.0f), 255.0f);                                 // NaN -> 0
+    return truncf(v);
+}
+__device__ __forceinline__ float kpx_png8_raw(float x) {
+    float v = kpx_mul_rn(x, 255.0f);
+    v = fminf(fmaxf(v, 0.0f), 255.0f);                                 // NaN -> 0
+    return truncf(v);
+}
+
 // uint8 -> [-1,1] with the loaders' arithmetic (kpx_u8_to_unit_f32, the augmentation's last stage): numpy's float64 division, tf.data's
 // float32 cast, then map_fn in float32 (v * 2 is exact, so the subtraction is the only rounding whether or not it is contracted).
 __device__ __forceinline__ float kpx_u8_to_unit(unsigned char u) {

@@ -23,7 +23,7 @@
 // kpx_vgg_prep_png8_f32 is the VGG input of those frames: q - mean, BGR, of the same 8-bit quantisation.
 //
 // Motion metrics (evaluate.py --motion-metrics): how far the D draws of z of one sample lie apart, and the key-point error of each.
-//   - kpx_draw_moments_add_f32: per value of a rollout, sum += q and sumsq += q * q of its 8-bit value q (fm_png8), uint32, one call per
+//   - kpx_draw_moments_add_f32: per value of a rollout, sum += q and sumsq += q * q of its 8-bit value q (kpx_png8_unit), uint32, one call per
 //     draw: element-wise, 16 bytes per lane and array when the three pointers allow it.
 //   - kpx_draw_diversity_f32: V = D * sumsq - sum^2 = the sum over the D (D - 1) / 2 pairs of draws of (q_i - q_j)^2, an integer; one
 //     workgroup per frame sums V in uint64 (order-free, so exact and the same for every batch) and writes floor(2 sqrt(mean_c variance)) per
@@ -48,12 +48,6 @@ struct FmParams {
     double mse_scale;                 // 1, or 1 / 255^2 for png8
     double psnr_l;                    // 20 log10(L) of the reported scale
 };
-
-__device__ __forceinline__ float fm_png8(float x) {
-    float v = kpx_mul_rn(kpx_mul_rn(0.5f, kpx_add_rn(x, 1.0f)), 255.0f);
-    v = fminf(fmaxf(v, 0.0f), 255.0f);                                 // NaN -> 0
-    return truncf(v);
-}
 
 // lum * cs of one position and channel, in TF's order of operations.  Not contracted: for a == b the numerator and the denominator are
 // the same roundings, so the term is exactly 1.
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(FM_MAX_THREADS) void frame_metrics_kernel(const flo
         auto put = [&](int buf, f32x4 v) {
             if (PNG8) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fm_png8(v[e]);
+                for (int e = 0; e < 4; ++e) v[e] = kpx_png8_unit(v[e]);
             }
             *reinterpret_cast<f32x4*>(&stage[buf][img][j4]) = v;
         };
@@ -285,7 +279,7 @@ void fp_launch(const float* fa, const float* fb, int N, int P, int C4, int S, do
 
 __global__ __launch_bounds__(256) void vgg_prep_png8_kernel(const float* __restrict__ rgb, size_t P, float* __restrict__ bgr) {
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (size_t)gridDim.x * 256) {
-        const float r = fm_png8(rgb[p * 3 + 0]), g = fm_png8(rgb[p * 3 + 1]), b = fm_png8(rgb[p * 3 + 2]);
+        const float r = kpx_png8_unit(rgb[p * 3 + 0]), g = kpx_png8_unit(rgb[p * 3 + 1]), b = kpx_png8_unit(rgb[p * 3 + 2]);
         bgr[p * 3 + 0] = b - 103.939f; bgr[p * 3 + 1] = g - 116.779f; bgr[p * 3 + 2] = r - 123.68f;
     }
 }
@@ -306,7 +300,7 @@ __global__ __launch_bounds__(DM_THREADS) void draw_moments_add_kernel(const floa
         u32x4 s = reinterpret_cast<const u32x4*>(sum)[i], ss = reinterpret_cast<const u32x4*>(sumsq)[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const uint32_t q = (uint32_t)fm_png8(v[e]);
+            const uint32_t q = (uint32_t)kpx_png8_unit(v[e]);
             s[e] += q;
             ss[e] += q * q;
         }
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(DM_THREADS) void draw_moments_add_kernel(const floa
         reinterpret_cast<u32x4*>(sumsq)[i] = ss;
     }
     for (size_t i = 4 * nv + t0; i < n; i += stride) {
-        const uint32_t q = (uint32_t)fm_png8(x[i]);
+        const uint32_t q = (uint32_t)kpx_png8_unit(x[i]);
         sum[i] += q;
         sumsq[i] += q * q;
     }

@@ -1574,6 +1574,53 @@ def keypoint_draw_metrics(pts, real, diversity=True, out=None):
     return l2, div
 
 
+SHEET_PREMAPS = {'unit': 0, 'raw': 1}                                             # = KPX_SHEET_* of include/kpx.h
+SHEET_MAX_FRAMES = 64                                                             # = KPX_SHEET_MAX_FRAMES
+
+
+def sheet_paste(canvas, src, frames, row, col, premap):
+    """Frames of a rollout into a contact sheet, as the bytes evaluate.py writes.  canvas: contiguous uint8
+    [B, rows*H, cols*W, 3]; src: contiguous fp32 [B,F,H,W,C], C in (1, 3) (C = 1 goes to the three channels), on canvas's device; frames:
+    1 <= J <= 64 ints in [0, F), any order, repeats allowed.  canvas[b, row*H:(row+1)*H, (col+j)*W:(col+j+1)*W] = q(src[b, frames[j]]) for
+    every b and j; nothing else is written.  ``premap``: 'unit' the bytes of ``_save_img(rescale=True)`` (``frame_metrics(png8=True)``'s
+    quantiser), 'raw' those of ``_save_img(rescale=False)`` for values in [0, 1]; both clamp to [0, 255] and send NaN to 0.  rows and cols
+    (from the canvas shape) in [1, 64], H and W in [1, 1024], row < rows, col + J <= cols.  One launch on the current stream; the frame
+    indices travel in the launch arguments (capturable)."""
+    for name, t, dtype, dim in (('canvas', canvas, torch.uint8, 4), ('src', src, torch.float32, 5)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got %s for sheet_paste\'s %s); there is no CPU fallback'
+                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
+        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+            raise _lib.KpxError('sheet_paste: %s must be a contiguous %s tensor of %d dimensions (got %s %s, contiguous=%s)'
+                                % (name, dtype, dim, tuple(t.shape), t.dtype, t.is_contiguous()))
+    if canvas.device != src.device:
+        raise _lib.KpxError('sheet_paste: canvas and src must be on one device (got %s and %s)' % (canvas.device, src.device))
+    if premap not in SHEET_PREMAPS:
+        raise _lib.KpxError('sheet_paste: premap must be one of %s (got %r)' % (sorted(SHEET_PREMAPS), premap))
+    b, f, h, w, c = src.shape
+    if b < 1 or f < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
+        raise _lib.KpxError('sheet_paste: src needs B, F >= 1, H and W in [1, 1024] and C in (1, 3) (got %s)' % (tuple(src.shape),))
+    if canvas.shape[0] != b or canvas.shape[3] != 3 or canvas.shape[1] % h or canvas.shape[2] % w:
+        raise _lib.KpxError('sheet_paste: canvas must be [%d, rows * %d, cols * %d, 3] (got %s)' % (b, h, w, tuple(canvas.shape)))
+    rows, cols = canvas.shape[1] // h, canvas.shape[2] // w
+    if not (1 <= rows <= 64 and 1 <= cols <= 64):
+        raise _lib.KpxError('sheet_paste: a sheet has 1 to 64 rows and columns of cells (got %d x %d)' % (rows, cols))
+    try:
+        idx = [int(v) for v in frames]
+        row, col = int(row), int(col)
+    except (TypeError, ValueError):
+        raise _lib.KpxError('sheet_paste: frames must be a sequence of integers, row and col integers (got %r, %r, %r)' % (frames, row, col))
+    if any(i != v for i, v in zip(idx, frames)):
+        raise _lib.KpxError('sheet_paste: frames must be integers (got %r)' % (frames,))
+    if not 1 <= len(idx) <= SHEET_MAX_FRAMES or any(not 0 <= i < f for i in idx):
+        raise _lib.KpxError('sheet_paste: needs 1 to %d frame indices in [0, %d) (got %r)' % (SHEET_MAX_FRAMES, f, idx))
+    if not 0 <= row < rows or col < 0 or col + len(idx) > cols:
+        raise _lib.KpxError('sheet_paste: %d cells from (row %d, col %d) do not fit a sheet of %d x %d cells' % (len(idx), row, col, rows, cols))
+    check(lib.kpx_sheet_paste_u8_f32(src.data_ptr(), b, f, h, w, c, (_lib.c_int * len(idx))(*idx), len(idx), canvas.data_ptr(), rows, cols,
+                                     row, col, SHEET_PREMAPS[premap], _stream()), 'kpx_sheet_paste_u8_f32')
+    return canvas
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
