@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -38,6 +38,14 @@
    alone (--no-save: the key-point copies, accumulator updates and score launches) and with the sheets too: the pastes of both sheets and
    their two copies into page-locked host memory (not the PNG encoding, which is host work after the device is idle); the three alternated
    in one process; median ms per rollout of each and the overheads in %; the two copies alone, page-locked and pageable.
+
+``--drive`` measures the driven rollout (FinalModel.run(drive=...), evaluate.py --drive) instead:
+
+9. kpx_points_retarget_f32 alone at the configs[4] size (B = 64, T = 32, K = 15: 61 440 values, 240 KB out) in its four modes, shift 1:
+   device-event time of each launch after warm-up; median, minimum and maximum us.  It is a launch-bound call: no rate is quoted.
+10. The configs[4] rollout (B = 64, replayed HIP graphs) as the model's own rollout and as a driven rollout of each mode -- labels
+   (absolute, shift 0), hold, transfer (relative, shift 1) and transfer scaled --, the five alternated in one process; median ms per rollout
+   of each and the difference to the model's own in ms and %.
 
 Prints one JSON line.
 """
@@ -429,6 +437,70 @@ def actions_rollout_leg(dev, batches):
             'on_ms_all': [round(v, 2) for v in ms['on']]}
 
 
+DRIVES = (('labels', 'absolute', 0, False), ('hold', 'hold', 0, False), ('transfer', 'relative', 1, False),
+          ('transfer_scaled', 'relative', 1, True))
+
+
+def drive_kernel_leg(dev, launches):
+    from kpx_amd import ops
+    g = torch.Generator(device=dev).manual_seed(5)
+    k, t = 15, 32
+    src, first = (torch.rand((B, k, 2), generator=g, device=dev) * 1.6 - 0.8 for _ in range(2))
+    seq = torch.rand((B, t, k, 2), generator=g, device=dev) * 1.6 - 0.8
+    out = torch.empty((B, t, k, 2), dtype=torch.float32, device=dev)
+    res = {'shape': [B, t, k, 2], 'out_kb': round(out.numel() * 4 / 1e3, 1), 'launches': launches}
+    for name, mode, shift, scaled in (('hold', 'hold', 0, False), ('absolute', 'absolute', 1, False), ('relative', 'relative', 1, False),
+                                      ('relative_scaled', 'relative', 1, True)):
+        if mode == 'hold':
+            fn = lambda: ops.points_retarget(src, 'hold', frames=t, out=out)
+        else:
+            fn = lambda: ops.points_retarget(src, mode, first, seq, shift=shift, scaled=scaled, out=out)
+        us = _event_times(fn, launches, dev)
+        assert bool(torch.isfinite(out).all())
+        res[name] = {'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1)}
+    return res
+
+
+def drive_rollout_leg(dev, rollouts):
+    import kpx_amd
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    first = torch.rand((B, 15, 2), generator=g, device=dev) * 1.6 - 0.8
+    seq = torch.rand((B, 32, 15, 2), generator=g, device=dev) * 1.6 - 0.8
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    feed = {'image': im, 'action_code': act}
+    runs = {'model': lambda: fm.run(None, feed, z=z)}
+    for name, mode, shift, scaled in DRIVES:
+        drive = {'mode': mode, 'shift': shift, 'scaled': scaled}
+        if mode != 'hold':
+            drive.update(first=first, seq=seq)
+        runs[name] = (lambda d: lambda: fm.run(None, feed, drive=d))(drive)
+    for fn in runs.values():
+        for _ in range(3):                                # eager, capture, one replay
+            out = fn()
+        assert bool(torch.isfinite(out['pred_im_seq']).all())
+    torch.cuda.synchronize(dev)
+    ms = {name: [] for name in runs}
+    for _ in range(rollouts):
+        for name, fn in runs.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    own = statistics.median(ms['model'])
+    res = {'batch': B, 'frames': N_FRAMES, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == len(runs) and not fm._graph_failed}
+    for name in runs:
+        med = statistics.median(ms[name])
+        res[name] = {'ms': round(med, 3), 'frames_per_s': round(N_FRAMES / (med * 1e-3), 1), 'ms_all': [round(v, 2) for v in ms[name]]}
+        if name != 'model':
+            res[name].update(delta_ms=round(med - own, 3), delta_pct=round(100 * (med - own) / own, 2))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -436,9 +508,10 @@ def main():
     ap.add_argument('--vgg', action='store_true', help='measure the VGG feature-space metrics instead of the frame metrics')
     ap.add_argument('--motion', action='store_true', help='measure the motion metrics (draw diversity, key-point error) instead')
     ap.add_argument('--actions', action='store_true', help='measure the class sweep (contact-sheet paste, sheets and class scores) instead')
+    ap.add_argument('--drive', action='store_true', help='measure the driven rollout (key-point retargeting, every drive mode) instead')
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions > 1:
-        ap.error('--vgg, --motion and --actions are three measurements: pass one')
+    if args.vgg + args.motion + args.actions + args.drive > 1:
+        ap.error('--vgg, --motion, --actions and --drive are four measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
@@ -452,6 +525,12 @@ def main():
         res = {'actions_kernels': actions_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()
         res['actions_rollout_c4'] = actions_rollout_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
+    if args.drive:
+        res = {'drive_kernel': drive_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['drive_rollout_c4'] = drive_rollout_leg(dev, args.rollouts)
         print(json.dumps(res))
         return
     if args.motion:

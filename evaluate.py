@@ -5,6 +5,7 @@
                        [--synthetic N] [--colors_seed S] [--no-save]
                        [--metrics [--samples N] [--vgg-metrics [--synthetic-vgg]] [--motion-metrics]]
                        [--actions all|i,j,k [--sheet-frames f,g,h]]
+                       [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -38,6 +39,20 @@ default 3,7,...,31) and ``classes_points.png`` (the colourised key points of the
 are scored as draws are: ``act_kp_l2`` [samples, classes, draws, 32], ``act_kp_div`` / ``act_div_mse`` [samples, draws, 32] (two or more
 classes), ``act_own``, ``act_rank`` and ``actions`` in metrics.npz, an ``actions`` block in metrics.json (``summarise_actions``): under
 which class does the rollout land closest to the real motion?  DESIGN.md section 2 has the definitions.
+
+``--drive MODES`` (a comma list of ``labels``, ``hold``, ``transfer``) rolls the translator out on key points that come from outside the motion
+generator (``FinalModel.run(drive=...)``, ``kpx_amd.ops.points_retarget``), once per batch, whatever ``--samples`` is -- no z is involved:
+``labels`` (data path only) on the pseudo labels of the real frames, the translator's ceiling; ``hold`` on the detected key points of the
+input image at every frame, the static-pose floor; ``transfer`` (data path only) on the detected key points moved as the NEXT sample of the
+batch moves (its labels minus its frame-0 labels; ``--drive-scaled`` scales that motion by the ratio of the two constellations' spreads; a
+batch of one drives itself).  Per sample ``drive_labels/``, ``drive_hold/``, ``drive_transfer/`` (32 predicted PNGs each),
+``drive_transfer_points/`` (the colourised driven key points) and ``drive.png``, one sheet composed on the device with the rows ``real``,
+``labels``, ``model`` (the sample's own rollout, draw 0), ``hold``, ``driver`` (the driving sample's input image and real frames),
+``transfer`` -- those that apply -- and the columns of ``classes.png``; ``<save_dir>/drive.json`` records them.  With ``--metrics``, ``labels``
+and ``hold`` are scored against the real frames as the model's frames are: ``drive_labels_ssim`` ... ``drive_hold_mse`` [samples, 32] in
+metrics.npz and a ``drive`` block in metrics.json (``summarise_drive``) with ``skill`` = (model - hold) / (labels - hold) per metric.
+``--drive-only`` skips the model's own rollout (no ``model`` row, no pred_seq/ ..., metrics.npz holds the ``drive_*`` arrays alone) and needs
+no ``--checkpoint_stage2``: a stage-1 checkpoint can be evaluated before a stage-2 checkpoint exists.
 """
 import json
 import os
@@ -213,6 +228,52 @@ def summarise_actions(actions, act_own, act_kp_l2, act_kp_div=None, act_div_mse=
     return out
 
 
+DRIVE_MODES = ('labels', 'hold', 'transfer')                                      # the order of the runs and of the sheet's rows
+DRIVE_METRICS = ('ssim', 'psnr', 'mse')
+DRIVE_DEFINITION = (
+    'drive: the translator rolled out on key points that do not come from the motion generator; no z is drawn. labels: the 32 key-point '
+    'frames are the pseudo labels of the real frames, that is, the output of this project\'s own key-point detector on the real frames, not '
+    'human annotations: what the translator reaches when it is handed the true motion (a ceiling). hold: the detected key points of the '
+    'input image at all 32 frames: what it reaches when the pose never moves (a floor). Both are scored against the real frames exactly as '
+    'the model\'s own frames are (the 8-bit SSIM, PSNR and MSE above), once per sample: mean over samples and frames, per_frame over '
+    'samples. skill = (model - hold) / (labels - hold) on the means of a metric, the model\'s mean taken over samples, draws and frames: '
+    '0 is the static pose, 1 the true motion; it is null when the denominator is 0 or any of the three means is non-finite, and absent '
+    'unless labels, hold and the model\'s own rollout were all scored. transfer (the detected key points moved as the next sample of the '
+    'batch moves; with scaled, that motion times sqrt(v_src / v_drv), v the summed squared distance of a frame-0 constellation to its '
+    'mean) has no ground truth and is not scored.')
+
+
+def summarise_drive(drive, model=None):
+    """The ``drive`` block of metrics.json (DRIVE_DEFINITION); numpy only.  drive: {'labels' and / or 'hold': {'ssim', 'psnr', 'mse': [S, T]}};
+    model: the model's own {'ssim', 'psnr', 'mse': [S, N, T]}, or None when it was not rolled out (--drive-only)."""
+    if not drive or set(drive) - {'labels', 'hold'}:
+        raise ValueError('summarise_drive: scores of labels and / or hold (got %s)' % sorted(drive or ()))
+    out = {'definition': DRIVE_DEFINITION, 'modes': [m for m in DRIVE_MODES if m in drive]}
+    shape = None
+    for mode in out['modes']:
+        if set(drive[mode]) != set(DRIVE_METRICS):
+            raise ValueError('summarise_drive: %s holds ssim, psnr and mse (got %s)' % (mode, sorted(drive[mode])))
+        out[mode] = {}
+        for name in DRIVE_METRICS:
+            x = np.asarray(drive[mode][name], np.float64)
+            shape = x.shape if shape is None else shape
+            if x.ndim != 2 or x.shape != shape:
+                raise ValueError('summarise_drive: every array is [S, T] of one shape (got %s and %s)' % (shape, x.shape))
+            with np.errstate(invalid='ignore', over='ignore'):
+                out[mode][name] = {'mean': _json_num(x.mean()) if x.size else None,
+                                   'per_frame': [_json_num(v) for v in x.mean(axis=0)] if x.shape[0] else [None] * x.shape[1]}
+    if model is not None and 'labels' in drive and 'hold' in drive:
+        out['skill'] = {}
+        for name in DRIVE_METRICS:
+            own = np.asarray(model[name], np.float64)
+            with np.errstate(invalid='ignore', over='ignore'):
+                m = own.mean() if own.size else np.nan
+                top, floor = out['labels'][name]['mean'], out['hold'][name]['mean']
+                ok = top is not None and floor is not None and np.isfinite(m) and top != floor
+                out['skill'][name] = _json_num((m - floor) / (top - floor)) if ok else None
+    return out
+
+
 def _parse_index_list(text, what, limit):
     """'i,j,k' -> [i, j, k], distinct and in [0, limit); a ValueError names what is wrong"""
     try:
@@ -313,13 +374,118 @@ def _write_actions_json(save_dir, actions, sheet_frames, real_row, cell):
                    'cell': list(cell)}, f, indent=1)
 
 
-def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None):
+def _drive_rows(modes, real, own):
+    """the rows of drive.png, in order: ``real`` (there are real frames), ``own`` (the model's own rollout ran)"""
+    return ([r for r in ('real',) if real] + [r for r in ('labels',) if 'labels' in modes] + [r for r in ('model',) if own]
+            + [r for r in ('hold',) if 'hold' in modes] + [r for r in ('driver', 'transfer') if 'transfer' in modes])
+
+
+class _Drive:
+    """--drive for one batch: the driven rollouts, their PNGs, the sheet and the scores of labels and hold."""
+
+    def __init__(self, kpx_amd, model, modes, scaled, sheet_frames, batch, own, save, dev):
+        self.ops, self.model, self.modes, self.scaled, self.sheet_frames, self.save = kpx_amd.ops, model, modes, scaled, sheet_frames, save
+        self.batch = batch
+        self.image = batch['image'].contiguous()
+        self.bsz = bsz = self.image.shape[0]
+        self.shift = 1 % bsz                         # transfer: sample b is driven by sample b + 1 of its batch; a batch of one by itself
+        real = batch.get('real_im_seq')
+        self.rows = _drive_rows(modes, real is not None, own)
+        self.sheet = None
+        if save:
+            h, w = self.image.shape[1:3]
+            self.sheet = torch.empty((bsz, len(self.rows) * h, (1 + len(sheet_frames)) * w, 3), dtype=torch.uint8, device=dev)
+            if real is not None:
+                self.paste('real', self.image, real.contiguous())
+            if 'transfer' in modes:                  # the driving sample's input image and real frames
+                self.paste('driver', torch.roll(self.image, -self.shift, 0), torch.roll(real, -self.shift, 0).contiguous())
+
+    def paste(self, row, image, seq):
+        r = self.rows.index(row)
+        self.ops.sheet_paste(self.sheet, image.unsqueeze(1), [0], r, 0, 'unit')
+        self.ops.sheet_paste(self.sheet, seq, self.sheet_frames, r, 1, 'unit')
+
+    def drive_of(self, mode):
+        if mode == 'hold':
+            return {'mode': 'hold', 'shift': 0, 'scaled': False}
+        driver = {'first': self.batch['keypoints'].contiguous(), 'seq': self.batch['real_seq'].contiguous()}
+        if mode == 'labels':
+            return dict(driver, mode='absolute', shift=0, scaled=False)
+        return dict(driver, mode='relative', shift=self.shift, scaled=self.scaled)
+
+    def run(self, save_dir, first_sample, real_flat, drive_scores):
+        """One driven rollout per listed mode; -> the frames predicted"""
+        for mode in self.modes:
+            out = self.model.run(None, {'image': self.image, 'action_code': self.batch['action_code']}, drive=self.drive_of(mode))
+            pred = out['pred_im_seq'].contiguous()   # consumed before the next run() of this mode overwrites the graph's output buffers
+            if drive_scores is not None and mode in drive_scores:
+                drive_scores[mode].append(self.ops.frame_metrics(pred.reshape(-1, *pred.shape[2:]), real_flat, png8=True))
+            if self.save:
+                self.paste(mode, self.image, pred)
+                frames, points = pred.cpu().numpy(), out['future_points'].cpu().numpy() if mode == 'transfer' else None
+                for batch_idx in range(self.bsz):
+                    d = osp.join(save_dir, '%04d' % (first_sample + batch_idx))
+                    _save_img_sequence(osp.join(d, 'drive_' + mode), frames[batch_idx], rescale=True)
+                    if points is not None:
+                        _save_img_sequence(osp.join(d, 'drive_transfer_points'), points[batch_idx], rescale=False)
+        return self.bsz * N_FUTURE_FRAMES * len(self.modes)
+
+    def write_sheet(self, save_dir, first_sample):
+        from PIL import Image
+        host = _sheet_to_host(self.sheet)            # the one copy: the bytes of the PNGs
+        for batch_idx in range(self.bsz):
+            d = osp.join(save_dir, '%04d' % (first_sample + batch_idx))
+            os.makedirs(d, exist_ok=True)
+            Image.fromarray(host[batch_idx]).save(osp.join(d, 'drive.png'))
+
+
+def _write_drive_json(save_dir, rows, sheet_frames, cell, modes, scaled, n_self_driven):
+    os.makedirs(save_dir, exist_ok=True)
+    with open(osp.join(save_dir, 'drive.json'), 'w') as f:
+        json.dump({'rows': rows, 'sheet_frames': sheet_frames, 'cell': list(cell), 'modes': modes, 'scaled': scaled,
+                   'n_self_driven': n_self_driven}, f, indent=1)
+
+
+def _write_drive_only_metrics(save_dir, drive_scores, n_frames):
+    """--drive-only --metrics: the model's own rollout did not run, so metrics.npz holds the drive_* arrays and metrics.json the drive block"""
+    arrays, blocks = _drive_arrays(drive_scores, n_frames)
+    os.makedirs(save_dir, exist_ok=True)
+    np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
+    res = {'drive': summarise_drive(blocks)}
+    with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
+        json.dump(res, f, indent=1, allow_nan=False)
+    print(_drive_line(res['drive']))
+
+
+def _drive_arrays(drive_scores, n_frames):
+    """drive_scores: {mode: per batch a device tensor [B * T, 3] = (ssim, mse, psnr)} -> (the drive_* arrays of metrics.npz, each [S, T],
+    summarise_drive's first argument)"""
+    arrays, blocks = {}, {}
+    for mode, ts in drive_scores.items():
+        host = torch.cat(ts, dim=0).cpu().numpy() if ts else np.zeros((0, 3), np.float32)
+        host = host.reshape(-1, n_frames, 3)
+        blocks[mode] = {name: np.ascontiguousarray(host[..., i]) for i, name in enumerate(('ssim', 'mse', 'psnr'))}
+        for name in DRIVE_METRICS:
+            arrays['drive_%s_%s' % (mode, name)] = blocks[mode][name]
+    return arrays, blocks
+
+
+def _drive_line(blk):
+    fmt = lambda v, spec: 'n/a' if v is None else spec % v
+    parts = ['%s SSIM %s, PSNR %s dB' % (m, fmt(blk[m]['ssim']['mean'], '%.4f'), fmt(blk[m]['psnr']['mean'], '%.2f')) for m in blk['modes']]
+    if 'skill' in blk:
+        parts.append('skill SSIM %s, PSNR %s' % (fmt(blk['skill']['ssim'], '%.3f'), fmt(blk['skill']['psnr'], '%.3f')))
+    return 'drive: ' + '; '.join(parts)
+
+
+def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
     per batch [B * T]}.
     action_scores (--actions): {'actions': [A], 'own': per batch the action codes [B, n_action], 'kp_l2': per batch [draws, A, B, T]} and for
-    two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}."""
+    two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}.
+    drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -355,11 +521,17 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
                 act['act_' + name] = np.ascontiguousarray(host(action_scores[name], (n_draws, 0, n_frames), 1).transpose(1, 0, 2))
         act['act_rank'] = action_ranks(actions, act['act_own'], act['act_kp_l2'])[1]
         arrays.update(act)
+    drive = None
+    if drive_scores:
+        drive_arrays, drive = _drive_arrays(drive_scores, n_frames)
+        arrays.update(drive_arrays)
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
     if act is not None:
         res['actions'] = summarise_actions(actions, act['act_own'], act['act_kp_l2'], act.get('act_kp_div'), act.get('act_div_mse'))
+    if drive is not None:
+        res['drive'] = summarise_drive(drive, model={'ssim': ssim, 'psnr': psnr, 'mse': mse})
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
@@ -379,6 +551,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         line += ', class top-1 %s (chance %.4f), class diversity %s' % (fmt(blk['top1'], '%.4f'), blk['chance'],
                                                                         fmt(blk['kp_div']['mean'], '%.4f') if 'kp_div' in blk else 'n/a')
     print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
+    if drive is not None:
+        print(_drive_line(res['drive']))
 
 
 def _save_img_sequence(output_dir, img_seq, rescale=False, raw=False):
@@ -393,7 +567,8 @@ def main(argv=None):
     parser = ArgumentParser()
     parser.add_argument('--config', type=str, required=True, help='path of the configuration file')
     parser.add_argument('--checkpoint_stage1', type=str, required=True, help='path of the stage1 checkpoint')
-    parser.add_argument('--checkpoint_stage2', type=str, required=True, help='path of the stage2 checkpoint')
+    parser.add_argument('--checkpoint_stage2', type=str, required=False, default=None,
+                        help='path of the stage2 checkpoint (required unless --drive-only)')
     parser.add_argument('--save_dir', type=str, required=False, help='root dir to save results', default='results/eval')
     parser.add_argument('--synthetic', type=int, default=0)
     parser.add_argument('--batch', type=int, default=8)             # reference :27
@@ -409,10 +584,45 @@ def main(argv=None):
     parser.add_argument('--actions', type=str, default=None,
                         help="'all' or i,j,k: also roll every image out under these action classes at the same z: classes.png, "
                              'classes_points.png, actions.json and, with --metrics, the class scores')
-    parser.add_argument('--sheet-frames', type=str, default=None, help='with --actions: the predicted frames of a sheet (default 3,7,...,31)')
+    parser.add_argument('--sheet-frames', type=str, default=None,
+                        help='with --actions or --drive: the predicted frames of a sheet (default 3,7,...,31)')
+    parser.add_argument('--drive', type=str, default=None,
+                        help='comma list of labels, hold, transfer: also roll the translator out on given key points: drive_*/, drive.png, '
+                             'drive.json and, with --metrics, the scores of labels and hold')
+    parser.add_argument('--drive-scaled', action='store_true',
+                        help='with --drive transfer: scale the driving motion by the ratio of the two constellations\' spreads')
+    parser.add_argument('--drive-only', action='store_true',
+                        help="with --drive: skip the model's own rollout; --checkpoint_stage2 may then be omitted")
     args = parser.parse_args(argv)
-    if args.sheet_frames is not None and args.actions is None:
-        parser.error('--sheet-frames picks the frames of the sheets of --actions and needs it')
+    if args.sheet_frames is not None and args.actions is None and args.drive is None:
+        parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive and needs it')
+    drive_modes = None
+    if args.drive is not None:
+        listed = [m.strip() for m in args.drive.split(',')] if args.drive.strip() else []
+        if not listed:
+            parser.error('--drive lists nothing (modes: %s)' % ', '.join(DRIVE_MODES))
+        for m in listed:
+            if m not in DRIVE_MODES:
+                parser.error('--drive takes a comma list of %s (got %r)' % (', '.join(DRIVE_MODES), m))
+        if len(set(listed)) != len(listed):
+            parser.error('--drive lists a mode twice (got %r)' % args.drive)
+        drive_modes = [m for m in DRIVE_MODES if m in listed]          # run and shown in the one order of DRIVE_MODES
+        if args.synthetic and set(drive_modes) - {'hold'}:
+            parser.error('--drive labels and transfer take their key points from the pseudo labels, and --synthetic inputs have none '
+                         '(hold is allowed)')
+    if args.drive_scaled and 'transfer' not in (drive_modes or ()):
+        parser.error('--drive-scaled scales the motion of --drive transfer and needs it')
+    if args.drive_only:
+        if drive_modes is None:
+            parser.error('--drive-only keeps the rollouts of --drive alone and needs it')
+        for flag, on in (('--samples > 1', args.samples > 1), ('--actions', args.actions is not None), ('--vgg-metrics', args.vgg_metrics),
+                         ('--motion-metrics', args.motion_metrics)):
+            if on:
+                parser.error("--drive-only skips the model's own rollout, which %s is about" % flag)
+        if args.metrics and not set(drive_modes) & {'labels', 'hold'}:
+            parser.error('--drive-only --metrics scores labels and hold, and --drive lists neither (transfer has no ground truth)')
+    elif args.checkpoint_stage2 is None:
+        parser.error('the following arguments are required: --checkpoint_stage2 (unless --drive-only)')
     if args.vgg_metrics and not args.metrics:
         parser.error('--vgg-metrics adds to the scores of --metrics and needs it')
     if args.motion_metrics and not args.metrics:
@@ -425,10 +635,11 @@ def main(argv=None):
         parser.error('--samples must be >= 1 (got %d)' % args.samples)
     config = load_config(args.config)
     actions = sheet_frames = None
-    if args.actions is not None:
+    if args.actions is not None or drive_modes is not None:
         n_cls_all = config['model'].get('n_action', 9)
         try:
-            actions = list(range(n_cls_all)) if args.actions.strip() == 'all' else _parse_index_list(args.actions, '--actions', n_cls_all)
+            if args.actions is not None:
+                actions = list(range(n_cls_all)) if args.actions.strip() == 'all' else _parse_index_list(args.actions, '--actions', n_cls_all)
             sheet_frames = list(SHEET_FRAMES_DEFAULT)
             if args.sheet_frames is not None:
                 sheet_frames = _parse_index_list(args.sheet_frames, '--sheet-frames', N_FUTURE_FRAMES)
@@ -436,10 +647,11 @@ def main(argv=None):
                     raise ValueError('--sheet-frames takes at most 63 increasing frame indices (got %r)' % args.sheet_frames)
         except ValueError as e:
             parser.error(str(e))
-        if len(actions) * args.samples > MAX_MOTION_DRAWS:
+        if actions is not None and len(actions) * args.samples > MAX_MOTION_DRAWS:
             parser.error('--actions scores classes x --samples as draws and holds at most %d of them (got %d x %d)'
                          % (MAX_MOTION_DRAWS, len(actions), args.samples))
-    for p in (args.checkpoint_stage1, args.checkpoint_stage2):       # reference :34-38
+    checkpoints = [args.checkpoint_stage1] + ([args.checkpoint_stage2] if args.checkpoint_stage2 is not None else [])
+    for p in checkpoints:                                            # reference :34-38
         if not (osp.exists(p) or osp.exists(p + '.index')):                 # .npz file or TensorFlow bundle prefix
             raise Exception('checkpoint not found at %s' % p)
     vggnet = config.get('paths', {}).get('vggnet')
@@ -453,8 +665,8 @@ def main(argv=None):
     model = kpx_amd.FinalModel(config, device=dev, point_maps=not args.no_save, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
-    model.restore(None, args.checkpoint_stage1)                      # reference :76-77: two partial restores by name
-    model.restore(None, args.checkpoint_stage2)
+    for p in checkpoints:                                            # reference :76-77: two partial restores by name
+        model.restore(None, p)
     n_action = config['model']['n_action']
     sample_idx, frames, t0 = 0, 0, time.time()
     if not args.synthetic:                       # reference :43-51, :84-130: the test subset through the sequence loader
@@ -469,8 +681,26 @@ def main(argv=None):
                 action_scores.update(kp_div=[], div_mse=[])
         if args.motion_metrics:
             motion_scores = {'kp_l2': []} if args.samples < 2 else {'kp_l2': [], 'kp_div': [], 'div_mse': []}
+        drive_scores = {m: [] for m in drive_modes if m != 'transfer'} if drive_modes and args.metrics else None
+        n_self_driven = 0
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
+            if args.drive_only:              # the driven rollouts alone: no own rollout, so no draws and nothing of what they write
+                real_flat = batch['real_im_seq'].reshape(bsz * n_frames, *batch['real_im_seq'].shape[2:]) if args.metrics else None
+                if not args.no_save:
+                    image, real = batch['image'].cpu().numpy(), batch['real_im_seq'].cpu().numpy()
+                    for batch_idx in range(bsz):
+                        d = osp.join(args.save_dir, '%04d' % (sample_idx + batch_idx))
+                        os.makedirs(d, exist_ok=True)
+                        _save_img(osp.join(d, 'input_im.png'), image[batch_idx], rescale=True)
+                        _save_img_sequence(osp.join(d, 'real_seq'), real[batch_idx], rescale=True)
+                driven = _Drive(kpx_amd, model, drive_modes, args.drive_scaled, sheet_frames, batch, False, not args.no_save, dev)
+                frames += driven.run(args.save_dir, sample_idx, real_flat, drive_scores)
+                if not args.no_save:
+                    driven.write_sheet(args.save_dir, sample_idx)
+                n_self_driven += bsz if 'transfer' in drive_modes and bsz == 1 else 0
+                sample_idx += bsz
+                continue
             if args.metrics:
                 real_seq = batch['real_im_seq']
                 n_frames = real_seq.shape[1]
@@ -535,6 +765,16 @@ def main(argv=None):
                         _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                         _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                         sample_idx += 1
+                if drive_modes and draw == 0:    # once per batch: the driven rollouts do not depend on z (their graphs are their own:
+                    # this draw's own outputs stay), before the sweep replays the own rollout's graph
+                    first = sample_idx - bsz if not args.no_save else 0
+                    driven = _Drive(kpx_amd, model, drive_modes, args.drive_scaled, sheet_frames, batch, True, not args.no_save, dev)
+                    if not args.no_save:
+                        driven.paste('model', driven.image, outputs['pred_im_seq'].contiguous())
+                    frames += driven.run(args.save_dir, first, real_flat if args.metrics else None, drive_scores)
+                    if not args.no_save:
+                        driven.write_sheet(args.save_dir, first)
+                    n_self_driven += bsz if 'transfer' in drive_modes and bsz == 1 else 0
                 if sweep is not None:        # after everything that reads this draw's own rollout: the sweep replays the same graph
                     frames += sweep.run(draw, z)
                     if draw == 0 and not args.no_save:
@@ -545,8 +785,13 @@ def main(argv=None):
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
         if actions and not args.no_save:
             _write_actions_json(args.save_dir, actions, sheet_frames, True, (model.image_size, model.image_size))
-        if args.metrics:
-            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores)
+        if drive_modes and not args.no_save:
+            _write_drive_json(args.save_dir, _drive_rows(drive_modes, True, not args.drive_only), sheet_frames,
+                              (model.image_size, model.image_size), drive_modes, args.drive_scaled, n_self_driven)
+        if args.metrics and args.drive_only:
+            _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
+        elif args.metrics:
+            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)
@@ -554,6 +799,19 @@ def main(argv=None):
         im = (rs.randint(0, 256, size=(bsz, 128, 128, 3)).astype(np.float32) / 255.0 * 2.0 - 1.0)
         act = np.eye(n_action, dtype=np.float32)[rs.randint(0, n_action, size=bsz)]
         image = torch.from_numpy(im).to(dev)
+        if args.drive_only:                  # hold alone, without the model's own rollout
+            if not args.no_save:
+                for batch_idx in range(bsz):
+                    d = osp.join(args.save_dir, '%04d' % (sample_idx + batch_idx))
+                    os.makedirs(d, exist_ok=True)
+                    _save_img(osp.join(d, 'input_im.png'), im[batch_idx], rescale=True)
+            driven = _Drive(kpx_amd, model, drive_modes, False, sheet_frames, {'image': image, 'action_code': torch.from_numpy(act).to(dev)},
+                            False, not args.no_save, dev)
+            frames += driven.run(args.save_dir, sample_idx, None, None)
+            if not args.no_save:
+                driven.write_sheet(args.save_dir, sample_idx)
+            sample_idx += bsz
+            continue
         z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None       # --actions: shared with the sweep below
         outputs = model.run(None, {'image': image, 'action_code': torch.from_numpy(act).to(dev)}, z=z)
         frames += bsz * 32
@@ -569,6 +827,15 @@ def main(argv=None):
                 _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                 _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                 sample_idx += 1
+        if drive_modes:
+            first = sample_idx - bsz if not args.no_save else 0
+            driven = _Drive(kpx_amd, model, drive_modes, False, sheet_frames, {'image': image, 'action_code': torch.from_numpy(act).to(dev)},
+                            True, not args.no_save, dev)
+            if not args.no_save:
+                driven.paste('model', driven.image, outputs['pred_im_seq'].contiguous())
+            frames += driven.run(args.save_dir, first, None, None)
+            if not args.no_save:
+                driven.write_sheet(args.save_dir, first)
         if actions:
             sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, image, None, not args.no_save, 1, None, dev)
             frames += sweep.run(0, z)
@@ -576,6 +843,9 @@ def main(argv=None):
                 sweep.write_sheets(args.save_dir, sample_idx - bsz)
     if actions and not args.no_save:
         _write_actions_json(args.save_dir, actions, sheet_frames, False, (model.image_size, model.image_size))
+    if drive_modes and not args.no_save:
+        _write_drive_json(args.save_dir, _drive_rows(drive_modes, False, not args.drive_only), sheet_frames,
+                          (model.image_size, model.image_size), drive_modes, False, 0)
     torch.cuda.synchronize()
     print('iteration through synthetic set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
 

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 14
+#define KPX_ABI_VERSION 15
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -399,6 +399,26 @@ int kpx_keypoint_draw_metrics_f32(const float* pts /*[D,N,T,K,2]*/, const float*
 enum { KPX_SHEET_UNIT = 0, KPX_SHEET_RAW = 1 };
 int kpx_sheet_paste_u8_f32(const float* src /*[B,F,H,W,C]*/, int B, int F, int H, int W, int C, const int* frames /*host [J]*/, int J,
                            uint8_t* canvas /*[B,rows*H,cols*W,3]*/, int rows, int cols, int row, int col, int premap, void* stream);
+
+/* ---- key-point retargeting (FinalModel.run(drive=...), evaluate.py --drive), DESIGN.md sections 2 and 4.4: the key-point sequence of a
+ * rollout whose motion comes from outside the motion generator.  src_first fp32 [B,K,2]: the source images' detected key points; drv_first
+ * fp32 [B,K,2] and drv_seq fp32 [B,T,K,2]: the drivers' key points at frame 0 and at frames 1..T; out fp32 [B,T,K,2].  Sample b is driven by
+ * sample j = (b + shift) mod B.  For every (b, t, k, axis):
+ *   KPX_RETARGET_HOLD             out = src_first[b,k]                                                      (a bit copy)
+ *   KPX_RETARGET_ABSOLUTE         out = drv_seq[j,t,k]                                                      (a bit copy)
+ *   KPX_RETARGET_RELATIVE         out = src_first[b,k] + (drv_seq[j,t,k] - drv_first[j,k])
+ *   KPX_RETARGET_RELATIVE_SCALED  out = src_first[b,k] + s_b * (drv_seq[j,t,k] - drv_first[j,k])
+ * s_b = sqrt(v_src / v_drv) with v = sum_k |p_k - c|^2 and c = (sum_k p_k) / K of src_first[b] and of drv_first[j]; s_b = 1 unless both v
+ * are finite and > 0.  The last two modes in fp64, every operation rounded once (no fma), the sums in the order k = 0..K-1, the result
+ * rounded to fp32 once, at the store.  A sample reads its own source and its own driver alone: non-finite inputs reach the outputs that
+ * read them and no others.  Pointers a mode does not read may be NULL (HOLD: drv_first, drv_seq; ABSOLUTE: src_first, drv_first).
+ *   Limits: B, T >= 1, 1 <= K <= 1024, 0 <= shift < B, B*T*K*2 < 2^31; every pointer the mode uses 4-byte aligned.  KPX_EINVAL before any
+ *   device call for anything else, a null pointer the mode uses or an unknown mode.
+ * One launch, one workgroup per sample; 16-byte accesses when K is even and every pointer the mode uses is 16-byte aligned, 4-byte accesses
+ * otherwise -- the same values on both paths.  No allocation, copy, synchronisation or atomics (capturable).  Added in ABI version 15. */
+enum { KPX_RETARGET_HOLD = 0, KPX_RETARGET_ABSOLUTE = 1, KPX_RETARGET_RELATIVE = 2, KPX_RETARGET_RELATIVE_SCALED = 3 };
+int kpx_points_retarget_f32(const float* src_first /*[B,K,2]*/, const float* drv_first /*[B,K,2]*/, const float* drv_seq /*[B,T,K,2]*/,
+                            int B, int T, int K, int shift, int mode, float* out /*[B,T,K,2]*/, void* stream);
 
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */

@@ -6,6 +6,10 @@ Outputs are the tensors evaluate.py saves.  With ``point_maps=True`` they includ
 (``model_utils.render_point_maps``).  The palette ``self.colors`` is the reference's ``get_n_colors`` (:37) drawn from
 ``random.Random(colors_seed)``: the reference draws it from the unseeded module-level ``random``, so ``colors_seed=s`` reproduces its
 palette after ``random.seed(s)``.  ``z`` can be injected for deterministic parity tests (the reference draws it unseeded, :71).
+
+``run(..., drive=...)`` is the driven rollout (not in the reference): the 32 key-point frames come from outside --
+``ops.points_retarget`` on the detected key points and a driver's -- in the place of ``vae_decoder``, and everything after them is the same
+code.  It isolates the translator: no z is drawn or read and the stage-2 variables are not touched.
 """
 import logging
 import os
@@ -58,9 +62,15 @@ class FinalModel(BaseModel):
             networks.translator(joint, False, final_res=r, cin=emb[-2].shape[-1] + 2 * k)
         self.store.materialise()
 
-    def run(self, sess, feed_dict, z=None):
+    def run(self, sess, feed_dict, z=None, drive=None):
         """reference run (:124-125).  feed_dict: {'image': [B,H,W,3] in [-1,1], 'action_code': [B,n_action] one-hot,
-        optional 'real_im_seq', 'real_seq'}.  z: the VAE latent [B, vae_dim]; drawn from N(0,1) when not given (:71)."""
+        optional 'real_im_seq', 'real_seq'}.  z: the VAE latent [B, vae_dim]; drawn from N(0,1) when not given (:71).
+        drive: {'mode': 'hold' | 'absolute' | 'relative', 'first': [B,K,2], 'seq': [B,32,K,2], 'shift': int, 'scaled': bool} -- the 32
+        key-point frames come from ``ops.points_retarget`` on the detected key points instead of the motion generator ('first' and 'seq'
+        are the driver's key points at frame 0 and at frames 1..32, absent for 'hold'; 'first' is read by 'relative' alone; sample b is
+        driven by sample (b + shift) mod B).  z and 'action_code' are then neither drawn nor read."""
+        if drive is not None:
+            return self._run_driven(feed_dict, drive)
         im, act = feed_dict['image'], feed_dict['action_code']
         if not (GRAPH and not self._graph_failed and im.is_cuda and im.dtype == torch.float32):
             return self._run_eager(feed_dict, z)
@@ -105,18 +115,94 @@ class FinalModel(BaseModel):
         res['real_im_seq'] = feed_dict.get('real_im_seq')
         return res
 
-    def _run_eager(self, feed_dict, z=None):
-        """The rollout enqueued launch by launch (also the function a capture records)."""
+    def _check_drive(self, im, drive):
+        """-> (mode, shift, scaled, {'first' / 'seq': contiguous tensors the mode reads}); everything ops.points_retarget would refuse is
+        refused here, before any copy into a graph's static buffers"""
+        if not isinstance(drive, dict) or set(drive) - {'mode', 'first', 'seq', 'shift', 'scaled'}:
+            raise ops._lib.KpxError("FinalModel.run: drive is a dict of 'mode', 'first', 'seq', 'shift' and 'scaled' (got %r)"
+                                    % (sorted(drive) if isinstance(drive, dict) else type(drive).__name__,))
+        mode, shift, scaled = drive.get('mode'), drive.get('shift', 0), drive.get('scaled', False)
+        b, k, t = im.shape[0], self.n_points, N_FUTURE_FRAMES
+        if mode not in ops.RETARGET_MODES:
+            raise ops._lib.KpxError('FinalModel.run: drive mode must be one of %s (got %r)' % (sorted(ops.RETARGET_MODES), mode))
+        if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift < b:
+            raise ops._lib.KpxError('FinalModel.run: drive shift must be an integer in [0, B = %d) (got %r)' % (b, shift))
+        if not isinstance(scaled, bool) or (scaled and mode != 'relative'):
+            raise ops._lib.KpxError("FinalModel.run: drive scaled is a bool and belongs to mode 'relative' (got %r for %r)" % (scaled, mode))
+        if mode == 'hold' and ('first' in drive or 'seq' in drive):
+            raise ops._lib.KpxError("FinalModel.run: drive mode 'hold' takes no 'first' or 'seq'")
+        tensors = {}
+        for name, shape in (('first', (b, k, 2)), ('seq', (b, t, k, 2))):
+            if mode == 'hold' or (name == 'first' and mode != 'relative'):
+                continue
+            v = drive.get(name)
+            if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != im.device or tuple(v.shape) != shape:
+                raise ops._lib.KpxError('FinalModel.run: drive %r must be an fp32 tensor %s on %s (got %s)'
+                                        % (name, list(shape), im.device, '%s %s on %s' % (tuple(v.shape), v.dtype, v.device)
+                                           if isinstance(v, torch.Tensor) else type(v).__name__))
+            tensors[name] = v.contiguous()
+        return mode, shift, scaled, tensors
+
+    def _run_driven(self, feed_dict, drive):
+        """run(drive=...): as run(), with the driver's key points in the place of z.  The scalars (mode, shift, scaled) are launch arguments
+        of the captured points_retarget, so they are part of the graph's key."""
+        im, act = feed_dict['image'], feed_dict.get('action_code')
+        mode, shift, scaled, tensors = self._check_drive(im, drive)
+        eager = lambda image, ts: self._run_eager({'image': image}, drive=dict(ts, mode=mode, shift=shift, scaled=scaled))
+        if not (GRAPH and not self._graph_failed and im.is_cuda and im.dtype == torch.float32):
+            return dict(eager(im, tensors), real_im_seq=feed_dict.get('real_im_seq'))
+        key = (tuple(im.shape), None if act is None else tuple(act.shape), im.device.index, mode, shift, scaled)
+        feeds = dict(tensors, image=im)
+        ent = self._graphs.get(key)
+        if ent is not None and ent[3] != self.store.version:         # the parameters changed since the capture: as in run()
+            del self._graphs[key]
+            self._eager_runs[key] = 0
+            ent = None
+        if ent is None:
+            if self._eager_runs.get(key, 0) < 1:                     # one eager run first, as in run()
+                self._eager_runs[key] = 1
+                return dict(eager(im, tensors), real_im_seq=feed_dict.get('real_im_seq'))
+            static = {k_: torch.empty_like(v, memory_format=torch.contiguous_format) for k_, v in feeds.items()}
+            for k_, v in feeds.items():
+                static[k_].copy_(v)
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph):
+                    out = eager(static['image'], {k_: static[k_] for k_ in tensors})
+            except Exception as e:          # noqa: BLE001 -- whatever the runtime refuses: stay on the eager path
+                log.warning('HIP graph capture of the driven rollout failed (%s: %s); continuing with eager launches', type(e).__name__, e)
+                self._graph_failed = True
+                torch.cuda.synchronize(im.device)
+                self.store.touch()
+                ops.reset_after_failed_capture()
+                return dict(eager(im, tensors), real_im_seq=feed_dict.get('real_im_seq'))
+            ent = self._graphs[key] = (graph, static, out, self.store.version)
+        graph, static, out, _ = ent
+        for k_, v in feeds.items():
+            v = v.contiguous()
+            ops.flat_copy_raw(v.data_ptr(), static[k_].data_ptr(), v.numel())
+        graph.replay()
+        res = dict(out)
+        res['im'] = im
+        res['real_im_seq'] = feed_dict.get('real_im_seq')
+        return res
+
+    def _run_eager(self, feed_dict, z=None, drive=None):
+        """The rollout enqueued launch by launch (also the function a capture records).  ``drive``: a checked drive dict (_check_drive)."""
         im = feed_dict['image'].contiguous()
-        act = feed_dict['action_code'].contiguous()
+        act = feed_dict['action_code'].contiguous() if drive is None else None
         b, r, k, t = im.shape[0], self.image_size, self.n_points, N_FUTURE_FRAMES
         dev = im.device
         with variables.as_default(self.store), torch.no_grad():
             emb = networks.image_encoder(im, False)[-2]                                          # :61-62
             first_pt = networks.pose_encoder(im, k, False, final_res=r)                          # :68
-            if z is None:
-                z = torch.randn((b, self.vae_dim), dtype=torch.float32, device=dev)              # :71
-            pred_seq = networks.vae_decoder(z, first_pt.reshape(b, 2 * k), act, self.cell_info, self.vae_dim, k)   # :72-77
+            if drive is not None:             # the driven rollout: the key points come from outside, no z
+                pred_seq = ops.points_retarget(first_pt.reshape(b, k, 2).contiguous(), drive['mode'], drive.get('first'), drive.get('seq'),
+                                               shift=drive['shift'], scaled=drive['scaled'], frames=t if drive['mode'] == 'hold' else None)
+            else:
+                if z is None:
+                    z = torch.randn((b, self.vae_dim), dtype=torch.float32, device=dev)          # :71
+                pred_seq = networks.vae_decoder(z, first_pt.reshape(b, 2 * k), act, self.cell_info, self.vae_dim, k)   # :72-77
             pred_pts = pred_seq.reshape(b * t, k, 2)
             # joint embedding [B*T, h, h, C+2K (+pad)]: tiled image embedding ‖ tiled current map ‖ per-frame predicted map
             c = emb.shape[-1]

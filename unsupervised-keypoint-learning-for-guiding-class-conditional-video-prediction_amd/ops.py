@@ -1621,6 +1621,65 @@ def sheet_paste(canvas, src, frames, row, col, premap):
     return canvas
 
 
+RETARGET_MODES = {'hold': 0, 'absolute': 1, 'relative': 2}                        # = KPX_RETARGET_* of include/kpx.h ('relative' + scaled: 3)
+RETARGET_MAX_POINTS = 1024
+
+
+def points_retarget(src_first, mode, drv_first=None, drv_seq=None, shift=0, scaled=False, frames=None, out=None):
+    """The key-point sequence of a driven rollout (DESIGN.md section 2): src_first contiguous fp32 [B,K,2], the source images' key points;
+    drv_first [B,K,2] and drv_seq [B,T,K,2], the drivers' key points at frame 0 and at frames 1..T; sample b is driven by sample
+    (b + shift) mod B -> out fp32 [B,T,K,2]:
+      'hold'      out[b,t] = src_first[b] (T from ``frames``; takes no driver)
+      'absolute'  out[b,t] = drv_seq[j,t] (drv_first is not read and may be omitted)
+      'relative'  out[b,t] = src_first[b] + s_b * (drv_seq[j,t] - drv_first[j]); s_b = 1, or with ``scaled`` the ratio of the spreads of
+                  the two frame-0 constellations about their means (1 when either is 0 or non-finite)
+    'hold' and 'absolute' are bit copies, 'relative' is computed in fp64 and rounded once.  1 <= K <= 1024, 0 <= shift < B,
+    B*T*K*2 < 2^31.  One launch on the current stream; capturable."""
+    if mode not in RETARGET_MODES:
+        raise _lib.KpxError('points_retarget: mode must be one of %s (got %r)' % (sorted(RETARGET_MODES), mode))
+    if scaled and mode != 'relative':
+        raise _lib.KpxError("points_retarget: scaled belongs to mode 'relative' (got %r)" % (mode,))
+    if mode == 'hold':
+        if drv_first is not None or drv_seq is not None:
+            raise _lib.KpxError("points_retarget: mode 'hold' takes no driver")
+        drv_first = None
+    elif drv_seq is None or (mode == 'relative' and drv_first is None):
+        raise _lib.KpxError('points_retarget: mode %r needs %s' % (mode, 'drv_first and drv_seq' if mode == 'relative' else 'drv_seq'))
+    elif frames is not None:
+        raise _lib.KpxError("points_retarget: frames belongs to mode 'hold'; mode %r takes T from drv_seq" % (mode,))
+    for name, t, dim in (('src_first', src_first, 3), ('drv_first', drv_first, 3), ('drv_seq', drv_seq, 4), ('out', out, 4)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got %s for points_retarget\'s %s); there is no CPU fallback'
+                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
+        if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous() or t.shape[-1] != 2 or t.device != src_first.device:
+            raise _lib.KpxError('points_retarget: %s must be a contiguous fp32 tensor of %d dimensions ending in 2 on %s (got %s %s on %s, '
+                                'contiguous=%s)' % (name, dim, src_first.device, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
+    b, k, _ = src_first.shape
+    if mode == 'hold':
+        if isinstance(frames, bool) or not isinstance(frames, int):
+            raise _lib.KpxError("points_retarget: mode 'hold' takes the number of frames as frames= (got %r)" % (frames,))
+        t_ = frames
+    else:
+        t_ = drv_seq.shape[1]
+        if tuple(drv_seq.shape) != (b, t_, k, 2) or (drv_first is not None and tuple(drv_first.shape) != (b, k, 2)):
+            raise _lib.KpxError('points_retarget: src_first %s, drv_first %s and drv_seq %s must be [B,K,2], [B,K,2] and [B,T,K,2] of one B and K'
+                                % (tuple(src_first.shape), None if drv_first is None else tuple(drv_first.shape), tuple(drv_seq.shape)))
+    if b < 1 or t_ < 1 or not 1 <= k <= RETARGET_MAX_POINTS or b * t_ * k * 2 >= 2 ** 31:
+        raise _lib.KpxError('points_retarget: needs B, T >= 1, 1 <= K <= %d and B*T*K*2 < 2^31 (got B = %d, T = %d, K = %d)'
+                            % (RETARGET_MAX_POINTS, b, t_, k))
+    if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift < b:
+        raise _lib.KpxError('points_retarget: shift must be an integer in [0, B = %d) (got %r)' % (b, shift))
+    if out is None:
+        out = torch.empty((b, t_, k, 2), dtype=torch.float32, device=src_first.device)
+    elif tuple(out.shape) != (b, t_, k, 2):
+        raise _lib.KpxError('points_retarget: out must be %s (got %s)' % ([b, t_, k, 2], tuple(out.shape)))
+    check(lib.kpx_points_retarget_f32(src_first.data_ptr(), _ptr(drv_first) if mode == 'relative' else None, _ptr(drv_seq), b, t_, k, shift,
+                                      RETARGET_MODES[mode] + (1 if scaled else 0), out.data_ptr(), _stream()), 'kpx_points_retarget_f32')
+    return out
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
