@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -46,6 +46,17 @@
 10. The configs[4] rollout (B = 64, replayed HIP graphs) as the model's own rollout and as a driven rollout of each mode -- labels
    (absolute, shift 0), hold, transfer (relative, shift 1) and transfer scaled --, the five alternated in one process; median ms per rollout
    of each and the difference to the model's own in ms and %.
+
+``--frechet`` measures the Fréchet distance's device passes (evaluate.py --frechet) instead:
+
+11. kpx_feature_pool_f64 alone on the five VGG19 feature shapes of 512 frames at 128x128: device-event time of each call (its two launches)
+   after warm-up; median us, bytes/s of the one input read once and the fraction of the copy rate, beside a float4 device copy of the same
+   tensor (read + write bytes) and beside kpx_feature_pair_metrics_f32 on the same shape (two inputs), all in this process.
+12. kpx_moments_add_f64 alone: M = 2 048 rows (the frames of a configs[4] rollout) at D = 64, 128, 256, 512 and M = 64 rows (its rollouts) at
+   D = 1024; median, minimum and maximum us and the fp64 GFLOP/s (2 M D^2).
+13. The configs[4] rollout scored through vgg.FeatureScorer without and with the accumulators (frechet=: pooling, both levels' moments, into
+   the two accumulators of draw 0), alternated in one process beside the bare rollout; median ms of each, the cost of --frechet on top of
+   --vgg-metrics in ms and %.
 
 Prints one JSON line.
 """
@@ -191,6 +202,81 @@ def vgg_rollout_leg(dev, rollouts):
             'real_features_gb': round(sum(f.numel() * 4 for c in scorer.real for f in c) / 1e9, 2), 'real_features_first_ms': round(real_ms, 1),
             'off_ms': round(off, 3), 'on_ms': round(on, 3), 'delta_ms': round(on - off, 3), 'overhead_pct': round(100 * (on - off) / off, 2),
             'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
+
+
+def frechet_kernel_leg(dev, launches):
+    from kpx_amd import ops
+    pool, moments = [], []
+    for name, hw, c in VGG_SHAPES:
+        g = torch.Generator(device=dev).manual_seed(2)
+        a = torch.randn((VGG_PAIRS, hw, hw, c), generator=g, device=dev).relu_()
+        b = torch.randn((VGG_PAIRS, hw, hw, c), generator=g, device=dev).relu_()
+        out = torch.empty((VGG_PAIRS, c), dtype=torch.float64, device=dev)
+        pair_out = torch.empty((VGG_PAIRS, 2), dtype=torch.float32, device=dev)
+        nbytes = a.numel() * 4
+        row = {'layer': name, 'shape': [VGG_PAIRS, hw, hw, c], 'input_mb': round(nbytes / 1e6, 1), 'launches': launches,
+               'workspace_mb': round(ops.lib.kpx_feature_pool_workspace_bytes(VGG_PAIRS, hw, hw, c) / 1e6, 2)}
+        for key, moved, fn in (('pool', nbytes, lambda: ops.feature_pool(a, out=out)), ('copy', 2 * nbytes, lambda: b.copy_(a)),
+                               ('pair', 2 * nbytes, lambda: ops.feature_pair_metrics(a, b, out=pair_out))):
+            us = _event_times(fn, launches, dev)
+            med = statistics.median(us)
+            row[key] = {'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                        'gb_per_s': round(moved / (med * 1e-6) / 1e9, 1), 'frac_of_copy_rate': round(moved / (med * 1e-6) / COPY_RATE, 3)}
+        assert bool(torch.isfinite(out).all())
+        pool.append(row)
+        del a, b
+        torch.cuda.empty_cache()
+    for m, d in ((N_FRAMES, 64), (N_FRAMES, 128), (N_FRAMES, 256), (N_FRAMES, 512), (B, 1024)):
+        g = torch.Generator(device=dev).manual_seed(3)
+        x = torch.randn((m, d), generator=g, device=dev, dtype=torch.float64)
+        s, o = torch.zeros((d,), dtype=torch.float64, device=dev), torch.zeros((d, d), dtype=torch.float64, device=dev)
+        us = _event_times(lambda: ops.moments_add(x, s, o), launches, dev)
+        med = statistics.median(us)
+        assert bool(torch.isfinite(o).all())
+        moments.append({'M': m, 'D': d, 'launches': launches, 'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                        'fp64_gflops': round(2.0 * m * d * d / (med * 1e-6) / 1e9, 1)})
+    return {'feature_pool': pool, 'moments_add': moments}
+
+
+def frechet_rollout_leg(dev, rollouts):
+    import kpx_amd
+    from kpx_amd import frechet as K, vgg as V
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    real = torch.rand((N_FRAMES, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    out = torch.empty((N_FRAMES, len(V.FEATURE_LAYERS), 2), dtype=torch.float32, device=dev)
+    feed = {'image': im, 'action_code': act}
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    net = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev)
+    dims = [int(net.params[name][0].shape[3]) for name in V.FEATURE_LAYERS]
+    accs = [K.FrechetAccumulator(dims, dev) for _ in range(4)]
+    scorer = V.FeatureScorer(net, real, frechet=K.FrechetSplit(accs[:2]), frames_per_video=32)
+    for _ in range(3):                                        # eager, capture, one replay
+        o = fm.run(None, feed, z=z)
+    scorer(o['pred_im_seq'].reshape(N_FRAMES, RES, RES, 3), out=out, frechet=accs[2:])
+    torch.cuda.synchronize(dev)
+    modes = ('rollout', 'vgg', 'vgg_frechet')
+    ms = {m: [] for m in modes}
+    for _ in range(rollouts):
+        for m in modes:
+            t0 = time.perf_counter()
+            o = fm.run(None, feed, z=z)
+            if m != 'rollout':
+                scorer(o['pred_im_seq'].reshape(N_FRAMES, RES, RES, 3), out=out, frechet=accs[2:] if m == 'vgg_frechet' else None)
+            torch.cuda.synchronize(dev)
+            ms[m].append((time.perf_counter() - t0) * 1e3)
+    stats = accs[2].stats()
+    assert all(s['n'] == N_FRAMES * (1 + rollouts) for s in stats['frame']) and all(s['n'] == B * (1 + rollouts) for s in stats['video'])
+    bare, vgg, both = (statistics.median(ms[m]) for m in modes)
+    return {'batch': B, 'frames': N_FRAMES, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 1, 'accumulators_per_call': 2,
+            'rollout_ms': round(bare, 3), 'vgg_ms': round(vgg, 3), 'vgg_frechet_ms': round(both, 3), 'delta_ms': round(both - vgg, 3),
+            'overhead_on_vgg_pct': round(100 * (both - vgg) / vgg, 2), 'overhead_on_rollout_pct': round(100 * (both - vgg) / bare, 2),
+            'rollout_ms_all': [round(v, 2) for v in ms['rollout']], 'vgg_ms_all': [round(v, 2) for v in ms['vgg']],
+            'vgg_frechet_ms_all': [round(v, 2) for v in ms['vgg_frechet']]}
 
 
 MOTION_DRAWS = 4
@@ -509,9 +595,10 @@ def main():
     ap.add_argument('--motion', action='store_true', help='measure the motion metrics (draw diversity, key-point error) instead')
     ap.add_argument('--actions', action='store_true', help='measure the class sweep (contact-sheet paste, sheets and class scores) instead')
     ap.add_argument('--drive', action='store_true', help='measure the driven rollout (key-point retargeting, every drive mode) instead')
+    ap.add_argument('--frechet', action='store_true', help="measure the Fréchet distance's pooling and moment kernels and its cost per rollout instead")
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions + args.drive > 1:
-        ap.error('--vgg, --motion, --actions and --drive are four measurements: pass one')
+    if args.vgg + args.motion + args.actions + args.drive + args.frechet > 1:
+        ap.error('--vgg, --motion, --actions, --drive and --frechet are five measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
@@ -519,6 +606,12 @@ def main():
         res = {'vgg_kernel': vgg_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()
         res['vgg_rollout_c4'] = vgg_rollout_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
+    if args.frechet:
+        res = {'frechet_kernels': frechet_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['frechet_rollout_c4'] = frechet_rollout_leg(dev, args.rollouts)
         print(json.dumps(res))
         return
     if args.actions:

@@ -3,7 +3,7 @@
 
     python evaluate.py --config configs/penn.yaml --checkpoint_stage1 S1.npz --checkpoint_stage2 S2.npz [--save_dir results/eval]
                        [--synthetic N] [--colors_seed S] [--no-save]
-                       [--metrics [--samples N] [--vgg-metrics [--synthetic-vgg]] [--motion-metrics]]
+                       [--metrics [--samples N] [--vgg-metrics [--synthetic-vgg] [--frechet]] [--motion-metrics]]
                        [--actions all|i,j,k [--sheet-frames f,g,h]]
                        [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
 
@@ -23,6 +23,18 @@ fresh z; the PNGs come from draw 0.
 network of ``paths.vggnet`` -- ``--synthetic-vgg`` for He-normal weights --, the real frames' features computed once per batch and reused
 by every draw): ``vgg_cos`` and ``vgg_l1`` [samples, draws, 32] and their per-layer parts ``vgg_cos_layers`` / ``vgg_l1_layers``
 [samples, draws, 32, 5] in metrics.npz, ``vgg_cos`` / ``vgg_l1`` blocks in metrics.json.  DESIGN.md section 2 has the definition.
+
+``--frechet`` (with ``--metrics --vgg-metrics``) adds a set-level score, which does not punish a draw of z for being a plausible but different
+future: the Frechet distance between the feature distributions of the real and the predicted frames, in the feature space of the same VGG19
+(this project's own quantity: NOT FID and NOT FVD, which are defined on Inception / I3D features, and not comparable with published figures).
+The features the scorer computes anyway are pooled over positions (``kpx_amd.ops.feature_pool``) and their fp64 moments accumulated on the
+device (``kpx_amd.ops.moments_add``, ``kpx_amd.frechet.FrechetAccumulator``) over the whole test set, per layer at two levels: frames, and
+rollouts of 32 frames (mean pooled feature and mean absolute frame-to-frame change).  metrics.npz gains ``vgg_fd_layers``,
+``vgg_fvd_layers`` (all draws against all real frames), ``vgg_fd_draw0_layers`` (the written PNGs) and ``vgg_fd_floor_layers`` /
+``vgg_fvd_floor_layers`` (the real even-numbered samples against the real odd-numbered ones: the finite-sample noise floor), each [5], NaN
+where a set has fewer than two rows; metrics.json a ``frechet`` block (``summarise_frechet``); and ``<save_dir>/frechet.npz`` holds n, mean
+and covariance per set, layer and level (about 120 MB at full width), which ``python -m kpx_amd.frechet a.npz b.npz`` compares later without
+a GPU.  The rollouts of ``--actions`` and ``--drive`` are not accumulated.
 
 ``--motion-metrics`` (with ``--metrics``; at most 4096 ``--samples``) adds what needs no network: ``kp_l2`` [samples, draws, 32], the mean
 distance of each draw's predicted key points to the pseudo labels of the real frames (``kpx_amd.ops.keypoint_draw_metrics``), and with
@@ -165,6 +177,42 @@ def summarise_metrics(ssim, psnr, mse, extras=None, motion=None):
         with np.errstate(invalid='ignore'):
             out[name] = {'mean': _json_num(x.mean()), 'per_frame': [_json_num(v) for v in x.mean(axis=0)]}
     return out
+
+
+FRECHET_DEFINITION = (
+    'frechet: Frechet distance |m1 - m2|^2 + tr C1 + tr C2 - 2 tr (C1 C2)^(1/2) between the Gaussians fitted to two sets of feature vectors '
+    'of the same VGG19 and 8-bit frames as vgg_cos, per layer of vgg_layers; vgg_fd / vgg_fvd are the values of conv5_4. This is the '
+    'project\'s own VGG19 quantity: not FID/FVD (those use Inception / I3D features) and not comparable with published figures. Frame level '
+    '(fd): one vector per frame, the mean of the layer\'s features over positions (D = C). Video level (fvd): one vector per rollout of T '
+    'frames, concat(mean_t p_t, mean_t |p_(t+1) - p_t|) of its pooled frames p (D = 2 C; the second half is 0 for a frozen pose). Pooling '
+    'and the first and second moments are accumulated in float64 on the device over the whole test set; cov = (sum x x^T - n mu mu^T) / '
+    '(n - 1). fd, fvd: the predictions of all draws of z against all real frames; fd_draw0: draw 0 (the written PNGs) alone; fd_floor, '
+    'fvd_floor: the real even-numbered samples against the real odd-numbered ones, the finite-sample noise floor that gives the others a '
+    'scale. A value is null where a set has fewer than two rows; rank_deficient marks layers where a set has n <= D rows, whose covariance '
+    'is singular and whose distance is a lower-quality estimate. The distance is not clamped at 0.')
+
+
+def summarise_frechet(stats):
+    """-> (the vgg_f*_layers arrays of metrics.npz, each float64 [layers], the ``frechet`` block of metrics.json); numpy only.  stats: the
+    ``FrechetAccumulator.stats()`` of the sets 'real', 'pred', 'pred_draw0', 'real_even' and 'real_odd'."""
+    from kpx_amd import frechet as F
+    pairs = {'vgg_fd_layers': ('pred', 'real', 'frame'), 'vgg_fvd_layers': ('pred', 'real', 'video'),
+             'vgg_fd_draw0_layers': ('pred_draw0', 'real', 'frame'),
+             'vgg_fd_floor_layers': ('real_even', 'real_odd', 'frame'), 'vgg_fvd_floor_layers': ('real_even', 'real_odd', 'video')}
+    arrays = {name: F.layer_distances(stats[a], stats[b], level) for name, (a, b, level) in pairs.items()}
+    nums = lambda x: [_json_num(v) for v in x]
+    dims = {level: [s['mean'].size if s['mean'] is not None else None for s in stats['real'][level]] for level in F.LEVELS}
+    count = lambda name, level: int(stats[name][level][0]['n']) if stats[name][level] else 0
+    head = len(arrays['vgg_fd_layers']) - 1                                      # conv5_4, the last layer of VGG_FEATURE_LAYERS
+    block = {'definition': FRECHET_DEFINITION, 'vgg_layers': list(VGG_FEATURE_LAYERS),
+             'vgg_fd': _json_num(arrays['vgg_fd_layers'][head]), 'vgg_fvd': _json_num(arrays['vgg_fvd_layers'][head]),
+             'n_real': count('real', 'frame'), 'n_pred': count('pred', 'frame'),
+             'n_real_videos': count('real', 'video'), 'n_pred_videos': count('pred', 'video'), 'dims': dims,
+             'rank_deficient': {level: [d is None or min(count('real', level), count('pred', level)) <= d for d in dims[level]]
+                                for level in F.LEVELS}}
+    for name, x in arrays.items():
+        block[name] = nums(x)
+    return arrays, block
 
 
 ACTIONS_DEFINITION = (
@@ -478,14 +526,16 @@ def _drive_line(blk):
     return 'drive: ' + '; '.join(parts)
 
 
-def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None):
+def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None,
+                   frechet=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
     per batch [B * T]}.
     action_scores (--actions): {'actions': [A], 'own': per batch the action codes [B, n_action], 'kp_l2': per batch [draws, A, B, T]} and for
     two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}.
-    drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}."""
+    drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}.
+    frechet (--frechet): the accumulators {'real_even', 'real_odd', 'pred', 'pred_draw0'}; also writes frechet.npz."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -525,9 +575,24 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     if drive_scores:
         drive_arrays, drive = _drive_arrays(drive_scores, n_frames)
         arrays.update(drive_arrays)
+    frechet_block = None
+    if frechet is not None:
+        from kpx_amd import frechet as F
+        stats = {name: acc.stats() for name, acc in frechet.items()}
+        stats['real'] = F.FrechetAccumulator(frechet['real_even'].dims, 'cpu').merge(frechet['real_even']).merge(frechet['real_odd']).stats()
+        frechet_arrays, frechet_block = summarise_frechet(stats)
+        arrays.update(frechet_arrays)
+        stored = {'layers': np.array(VGG_FEATURE_LAYERS)}
+        for name in ('real', 'pred', 'pred_draw0', 'real_even', 'real_odd'):
+            stored.update(F.stats_arrays(name, stats[name], VGG_FEATURE_LAYERS))
+        os.makedirs(save_dir, exist_ok=True)
+        np.savez(osp.join(save_dir, 'frechet.npz'), **stored)
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
+    if frechet_block is not None:
+        res['definition'] += ' ' + FRECHET_DEFINITION
+        res['frechet'] = frechet_block
     if act is not None:
         res['actions'] = summarise_actions(actions, act['act_own'], act['act_kp_l2'], act.get('act_kp_div'), act.get('act_div_mse'))
     if drive is not None:
@@ -542,6 +607,10 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         line += (', VGG cos %s (best of draws %s), VGG L1 %s (best of draws %s)'
                  % (fmt(res['vgg_cos']['mean'], '%.4f'), fmt(res['vgg_cos']['best_of_draws'], '%.4f'),
                     fmt(res['vgg_l1']['mean'], '%.4f'), fmt(res['vgg_l1']['best_of_draws'], '%.4f')))
+    if frechet_block is not None:
+        line += (', VGG Frechet (not FID/FVD) frames %s (floor %s), videos %s (floor %s)'
+                 % (fmt(frechet_block['vgg_fd'], '%.4g'), fmt(frechet_block['vgg_fd_floor_layers'][-1], '%.4g'),
+                    fmt(frechet_block['vgg_fvd'], '%.4g'), fmt(frechet_block['vgg_fvd_floor_layers'][-1], '%.4g')))
     if motion is not None:
         line += ', key-point L2 %s (best of draws %s)' % (fmt(res['kp_l2']['mean'], '%.4f'), fmt(res['kp_l2']['best_of_draws'], '%.4f'))
         if 'kp_div' in res:
@@ -579,6 +648,11 @@ def main(argv=None):
     parser.add_argument('--vgg-metrics', action='store_true',
                         help='with --metrics: VGG19 feature-space cosine similarity and perceptual L1 per predicted frame (paths.vggnet)')
     parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
+    parser.add_argument('--frechet', action='store_true',
+                        help='with --metrics --vgg-metrics: the Frechet distance between the real and the predicted frames (and rollouts) '
+                             'in the feature space of the same VGG19, with its even / odd noise floor, and <save_dir>/frechet.npz.  This '
+                             "project's own quantity: not FID/FVD, not comparable with published figures.  The rollouts of --actions and "
+                             '--drive are not accumulated')
     parser.add_argument('--motion-metrics', action='store_true',
                         help='with --metrics: key-point error against the pseudo labels and, for --samples >= 2, the diversity of the draws')
     parser.add_argument('--actions', type=str, default=None,
@@ -616,7 +690,7 @@ def main(argv=None):
         if drive_modes is None:
             parser.error('--drive-only keeps the rollouts of --drive alone and needs it')
         for flag, on in (('--samples > 1', args.samples > 1), ('--actions', args.actions is not None), ('--vgg-metrics', args.vgg_metrics),
-                         ('--motion-metrics', args.motion_metrics)):
+                         ('--frechet', args.frechet), ('--motion-metrics', args.motion_metrics)):
             if on:
                 parser.error("--drive-only skips the model's own rollout, which %s is about" % flag)
         if args.metrics and not set(drive_modes) & {'labels', 'hold'}:
@@ -625,6 +699,8 @@ def main(argv=None):
         parser.error('the following arguments are required: --checkpoint_stage2 (unless --drive-only)')
     if args.vgg_metrics and not args.metrics:
         parser.error('--vgg-metrics adds to the scores of --metrics and needs it')
+    if args.frechet and not (args.metrics and args.vgg_metrics):
+        parser.error('--frechet adds to the features of --metrics --vgg-metrics and needs both')
     if args.motion_metrics and not args.metrics:
         parser.error('--motion-metrics adds to the scores of --metrics and needs it')
     if args.motion_metrics and args.samples > MAX_MOTION_DRAWS:
@@ -674,6 +750,11 @@ def main(argv=None):
                                                  random_order=False, randomness=False, with_image_seq=True)
         scores, n_frames = [], 32
         vgg_scores = [] if args.vgg_metrics else None
+        frechet = None
+        if args.frechet:             # moments over the whole test set: the real samples by parity, every draw of the predictions, draw 0
+            dims = [int(vgg.params[name][0].shape[3]) for name in VGG_FEATURE_LAYERS]
+            frechet = {name: kpx_amd.frechet.FrechetAccumulator(dims, dev) for name in ('real_even', 'real_odd', 'pred', 'pred_draw0')}
+        n_scored = 0                                                     # samples scored so far: the parity of a real sample
         motion_scores = action_scores = None
         if actions and args.metrics:
             action_scores = {'actions': actions, 'own': [], 'kp_l2': []}
@@ -708,7 +789,12 @@ def main(argv=None):
                 score = torch.empty((args.samples, bsz * n_frames, 3), dtype=torch.float32, device=dev)
                 scores.append(score)
                 if args.vgg_metrics:         # the real frames' features once per batch, reused by every draw
-                    scorer = kpx_amd.FeatureScorer(vgg, real_flat)
+                    if frechet is not None:
+                        split = kpx_amd.frechet.FrechetSplit([frechet['real_even'], frechet['real_odd']], n_scored)
+                        scorer = kpx_amd.FeatureScorer(vgg, real_flat, frechet=split, frames_per_video=n_frames)
+                    else:
+                        scorer = kpx_amd.FeatureScorer(vgg, real_flat)
+                    n_scored += bsz
                     vgg_score = torch.empty((args.samples, bsz * n_frames, len(VGG_FEATURE_LAYERS), 2), dtype=torch.float32, device=dev)
                     vgg_scores.append(vgg_score)
                 if args.motion_metrics:      # every draw's key points, and two integer accumulators per value of the predicted frames
@@ -732,7 +818,9 @@ def main(argv=None):
                     pred = outputs['pred_im_seq']
                     pred_flat = pred.reshape(bsz * n_frames, *pred.shape[2:])
                     kpx_amd.ops.frame_metrics(pred_flat, real_flat, png8=True, out=score[draw])
-                    if args.vgg_metrics:
+                    if frechet is not None:
+                        scorer(pred_flat, out=vgg_score[draw], frechet=[frechet['pred'], frechet['pred_draw0']] if draw == 0 else frechet['pred'])
+                    elif args.vgg_metrics:
                         scorer(pred_flat, out=vgg_score[draw])
                     if args.motion_metrics:
                         kpx_amd.ops.flat_copy_tensor(outputs['fut_pt_raw'].contiguous(), kp_pred[draw].data_ptr())
@@ -791,7 +879,7 @@ def main(argv=None):
         if args.metrics and args.drive_only:
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
-            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores)
+            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores, frechet)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

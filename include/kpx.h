@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 15
+#define KPX_ABI_VERSION 16
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -379,6 +379,25 @@ int kpx_draw_diversity_f32(const uint32_t* sum, const uint32_t* sumsq, int N, in
                            uint8_t* std_map /*[N,H,W] or NULL*/, void* stream);
 int kpx_keypoint_draw_metrics_f32(const float* pts /*[D,N,T,K,2]*/, const float* real /*[N,T,K,2]*/, int D, int N, int T, int K,
                                   float* l2 /*[D,N,T]*/, float* div /*[N,T] or NULL*/, void* stream);
+
+/* ---- Frechet distance in VGG19 feature space (evaluate.py --frechet), DESIGN.md section 2: the two device passes under
+ * kpx_amd.frechet.FrechetAccumulator.  Both: no allocation, copy or synchronisation (capturable); no atomics; KPX_EINVAL before any device
+ * call for a null or misaligned pointer or an argument out of range.  Added in ABI version 16.
+ *
+ * kpx_feature_pool_f64: f fp32 NHWC [N,H,W,C] contiguous on a 16-byte aligned pointer, C % 4 == 0, 4 <= C <= 512, H and W in [1,1024],
+ *   N >= 1 (kpx_feature_pair_metrics_f32's limits) -> pooled fp64 [N,C], pooled[n,c] = (sum over the H*W positions of f[n,.,.,c]) / (H*W).
+ *   Every fp32 value is converted to fp64 (exactly) before its first addition; nothing is summed in fp32.  Two launches: per-slab fp64
+ *   partials into `work` (kpx_feature_pool_workspace_bytes, 0 for a shape out of range; 8-byte aligned, as pooled), then a fold of a
+ *   frame's slabs in ascending order and one division.  The slab count and the order of every addition depend on (H, W, C) alone: frame
+ *   n's row is bitwise the same for every N, every position in the batch and every run.  N may exceed 65535.
+ *
+ * kpx_moments_add_f64: x fp64 [M,D] row-major, 1 <= M <= 2^20, 1 <= D <= 1024, 8-byte aligned pointers.  sum[j] += sum_m x[m,j] (fp64 [D])
+ *   and outer[i,j] += sum_m x[m,i] * x[m,j] (fp64 [D,D], written in full), in place: the caller zeroes the accumulators once and adds
+ *   batch after batch.  Each output element is owned by one lane of one workgroup, which reads the old value and adds the rows in ascending
+ *   m, one fma per row for outer: bitwise reproducible from run to run, and outer stays bitwise symmetric when it starts symmetric. */
+size_t kpx_feature_pool_workspace_bytes(int N, int H, int W, int C);
+int kpx_feature_pool_f64(const float* f, int N, int H, int W, int C, double* work, double* pooled /*[N,C]*/, void* stream);
+int kpx_moments_add_f64(const double* x /*[M,D]*/, int M, int D, double* sum /*[D]*/, double* outer /*[D,D]*/, void* stream);
 
 /* ---- contact sheets (evaluate.py --actions), DESIGN.md section 4.4: frames of a rollout quantised to the bytes evaluate.py writes and
  * pasted into an 8-bit RGB sheet of rows x cols cells of H x W pixels, on the device.

@@ -1472,7 +1472,59 @@ def feature_pair_metrics(fa, fb, out=None):
     return out
 
 
-MAX_DRAWS = 4096                                                                  # draws of z the uint32 accumulators hold exactly
+def feature_pool(f, out=None):
+    """The mean over the H * W positions of one layer's features (the Fréchet distance): f contiguous fp32 [N,H,W,C]
+    at a 16-byte aligned address, C a multiple of 4 in [4, 512], H and W in [1, 1024] -> fp64 [N,C], every value converted to fp64 before
+    its first addition.  ``out``: a contiguous fp64 [N,C] tensor to write into.  Two launches on the current stream; frame n's row is
+    bitwise independent of the batch."""
+    if not f.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % f.device)
+    if f.dtype != torch.float32 or not f.is_contiguous():
+        raise _lib.KpxError('feature_pool: f must be a contiguous fp32 tensor (got %s, contiguous=%s)' % (f.dtype, f.is_contiguous()))
+    if f.dim() != 4:
+        raise _lib.KpxError('feature_pool: f must be [N,H,W,C] (got %s)' % (tuple(f.shape),))
+    n, h, w, c = f.shape
+    if n < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c % 4 or not 4 <= c <= 512:
+        raise _lib.KpxError('feature_pool: needs N >= 1, H and W in [1, 1024] and C a multiple of 4 in [4, 512] (got %s)' % (tuple(f.shape),))
+    if f.data_ptr() % 16:
+        raise _lib.KpxError('feature_pool: f must start on a 16-byte boundary')
+    if out is None:
+        out = torch.empty((n, c), dtype=torch.float64, device=f.device)
+    elif tuple(out.shape) != (n, c) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != f.device:
+        raise _lib.KpxError('feature_pool: out must be a contiguous fp64 [%d,%d] tensor on %s' % (n, c, f.device))
+    work = scratch.get('feature_pool', lib.kpx_feature_pool_workspace_bytes(n, h, w, c), f.device)
+    check(lib.kpx_feature_pool_f64(f.data_ptr(), n, h, w, c, work.data_ptr(), out.data_ptr(), _stream()), 'kpx_feature_pool_f64')
+    return out
+
+
+MAX_MOMENT_ROWS, MAX_MOMENT_DIM = 1 << 20, 1024                                   # kpx_moments_add_f64's limits on M and D
+
+
+def moments_add(x, sum, outer):
+    """Rows into the moment accumulators of the Fréchet distance: x contiguous fp64 [M,D], 1 <= M <= 2^20,
+    1 <= D <= 1024; sum [D] += the column sums, outer [D,D] += x^T x, both contiguous fp64 on x's device, zeroed by the caller before the
+    first call.  One launch on the current stream; each element adds the rows in ascending order, so the result is bitwise reproducible
+    and ``outer`` stays bitwise symmetric.  -> (sum, outer)."""
+    for t in (x, sum, outer):
+        if not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % t.device)
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise _lib.KpxError('moments_add: x, sum and outer must be contiguous fp64 tensors (got %s, contiguous=%s)'
+                                % (t.dtype, t.is_contiguous()))
+    if x.dim() != 2 or not 1 <= x.shape[0] <= MAX_MOMENT_ROWS or not 1 <= x.shape[1] <= MAX_MOMENT_DIM:
+        raise _lib.KpxError('moments_add: x must be [M,D] with 1 <= M <= %d and 1 <= D <= %d (got %s)'
+                            % (MAX_MOMENT_ROWS, MAX_MOMENT_DIM, tuple(x.shape)))
+    m, d = x.shape
+    if tuple(sum.shape) != (d,) or tuple(outer.shape) != (d, d) or sum.device != x.device or outer.device != x.device:
+        raise _lib.KpxError('moments_add: sum must be [%d] and outer [%d,%d] on %s (got %s on %s, %s on %s)'
+                            % (d, d, d, x.device, tuple(sum.shape), sum.device, tuple(outer.shape), outer.device))
+    if x.data_ptr() % 8 or sum.data_ptr() % 8 or outer.data_ptr() % 8:
+        raise _lib.KpxError('moments_add: x, sum and outer must start on 8-byte boundaries')
+    check(lib.kpx_moments_add_f64(x.data_ptr(), m, d, sum.data_ptr(), outer.data_ptr(), _stream()), 'kpx_moments_add_f64')
+    return sum, outer
+
+
+MAX_DRAWS = 4096                                                                 # draws of z the uint32 accumulators hold exactly
 
 
 def _draw_accumulators(what, sum, sumsq):

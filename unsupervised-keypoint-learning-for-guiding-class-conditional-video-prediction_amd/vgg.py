@@ -13,6 +13,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from . import frechet as frechet_mod
 from . import ops
 from ._lib import lib, check
 
@@ -136,16 +137,31 @@ class FeatureScorer:
     ``real_frames`` [N,H,W,3] fp32 in [-1,1]: their features (of the 8-bit frames, ``png8``) are computed once, FEATURE_CHUNK frames per VGG
     forward, and kept, so every draw of z scores against the same tensors -- about 8 MB per 128 x 128 frame.  ``scorer(pred_frames, out=)``
     -> fp32 [N,5,2] on the device: per frame and layer of FEATURE_LAYERS (cos_layer, l1_layer) of ``ops.feature_pair_metrics``; vgg_cos and
-    vgg_l1 are their means over the five layers.  fp32 activations only."""
+    vgg_l1 are their means over the five layers.  fp32 activations only.
 
-    def __init__(self, vgg, real_frames):
+    ``frechet`` (evaluate.py --frechet; here for the real frames, in the call for the predicted ones): a ``frechet.FrechetAccumulator``, a
+    ``frechet.FrechetSplit`` or a list of them.  The features this scorer computes anyway are also pooled (``ops.feature_pool``) and added to
+    it as rollouts of ``frames_per_video`` frames (None: the N frames are one rollout); the network does not run a second time."""
+
+    def __init__(self, vgg, real_frames, frechet=None, frames_per_video=None):
         if ops.act_dtype() != torch.float32:
             raise ops._lib.KpxError('FeatureScorer: the VGG feature metrics are defined on fp32 activations; the bf16 configuration is not built')
         self._check(real_frames, None)
+        if frames_per_video is not None and (int(frames_per_video) < 1 or real_frames.shape[0] % int(frames_per_video)):
+            raise ops._lib.KpxError('FeatureScorer: %d frames do not split into videos of %s frames' % (real_frames.shape[0], frames_per_video))
         self.vgg = vgg
         self.shape = tuple(real_frames.shape)
+        self.frames_per_video = frames_per_video
         self.chunk = max(1, int(FEATURE_CHUNK))
         self.real = [vgg.build(real_frames[i:i + self.chunk], png8=True) for i in range(0, self.shape[0], self.chunk)]
+        if frechet is not None:
+            self._feed(frechet, [frechet_mod.pool_features(feats) for feats in self.real])
+
+    def _feed(self, frechet, pooled_chunks):
+        """the pooled rows of every chunk, joined per layer (a few KB), into the accumulator(s)"""
+        pooled = [torch.cat(rows, dim=0) if len(rows) > 1 else rows[0] for rows in zip(*pooled_chunks)]
+        for acc in (frechet if isinstance(frechet, (list, tuple)) else [frechet]):
+            acc.add_pooled(pooled, self.frames_per_video)
 
     @staticmethod
     def _check(frames, shape):
@@ -156,7 +172,7 @@ class FeatureScorer:
         if shape is not None and tuple(frames.shape) != shape:
             raise ops._lib.KpxError('FeatureScorer: predicted frames %s do not match the real frames %s' % (tuple(frames.shape), shape))
 
-    def __call__(self, pred_frames, out=None):
+    def __call__(self, pred_frames, out=None, frechet=None):
         if ops.act_dtype() != torch.float32:
             raise ops._lib.KpxError('FeatureScorer: the VGG feature metrics are defined on fp32 activations; the bf16 configuration is not built')
         self._check(pred_frames, self.shape)
@@ -167,12 +183,17 @@ class FeatureScorer:
         elif tuple(out.shape) != (n, nl, 2) or out.dtype != torch.float32 or out.device != dev:
             raise ops._lib.KpxError('FeatureScorer: out must be an fp32 [%d,%d,2] tensor on %s' % (n, nl, dev))
         per_layer = torch.empty((nl, n, 2), dtype=torch.float32, device=dev)       # what the kernel writes: [N,2] per layer
+        pooled_chunks = []
         for k, real in enumerate(self.real):
             i0 = k * self.chunk
             i1 = min(n, i0 + self.chunk)
             feats = self.vgg.build(pred_frames[i0:i1], png8=True)
             for layer, (fp, fr) in enumerate(zip(feats, real)):
                 ops.feature_pair_metrics(fp, fr, out=per_layer[layer, i0:i1])
+            if frechet is not None:
+                pooled_chunks.append(frechet_mod.pool_features(feats))
+        if frechet is not None:
+            self._feed(frechet, pooled_chunks)
         out.copy_(per_layer.permute(1, 0, 2))                                        # [N,5,2]: a few KB of glue
         return out
 
