@@ -586,6 +586,86 @@ def drive_rollout_leg(dev, rollouts):
             res[name].update(delta_ms=round(med - own, 3), delta_pct=round(100 * (med - own) / own, 2))
     return res
 
+CLASSIFIER_CELLS = [256, 256]                             # = kpx_amd.action_classifier_model.DEFAULT_CELLS
+
+
+def classifier_kernel_leg(dev, launches):
+    """The three launches of csrc/classify.hip alone, at the rows a configs[4] rollout scores (64) and at 1024 rows, A = 9."""
+    from kpx_amd import ops
+    from kpx_amd._lib import lib, check
+    res = {}
+    g = torch.Generator(device=dev).manual_seed(5)
+    for rows in (B, 1024):
+        a = ACTION_CLASSES
+        x = torch.randn((rows, a), generator=g, device=dev)
+        t = torch.randint(0, a, (rows,), generator=g, device=dev).to(torch.int32)
+        y = torch.eye(a, device=dev)[t.long()].contiguous()
+        loss, lse, dl = torch.empty(1, device=dev), torch.empty(rows, device=dev), torch.empty((rows, a), device=dev)
+        conf = torch.zeros((a, a), dtype=torch.int32, device=dev)
+        out = (torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, dtype=torch.int32, device=dev), torch.empty(rows, device=dev))
+        fns = {'softmax_xent_fwd': lambda: check(lib.kpx_softmax_xent_fwd_f32(x.data_ptr(), y.data_ptr(), rows, a, loss.data_ptr(), lse.data_ptr(),
+                                                                               ops._stream()), 'fwd'),
+               'softmax_xent_bwd': lambda: check(lib.kpx_softmax_xent_bwd_f32(x.data_ptr(), y.data_ptr(), lse.data_ptr(), rows, a, None, 1.0,
+                                                                               dl.data_ptr(), ops._stream()), 'bwd'),
+               'class_scores': lambda: ops.class_scores(x, t, conf, out=out, check_target=False)}
+        row = {}
+        for name, fn in fns.items():                      # launch-bound calls: no rate is quoted
+            us = _event_times(fn, launches, dev)
+            row[name] = {'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1)}
+        assert bool(torch.isfinite(loss).all()) and bool(torch.isfinite(dl).all()) and int(conf.sum()) == rows * (3 + launches)
+        res['rows_%d' % rows] = dict(row, classes=a, launches=launches)
+    return res
+
+
+def classifier_rollout_leg(dev, rollouts):
+    """--action-accuracy beside a configs[4] rollout: classify + class_scores + the fp64 moments of the features of one draw (the two
+    accumulators of draw 0), alternated with the bare rollout in one process.  The recogniser has its initial values: the time does not
+    depend on them."""
+    import kpx_amd
+    from kpx_amd import ops
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9, 'classifier_cells': CLASSIFIER_CELLS},
+           'training': {'batch_size': B, 'lr': None}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    target = torch.randint(0, 9, (B,), generator=g, device=dev).to(torch.int32)
+    act = torch.eye(9, device=dev)[target.long()]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    feed = {'image': im, 'action_code': act}
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    cm = kpx_amd.ActionClassifierModel(cfg, is_training=False, device=dev)
+    cm.build()
+    u = CLASSIFIER_CELLS[-1]
+    conf = torch.zeros((9, 9), dtype=torch.int32, device=dev)
+    out = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, device=dev))
+    moments = [(torch.zeros(u, dtype=torch.float64, device=dev), torch.zeros((u, u), dtype=torch.float64, device=dev)) for _ in range(2)]
+
+    def rollout(score):
+        o = fm.run(None, feed, z=z)
+        if score:
+            logits, feats = cm.classify(o['fut_pt_raw'])
+            ops.class_scores(logits, target, conf, out=out, check_target=False)
+            feats = feats.double()
+            for s_, o_ in moments:
+                ops.moments_add(feats, s_, o_)
+
+    for _ in range(3):                                    # eager, capture, one replay
+        rollout(True)
+    torch.cuda.synchronize(dev)
+    ms = {False: [], True: []}
+    for _ in range(rollouts):
+        for score in (False, True):
+            t0 = time.perf_counter()
+            rollout(score)
+            torch.cuda.synchronize(dev)
+            ms[score].append((time.perf_counter() - t0) * 1e3)
+    assert bool(torch.isfinite(out[2]).all()) and bool(torch.isfinite(moments[0][1]).all())
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    return {'batch': B, 'frames': N_FRAMES, 'classifier_cells': CLASSIFIER_CELLS, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 1,
+            'off_ms_per_rollout': round(off, 3), 'on_ms_per_rollout': round(on, 3), 'delta_ms_per_rollout': round(on - off, 3),
+            'overhead_pct': round(100 * (on - off) / off, 2),
+            'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -596,9 +676,11 @@ def main():
     ap.add_argument('--actions', action='store_true', help='measure the class sweep (contact-sheet paste, sheets and class scores) instead')
     ap.add_argument('--drive', action='store_true', help='measure the driven rollout (key-point retargeting, every drive mode) instead')
     ap.add_argument('--frechet', action='store_true', help="measure the Fréchet distance's pooling and moment kernels and its cost per rollout instead")
+    ap.add_argument('--classifier', action='store_true',
+                    help="measure the action classifier's loss and score launches and the cost of --action-accuracy per rollout instead")
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions + args.drive + args.frechet > 1:
-        ap.error('--vgg, --motion, --actions, --drive and --frechet are five measurements: pass one')
+    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier > 1:
+        ap.error('--vgg, --motion, --actions, --drive, --frechet and --classifier are six measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
@@ -606,6 +688,12 @@ def main():
         res = {'vgg_kernel': vgg_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()
         res['vgg_rollout_c4'] = vgg_rollout_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
+    if args.classifier:
+        res = {'classifier_kernels': classifier_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['classifier_rollout_c4'] = classifier_rollout_leg(dev, args.rollouts)
         print(json.dumps(res))
         return
     if args.frechet:

@@ -6,6 +6,7 @@
                        [--metrics [--samples N] [--vgg-metrics [--synthetic-vgg] [--frechet]] [--motion-metrics]]
                        [--actions all|i,j,k [--sheet-frames f,g,h]]
                        [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
+                       [--metrics --action-accuracy CKPT]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -65,6 +66,18 @@ and ``hold`` are scored against the real frames as the model's frames are: ``dri
 metrics.npz and a ``drive`` block in metrics.json (``summarise_drive``) with ``skill`` = (model - hold) / (labels - hold) per metric.
 ``--drive-only`` skips the model's own rollout (no ``model`` row, no pred_seq/ ..., metrics.npz holds the ``drive_*`` arrays alone) and needs
 no ``--checkpoint_stage2``: a stage-1 checkpoint can be evaluated before a stage-2 checkpoint exists.
+
+``--action-accuracy CKPT`` (with ``--metrics``; data path only) asks a recogniser whether a rollout looks like its class: CKPT is a checkpoint
+of ``train.py --mode action_classifier`` (``kpx_amd.ActionClassifierModel``, built from the same config: ``model.classifier_cells``), a
+stacked LSTM over the 32 key-point sets trained on the pseudo labels stage 2 learns from.  Per batch it classifies the real key points (the
+ceiling) and every draw's predicted key points against the sample's own class, and with ``--actions`` every class rollout of the sweep
+against the class that was COMMANDED (``kpx_amd.ops.class_scores``, one launch each).  metrics.npz gains ``cls_own`` [samples],
+``cls_real_pred`` / ``_rank`` / ``_logp`` [samples], ``cls_pred_pred`` / ``_rank`` / ``_logp`` [samples, draws], ``cls_confusion_real`` /
+``cls_confusion_pred`` [A, A] and, with ``--actions``, ``cls_act_pred`` / ``_rank`` / ``_logp`` [samples, classes, draws] and
+``cls_confusion_commanded``; ``kp_fd``, ``kp_fd_draw0`` and ``kp_fd_floor`` are Frechet distances in the recogniser's feature space (fp64
+moments on the device, ``kpx_amd.ops.moments_add``); metrics.json an ``action_accuracy`` block (``summarise_action_accuracy``).  This is the
+project's own key-point-space quantity: the recogniser never sees a pixel, and the figures are not comparable with published
+action-recognition accuracies or FVD.
 """
 import json
 import os
@@ -276,6 +289,150 @@ def summarise_actions(actions, act_own, act_kp_l2, act_kp_div=None, act_div_mse=
     return out
 
 
+ACTION_ACCURACY_DEFINITION = (
+    'action_accuracy: a recogniser trained by this project (train.py --mode action_classifier: stacked LSTM over the 32 key-point sets of '
+    'a sequence, softmax over the A classes, trained on the pseudo labels) classifies key-point sequences. real: the pseudo labels of the '
+    'real frames against the sample\'s own class, the ceiling. pred: the predicted key points of every draw of z against the sample\'s own '
+    'class. commanded (with --actions): the rollout under each listed class at the shared z against the class that was commanded. Per '
+    'sequence: pred = the lowest index among the maxima of its logits; rank = 1 + the number of OTHER classes whose logit is >= the '
+    'target\'s, so a tie counts against the model; logp = the log-softmax at the target. A sequence with a non-finite logit has pred -1, '
+    'rank A and logp NaN: it counts as wrong in top1 and mean_rank, is counted in n_nonfinite and is left out of nll and confusion. '
+    'top1 = share with rank 1, chance = 1 / A, mean_rank, nll = -mean logp over the finite sequences, per_class_top1[c] = top1 of the '
+    'sequences whose target is c (null for a class without one), confusion[t][p] = finite sequences with target t and pred p, '
+    'best_of_draws_top1 = share of samples (commanded: of sample-class pairs) with rank 1 in at least one draw. kp_fd: the Frechet distance '
+    '|m1 - m2|^2 + tr C1 + tr C2 - 2 tr (C1 C2)^(1/2) between the Gaussians fitted to the recogniser\'s features (its top LSTM layer at the '
+    'last step, dimension dim) of all real sequences and of the predictions of all draws; kp_fd_draw0: draw 0 alone; kp_fd_floor: the real '
+    'even-numbered samples against the odd-numbered ones, the finite-sample noise floor; null where a set has fewer than two rows, '
+    'rank_deficient where a set has n <= dim rows; moments in float64, cov = (sum x x^T - n mu mu^T) / (n - 1), not clamped at 0. '
+    'This is the project\'s own key-point-space quantity, computed by a recogniser that never sees a pixel and is trained on this '
+    'project\'s pseudo labels: it is not comparable with published action-recognition accuracies or FVD figures.')
+
+
+def summarise_action_accuracy(arrays):
+    """The ``action_accuracy`` block of metrics.json (ACTION_ACCURACY_DEFINITION) from the arrays --action-accuracy puts into metrics.npz:
+    cls_own [S], cls_real_{pred,rank,logp} [S], cls_pred_{pred,rank,logp} [S, D], cls_confusion_{real,pred} [A, A], kp_fd, kp_fd_draw0,
+    kp_fd_floor, kp_fd_dim and, with --actions, actions [C], cls_act_{pred,rank,logp} [S, C, D] and cls_confusion_commanded; numpy only."""
+    own = np.asarray(arrays['cls_own']).reshape(-1).astype(np.int64)
+    n_cls = int(np.asarray(arrays['cls_confusion_real']).shape[0])
+    s = own.size
+
+    def block(prefix, target, confusion, draws_axis):
+        pred, rank = np.asarray(arrays[prefix + 'pred']).astype(np.int64), np.asarray(arrays[prefix + 'rank']).astype(np.int64)
+        logp = np.asarray(arrays[prefix + 'logp'], np.float64)
+        if pred.shape != target.shape or rank.shape != target.shape or logp.shape != target.shape:
+            raise ValueError('summarise_action_accuracy: %spred, rank and logp must be %s (got %s, %s, %s)'
+                             % (prefix, list(target.shape), pred.shape, rank.shape, logp.shape))
+        hit, finite = rank == 1, pred >= 0
+        out = {'n': int(rank.size), 'chance': 1.0 / n_cls, 'top1': float(hit.mean()) if rank.size else None,
+               'mean_rank': float(rank.astype(np.float64).mean()) if rank.size else None,
+               'nll': _json_num(-logp[finite].mean()) if finite.any() else None,
+               'per_class_top1': [float(hit[target == c].mean()) if (target == c).any() else None for c in range(n_cls)],
+               'confusion': [[int(v) for v in row] for row in np.asarray(confusion)], 'n_nonfinite': int((~finite).sum())}
+        if draws_axis is not None:
+            any_hit = hit.any(axis=draws_axis)
+            out['best_of_draws_top1'] = float(any_hit.mean()) if any_hit.size else None
+        return out
+
+    d = int(np.asarray(arrays['cls_pred_rank']).shape[1]) if np.asarray(arrays['cls_pred_rank']).ndim == 2 else 0
+    res = {'definition': ACTION_ACCURACY_DEFINITION, 'n_samples': s, 'n_draws': d, 'n_classes': n_cls,
+           'real': block('cls_real_', own, arrays['cls_confusion_real'], None),
+           'pred': block('cls_pred_', np.broadcast_to(own[:, None], (s, d)), arrays['cls_confusion_pred'], 1)}
+    if 'cls_act_rank' in arrays:
+        actions = np.asarray(arrays['actions']).reshape(-1).astype(np.int64)
+        shape = np.asarray(arrays['cls_act_rank']).shape
+        res['actions'] = [int(a) for a in actions]
+        res['commanded'] = block('cls_act_', np.broadcast_to(actions[None, :, None], shape), arrays['cls_confusion_commanded'], 2)
+    dim = int(arrays['kp_fd_dim'])
+    n_sets = {'kp_fd': (s, s * d), 'kp_fd_draw0': (s, s if d else 0), 'kp_fd_floor': ((s + 1) // 2, s // 2)}
+    res['kp_fd'] = {'dim': dim, 'n_real': s, 'n_pred': s * d}
+    for name, counts in n_sets.items():
+        res['kp_fd'][name] = _json_num(arrays[name])
+    res['kp_fd']['rank_deficient'] = {name: min(counts) <= dim for name, counts in n_sets.items()}
+    return res
+
+
+class _ActionAccuracy:
+    """--action-accuracy: the recogniser, its scores per batch (device tensors until the end) and the moments of its features."""
+    SETS = ('real_even', 'real_odd', 'pred', 'pred_draw0')
+
+    def __init__(self, kpx_amd, config, checkpoint, dev, samples, actions):
+        self.ops, self.F, self.dev, self.samples, self.actions = kpx_amd.ops, kpx_amd.frechet, dev, samples, actions
+        self.model = kpx_amd.ActionClassifierModel(config, is_training=False, device=dev)
+        self.model.build(None)
+        self.model.restore(None, checkpoint, strict=True)
+        a, u = self.model.n_action, self.model.cells[-1]
+        self.n_action, self.dim = a, u
+        zi = lambda: torch.zeros((a, a), dtype=torch.int32, device=dev)
+        self.confusion = {'real': zi(), 'pred': zi()}
+        if actions:
+            self.confusion['commanded'] = zi()
+            self.commanded = [torch.full((1,), c, dtype=torch.int32, device=dev) for c in actions]
+        self.moments = {name: {'n': 0, 'sum': torch.zeros(u, dtype=torch.float64, device=dev),
+                               'outer': torch.zeros((u, u), dtype=torch.float64, device=dev)} for name in self.SETS}
+        self.own, self.real, self.pred, self.act = [], [], [], []
+        self.n_scored = 0
+
+    def _add(self, name, rows):
+        if rows.shape[0]:
+            m = self.moments[name]
+            self.ops.moments_add(rows.contiguous(), m['sum'], m['outer'])
+            m['n'] += int(rows.shape[0])
+
+    def begin_batch(self, batch):
+        """The real key points of a batch against its own classes; the targets every draw of this batch is scored against."""
+        bsz = batch['real_seq'].shape[0]
+        self.target = batch['action_code'].argmax(dim=1).to(torch.int32).contiguous()
+        self.own.append(self.target)
+        logits, feats = self.model.classify(batch['real_seq'])
+        self.real.append(self.ops.class_scores(logits, self.target, self.confusion['real'], check_target=False))
+        feats = feats.double()
+        first = self.n_scored % 2                    # the parity of this batch's first sample among all samples
+        self._add('real_even', feats[first::2])
+        self._add('real_odd', feats[1 - first::2])
+        self.n_scored += bsz
+        mk = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.dev)
+        self.pred.append(tuple(mk((self.samples, bsz), dt) for dt in (torch.int32, torch.int32, torch.float32)))
+        if self.actions:
+            self.act.append(tuple(mk((self.samples, len(self.actions), bsz), dt) for dt in (torch.int32, torch.int32, torch.float32)))
+
+    def own_draw(self, draw, fut_pt_raw):
+        """One draw of the batch's own rollout, enqueued before the next run() replays the graph over ``fut_pt_raw``."""
+        logits, feats = self.model.classify(fut_pt_raw)
+        self.ops.class_scores(logits, self.target, self.confusion['pred'], out=tuple(t[draw] for t in self.pred[-1]), check_target=False)
+        feats = feats.double()
+        self._add('pred', feats)
+        if draw == 0:
+            self._add('pred_draw0', feats)
+
+    def class_rollout(self, draw, a, fut_pt_raw):
+        """The rollout under the listed class ``a`` at this draw's z, against the class that was commanded."""
+        logits, _ = self.model.classify(fut_pt_raw)
+        target = self.commanded[a].expand(logits.shape[0]).contiguous()
+        self.ops.class_scores(logits, target, self.confusion['commanded'], out=tuple(t[draw, a] for t in self.act[-1]), check_target=False)
+
+    def arrays(self):
+        """-> the cls_* and kp_fd* arrays of metrics.npz (one copy to the host per kind)"""
+        host = lambda ts, shape, dt, dim=0: torch.cat(ts, dim=dim).cpu().numpy() if ts else np.zeros(shape, dt)
+        kinds = (('pred', np.int32), ('rank', np.int32), ('logp', np.float32))
+        d, c = self.samples, len(self.actions or ())
+        out = {'cls_own': host(self.own, (0,), np.int32)}
+        for i, (name, dt) in enumerate(kinds):
+            out['cls_real_' + name] = host([r[i] for r in self.real], (0,), dt)
+            out['cls_pred_' + name] = np.ascontiguousarray(host([r[i] for r in self.pred], (d, 0), dt, 1).T)                        # [S, D]
+            if self.actions:
+                out['cls_act_' + name] = np.ascontiguousarray(host([r[i] for r in self.act], (d, c, 0), dt, 2).transpose(2, 1, 0))   # [S, C, D]
+        for name, t in self.confusion.items():
+            out['cls_confusion_' + name] = t.cpu().numpy()
+        st = {name: self.F.stats_from_moments(m['n'], m['sum'].cpu().numpy(), m['outer'].cpu().numpy()) for name, m in self.moments.items()}
+        even, odd = self.moments['real_even'], self.moments['real_odd']
+        st['real'] = self.F.stats_from_moments(even['n'] + odd['n'], (even['sum'] + odd['sum']).cpu().numpy(),
+                                               (even['outer'] + odd['outer']).cpu().numpy())
+        fd = lambda x, y: np.float64(self.F.frechet_distance(st[x]['mean'], st[x]['cov'], st[y]['mean'], st[y]['cov']))
+        out.update(kp_fd=fd('pred', 'real'), kp_fd_draw0=fd('pred_draw0', 'real'), kp_fd_floor=fd('real_even', 'real_odd'),
+                   kp_fd_dim=np.int32(self.dim))
+        return out
+
+
 DRIVE_MODES = ('labels', 'hold', 'transfer')                                      # the order of the runs and of the sheet's rows
 DRIVE_METRICS = ('ssim', 'psnr', 'mse')
 DRIVE_DEFINITION = (
@@ -359,6 +516,7 @@ class _ClassSweep:
         self.codes = torch.eye(n_action, dtype=torch.float32, device=dev)[actions]                    # [A, n_action] one-hot rows
         self.real_row = 1 if real_im_seq is not None else 0
         self.classes = self.points = None
+        self.on_class = None                 # --action-accuracy: called with (draw, class position, fut_pt_raw) for every rollout of the sweep
         if save:
             h, w = image.shape[1:3]
             cols = 1 + len(sheet_frames)
@@ -383,6 +541,8 @@ class _ClassSweep:
                 ops.sheet_paste(self.classes, pred, self.sheet_frames, self.real_row + a, 1, 'unit')
                 ops.sheet_paste(self.points, out['current_points'].contiguous().unsqueeze(1), [0], a, 0, 'raw')
                 ops.sheet_paste(self.points, out['future_points'].contiguous(), self.sheet_frames, a, 1, 'raw')
+            if self.on_class is not None:
+                self.on_class(draw, a, out['fut_pt_raw'])
             if self.kp_real is not None:
                 ops.flat_copy_tensor(out['fut_pt_raw'].contiguous(), self.kp[draw, a].data_ptr())
                 if n_cls >= 2:
@@ -527,7 +687,7 @@ def _drive_line(blk):
 
 
 def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None,
-                   frechet=None):
+                   frechet=None, accuracy=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
@@ -535,7 +695,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     action_scores (--actions): {'actions': [A], 'own': per batch the action codes [B, n_action], 'kp_l2': per batch [draws, A, B, T]} and for
     two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}.
     drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}.
-    frechet (--frechet): the accumulators {'real_even', 'real_odd', 'pred', 'pred_draw0'}; also writes frechet.npz."""
+    frechet (--frechet): the accumulators {'real_even', 'real_odd', 'pred', 'pred_draw0'}; also writes frechet.npz.
+    accuracy (--action-accuracy): the _ActionAccuracy of the run."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -587,6 +748,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
             stored.update(F.stats_arrays(name, stats[name], VGG_FEATURE_LAYERS))
         os.makedirs(save_dir, exist_ok=True)
         np.savez(osp.join(save_dir, 'frechet.npz'), **stored)
+    if accuracy is not None:
+        arrays.update(accuracy.arrays())
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
@@ -597,6 +760,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         res['actions'] = summarise_actions(actions, act['act_own'], act['act_kp_l2'], act.get('act_kp_div'), act.get('act_div_mse'))
     if drive is not None:
         res['drive'] = summarise_drive(drive, model={'ssim': ssim, 'psnr': psnr, 'mse': mse})
+    if accuracy is not None:
+        res['action_accuracy'] = summarise_action_accuracy(arrays)
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
@@ -619,6 +784,13 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         blk = res['actions']
         line += ', class top-1 %s (chance %.4f), class diversity %s' % (fmt(blk['top1'], '%.4f'), blk['chance'],
                                                                         fmt(blk['kp_div']['mean'], '%.4f') if 'kp_div' in blk else 'n/a')
+    if accuracy is not None:
+        blk = res['action_accuracy']
+        line += (', key-point recogniser (own quantity, not comparable with published figures) top-1 real %s, predicted %s%s (chance %.4f), '
+                 'key-point Frechet %s (floor %s)'
+                 % (fmt(blk['real']['top1'], '%.4f'), fmt(blk['pred']['top1'], '%.4f'),
+                    ', commanded %s' % fmt(blk['commanded']['top1'], '%.4f') if 'commanded' in blk else '', blk['real']['chance'],
+                    fmt(blk['kp_fd']['kp_fd'], '%.4g'), fmt(blk['kp_fd']['kp_fd_floor'], '%.4g')))
     print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
     if drive is not None:
         print(_drive_line(res['drive']))
@@ -667,6 +839,11 @@ def main(argv=None):
                         help='with --drive transfer: scale the driving motion by the ratio of the two constellations\' spreads')
     parser.add_argument('--drive-only', action='store_true',
                         help="with --drive: skip the model's own rollout; --checkpoint_stage2 may then be omitted")
+    parser.add_argument('--action-accuracy', type=str, default=None, metavar='CKPT',
+                        help='with --metrics: a checkpoint of train.py --mode action_classifier; its recogniser classifies the real and the '
+                             'predicted key points (with --actions: every class rollout against the commanded class) and gives a Frechet '
+                             "distance in its feature space.  This project's own key-point-space quantity: not comparable with published "
+                             'action-recognition or FVD figures')
     args = parser.parse_args(argv)
     if args.sheet_frames is not None and args.actions is None and args.drive is None:
         parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive and needs it')
@@ -690,7 +867,8 @@ def main(argv=None):
         if drive_modes is None:
             parser.error('--drive-only keeps the rollouts of --drive alone and needs it')
         for flag, on in (('--samples > 1', args.samples > 1), ('--actions', args.actions is not None), ('--vgg-metrics', args.vgg_metrics),
-                         ('--frechet', args.frechet), ('--motion-metrics', args.motion_metrics)):
+                         ('--frechet', args.frechet), ('--motion-metrics', args.motion_metrics),
+                         ('--action-accuracy', args.action_accuracy is not None)):
             if on:
                 parser.error("--drive-only skips the model's own rollout, which %s is about" % flag)
         if args.metrics and not set(drive_modes) & {'labels', 'hold'}:
@@ -705,6 +883,11 @@ def main(argv=None):
         parser.error('--motion-metrics adds to the scores of --metrics and needs it')
     if args.motion_metrics and args.samples > MAX_MOTION_DRAWS:
         parser.error('--motion-metrics holds at most %d --samples in its exact accumulators (got %d)' % (MAX_MOTION_DRAWS, args.samples))
+    if args.action_accuracy is not None and args.synthetic:
+        parser.error('--action-accuracy classifies the pseudo labels of the real frames and the rollouts of their classes, and --synthetic '
+                     'inputs have neither')
+    if args.action_accuracy is not None and not args.metrics:
+        parser.error('--action-accuracy adds to the scores of --metrics and needs it')
     if args.metrics and args.synthetic:
         parser.error('--metrics scores predictions against the real future frames, and --synthetic inputs have no ground truth')
     if args.samples < 1:
@@ -727,7 +910,7 @@ def main(argv=None):
             parser.error('--actions scores classes x --samples as draws and holds at most %d of them (got %d x %d)'
                          % (MAX_MOTION_DRAWS, len(actions), args.samples))
     checkpoints = [args.checkpoint_stage1] + ([args.checkpoint_stage2] if args.checkpoint_stage2 is not None else [])
-    for p in checkpoints:                                            # reference :34-38
+    for p in checkpoints + ([args.action_accuracy] if args.action_accuracy is not None else []):    # reference :34-38
         if not (osp.exists(p) or osp.exists(p + '.index')):                 # .npz file or TensorFlow bundle prefix
             raise Exception('checkpoint not found at %s' % p)
     vggnet = config.get('paths', {}).get('vggnet')
@@ -764,6 +947,7 @@ def main(argv=None):
             motion_scores = {'kp_l2': []} if args.samples < 2 else {'kp_l2': [], 'kp_div': [], 'div_mse': []}
         drive_scores = {m: [] for m in drive_modes if m != 'transfer'} if drive_modes and args.metrics else None
         n_self_driven = 0
+        accuracy = _ActionAccuracy(kpx_amd, config, args.action_accuracy, dev, args.samples, actions) if args.action_accuracy is not None else None
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
             if args.drive_only:              # the driven rollouts alone: no own rollout, so no draws and nothing of what they write
@@ -803,12 +987,16 @@ def main(argv=None):
                     if args.samples >= 2:
                         moments = torch.empty((2, real_flat.numel()), dtype=torch.int32, device=dev)
                         kpx_amd.ops.fill_raw_(moments, 0.0)
+                if accuracy is not None:
+                    accuracy.begin_batch(batch)
             sweep = None
             if actions:
                 sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, batch['image'], batch['real_im_seq'], not args.no_save,
                                     args.samples, batch['real_seq'].contiguous() if args.metrics else None, dev)
                 if args.metrics:
                     action_scores['own'].append(batch['action_code'].clone())
+                if accuracy is not None:
+                    sweep.on_class = accuracy.class_rollout
             for draw in range(args.samples):
                 # --actions: one z per batch and draw, drawn here, for the batch's own rollout and for every class of the sweep
                 z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None
@@ -822,6 +1010,8 @@ def main(argv=None):
                         scorer(pred_flat, out=vgg_score[draw], frechet=[frechet['pred'], frechet['pred_draw0']] if draw == 0 else frechet['pred'])
                     elif args.vgg_metrics:
                         scorer(pred_flat, out=vgg_score[draw])
+                    if accuracy is not None:
+                        accuracy.own_draw(draw, outputs['fut_pt_raw'])
                     if args.motion_metrics:
                         kpx_amd.ops.flat_copy_tensor(outputs['fut_pt_raw'].contiguous(), kp_pred[draw].data_ptr())
                         if args.samples >= 2:
@@ -879,7 +1069,8 @@ def main(argv=None):
         if args.metrics and args.drive_only:
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
-            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores, frechet)
+            _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores, frechet,
+                           accuracy)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

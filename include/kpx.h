@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 16
+#define KPX_ABI_VERSION 17
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -655,6 +655,26 @@ int kpx_augment_filter_f32(const unsigned char* tiles, const int32_t* lsum, cons
 #define KPX_SEQ_MAX_ACTIONS 256
 int kpx_keypoint_seq_augment_f32(const float* labels, const int64_t* label_off, const int32_t* rows, int n_rows, int n_points,
                                  int n_action, const double* trig, float* keypoints, float* real_seq, float* action_code, void* stream);
+
+/* ---- key-point action classifier (csrc/classify.hip) ---------------------------------------------------------------------------------
+ * Softmax cross-entropy of logits [B][A] against label rows [B][A] (tf.nn.softmax_cross_entropy_with_logits + reduce_mean) and the scores
+ * evaluate.py --action-accuracy reads.  1 <= A <= 1024, 1 <= B, M <= 2^20; every pointer 4-byte aligned; null or out-of-range arguments
+ * return KPX_EINVAL before any device call.  Each entry is ONE launch on `stream` (capturable), uses no float atomics and computes in
+ * fp64 in a fixed order, rounding to fp32 once.
+ *   fwd    lse_out[i] = max_j + log(sum_j exp(logits_ij - max_j)); loss_out[0] = (sum_i -sum_j labels_ij (logits_ij - lse_i)) / B, the
+ *          rows added in ascending order (lse_i unrounded inside the loss).
+ *   bwd    dlogits_ij = g / B * (exp(logits_ij - lse_i) - labels_ij), lse the fp32 values fwd wrote, g = gscale_host * (gscale_dev ?
+ *          *gscale_dev : 1) as in kpx_l1_pair_bwd_f32.  (TensorFlow's gradient: exact when every label row sums to 1.)
+ *   scores pred_i = the lowest index among the row's maxima; rank_i = 1 + #{j != t : logits_ij >= logits_it}, t = target[i] (a tie counts
+ *          against the model); logp_i = logits_it - lse_i; confusion[t][pred_i] += 1 (int32 [A][A], integer atomics, may be NULL).
+ *          A row with a non-finite logit gets pred = -1, rank = A, logp = NaN and is left out of `confusion`.  The caller keeps
+ *          target inside [0, A) (kpx_amd.ops.class_scores refuses others); the kernel reads nothing for such a row and answers
+ *          rank = A, logp = NaN. */
+int kpx_softmax_xent_fwd_f32(const float* logits, const float* labels, int B, int A, float* loss_out, float* lse_out, void* stream);
+int kpx_softmax_xent_bwd_f32(const float* logits, const float* labels, const float* lse, int B, int A, const float* gscale_dev,
+                             float gscale_host, float* dlogits, void* stream);
+int kpx_class_scores_f32(const float* logits, const int32_t* target, int M, int A, int32_t* pred, int32_t* rank, float* logp,
+                         int32_t* confusion, void* stream);
 
 #ifdef __cplusplus
 }

@@ -4,14 +4,21 @@
     python train.py --mode detector_translator --config configs/penn.yaml [--synthetic] [--steps N]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py --mode ... (data parallel)
 
-Both modes are built: ``detector_translator`` (stage 1, the BASELINE.json hot path) and ``motion_generator`` (stage 2, the
-sequence VAE-GAN over the pseudo labels written by make_pseudo_labels.py).  Without ``--synthetic`` the frames come from ``paths.data_dir`` through kpx_amd.data.ImagePairDataLoader (the
+    python train.py --mode action_classifier --config configs/penn.yaml [--synthetic] [--resident-labels] [--steps N]
+
+Three modes are built: ``detector_translator`` (stage 1, the BASELINE.json hot path), ``motion_generator`` (stage 2, the
+sequence VAE-GAN over the pseudo labels written by make_pseudo_labels.py) and ``action_classifier`` (this project's own recogniser
+over the same key-point sequences and classes, the network evaluate.py --action-accuracy scores rollouts with; it has no
+counterpart in the reference).  Without ``--synthetic`` the frames come from ``paths.data_dir`` through kpx_amd.data.ImagePairDataLoader (the
 reference's data/image_pair_dataloader.py + tf.data pipeline: threaded PIL augmentation, uint8 batches in pinned memory, async
 copy + on-device conversion); ``--synthetic`` feeds Penn-shaped random pairs with the same output contract (float32 NHWC in
 [-1,1], keys image / future_image).  ``--resident-data`` (detector_translator) decodes every frame of both subsets once into HBM and augments on the
 GPU (kpx_amd.resident): the same batches bit for bit, without the per-step JPEG decoding.  ``--resident-labels`` (motion_generator) keeps
 every video's pseudo labels in HBM and builds each key-point batch with one HIP launch: the same batches bit for bit, with no file read,
 PIL call or numpy work per step; the start frames, which only the image summary shows, are rendered for its two samples alone.
+``action_classifier`` reads the batches ``motion_generator`` reads (``--resident-labels`` included) and uses their ``real_seq`` and
+``action_code``; its ``--synthetic`` feeds a planted problem in which the class decides the direction the points drift in
+(kpx_amd.synthetic.planted_action_batch).
 """
 import logging
 import os
@@ -41,15 +48,22 @@ def _get_model_by_mode(mode, config, global_step, **kw):
         from kpx_amd import MotionGeneratorModel
         kw.pop('vgg', None)
         return MotionGeneratorModel(config, global_step, is_training=True, **kw)
+    if mode == 'action_classifier':
+        from kpx_amd import ActionClassifierModel
+        kw.pop('vgg', None)
+        kw.pop('colors_seed', None)
+        return ActionClassifierModel(config, global_step, is_training=True, **kw)
     raise Exception('unknown model %s' % mode)
 
 
 def _train_motion_generator(args, config, dev, rank, world):
-    """reference train.py:136-147 (SequenceDataLoader, is_train -> random_order + randomness) + the common loop (:84-113)."""
+    """reference train.py:136-147 (SequenceDataLoader, is_train -> random_order + randomness) + the common loop (:84-113).  The
+    action_classifier mode runs the same loop over the same loaders; it writes no image summary, so it asks for no start frames."""
     import numpy as np
     import kpx_amd
     paths_config, train_config, model_config = config['paths'], config['training'], config['model']
-    model = _get_model_by_mode('motion_generator', config, 0, device=dev, colors_seed=args.colors_seed)
+    classifier = args.mode == 'action_classifier'
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']
@@ -69,11 +83,14 @@ def _train_motion_generator(args, config, dev, rank, world):
     def test_feeds(it):
         """The batches of one test pass; the resident iterator has no 'image', so the batch the summary is written from gets its two."""
         for i, f in enumerate(it):
-            if i == 0 and args.resident_labels:
+            if i == 0 and args.resident_labels and not classifier:
                 f = dict(f, image=it.start_images(2))
             yield f
 
     def synthetic(seed):
+        if classifier:
+            from kpx_amd.synthetic import planted_action_batch
+            return {n: torch.from_numpy(v).to(dev) for n, v in planted_action_batch(batch_size, k, a, seed=seed).items()}
         rs = np.random.RandomState(seed)
         d = {'keypoints': rs.rand(batch_size, k, 2) * 1.6 - 0.8, 'real_seq': rs.rand(batch_size, 32, k, 2) * 1.6 - 0.8,
              'action_code': np.eye(a)[rs.randint(0, a, size=batch_size)]}
@@ -83,7 +100,7 @@ def _train_motion_generator(args, config, dev, rank, world):
     for step in range(model.global_step, n_steps):
         feed = next(train_it) if train_it is not None else synthetic(step * world + rank)
         should_write_summary = _should_write_summary(train_config, step, rank)
-        if args.resident_labels and should_write_summary:
+        if args.resident_labels and should_write_summary and not classifier:
             feed = dict(feed, image=train_it.start_images(2))
         model.train_step(None, feed, step, batch_size, should_write_log=step % train_config['log_interval'] == 0 and rank == 0,
                          should_write_summary=should_write_summary)
@@ -105,14 +122,16 @@ def _should_write_summary(train_config, step, rank):
 
 def main(argv=None):
     parser = ArgumentParser()
-    parser.add_argument('--mode', type=str, choices=['detector_translator', 'motion_generator'], help='which mode to train')
+    parser.add_argument('--mode', type=str, choices=['detector_translator', 'motion_generator', 'action_classifier'],
+                        help='which mode to train: stage 1, stage 2, or the key-point action recogniser evaluate.py --action-accuracy reads')
     parser.add_argument('--config', type=str, help='path of the configuration file')
-    parser.add_argument('--synthetic', action='store_true', help='synthetic Penn-shaped pairs instead of the JPEG pipeline')
+    parser.add_argument('--synthetic', action='store_true', help='synthetic Penn-shaped pairs instead of the JPEG pipeline (action_classifier: a planted problem, the class decides '
+                             'the direction the points drift in)')
     parser.add_argument('--resident-data', action='store_true',
                         help='detector_translator: decode every frame once, keep the frames in HBM and augment with HIP kernels '
                              '(ImagePairDataLoader.batches(resident=True)); the same batches as without the flag')
     parser.add_argument('--resident-labels', action='store_true',
-                        help='motion_generator: keep the pseudo labels of every listed video in HBM and build each key-point batch with '
+                        help='motion_generator / action_classifier: keep the pseudo labels of every listed video in HBM and build each key-point batch with '
                              'one HIP launch (SequenceDataLoader.batches(resident=True)); the same batches and summaries as without the flag')
     parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
     parser.add_argument('--steps', type=int, default=None, help='override training.n_steps')
@@ -127,8 +146,9 @@ def main(argv=None):
                         help='seed of the key-point palette of the image summaries (the reference draws it from the unseeded random module)')
     args = parser.parse_args(argv)
     if args.resident_data and (args.mode != 'detector_translator' or args.synthetic):
-        parser.error('--resident-data keeps JPEG frames in HBM: the motion_generator mode reads key-point files and --synthetic reads no frames')
-    if args.resident_labels and (args.mode != 'motion_generator' or args.synthetic):
+        parser.error('--resident-data keeps JPEG frames in HBM: the motion_generator and action_classifier modes read key-point files and '
+                     '--synthetic reads no frames')
+    if args.resident_labels and (args.mode not in ('motion_generator', 'action_classifier') or args.synthetic):
         parser.error('--resident-labels keeps pseudo labels in HBM: the detector_translator mode reads frames (see --resident-data) and '
                      '--synthetic reads no label files')
     logging.basicConfig(level=logging.INFO, format='%(message)s')
@@ -146,7 +166,7 @@ def main(argv=None):
     import kpx_amd
     from kpx_amd.synthetic import synthetic_pair
     vgg = None
-    if args.mode == 'motion_generator':
+    if args.mode in ('motion_generator', 'action_classifier'):
         return _train_motion_generator(args, config, dev, rank, world)
     if args.synthetic_vgg or not os.path.exists(str(paths_config.get('vggnet'))):
         if not args.synthetic_vgg:

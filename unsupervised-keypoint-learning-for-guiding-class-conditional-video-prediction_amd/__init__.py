@@ -9,11 +9,12 @@ from .detector_translator_model import DetectorTranslatorModel  # noqa: F401
 from .keypoint_model import KeypointModel  # noqa: F401
 from .final_model import FinalModel  # noqa: F401
 from .motion_generator_model import MotionGeneratorModel  # noqa: F401
+from .action_classifier_model import ActionClassifierModel  # noqa: F401
 from .vgg import FeatureScorer, Vgg19, synthetic_vgg19_weights  # noqa: F401
 from . import data  # noqa: F401
 from . import resident  # noqa: F401
 from . import frechet  # noqa: F401
 from .data import ImagePairDataLoader, KeypointDataLoader, SequenceDataLoader  # noqa: F401
 
-__all__ = ['BaseModel', 'DetectorTranslatorModel', 'KeypointModel', 'FinalModel', 'MotionGeneratorModel', 'Vgg19', 'FeatureScorer', 'synthetic_vgg19_weights', 'ImagePairDataLoader', 'KeypointDataLoader', 'SequenceDataLoader', 'data', 'resident', 'frechet', 'layers', 'model_utils',
+__all__ = ['BaseModel', 'DetectorTranslatorModel', 'KeypointModel', 'FinalModel', 'MotionGeneratorModel', 'ActionClassifierModel', 'Vgg19', 'FeatureScorer', 'synthetic_vgg19_weights', 'ImagePairDataLoader', 'KeypointDataLoader', 'SequenceDataLoader', 'data', 'resident', 'frechet', 'layers', 'model_utils',
            'networks', 'ops', 'summary', 'variables']

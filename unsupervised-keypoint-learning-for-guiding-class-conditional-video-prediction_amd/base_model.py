@@ -88,15 +88,19 @@ class BaseModel(ABC):
     def restore(self, sess, checkpoint_path):
         """reference :83-91: restore the intersection of checkpoint variables and model variables, by name.  Accepts the .npz
         container or the prefix of a TensorFlow V2 bundle (e.g. the published stage-1 / stage-2 checkpoints)."""
-        from . import tf_bundle
-        if tf_bundle.is_bundle(checkpoint_path):
-            arrays = tf_bundle.read_bundle(checkpoint_path)
-        else:
-            data = np.load(checkpoint_path)
-            arrays = {k.replace('|', '/'): data[k] for k in data.files}
+        arrays = self.read_checkpoint(checkpoint_path)
         self.store.load_numpy(arrays, strict=False)
         self._restore_extra(arrays)
         return sorted(arrays)
+
+    @staticmethod
+    def read_checkpoint(checkpoint_path):
+        """{variable name: array} of either container"""
+        from . import tf_bundle
+        if tf_bundle.is_bundle(checkpoint_path):
+            return tf_bundle.read_bundle(checkpoint_path)
+        data = np.load(checkpoint_path)
+        return {k.replace('|', '/'): data[k] for k in data.files}
 
     def _restore_extra(self, arrays):
         pass

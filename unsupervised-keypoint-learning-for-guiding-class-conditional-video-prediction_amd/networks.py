@@ -201,3 +201,20 @@ def seq_discr(x, discr_cells=(1024, 1024)):
         with st.variable_scope('rnn'):
             out = cell.sequence(x.transpose(0, 1).contiguous())
         return layers.fully_connected(out[-1], 1, trainable=True)
+
+
+def seq_classifier(x, n_action, cells=(256, 256)):
+    """The project's own action recogniser over key-point sequences (no counterpart in the reference): stacked LSTM over x [B,32,2K]
+    as in ``seq_discr``, then fully_connected(last output, n_action) without activation -> (logits [B,A], features [B,U]);
+    ``features`` is the top layer's output at the last step, the space evaluate.py --action-accuracy takes its Fréchet distance in."""
+    st = default_store()
+    with st.variable_scope('seq_classifier'):
+        cell = layers.lstm_model(list(cells))
+        if is_sym(x):
+            with st.variable_scope('rnn'):
+                cell.declare(x.shape[-1])
+            return layers.fully_connected(Sym(x.shape[0], cells[-1]), n_action, act=ACT_NONE), Sym(x.shape[0], cells[-1])
+        with st.variable_scope('rnn'):
+            out = cell.sequence(x.transpose(0, 1).contiguous())
+        features = out[-1]
+        return layers.fully_connected(features, n_action, act=ACT_NONE, trainable=True), features

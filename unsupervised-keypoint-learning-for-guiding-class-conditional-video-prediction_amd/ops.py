@@ -1869,6 +1869,92 @@ def sigmoid_xent(logits, n0, label0, n1=0, label1=0.0):
     return SigmoidXentFn.apply(logits, n0, float(label0), n1, float(label1))
 
 
+MAX_CLASS_ROWS, MAX_CLASSES = 1 << 20, 1024                                      # limits of the three classifier entries on B / M and A
+
+
+def _class_rows(what, logits):
+    """(rows, classes) of a logits tensor the classifier entries take: contiguous fp32 [rows, A] on the GPU within the limits."""
+    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(logits, 'device', type(logits)))
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 2:
+        raise _lib.KpxError('%s: logits must be a contiguous fp32 [rows, classes] tensor (got %s %s, contiguous=%s)'
+                            % (what, logits.dtype, tuple(logits.shape), logits.is_contiguous()))
+    m, a = logits.shape
+    if not 1 <= m <= MAX_CLASS_ROWS or not 1 <= a <= MAX_CLASSES:
+        raise _lib.KpxError('%s: needs 1 <= rows <= %d and 1 <= classes <= %d (got %s)' % (what, MAX_CLASS_ROWS, MAX_CLASSES, tuple(logits.shape)))
+    return m, a
+
+
+class SoftmaxXentFn(torch.autograd.Function):
+    """reduce_mean(tf.nn.softmax_cross_entropy_with_logits(labels, logits)) over logits [B,A] and label rows [B,A] -> loss [1].
+    Differentiated with respect to the logits only (TensorFlow's gradient: exact when every label row sums to 1)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels):
+        b, a = _class_rows('softmax_xent', logits)
+        if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(labels, 'device', type(labels)))
+        if labels.dtype != torch.float32 or not labels.is_contiguous() or tuple(labels.shape) != (b, a) or labels.device != logits.device:
+            raise _lib.KpxError('softmax_xent: labels must be a contiguous fp32 %s tensor on %s (got %s %s on %s, contiguous=%s)'
+                                % ([b, a], logits.device, labels.dtype, tuple(labels.shape), labels.device, labels.is_contiguous()))
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+        lse = torch.empty(b, dtype=torch.float32, device=logits.device)
+        check(lib.kpx_softmax_xent_fwd_f32(logits.data_ptr(), labels.data_ptr(), b, a, loss.data_ptr(), lse.data_ptr(), _stream()),
+              'kpx_softmax_xent_fwd_f32')
+        ctx.save_for_backward(logits, labels, lse)
+        ctx.mark_non_differentiable(lse)
+        return loss, lse
+
+    @staticmethod
+    def backward(ctx, dloss, _dlse):
+        logits, labels, lse = ctx.saved_tensors
+        b, a = logits.shape
+        dloss = dloss.contiguous()
+        dl = torch.empty_like(logits)
+        check(lib.kpx_softmax_xent_bwd_f32(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), b, a, dloss.data_ptr(), 1.0, dl.data_ptr(),
+                                           _stream()), 'kpx_softmax_xent_bwd_f32')
+        return dl, None
+
+
+def softmax_xent(logits, labels):
+    """-> loss [1] (see SoftmaxXentFn); logits and labels contiguous fp32 [B,A] on one GPU, 1 <= B <= 2^20, 1 <= A <= 1024."""
+    return SoftmaxXentFn.apply(logits, labels)[0]
+
+
+def class_scores(logits, target, confusion=None, out=None, check_target=True):
+    """Per row of logits (contiguous fp32 [M,A]) against target (contiguous int32 [M], every value in [0, A)) -> (pred int32 [M], rank
+    int32 [M], logp fp32 [M]): pred = the lowest index among the row's maxima, rank = 1 + the number of other
+    classes whose logit is >= the target's (a tie counts against the model), logp = the target's log-softmax.  ``confusion``: a contiguous
+    int32 [A,A] tensor, [target, pred] += 1 (zeroed by the caller before the first call).  A row with a non-finite logit gets pred = -1,
+    rank = A, logp = NaN and is left out of ``confusion``.  ``out``: (pred, rank, logp) tensors to write into.  One launch.  The range
+    check of the targets reads them back to the host before the launch; a caller that has checked them (or is capturing a graph, where
+    nothing can be read back) passes ``check_target=False``."""
+    m, a = _class_rows('class_scores', logits)
+    dev = logits.device
+    if not isinstance(target, torch.Tensor) or not target.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(target, 'device', type(target)))
+    if target.dtype != torch.int32 or not target.is_contiguous() or tuple(target.shape) != (m,) or target.device != dev:
+        raise _lib.KpxError('class_scores: target must be a contiguous int32 [%d] tensor on %s (got %s %s on %s)'
+                            % (m, dev, target.dtype, tuple(target.shape), target.device))
+    if confusion is not None and (not isinstance(confusion, torch.Tensor) or confusion.dtype != torch.int32 or not confusion.is_contiguous()
+                                  or tuple(confusion.shape) != (a, a) or confusion.device != dev):
+        raise _lib.KpxError('class_scores: confusion must be a contiguous int32 [%d,%d] tensor on %s' % (a, a, dev))
+    pred, rank, logp = out if out is not None else (None, None, None)
+    for name, o, dt in (('pred', pred, torch.int32), ('rank', rank, torch.int32), ('logp', logp, torch.float32)):
+        if o is not None and (not isinstance(o, torch.Tensor) or tuple(o.shape) != (m,) or o.dtype != dt or not o.is_contiguous() or o.device != dev):
+            raise _lib.KpxError('class_scores: out %s must be a contiguous %s [%d] tensor on %s' % (name, dt, m, dev))
+    if check_target and not torch.cuda.is_current_stream_capturing():
+        lo, hi = (int(v) for v in torch.aminmax(target))
+        if lo < 0 or hi >= a:
+            raise _lib.KpxError('class_scores: every target must lie in [0, %d) (got values from %d to %d)' % (a, lo, hi))
+    pred = torch.empty(m, dtype=torch.int32, device=dev) if pred is None else pred
+    rank = torch.empty(m, dtype=torch.int32, device=dev) if rank is None else rank
+    logp = torch.empty(m, dtype=torch.float32, device=dev) if logp is None else logp
+    check(lib.kpx_class_scores_f32(logits.data_ptr(), target.data_ptr(), m, a, pred.data_ptr(), rank.data_ptr(), logp.data_ptr(),
+                                   _ptr(confusion), _stream()), 'kpx_class_scores_f32')
+    return pred, rank, logp
+
+
 # ----------------------------------------------------------------------------------------------- optimiser
 def adam_tf_flat_(p, g, m, v, alpha, beta1, beta2, eps, gscale=1.0):
     """In-place tf.train.AdamOptimizer update of one flat bucket (reference detector_translator_model.py:198-202)."""
