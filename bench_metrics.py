@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -57,6 +57,14 @@
 13. The configs[4] rollout scored through vgg.FeatureScorer without and with the accumulators (frechet=: pooling, both levels' moments, into
    the two accumulators of draw 0), alternated in one process beside the bare rollout; median ms of each, the cost of --frechet on top of
    --vgg-metrics in ms and %.
+
+``--stability`` measures the detector's equivariance score (make_pseudo_labels.py --stability) instead:
+
+14. kpx_affine_warp_f32 alone at [128 frames x 4 maps, 128, 128, 3] (per output row about a frame read and a frame written: 201 MB, which
+   fits the 256 MB Infinity Cache) beside a float4 device copy of the same bytes in the same process; median us, bytes/s and the fraction
+   of the copy.  kpx_equivariance_scores_f32 alone at K = 40 on the 1 326 rows of a 663-frame video at W = 2: a launch-bound call.
+15. A 663-frame video through KeypointModel.run (K = 40) without and with stability() at W = 2, alternated in one process; the warp of its
+   1 326 warped frames alone beside the detector on them.
 
 Prints one JSON line.
 """
@@ -667,6 +675,95 @@ def classifier_rollout_leg(dev, rollouts):
             'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
 
 
+STAB_FRAMES, STAB_WARPS, STAB_POINTS, VIDEO_FRAMES = 128, 4, 40, 663
+
+
+def stability_kernel_leg(dev, launches):
+    """kpx_affine_warp_f32 at [128 frames x 4 maps, 128, 128, 3] beside a float4 device copy of the same bytes (every output row reads about a
+    frame and writes one: 2 x the output), and kpx_equivariance_scores_f32 at K = 40 on the rows of a 663-frame video at W = 2."""
+    from kpx_amd import ops, stability
+    g = torch.Generator(device=dev).manual_seed(6)
+    frames = torch.rand((STAB_FRAMES, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    coef, _ = stability.draw_warps(STAB_FRAMES, STAB_WARPS, seed=1, res=RES)
+    r = STAB_FRAMES * STAB_WARPS
+    rows = torch.arange(STAB_FRAMES, dtype=torch.int32, device=dev).repeat_interleave(STAB_WARPS).contiguous()
+    coef = torch.from_numpy(coef.reshape(r, 6)).to(dev)
+    out, other = torch.empty((r, RES, RES, 3), device=dev), torch.empty((r, RES, RES, 3), device=dev)
+    nbytes = 2 * out.numel() * 4
+    res = {'warp': {'shape': [r, RES, RES, 3], 'frames': STAB_FRAMES, 'maps_per_frame': STAB_WARPS, 'mb': round(nbytes / 1e6, 1),
+                    'fits_infinity_cache': nbytes < 256e6, 'launches': launches}}
+    for key, fn in (('warp', lambda: ops.affine_warp(frames, rows, coef, out=out, check_tables=False)), ('copy', lambda: other.copy_(out))):
+        us = _event_times(fn, launches, dev)
+        med = statistics.median(us)
+        res['warp'][key] = {'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                            'gb_per_s': round(nbytes / (med * 1e-6) / 1e9, 1), 'frac_of_copy_rate': round(nbytes / (med * 1e-6) / COPY_RATE, 3)}
+    res['warp']['frac_of_copy_in_this_process'] = round(res['warp']['copy']['median_us'] / res['warp']['warp']['median_us'], 3)
+    assert bool(torch.isfinite(out).all())
+    del out, other
+    torch.cuda.empty_cache()
+    n, w, k = VIDEO_FRAMES, 2, STAB_POINTS
+    _, fwd = stability.draw_warps(n, w, seed=2, res=RES)
+    pts = torch.rand((n, k, 2), generator=g, device=dev) * 1.6 - 0.8
+    pts_w = torch.rand((n * w, k, 2), generator=g, device=dev) * 1.6 - 0.8
+    rows = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(w).contiguous()
+    fwd = torch.from_numpy(fwd.reshape(n * w, 6)).to(dev)
+    outs = ops.equivariance_scores(pts, pts_w, rows, fwd)
+    us = _event_times(lambda: ops.equivariance_scores(pts, pts_w, rows, fwd, out=outs, check_tables=False), launches, dev)
+    assert int(outs[3].sum()) > 0                             # a launch-bound call: no rate is quoted
+    res['scores'] = {'rows': n * w, 'points': k, 'launches': launches, 'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1),
+                     'max_us': round(max(us), 1)}
+    return res
+
+
+def stability_video_leg(dev, rollouts):
+    """A 663-frame video through KeypointModel.run (K = 40, 128 x 128) without and with stability() at W = 2 (the points of run() reused),
+    alternated in one process; and the warp of those 2 x 663 frames alone beside the detector on them."""
+    import kpx_amd
+    from kpx_amd import ops, stability
+    cfg = {'model': {'n_pts': STAB_POINTS}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(8)
+    n, w = VIDEO_FRAMES, 2
+    video = torch.rand((1, n, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    coef, fwd = stability.draw_warps(n, w, seed=3, res=RES)
+    model = kpx_amd.KeypointModel(cfg, device=dev)
+    model.build(None)
+
+    def one(score):
+        o = model.run(None, {'image': video})
+        if score:
+            return model.stability(video[0], coef, fwd, pts=o['pts'][0])
+
+    for _ in range(2):
+        last = one(True)
+    torch.cuda.synchronize(dev)
+    ms = {False: [], True: []}
+    for _ in range(rollouts):
+        for score in (False, True):
+            t0 = time.perf_counter()
+            one(score)
+            torch.cuda.synchronize(dev)
+            ms[score].append((time.perf_counter() - t0) * 1e3)
+    assert int(last['n_valid'].sum()) > 0
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    rows = torch.arange(n, dtype=torch.int32, device=dev).repeat_interleave(w).contiguous()
+    coef_dev = torch.from_numpy(coef.reshape(n * w, 6)).to(dev)
+    warped = torch.empty((n * w, RES, RES, 3), device=dev)
+    warp_us = statistics.median(_event_times(lambda: ops.affine_warp(video[0], rows, coef_dev, out=warped, check_tables=False), 10, dev))
+    detect = []
+    for _ in range(max(3, rollouts // 2)):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        model.run(None, {'image': warped[None]})
+        torch.cuda.synchronize(dev)
+        detect.append((time.perf_counter() - t0) * 1e3)
+    det = statistics.median(detect)
+    return {'frames': n, 'maps_per_frame': w, 'points': STAB_POINTS, 'frames_per_launch': model.frames_per_launch, 'runs_each': rollouts,
+            'run_ms': round(off, 3), 'run_and_stability_ms': round(on, 3), 'delta_ms': round(on - off, 3), 'delta_over_run': round((on - off) / off, 3),
+            'warp_of_the_warped_frames_ms': round(warp_us / 1e3, 3), 'detector_on_the_warped_frames_ms': round(det, 3),
+            'warp_over_detector': round(warp_us / 1e3 / det, 4),
+            'run_ms_all': [round(v, 2) for v in ms[False]], 'run_and_stability_ms_all': [round(v, 2) for v in ms[True]]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -678,9 +775,11 @@ def main():
     ap.add_argument('--frechet', action='store_true', help="measure the Fréchet distance's pooling and moment kernels and its cost per rollout instead")
     ap.add_argument('--classifier', action='store_true',
                     help="measure the action classifier's loss and score launches and the cost of --action-accuracy per rollout instead")
+    ap.add_argument('--stability', action='store_true',
+                    help="measure the detector's equivariance score (the affine warp, the score launch, the cost of stability() per video) instead")
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier > 1:
-        ap.error('--vgg, --motion, --actions, --drive, --frechet and --classifier are six measurements: pass one')
+    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability > 1:
+        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier and --stability are seven measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
@@ -688,6 +787,12 @@ def main():
         res = {'vgg_kernel': vgg_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()
         res['vgg_rollout_c4'] = vgg_rollout_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
+    if args.stability:
+        res = {'stability_kernels': stability_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['stability_video'] = stability_video_leg(dev, args.rollouts)
         print(json.dumps(res))
         return
     if args.classifier:

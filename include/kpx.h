@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 17
+#define KPX_ABI_VERSION 18
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -675,6 +675,44 @@ int kpx_softmax_xent_bwd_f32(const float* logits, const float* labels, const flo
                              float gscale_host, float* dlogits, void* stream);
 int kpx_class_scores_f32(const float* logits, const int32_t* target, int M, int A, int32_t* pred, int32_t* rank, float* logp,
                          int32_t* confusion, void* stream);
+
+/* ---- equivariance score of the key-point detector (csrc/stability.hip; make_pseudo_labels.py --stability, kpx_amd/stability.py), DESIGN.md
+ * section 2: warp every frame by a known affine map, detect again, and compare the detected points with the mapped originals.  No reference
+ * counterpart (the reference never scores its detector).  Both entries: ONE launch on `stream`, no allocation, copy, synchronisation or
+ * atomics (capturable), nothing written outside their outputs; KPX_EINVAL before any device call for a null or misaligned pointer (4 bytes;
+ * 8 for the double tables) or a size out of range.  Added in ABI version 18.
+ *
+ * kpx_affine_warp_f32: in fp32 [N,H,W,C] contiguous, C in {1,3}, H and W in [1,1024], N >= 1; rows int32 [R], the source frame of each
+ *   output row (any order, repeats allowed); coef double [R][6], the INVERSE map of each row in pixel units; out fp32 [R,H,W,C];
+ *   1 <= R <= KPX_WARP_MAX_ROWS.  For output pixel (x, y) of row r, with c = coef[r] and v = in[rows[r]]:
+ *     sx = (c0*x + c1*y) + c2,  sy = (c3*x + c4*y) + c5, clamped to [0, W-1] and [0, H-1] (edge replication; NaN -> 0)
+ *     x0 = floor(sx), lowered to max(W-2, 0) if it exceeds W-2;  fx = sx - x0;  x1 = min(x0 + 1, W-1);  y0, fy, y1 alike
+ *     top = (1-fx)*v[y0,x0] + fx*v[y0,x1],  bot = (1-fx)*v[y1,x0] + fx*v[y1,x1],  out = (1-fy)*top + fy*bot
+ *   Everything in fp64, no product or sum fused (as kpx_keypoint_seq_augment_f32), the result cast to fp32 once: bit for bit what numpy
+ *   float64 gives in this order.  Maps that send pixels to pixels (identity, integer shifts, flips, quarter turns of a square frame) copy
+ *   input bits (fx, fy in {0, 1}; only a -0.0 beside a value of the other sign comes out as +0.0).  Frames are finite by contract (0 * inf
+ *   is NaN).  The clamp keeps every tap inside the frame for any coefficients; the frame numbers are trusted: the HOST rejects, before the
+ *   launch, a frame number outside [0, N) and a non-finite coefficient (kpx_amd.ops.affine_warp).
+ *   A workgroup writes a 16-row tile of one output row; 16-byte stores when W % 4 == 0 and out is 16-byte aligned, 4-byte stores otherwise
+ *   -- the same bits on both paths; `in` needs 4-byte alignment only.
+ *
+ * kpx_equivariance_scores_f32: pts fp32 [N][K][2] (x, y), the detector on the original frames; pts_w fp32 [R][K][2], the detector on the
+ *   warped frames; rows int32 [R] as above (trusted alike); fwd double [R][6], the FORWARD map of each row in the normalised coordinates of
+ *   the key points ([-1,1], pixel i at -1 + 2i/(res-1)); 1 <= K <= 1024, 1 <= R <= KPX_EQUIV_MAX_ROWS.  For row r and point k, p =
+ *   pts[rows[r]][k], q = pts_w[r][k], m = fwd[r]:
+ *     target = ((m0*p.x + m1*p.y) + m2, (m3*p.x + m4*p.y) + m5)
+ *     out[r][k] = (err, moved) (fp32 [R][K][2]): err = |q - target|, moved = |target - p|, Euclidean, in fp64 (no fma), each rounded once
+ *     valid[r][k] (uint8 [R][K]) = 1 when p, q and target are finite and target lies in [-1,1] x [-1,1], bounds included; else 0
+ *     frame_mean[r] (fp32 [R][2]) = (mean err, mean moved) over the row's valid points: the unrounded fp64 values added in ascending k,
+ *       divided by their number, rounded once; (NaN, NaN) when there are none.  n_valid[r] (int32 [R]) = their number.
+ *   One wavefront per row; the order of every addition is fixed. */
+#define KPX_WARP_MAX_ROWS 65536
+#define KPX_EQUIV_MAX_ROWS (1 << 20)
+int kpx_affine_warp_f32(const float* in /*[N,H,W,C]*/, int N, int H, int W, int C, const int32_t* rows /*[R]*/, const double* coef /*[R][6]*/,
+                        int R, float* out /*[R,H,W,C]*/, void* stream);
+int kpx_equivariance_scores_f32(const float* pts /*[N,K,2]*/, const float* pts_w /*[R,K,2]*/, const int32_t* rows /*[R]*/,
+                                const double* fwd /*[R][6]*/, int R, int K, float* out /*[R,K,2]*/, uint8_t* valid /*[R,K]*/,
+                                float* frame_mean /*[R,2]*/, int32_t* n_valid /*[R]*/, void* stream);
 
 #ifdef __cplusplus
 }

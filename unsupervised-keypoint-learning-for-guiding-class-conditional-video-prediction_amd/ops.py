@@ -1732,6 +1732,100 @@ def points_retarget(src_first, mode, drv_first=None, drv_seq=None, shift=0, scal
     return out
 
 
+WARP_MAX_ROWS = 1 << 16                                                           # = KPX_WARP_MAX_ROWS
+EQUIV_MAX_ROWS, EQUIV_MAX_POINTS = 1 << 20, 1024                                  # = KPX_EQUIV_MAX_ROWS; K of kpx_equivariance_scores_f32
+
+
+def _map_tables(what, rows, maps, maps_name, n, max_rows, dev, check_tables):
+    """The two tables the stability entries share: rows contiguous int32 [R] (every value in [0, n)) and maps contiguous fp64 [R,6] (finite)
+    on ``dev``, 1 <= R <= max_rows -> R.  The value checks read the tables back to the host; ``check_tables=False`` (or a stream that is
+    capturing, where nothing can be read back) skips them."""
+    for name, t, dtype, dim in (('rows', rows, torch.int32, 1), (maps_name, maps, torch.float64, 2)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got %s for %s\'s %s); there is no CPU fallback'
+                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, what, name))
+        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous() or t.device != dev:
+            raise _lib.KpxError('%s: %s must be a contiguous %s tensor of %d dimension(s) on %s (got %s %s on %s, contiguous=%s)'
+                                % (what, name, dtype, dim, dev, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
+    r = rows.shape[0]
+    if not 1 <= r <= max_rows or tuple(maps.shape) != (r, 6):
+        raise _lib.KpxError('%s: needs 1 <= R <= %d rows and %s [R,6] (got rows %s, %s %s)'
+                            % (what, max_rows, maps_name, tuple(rows.shape), maps_name, tuple(maps.shape)))
+    if check_tables and not torch.cuda.is_current_stream_capturing():
+        lo, hi = (int(v) for v in torch.aminmax(rows))
+        if lo < 0 or hi >= n:
+            raise _lib.KpxError('%s: every frame number must lie in [0, %d) (got values from %d to %d)' % (what, n, lo, hi))
+        if not bool(torch.isfinite(maps).all()):
+            raise _lib.KpxError('%s: %s has a non-finite coefficient' % (what, maps_name))
+    return r
+
+
+def affine_warp(frames, rows, coef, out=None, check_tables=True):
+    """Frames resampled through affine maps (the detector's stability): frames contiguous fp32 [N,H,W,C], C in (1, 3),
+    H and W in [1, 1024], finite; rows contiguous int32 [R], the source frame of each output row (any order, repeats allowed); coef contiguous
+    fp64 [R,6], the INVERSE map of each row in pixel units: output pixel (x, y) reads the source at (c0 x + c1 y + c2, c3 x + c4 y + c5),
+    clamped to the frame (edge replication), bilinear -> fp32 [R,H,W,C].  fp64 arithmetic, nothing fused, one rounding: the bits of the numpy
+    float64 restatement; maps that send pixels to pixels copy input bits.  1 <= R <= 65536.  ``out``: a contiguous fp32 [R,H,W,C] tensor
+    to write into.  One launch on the current stream (capturable with ``check_tables=False``, which skips reading the tables back for the
+    range check of the frame numbers and the finiteness of the coefficients)."""
+    _require_gpu(frames)
+    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.dim() != 4:
+        raise _lib.KpxError('affine_warp: frames must be a contiguous fp32 [N,H,W,C] tensor (got %s %s, contiguous=%s)'
+                            % (tuple(frames.shape), frames.dtype, frames.is_contiguous()))
+    n, h, w, c = frames.shape
+    if n < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
+        raise _lib.KpxError('affine_warp: needs N >= 1, H and W in [1, 1024] and C in (1, 3) (got %s)' % (tuple(frames.shape),))
+    dev = frames.device
+    r = _map_tables('affine_warp', rows, coef, 'coef', n, WARP_MAX_ROWS, dev, check_tables)
+    if out is None:
+        out = torch.empty((r, h, w, c), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (r, h, w, c) or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != dev):
+        raise _lib.KpxError('affine_warp: out must be a contiguous fp32 [%d,%d,%d,%d] tensor on %s' % (r, h, w, c, dev))
+    check(lib.kpx_affine_warp_f32(frames.data_ptr(), n, h, w, c, rows.data_ptr(), coef.data_ptr(), r, out.data_ptr(), _stream()),
+          'kpx_affine_warp_f32')
+    return out
+
+
+def equivariance_scores(pts, pts_w, rows, fwd, out=None, check_tables=True):
+    """The detector's equivariance error (DESIGN.md section 2): pts contiguous fp32 [N,K,2] (x, y), the key points of the original frames;
+    pts_w contiguous fp32 [R,K,2], those of the warped frames; rows contiguous int32 [R], the original frame of each row; fwd contiguous fp64
+    [R,6], the FORWARD map of each row in the key points' normalised coordinates -> (scores fp32 [R,K,2], valid uint8 [R,K], frame_mean fp32
+    [R,2], n_valid int32 [R]): scores = (err, moved) = (|pts_w - target|, |target - p|) with target = M p + t; valid = 1 where p, pts_w and
+    the target are finite and the target lies in [-1, 1]^2; frame_mean = the means of both over the row's valid points (NaN without any);
+    n_valid their number.  fp64 arithmetic in a fixed order, rounded once.  1 <= K <= 1024, 1 <= R <= 2^20.  ``out``: the four tensors to
+    write into.  One launch on the current stream (``check_tables`` as in ``affine_warp``)."""
+    for name, t in (('pts', pts), ('pts_w', pts_w)):
+        if not isinstance(t, torch.Tensor):
+            raise _lib.KpxError('equivariance_scores: %s must be a tensor (got %s)' % (name, type(t).__name__))
+        _require_gpu(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 or t.shape[2] != 2:
+            raise _lib.KpxError('equivariance_scores: %s must be a contiguous fp32 [.,K,2] tensor (got %s %s, contiguous=%s)'
+                                % (name, tuple(t.shape), t.dtype, t.is_contiguous()))
+    n, k, _ = pts.shape
+    dev = pts.device
+    if n < 1 or not 1 <= k <= EQUIV_MAX_POINTS or pts_w.shape[1] != k or pts_w.device != dev:
+        raise _lib.KpxError('equivariance_scores: pts [N,K,2] and pts_w [R,K,2] need N >= 1 and one K in [1, %d] on one device (got %s on %s, '
+                            '%s on %s)' % (EQUIV_MAX_POINTS, tuple(pts.shape), dev, tuple(pts_w.shape), pts_w.device))
+    r = _map_tables('equivariance_scores', rows, fwd, 'fwd', n, EQUIV_MAX_ROWS, dev, check_tables)
+    if pts_w.shape[0] != r:
+        raise _lib.KpxError('equivariance_scores: pts_w must have one entry per row (got %s for %d rows)' % (tuple(pts_w.shape), r))
+    specs = (('scores', (r, k, 2), torch.float32), ('valid', (r, k), torch.uint8), ('frame_mean', (r, 2), torch.float32),
+             ('n_valid', (r,), torch.int32))
+    outs = list(out) if out is not None else [None] * 4
+    if len(outs) != 4:
+        raise _lib.KpxError('equivariance_scores: out must be (scores, valid, frame_mean, n_valid)')
+    for i, (name, shape, dtype) in enumerate(specs):
+        o = outs[i]
+        if o is not None and (not isinstance(o, torch.Tensor) or tuple(o.shape) != shape or o.dtype != dtype or not o.is_contiguous()
+                              or o.device != dev):
+            raise _lib.KpxError('equivariance_scores: out %s must be a contiguous %s %s tensor on %s' % (name, dtype, list(shape), dev))
+    outs = [torch.empty(shape, dtype=dtype, device=dev) if o is None else o for o, (_, shape, dtype) in zip(outs, specs)]
+    check(lib.kpx_equivariance_scores_f32(pts.data_ptr(), pts_w.data_ptr(), rows.data_ptr(), fwd.data_ptr(), r, k, outs[0].data_ptr(),
+                                          outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), _stream()), 'kpx_equivariance_scores_f32')
+    return tuple(outs)
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
