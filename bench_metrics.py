@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -65,6 +65,15 @@
    of the copy.  kpx_equivariance_scores_f32 alone at K = 40 on the 1 326 rows of a 663-frame video at W = 2: a launch-bound call.
 15. A 663-frame video through KeypointModel.run (K = 40) without and with stability() at W = 2, alternated in one process; the warp of its
    1 326 warped frames alone beside the detector on them.
+
+``--joints`` measures the landmark regression (make_pseudo_labels.py --joints) instead:
+
+16. kpx_joint_targets_f32, kpx_joint_moments_add_f64 and kpx_joint_scores_f32 alone on the F = 663 frames of a video with J = 13 joints,
+   at K = 15 and at K = 40, each beside a device copy of the bytes the launch reads and writes in the same process; median, minimum and
+   maximum us.  All three are launch-bound at these sizes: no rate is quoted.
+17. A 663-frame video through KeypointModel.run (K = 40) without and with JointRegression.add for a train video (targets and moments, the
+   labels already read), alternated in one process, and JointRegression.finish (the host solve and one scores launch per video) over the
+   videos added, per video.
 
 Prints one JSON line.
 """
@@ -764,6 +773,94 @@ def stability_video_leg(dev, rollouts):
             'run_ms_all': [round(v, 2) for v in ms[False]], 'run_and_stability_ms_all': [round(v, 2) for v in ms[True]]}
 
 
+JOINT_COUNT = 13
+
+
+def _joint_inputs(dev, f, k, j, seed):
+    """Device inputs of the three joint launches for one video of f frames, from planted annotations of a 320 x 240 frame."""
+    import numpy as np
+    from kpx_amd import joints
+    labels = joints.planted_labels([seed, 0], f, j, (320, 240))
+    g = torch.Generator(device=dev).manual_seed(seed)
+    pts = (torch.rand((f, k, 2), generator=g, device=dev) * 1.8 - 0.9).contiguous()
+    xy = torch.from_numpy(np.stack([labels['x'], labels['y']], axis=-1).astype(np.float32)).to(dev)
+    vis = torch.from_numpy(labels['visibility'].astype(np.uint8)).to(dev)
+    bbox = torch.from_numpy(labels['bbox'].astype(np.float32)).to(dev)
+    cmap = torch.from_numpy(joints.crop_map(320, 240)).to(dev)
+    return labels, pts, xy, vis, bbox, cmap
+
+
+def joints_kernel_leg(dev, launches):
+    """The three launches alone at F = 663, J = 13 for K = 15 and K = 40, each beside a device copy of the bytes it reads and writes."""
+    from kpx_amd import ops
+    out = {}
+    f, j = VIDEO_FRAMES, JOINT_COUNT
+    for k in (15, 40):
+        d = 2 * k + 1
+        _, pts, xy, vis, bbox, cmap = _joint_inputs(dev, f, k, j, 20 + k)
+        target, mask, norm = ops.joint_targets(xy, vis, bbox, cmap)
+        gm, bm, n = (torch.zeros(s, dtype=t, device=dev) for s, t in (((j, d, d), torch.float64), ((j, d, 2), torch.float64), ((j,), torch.int64)))
+        w = (torch.rand((j, d, 2), dtype=torch.float64, device=dev) - 0.5) / d
+        alpha = torch.tensor([0.05, 0.1, 0.2], dtype=torch.float64, device=dev)
+        nbytes = {'targets': xy.numel() * 4 + vis.numel() + bbox.numel() * 4 + target.numel() * 4 + mask.numel() + norm.numel() * 4,
+                  'moments': pts.numel() * 4 + target.numel() * 4 + mask.numel() + 2 * (gm.numel() + bm.numel() + n.numel()) * 8,
+                  'scores': pts.numel() * 4 + target.numel() * 4 + mask.numel() + norm.numel() * 4 + w.numel() * 8 + f * j * (8 + 4 + 1)}
+        fns = {'targets': lambda: ops.joint_targets(xy, vis, bbox, cmap), 'moments': lambda: ops.joint_moments_add(pts, target, mask, gm, bm, n),
+               'scores': lambda: ops.joint_scores(pts, target, mask, norm, w, alpha)}
+        res = {'frames': f, 'points': k, 'joints': j, 'D': d, 'launches': launches}
+        for key in ('targets', 'moments', 'scores'):
+            us = _event_times(fns[key], launches, dev)
+            src, dst = torch.empty(nbytes[key] // 2, dtype=torch.uint8, device=dev), torch.empty(nbytes[key] // 2, dtype=torch.uint8, device=dev)
+            cp = _event_times(lambda: dst.copy_(src), launches, dev)
+            res[key] = {'bytes': nbytes[key], 'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                        'copy_median_us': round(statistics.median(cp), 1), 'copy_min_us': round(min(cp), 1)}
+        assert int(n.sum()) > 0 and bool(torch.isfinite(gm).all())
+        out['K%d' % k] = res
+    return out
+
+
+def joints_video_leg(dev, rollouts):
+    """A 663-frame video through KeypointModel.run (K = 40) without and with JointRegression.add as a train video, alternated in one
+    process; then finish() over the videos added, per video."""
+    import kpx_amd
+    from kpx_amd import joints
+    cfg = {'model': {'n_pts': STAB_POINTS}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(9)
+    n = VIDEO_FRAMES
+    video = torch.rand((1, n, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    labels = joints.planted_labels([9, 0], n, JOINT_COUNT, (320, 240))
+    model = kpx_amd.KeypointModel(cfg, device=dev)
+    model.build(None)
+    reg = joints.JointRegression(STAB_POINTS, JOINT_COUNT, device=dev)
+
+    def one(score):
+        o = model.run(None, {'image': video})
+        if score:
+            reg.add('train', len(reg.kept), o['pts'][0], labels, (320, 240))
+
+    for _ in range(2):
+        one(True)
+    torch.cuda.synchronize(dev)
+    ms = {False: [], True: []}
+    for _ in range(rollouts):
+        for score in (False, True):
+            t0 = time.perf_counter()
+            one(score)
+            torch.cuda.synchronize(dev)
+            ms[score].append((time.perf_counter() - t0) * 1e3)
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    out = reg.finish()
+    torch.cuda.synchronize(dev)
+    fin = (time.perf_counter() - t0) * 1e3
+    assert out['summary']['overall']['valid_entries'] > 0
+    return {'frames': n, 'points': STAB_POINTS, 'joints': JOINT_COUNT, 'runs_each': rollouts, 'run_ms': round(off, 3), 'run_and_add_ms': round(on, 3),
+            'delta_ms': round(on - off, 3), 'delta_over_run': round((on - off) / off, 4), 'videos_finished': len(reg.kept),
+            'finish_ms': round(fin, 3), 'finish_ms_per_video': round(fin / len(reg.kept), 3),
+            'run_ms_all': [round(v, 2) for v in ms[False]], 'run_and_add_ms_all': [round(v, 2) for v in ms[True]]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -777,9 +874,11 @@ def main():
                     help="measure the action classifier's loss and score launches and the cost of --action-accuracy per rollout instead")
     ap.add_argument('--stability', action='store_true',
                     help="measure the detector's equivariance score (the affine warp, the score launch, the cost of stability() per video) instead")
+    ap.add_argument('--joints', action='store_true',
+                    help='measure the landmark regression (its three launches, the cost of JointRegression per video) instead')
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability > 1:
-        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier and --stability are seven measurements: pass one')
+    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability + args.joints > 1:
+        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier, --stability and --joints are eight measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
@@ -793,6 +892,12 @@ def main():
         res = {'stability_kernels': stability_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()
         res['stability_video'] = stability_video_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
+    if args.joints:
+        res = {'joints_kernels': joints_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['joints_video'] = joints_video_leg(dev, args.rollouts)
         print(json.dumps(res))
         return
     if args.classifier:

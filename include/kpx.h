@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 18
+#define KPX_ABI_VERSION 19
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -713,6 +713,57 @@ int kpx_affine_warp_f32(const float* in /*[N,H,W,C]*/, int N, int H, int W, int 
 int kpx_equivariance_scores_f32(const float* pts /*[N,K,2]*/, const float* pts_w /*[R,K,2]*/, const int32_t* rows /*[R]*/,
                                 const double* fwd /*[R][6]*/, int R, int K, float* out /*[R,K,2]*/, uint8_t* valid /*[R,K]*/,
                                 float* frame_mean /*[R,2]*/, int32_t* n_valid /*[R]*/, void* stream);
+
+/* ---- landmark regression from the key points to annotated joints (csrc/joints.hip; make_pseudo_labels.py --joints, kpx_amd/joints.py),
+ * a linear map from the K points the detector found on a frame to the frame's J annotated joints, fitted per joint on the
+ * train split and scored on both.  No reference counterpart (the reference never reads Penn Action's annotations).  phi_f = (x_0, y_0, ...,
+ * x_{K-1}, y_{K-1}, 1) is the feature row of frame f, the fp32 key points pts[f] widened to fp64, and D = 2K + 1.  All three entries: ONE
+ * launch on `stream`, no allocation, copy, synchronisation or atomics (capturable), every sum in an order that does not depend on the
+ * launch, nothing written outside their outputs, all arithmetic in fp64; KPX_EINVAL before any device call for a null or misaligned pointer
+ * (4 bytes for fp32, 8 for double and int64 arrays, none for uint8) or a size out of range: 1 <= K <= KPX_JOINT_MAX_POINTS, 1 <= J <=
+ * KPX_JOINT_MAX_JOINTS, 1 <= F <= KPX_JOINT_MAX_FRAMES, 1 <= A <= KPX_JOINT_MAX_ALPHAS.  Added in ABI version 19.
+ *
+ * kpx_joint_targets_f32: xy fp32 [F][J][2], the annotated joints in the original frame's pixel coordinates; vis uint8 [F][J]; bbox fp32
+ *   [F][4] = (x0, y0, x1, y1) in the same pixels; map double [4] = (ax, bx, ay, by) (kpx_amd.joints.crop_map).  For frame f and joint j:
+ *     t = (ax*x + bx, ay*y + by), the product and the sum each rounded once in fp64 (no fma);  target[f][j] (fp32 [F][J][2]) = t, cast once
+ *     mask[f][j] (uint8 [F][J]) = 1 when vis[f][j] != 0, x and y are finite and the unrounded t lies in [-1,1] x [-1,1], bounds included;
+ *       else 0 (a non-finite map gives a NaN t and so 0)
+ *     norm[f] (fp32 [F]) = max(|ax|*(x1-x0), |ay|*(y1-y0)), each difference and product rounded once, cast once: the longer side of the box
+ *       in the normalised units of the crop, the frame's PCK normaliser.  NaN unless the four numbers are finite and x1 > x0 and y1 > y0.
+ *
+ * kpx_joint_moments_add_f64: pts fp32 [F][K][2]; target fp32 [F][J][2]; mask uint8 [F][J].  In place, for every joint j:
+ *     G[j]  (double [J][D][D]) += sum_f use[f][j] phi_f phi_f^T
+ *     Bm[j] (double [J][D][2]) += sum_f use[f][j] phi_f target[f][j]^T
+ *     n[j]  (int64 [J])        += sum_f use[f][j],      use[f][j] = mask[f][j] != 0 and all 2K coordinates of pts[f] are finite
+ *   Each element starts from its stored value and takes the frames with use = 1 in ascending f, ONE fma each: G[j][a][b] = fma(phi_f[a],
+ *   phi_f[b], G[j][a][b]), Bm[j][a][c] = fma(phi_f[a], target[f][j][c], Bm[j][a][c]); a frame with use = 0 touches nothing.  So F frames in
+ *   one call and the same frames in any split into consecutive calls give the same bits, a G that starts bitwise symmetric stays so, and a
+ *   frame with a non-finite key point contributes to no joint.  The caller zeroes the accumulators before the first call and keeps the
+ *   targets of the frames it masks in finite (kpx_joint_targets_f32 does).
+ *
+ * kpx_joint_scores_f32: pts, target, mask as above; norm fp32 [F]; W double [J][D][2], the regressor; alpha double [A], the PCK thresholds.
+ *   Per frame and joint, every product and sum rounded once (no fma):
+ *     p = (0 + phi_f[0]*W[j][0] + phi_f[1]*W[j][1] + ...) in ascending d, both components;  pred[f][j] (fp32 [F][J][2]) = p, cast once
+ *     e = sqrt(dx*dx + dy*dy), (dx, dy) = p - target[f][j];  err[f][j] (fp32 [F][J]) = e, cast once
+ *     valid = mask[f][j] != 0 and all 2K coordinates of pts[f] are finite;  pck = valid and norm[f] is finite
+ *     hits[f][j] (uint8 [F][J]): bit a set when pck and e <= alpha[a]*norm[f] (the unrounded e); 0 for an entry that is not pck
+ *   Per call and joint, written (not added to):
+ *     sum_err[j] (double [J]) = the unrounded e of the valid entries, added in ascending f from 0;  count[j] (int64 [J]) = their number
+ *     pck_count[j] (int64 [J]) = the number of pck entries;  hit_count[j][a] (int64 [J][A]) = the number of entries with bit a set
+ *   pred and err of an entry that is not valid are written as computed (NaN for a non-finite key point).  A W[j] of NaN (a joint without a
+ *   train frame) gives sum_err[j] = NaN and no hits wherever it has valid entries. */
+#define KPX_JOINT_MAX_POINTS 64
+#define KPX_JOINT_MAX_JOINTS 32
+#define KPX_JOINT_MAX_FRAMES (1 << 20)
+#define KPX_JOINT_MAX_ALPHAS 8
+int kpx_joint_targets_f32(const float* xy /*[F,J,2]*/, const uint8_t* vis /*[F,J]*/, const float* bbox /*[F,4]*/, const double* map /*[4]*/,
+                          int F, int J, float* target /*[F,J,2]*/, uint8_t* mask /*[F,J]*/, float* norm /*[F]*/, void* stream);
+int kpx_joint_moments_add_f64(const float* pts /*[F,K,2]*/, const float* target /*[F,J,2]*/, const uint8_t* mask /*[F,J]*/, int F, int K, int J,
+                              double* G /*[J,D,D]*/, double* Bm /*[J,D,2]*/, int64_t* n /*[J]*/, void* stream);
+int kpx_joint_scores_f32(const float* pts /*[F,K,2]*/, const float* target /*[F,J,2]*/, const uint8_t* mask /*[F,J]*/, const float* norm /*[F]*/,
+                         const double* W /*[J,D,2]*/, const double* alpha /*[A]*/, int F, int K, int J, int A, float* pred /*[F,J,2]*/,
+                         float* err /*[F,J]*/, uint8_t* hits /*[F,J]*/, double* sum_err /*[J]*/, int64_t* count /*[J]*/,
+                         int64_t* pck_count /*[J]*/, int64_t* hit_count /*[J,A]*/, void* stream);
 
 #ifdef __cplusplus
 }

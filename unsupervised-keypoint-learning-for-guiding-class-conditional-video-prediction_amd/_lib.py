@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/kpx.h one to one (tests/test_abi.py checks header vs this table)
-ABI_VERSION = 18      # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
+ABI_VERSION = 19      # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
 SIGNATURES = {
     'kpx_abi_version': (c_int, []),
     'kpx_reload_env': (c_int, []),
@@ -160,6 +160,9 @@ SIGNATURES = {
     'kpx_class_scores_f32': (c_int, [P, P, c_int, c_int, P, P, P, P, P]),
     'kpx_affine_warp_f32': (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, P, P]),
     'kpx_equivariance_scores_f32': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P, P]),
+    'kpx_joint_targets_f32': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P]),
+    'kpx_joint_moments_add_f64': (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P]),
+    'kpx_joint_scores_f32': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -383,6 +383,15 @@ class KeypointDataLoader(_ListedVideos):
             frames = list(pool.map(one, range(n)))
         return np.stack(frames), n, int(video.split('/')[-1])
 
+    def frame_size(self, idx):
+        """(w, h) of the original frames of the idx-th listed video (what ``render_video`` resizes and crops)."""
+        with self._frame(self._images[idx].split()[0], 0) as first:
+            return first.size
+
+    def video_ids(self):
+        """The video numbers in list order (``render_video``'s third value)."""
+        return [int(line.split()[0].split('/')[-1]) for line in self._images]
+
     def sample_generator(self):
         for idx in range(self._total):
             frames, n, vid = self.render_video(idx)

@@ -1826,6 +1826,99 @@ def equivariance_scores(pts, pts_w, rows, fwd, out=None, check_tables=True):
     return tuple(outs)
 
 
+JOINT_MAX_POINTS, JOINT_MAX_JOINTS, JOINT_MAX_FRAMES, JOINT_MAX_ALPHAS = 64, 32, 1 << 20, 8     # = KPX_JOINT_MAX_* of include/kpx.h
+
+
+def _joint_tensors(what, dev, specs):
+    """Every (name, tensor, dtype, shape) of specs is a contiguous tensor of that dtype and shape on ``dev`` (a GPU); a None in a shape
+    matches any size."""
+    for name, t, dtype, shape in specs:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got %s for %s\'s %s); there is no CPU fallback'
+                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, what, name))
+        if (t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)) or not t.is_contiguous()
+                or t.device != dev):
+            raise _lib.KpxError('%s: %s must be a contiguous %s %s tensor on %s (got %s %s on %s, contiguous=%s)'
+                                % (what, name, dtype, list(shape), dev, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
+
+
+def _joint_sizes(what, f, k, j):
+    if not (1 <= f <= JOINT_MAX_FRAMES and 1 <= k <= JOINT_MAX_POINTS and 1 <= j <= JOINT_MAX_JOINTS):
+        raise _lib.KpxError('%s: needs 1 <= F <= %d, 1 <= K <= %d and 1 <= J <= %d (got F = %d, K = %d, J = %d)'
+                            % (what, JOINT_MAX_FRAMES, JOINT_MAX_POINTS, JOINT_MAX_JOINTS, f, k, j))
+
+
+def joint_targets(xy, vis, bbox, crop_map):
+    """Annotated joints in the key points' coordinates (landmark regression): xy contiguous fp32 [F,J,2], the joints in
+    the original frame's pixels; vis contiguous uint8 [F,J]; bbox contiguous fp32 [F,4] = (x0, y0, x1, y1); crop_map contiguous fp64 [4] =
+    (ax, bx, ay, by) on the same device (``kpx_amd.joints.crop_map``) -> (target fp32 [F,J,2] = (ax x + bx, ay y + by) in fp64, rounded once;
+    mask uint8 [F,J] = visible, finite and inside [-1,1]^2; norm fp32 [F] = max(|ax| (x1 - x0), |ay| (y1 - y0)), NaN for a box that is not
+    finite or not positive).  1 <= F <= 2^20, 1 <= J <= 32.  One launch on the current stream."""
+    if not isinstance(xy, torch.Tensor) or xy.dim() != 3:
+        raise _lib.KpxError('joint_targets: xy must be a fp32 [F,J,2] tensor')
+    f, j, dev = xy.shape[0], xy.shape[1], xy.device
+    _joint_tensors('joint_targets', dev, (('xy', xy, torch.float32, (f, j, 2)), ('vis', vis, torch.uint8, (f, j)),
+                                          ('bbox', bbox, torch.float32, (f, 4)), ('crop_map', crop_map, torch.float64, (4,))))
+    _joint_sizes('joint_targets', f, 1, j)
+    target = torch.empty((f, j, 2), dtype=torch.float32, device=dev)
+    mask = torch.empty((f, j), dtype=torch.uint8, device=dev)
+    norm = torch.empty((f,), dtype=torch.float32, device=dev)
+    check(lib.kpx_joint_targets_f32(xy.data_ptr(), vis.data_ptr(), bbox.data_ptr(), crop_map.data_ptr(), f, j, target.data_ptr(), mask.data_ptr(),
+                                    norm.data_ptr(), _stream()), 'kpx_joint_targets_f32')
+    return target, mask, norm
+
+
+def joint_moments_add(pts, target, mask, g, bm, n):
+    """Frames into the masked normal equations of the landmark regression: pts contiguous fp32 [F,K,2]; target
+    contiguous fp32 [F,J,2]; mask contiguous uint8 [F,J]; in place g fp64 [J,D,D] += sum_f phi_f phi_f^T, bm fp64 [J,D,2] += sum_f phi_f
+    target[f,j]^T and n int64 [J] += the number of frames, over the frames with mask[f,j] set and finite key points, phi_f = (pts[f], 1),
+    D = 2K + 1; zeroed by the caller before the first call.  Every element takes its frames in ascending order with one fma each, so any
+    split of the frames into consecutive calls gives the same bits and g stays bitwise symmetric.  1 <= K <= 64, 1 <= J <= 32,
+    1 <= F <= 2^20.  One launch on the current stream.  -> (g, bm, n)."""
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 3 or not isinstance(target, torch.Tensor) or target.dim() != 3:
+        raise _lib.KpxError('joint_moments_add: pts must be a fp32 [F,K,2] and target a fp32 [F,J,2] tensor')
+    f, k, j, dev = pts.shape[0], pts.shape[1], target.shape[1], pts.device
+    d = 2 * k + 1
+    _joint_tensors('joint_moments_add', dev, (('pts', pts, torch.float32, (f, k, 2)), ('target', target, torch.float32, (f, j, 2)),
+                                              ('mask', mask, torch.uint8, (f, j)), ('g', g, torch.float64, (j, d, d)),
+                                              ('bm', bm, torch.float64, (j, d, 2)), ('n', n, torch.int64, (j,))))
+    _joint_sizes('joint_moments_add', f, k, j)
+    check(lib.kpx_joint_moments_add_f64(pts.data_ptr(), target.data_ptr(), mask.data_ptr(), f, k, j, g.data_ptr(), bm.data_ptr(), n.data_ptr(),
+                                        _stream()), 'kpx_joint_moments_add_f64')
+    return g, bm, n
+
+
+def joint_scores(pts, target, mask, norm, w, alpha):
+    """The landmark regressor applied: pts contiguous fp32 [F,K,2]; target contiguous fp32 [F,J,2]; mask contiguous
+    uint8 [F,J]; norm contiguous fp32 [F]; w contiguous fp64 [J,D,2], D = 2K + 1; alpha contiguous fp64 [A], 1 <= A <= 8 -> (pred fp32
+    [F,J,2] = phi_f W[j], err fp32 [F,J] = |pred - target|, hits uint8 [F,J] with bit a set when the entry is valid, norm[f] is finite and
+    err <= alpha[a] norm[f]; per call sum_err fp64 [J] and count int64 [J] over the valid entries (mask set, finite key points) in ascending
+    f, pck_count int64 [J] those of them with a finite norm, hit_count int64 [J,A]).  fp64 arithmetic in a fixed order, nothing fused, each
+    stored value rounded once.  One launch on the current stream."""
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 3 or not isinstance(target, torch.Tensor) or target.dim() != 3:
+        raise _lib.KpxError('joint_scores: pts must be a fp32 [F,K,2] and target a fp32 [F,J,2] tensor')
+    f, k, j, dev = pts.shape[0], pts.shape[1], target.shape[1], pts.device
+    d = 2 * k + 1
+    _joint_tensors('joint_scores', dev, (('pts', pts, torch.float32, (f, k, 2)), ('target', target, torch.float32, (f, j, 2)),
+                                         ('mask', mask, torch.uint8, (f, j)), ('norm', norm, torch.float32, (f,)),
+                                         ('w', w, torch.float64, (j, d, 2)), ('alpha', alpha, torch.float64, (None,))))
+    _joint_sizes('joint_scores', f, k, j)
+    a = alpha.shape[0]
+    if not 1 <= a <= JOINT_MAX_ALPHAS:
+        raise _lib.KpxError('joint_scores: needs 1 <= A <= %d thresholds (got %d)' % (JOINT_MAX_ALPHAS, a))
+    pred = torch.empty((f, j, 2), dtype=torch.float32, device=dev)
+    err = torch.empty((f, j), dtype=torch.float32, device=dev)
+    hits = torch.empty((f, j), dtype=torch.uint8, device=dev)
+    sum_err = torch.empty((j,), dtype=torch.float64, device=dev)
+    count = torch.empty((j,), dtype=torch.int64, device=dev)
+    pck_count = torch.empty((j,), dtype=torch.int64, device=dev)
+    hit_count = torch.empty((j, a), dtype=torch.int64, device=dev)
+    check(lib.kpx_joint_scores_f32(pts.data_ptr(), target.data_ptr(), mask.data_ptr(), norm.data_ptr(), w.data_ptr(), alpha.data_ptr(), f, k, j, a,
+                                   pred.data_ptr(), err.data_ptr(), hits.data_ptr(), sum_err.data_ptr(), count.data_ptr(), pck_count.data_ptr(),
+                                   hit_count.data_ptr(), _stream()), 'kpx_joint_scores_f32')
+    return pred, err, hits, sum_err, count, pck_count, hit_count
+
+
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
