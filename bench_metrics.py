@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -74,6 +74,19 @@
 17. A 663-frame video through KeypointModel.run (K = 40) without and with JointRegression.add for a train video (targets and moments, the
    labels already read), alternated in one process, and JointRegression.finish (the host solve and one scores launch per video) over the
    videos added, per video.
+
+``--gif`` measures the animated GIFs of rollouts (evaluate.py --gif) instead:
+
+18. kpx_color_hist_add_u32 and kpx_palette_map_u8 alone on the compare.gif canvases of a configs[4] batch (64 samples of 33 frames of
+   128 x 384 pixels: 311 MB of RGB, 104 MB of indices; two smooth image columns and a mostly black key-point column), the histogram also on
+   a canvas of uniform noise (no two neighbours share a cell), each beside a device copy of the canvas in the same process; device-event
+   time of each launch after warm-up, median us and the ratio to the copy; the map kernel's candidate evaluations per second.  Then, for 4
+   samples, the host route the kernels replace (the frames copied to the host as fp32, quantised there, PIL ``quantize`` per frame) against
+   ``ops.gif_indices`` plus the copy of the indices, wall-clock ms per sample; and the LZW of one sample's 33 frames in the library's host
+   code against the pure-Python encoder of tests/gif_ref.py.
+19. The configs[4] rollout without and with what --gif adds (``kpx_amd.gif.RolloutGifs.write``: both canvases composed, quantised, copied
+   and written as 128 GIF files), alternated in one process; ms per rollout of each, and the flag's cost split into the device part (through
+   the copy of the indices) and the host part (median cut, LZW, files).
 
 Prints one JSON line.
 """
@@ -861,6 +874,129 @@ def joints_video_leg(dev, rollouts):
             'run_ms_all': [round(v, 2) for v in ms[False]], 'run_and_add_ms_all': [round(v, 2) for v in ms[True]]}
 
 
+def _gif_canvas(dev, g, samples=B):
+    """compare.gif-like canvases uint8 [samples, 33, RES, 3 RES, 3]: two smooth image columns, one mostly black key-point column"""
+    low = torch.rand((samples * 33, 3, 8, 16), generator=g, device=dev)
+    smooth = torch.nn.functional.interpolate(low, size=(RES, 2 * RES), mode='bilinear', align_corners=False).permute(0, 2, 3, 1)
+    smooth = (smooth + 0.02 * torch.rand(smooth.shape, generator=g, device=dev)).clamp(0, 1)
+    canvas = torch.zeros((samples, 33, RES, 3 * RES, 3), dtype=torch.uint8, device=dev)
+    canvas[:, :, :, :2 * RES] = (smooth * 255).to(torch.uint8).view(samples, 33, RES, 2 * RES, 3)
+    for k in range(15):                                   # 15 coloured key-point blobs
+        y, x = 8 + 7 * k, 2 * RES + 10 + 7 * k
+        canvas[:, :, y:y + 5, x:x + 5] = torch.tensor([(37 * k) % 256, (91 * k + 60) % 256, (53 * k + 120) % 256], dtype=torch.uint8, device=dev)
+    return canvas
+
+
+def gif_kernel_leg(dev, launches):
+    import numpy as np
+    from PIL import Image
+    from kpx_amd import gif, ops
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tests'))
+    import gif_ref
+    g = torch.Generator(device=dev).manual_seed(20)
+    canvas = _gif_canvas(dev, g)
+    noise = torch.randint(0, 256, tuple(canvas.shape), generator=g, device=dev, dtype=torch.uint8)
+    dst = torch.empty_like(canvas)
+    hist = torch.zeros((B, 32768, 4), dtype=torch.int32, device=dev)
+    idx, palettes, sizes = ops.gif_indices(canvas)
+    pal_dev, sizes_dev = torch.from_numpy(palettes).to(dev), torch.from_numpy(sizes).to(dev)
+    pixels = canvas.numel() // 3
+    res = {'canvas': list(canvas.shape), 'rgb_mb': round(canvas.numel() / 1e6, 1), 'palette_sizes_min_max': [int(sizes.min()), int(sizes.max())]}
+    legs = (('device_copy', lambda: dst.copy_(canvas)), ('color_hist', lambda: ops.color_hist_add(canvas.view(B, -1, 3), hist)),
+            ('color_hist_noise', lambda: ops.color_hist_add(noise.view(B, -1, 3), hist)),
+            ('palette_map', lambda: ops.palette_map(canvas, pal_dev, sizes_dev, 0, out=idx)),
+            ('palette_map_dither8', lambda: ops.palette_map(canvas, pal_dev, sizes_dev, 8, out=idx)))
+    for name, fn in legs:
+        hist.zero_()                                      # (the repeated adds wrap modulo 2^32: a timing run, the sums are not read)
+        us = _event_times(fn, launches, dev)
+        res[name] = {'launches': launches, 'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1)}
+    copy_us = res['device_copy']['median_us']
+    for name, _ in legs[1:]:
+        res[name]['over_device_copy'] = round(res[name]['median_us'] / copy_us, 2)
+    evals = float(pixels) * float(sizes.astype(np.float64).mean())
+    res['palette_map']['candidates_per_s'] = round(evals / (res['palette_map']['median_us'] * 1e-6), 0)
+    res['device_copy']['gb_per_s'] = round(2 * canvas.numel() / (copy_us * 1e-6) / 1e9, 1)
+    # the host route: fp32 frames to the host, quantised there, PIL's quantiser per frame -- against the device route and the index copy
+    n = 4
+    frames32 = (canvas[:n].float() / 255 * 2 - 1).contiguous()
+    ms = {'host': [], 'device': []}
+    for _ in range(3):                                    # the first pair warms both routes up and is dropped
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        x = frames32.cpu().numpy()
+        q = ((0.5 * (x + 1.0)) * 255).astype(np.uint8)
+        for s in range(n):
+            for t in range(33):
+                Image.fromarray(q[s, t]).quantize(256)
+        ms['host'].append((time.perf_counter() - t0) * 1e3 / n)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        i4, _, _ = ops.gif_indices(canvas[:n])
+        i4.cpu()
+        ms['device'].append((time.perf_counter() - t0) * 1e3 / n)
+    res['route_ms_per_sample'] = {'samples': n, 'host_fp32_copy_and_pil_quantize': round(statistics.median(ms['host'][1:]), 2),
+                                  'device_gif_indices_and_copy': round(statistics.median(ms['device'][1:]), 2)}
+    one = idx[0].cpu().numpy()
+    t0 = time.perf_counter()
+    c_bytes = sum(len(gif.lzw(one[t], 8)) for t in range(33))
+    t1 = time.perf_counter()
+    py_bytes = sum(len(gif_ref.lzw(one[t].reshape(-1), 8)) for t in range(33))
+    t2 = time.perf_counter()
+    assert c_bytes == py_bytes
+    res['lzw_ms_per_sample'] = {'library_host_code': round((t1 - t0) * 1e3, 2), 'pure_python': round((t2 - t1) * 1e3, 2), 'bytes': c_bytes}
+    return res
+
+
+def gif_rollout_leg(dev, rollouts):
+    import shutil
+    import tempfile
+    import kpx_amd
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    real = torch.rand((B, 32, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256, point_maps=True)
+    fm.build()
+    gifs = kpx_amd.gif.RolloutGifs(10, 0)
+    out_dir = tempfile.mkdtemp(prefix='kpx_gif_bench_')
+    ops = kpx_amd.ops
+
+    def run(mode):
+        o = fm.run(None, {'image': im, 'action_code': act}, z=z)
+        cols = [('real', im, real, 'unit'), ('pred', o['im'], o['pred_im_seq'], 'unit'), ('points', o['current_points'], o['future_points'], 'raw')]
+        if mode == 'device':                              # what reaches the host: compose, histogram, median cut, map, the copy of the indices
+            for sel in (cols[1:2], cols):
+                canvas = gifs._canvas([c[1:] for c in sel])
+                gifs._host(ops.gif_indices(canvas, 0)[0])
+        elif mode == 'on':
+            gifs.write(out_dir, 0, cols)
+
+    try:
+        for _ in range(3):                                # eager, capture, one replay
+            run('off')
+        run('on')
+        torch.cuda.synchronize(dev)
+        modes = ('off', 'device', 'on')
+        ms = {m: [] for m in modes}
+        for _ in range(max(1, min(rollouts, 3))):
+            for m in modes:
+                t0 = time.perf_counter()
+                run(m)
+                torch.cuda.synchronize(dev)
+                ms[m].append((time.perf_counter() - t0) * 1e3)
+        size = sum(os.path.getsize(os.path.join(d, n)) for d, _, names in os.walk(out_dir) for n in names)
+    finally:
+        shutil.rmtree(out_dir, ignore_errors=True)
+    off, device, on = (statistics.median(ms[m]) for m in modes)
+    return {'batch': B, 'frames': N_FRAMES, 'graph_replay': len(fm._graphs) == 1, 'gif_files': 2 * B, 'gif_mb': round(size / 1e6, 1),
+            'off_ms_per_rollout': round(off, 2), 'on_ms_per_rollout': round(on, 2), 'flag_ms_per_rollout': round(on - off, 2),
+            'device_part_with_median_cut_ms': round(device - off, 2), 'lzw_and_files_ms': round(on - device, 2),
+            'flag_ms_per_sample': round((on - off) / B, 2), 'off_ms_all': [round(v, 1) for v in ms['off']],
+            'device_ms_all': [round(v, 1) for v in ms['device']], 'on_ms_all': [round(v, 1) for v in ms['on']]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -876,12 +1012,20 @@ def main():
                     help="measure the detector's equivariance score (the affine warp, the score launch, the cost of stability() per video) instead")
     ap.add_argument('--joints', action='store_true',
                     help='measure the landmark regression (its three launches, the cost of JointRegression per video) instead')
+    ap.add_argument('--gif', action='store_true',
+                    help='measure the animated GIFs (the colour histogram and palette-map kernels, the host route, the cost of --gif per rollout) instead')
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability + args.joints > 1:
-        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier, --stability and --joints are eight measurements: pass one')
+    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability + args.joints + args.gif > 1:
+        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier, --stability, --joints and --gif are nine measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
+    if args.gif:
+        res = {'gif_kernels': gif_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['gif_rollout_c4'] = gif_rollout_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
     if args.vgg:
         res = {'vgg_kernel': vgg_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()

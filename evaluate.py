@@ -7,6 +7,7 @@
                        [--actions all|i,j,k [--sheet-frames f,g,h]]
                        [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
                        [--metrics --action-accuracy CKPT]
+                       [--gif [--gif-fps N] [--gif-dither A]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -78,6 +79,17 @@ against the class that was COMMANDED (``kpx_amd.ops.class_scores``, one launch e
 moments on the device, ``kpx_amd.ops.moments_add``); metrics.json an ``action_accuracy`` block (``summarise_action_accuracy``).  This is the
 project's own key-point-space quantity: the recogniser never sees a pixel, and the figures are not comparable with published
 action-recognition accuracies or FVD.
+
+``--gif`` (data path and ``--synthetic``; not with ``--no-save``) writes the rollout as something that can be watched: per sample ``pred.gif``,
+the input image and then the 32 predicted frames of draw 0 -- the frames of input_im.png and pred_seq/ --, and ``compare.gif``, the same
+33 frames as one row of cells ``real | pred | points`` (``pred | points`` with ``--synthetic``): frame 0 holds the input image and
+current_points, frame t the t-th real frame, predicted frame and pred_points map.  With ``--drive-only`` the pred and points columns are
+those of the first driven mode.  The canvases are composed with ``kpx_amd.ops.sheet_paste`` and reduced to ONE palette of at most 256
+colours per GIF on the device (``kpx_amd.ops.gif_indices``: colour histogram, median cut, nearest-entry search), so one byte per pixel
+crosses to the host, where ``kpx_amd.gif.write_gif`` packs it (LZW in the library's host code).  ``--gif-fps N`` (1..50, default 10) is
+stored as the delay round(100 / N) centiseconds; ``--gif-dither A`` (0..64, default 0) adds a 4 x 4 ordered dither of that amplitude
+before the search.  ``<save_dir>/gif.json`` records the columns, fps, dither, the frame count and the palette size per sample.  DESIGN.md
+section 2 has the definition.  Without the flag every file keeps its bytes.
 """
 import json
 import os
@@ -625,6 +637,8 @@ class _Drive:
         """One driven rollout per listed mode; -> the frames predicted"""
         for mode in self.modes:
             out = self.model.run(None, {'image': self.image, 'action_code': self.batch['action_code']}, drive=self.drive_of(mode))
+            if mode == self.modes[0]:
+                self.first_out = out                 # --gif --drive-only: every mode replays a graph of its own, so these stay
             pred = out['pred_im_seq'].contiguous()   # consumed before the next run() of this mode overwrites the graph's output buffers
             if drive_scores is not None and mode in drive_scores:
                 drive_scores[mode].append(self.ops.frame_metrics(pred.reshape(-1, *pred.shape[2:]), real_flat, png8=True))
@@ -844,7 +858,22 @@ def main(argv=None):
                              'predicted key points (with --actions: every class rollout against the commanded class) and gives a Frechet '
                              "distance in its feature space.  This project's own key-point-space quantity: not comparable with published "
                              'action-recognition or FVD figures')
+    parser.add_argument('--gif', action='store_true',
+                        help='per sample pred.gif (the input image, then the predicted frames of draw 0) and compare.gif (real | pred | '
+                             'points side by side), quantised to one palette per GIF on the device; <save_dir>/gif.json')
+    parser.add_argument('--gif-fps', type=int, default=None, help='with --gif: frames per second, 1..50 (default 10)')
+    parser.add_argument('--gif-dither', type=int, default=None, help='with --gif: amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
     args = parser.parse_args(argv)
+    if (args.gif_fps is not None or args.gif_dither is not None) and not args.gif:
+        parser.error('--gif-fps and --gif-dither shape the files of --gif and need it')
+    if args.gif and args.no_save:
+        parser.error('--gif writes files, and --no-save writes none')
+    gif_fps = 10 if args.gif_fps is None else args.gif_fps
+    gif_dither = 0 if args.gif_dither is None else args.gif_dither
+    if not 1 <= gif_fps <= 50:
+        parser.error('--gif-fps takes 1..50 frames per second (got %d)' % gif_fps)
+    if not 0 <= gif_dither <= 64:
+        parser.error('--gif-dither takes an amplitude in 0..64 (got %d)' % gif_dither)
     if args.sheet_frames is not None and args.actions is None and args.drive is None:
         parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive and needs it')
     drive_modes = None
@@ -927,6 +956,7 @@ def main(argv=None):
     for p in checkpoints:                                            # reference :76-77: two partial restores by name
         model.restore(None, p)
     n_action = config['model']['n_action']
+    gifs = kpx_amd.gif.RolloutGifs(gif_fps, gif_dither) if args.gif else None
     sample_idx, frames, t0 = 0, 0, time.time()
     if not args.synthetic:                       # reference :43-51, :84-130: the test subset through the sequence loader
         loader = kpx_amd.data.SequenceDataLoader(config['paths']['data_dir'], 'test', n_points=config['model']['n_pts'], n_action=n_action,
@@ -963,6 +993,11 @@ def main(argv=None):
                 frames += driven.run(args.save_dir, sample_idx, real_flat, drive_scores)
                 if not args.no_save:
                     driven.write_sheet(args.save_dir, sample_idx)
+                if gifs is not None:
+                    o = driven.first_out
+                    gifs.write(args.save_dir, sample_idx, [('real', batch['image'], batch['real_im_seq'], 'unit'),
+                                                           ('pred', batch['image'], o['pred_im_seq'], 'unit'),
+                                                           ('points', o['current_points'], o['future_points'], 'raw')])
                 n_self_driven += bsz if 'transfer' in drive_modes and bsz == 1 else 0
                 sample_idx += bsz
                 continue
@@ -1043,6 +1078,10 @@ def main(argv=None):
                         _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                         _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                         sample_idx += 1
+                    if gifs is not None:     # before the driven rollouts and the sweep below replay the graph over these outputs
+                        gifs.write(args.save_dir, sample_idx - bsz, [('real', batch['image'], batch['real_im_seq'], 'unit'),
+                                                                     ('pred', outputs['im'], outputs['pred_im_seq'], 'unit'),
+                                                                     ('points', outputs['current_points'], outputs['future_points'], 'raw')])
                 if drive_modes and draw == 0:    # once per batch: the driven rollouts do not depend on z (their graphs are their own:
                     # this draw's own outputs stay), before the sweep replays the own rollout's graph
                     first = sample_idx - bsz if not args.no_save else 0
@@ -1066,6 +1105,8 @@ def main(argv=None):
         if drive_modes and not args.no_save:
             _write_drive_json(args.save_dir, _drive_rows(drive_modes, True, not args.drive_only), sheet_frames,
                               (model.image_size, model.image_size), drive_modes, args.drive_scaled, n_self_driven)
+        if gifs is not None:
+            gifs.write_json(args.save_dir)
         if args.metrics and args.drive_only:
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
@@ -1089,6 +1130,10 @@ def main(argv=None):
             frames += driven.run(args.save_dir, sample_idx, None, None)
             if not args.no_save:
                 driven.write_sheet(args.save_dir, sample_idx)
+            if gifs is not None:
+                o = driven.first_out
+                gifs.write(args.save_dir, sample_idx, [('pred', image, o['pred_im_seq'], 'unit'),
+                                                       ('points', o['current_points'], o['future_points'], 'raw')])
             sample_idx += bsz
             continue
         z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None       # --actions: shared with the sweep below
@@ -1106,6 +1151,9 @@ def main(argv=None):
                 _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                 _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                 sample_idx += 1
+            if gifs is not None:
+                gifs.write(args.save_dir, sample_idx - bsz, [('pred', outputs['im'], outputs['pred_im_seq'], 'unit'),
+                                                             ('points', outputs['current_points'], outputs['future_points'], 'raw')])
         if drive_modes:
             first = sample_idx - bsz if not args.no_save else 0
             driven = _Drive(kpx_amd, model, drive_modes, False, sheet_frames, {'image': image, 'action_code': torch.from_numpy(act).to(dev)},
@@ -1125,6 +1173,8 @@ def main(argv=None):
     if drive_modes and not args.no_save:
         _write_drive_json(args.save_dir, _drive_rows(drive_modes, False, not args.drive_only), sheet_frames,
                           (model.image_size, model.image_size), drive_modes, False, 0)
+    if gifs is not None:
+        gifs.write_json(args.save_dir)
     torch.cuda.synchronize()
     print('iteration through synthetic set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
 

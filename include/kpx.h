@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 19
+#define KPX_ABI_VERSION 20
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -418,6 +418,29 @@ int kpx_moments_add_f64(const double* x /*[M,D]*/, int M, int D, double* sum /*[
 enum { KPX_SHEET_UNIT = 0, KPX_SHEET_RAW = 1 };
 int kpx_sheet_paste_u8_f32(const float* src /*[B,F,H,W,C]*/, int B, int F, int H, int W, int C, const int* frames /*host [J]*/, int J,
                            uint8_t* canvas /*[B,rows*H,cols*W,3]*/, int rows, int cols, int row, int col, int premap, void* stream);
+
+/* ---- animated GIFs (evaluate.py --gif), DESIGN.md sections 2 and 4.4: 8-bit RGB canvases to palette indices on the device, and GIF's LZW on
+ * the host.  Integer arithmetic throughout: the same bits in any order of execution.  Added in ABI version 20.
+ *   kpx_color_hist_add_u32: rgb uint8 [G,n,3] (any byte alignment), hist uint32 [G,32768,4], updated in place:
+ *     hist[g, cell] += (count, sum r, sum g, sum b) over the pixels of group g with cell = (r >> 3) << 10 | (g >> 3) << 5 | b >> 3.
+ *     1 <= n <= 2^24 (the sums of one call cannot overflow; the caller zeroes hist, with a memset node under capture), 1 <= G <= 65535.
+ *     One launch; LDS and global integer atomics.
+ *   kpx_palette_map_u8: rgb uint8 [G,T,H,Wc,3] and idx uint8 [G,T,H,Wc] (any byte alignment, any width), palette uint8 [G,256,3], sizes
+ *     DEVICE int32 [G].  With P = min(max(sizes[g], 1), pmax): idx = the smallest j < P that minimises (r - pr)^2 + (g - pg)^2 + (b - pb)^2
+ *     in int32.  dither = A in [0,64]: before the search each channel c becomes clamp(c + (((2 M[y & 3][x & 3] - 15) A + 16) >> 5), 0, 255)
+ *     (arithmetic shift; M = [[0,8,2,10],[12,4,14,6],[3,11,1,9],[15,7,13,5]]; y the row of the frame, x the column of the canvas); A = 0 is
+ *     the plain search.  1 <= pmax <= 256 bounds every group's size on the host; G <= 65535, T H Wc < 2^31.  One launch, no atomics.
+ *   Both: no allocation, copy or synchronisation (capturable); KPX_EINVAL before any device call for a null pointer, a hist or sizes that is
+ *   not 4-byte aligned, or a size outside the limits.
+ *   kpx_gif_lzw_u8 (HOST pointers, no device call): idx[n], every index < 1 << min_code_size, min_code_size in [2,8] -> GIF's LZW byte
+ *     stream without sub-blocks (clear code first, least significant bit first, width + 1 when the next free code equals 2^width, up to 12,
+ *     clear and reset at 4096 codes, end code last).  Returns the bytes written, or KPX_EINVAL for a bad argument or a stream that does not
+ *     fit out_bytes; kpx_gif_lzw_bound(n) bytes always fit.  n <= 2^30. */
+int kpx_color_hist_add_u32(const uint8_t* rgb /*[G,n,3]*/, int G, size_t n, uint32_t* hist /*[G,32768,4]*/, void* stream);
+int kpx_palette_map_u8(const uint8_t* rgb /*[G,T,H,Wc,3]*/, int G, int T, int H, int Wc, const uint8_t* palette /*[G,256,3]*/,
+                       const int* sizes /*device [G]*/, int pmax, int dither, uint8_t* idx /*[G,T,H,Wc]*/, void* stream);
+size_t kpx_gif_lzw_bound(size_t n);
+int kpx_gif_lzw_u8(const uint8_t* idx /*host [n]*/, size_t n, int min_code_size, uint8_t* out /*host*/, size_t out_bytes);
 
 /* ---- key-point retargeting (FinalModel.run(drive=...), evaluate.py --drive), DESIGN.md sections 2 and 4.4: the key-point sequence of a
  * rollout whose motion comes from outside the motion generator.  src_first fp32 [B,K,2]: the source images' detected key points; drv_first

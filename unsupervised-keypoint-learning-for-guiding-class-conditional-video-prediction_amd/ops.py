@@ -1673,7 +1673,89 @@ def sheet_paste(canvas, src, frames, row, col, premap):
     return canvas
 
 
-RETARGET_MODES = {'hold': 0, 'absolute': 1, 'relative': 2}                        # = KPX_RETARGET_* of include/kpx.h ('relative' + scaled: 3)
+HIST_CELLS = 32768                                                                # 5-5-5 colour cells
+HIST_MAX_PIXELS = 1 << 24                                                         # per group and call: the uint32 sums cannot overflow
+GIF_MAX_DITHER = 64
+
+
+def _u8_gpu(what, name, t, dims=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got %s for %s\'s %s); there is no CPU fallback'
+                            % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, what, name))
+    if t.dtype != torch.uint8 or not t.is_contiguous() or (dims is not None and t.dim() != dims):
+        raise _lib.KpxError('%s: %s must be a contiguous uint8 tensor%s (got %s %s, contiguous=%s)'
+                            % (what, name, '' if dims is None else ' of %d dimensions' % dims, tuple(t.shape), t.dtype, t.is_contiguous()))
+
+
+def color_hist_add(rgb, hist):
+    """Colour statistics of 8-bit RGB pixels (DESIGN.md section 4.4).  rgb: contiguous uint8 [G, n, 3] (any storage offset), 1 <= n <= 2^24;
+    hist: contiguous int32 [G, 32768, 4] (the bits of uint32) on rgb's device, updated in place: hist[g, cell] += (count, sum r, sum g,
+    sum b) over group g's pixels with cell = (r >> 3) << 10 | (g >> 3) << 5 | b >> 3.  Zero hist first (``hist.zero_()``: a memset node
+    under capture).  Integer adds: the same bits in any order.  One launch."""
+    _u8_gpu('color_hist_add', 'rgb', rgb, 3)
+    if not isinstance(hist, torch.Tensor) or not hist.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (color_hist_add\'s hist); there is no CPU fallback')
+    g, n = int(rgb.shape[0]), int(rgb.shape[1])
+    if rgb.shape[2] != 3 or g < 1 or g > 65535 or not 1 <= n <= HIST_MAX_PIXELS:
+        raise _lib.KpxError('color_hist_add: rgb must be [G, n, 3] with 1 <= G <= 65535 and 1 <= n <= 2^24 (got %s)' % (tuple(rgb.shape),))
+    if hist.dtype != torch.int32 or not hist.is_contiguous() or tuple(hist.shape) != (g, HIST_CELLS, 4) or hist.device != rgb.device:
+        raise _lib.KpxError('color_hist_add: hist must be a contiguous int32 [%d, %d, 4] tensor on %s (got %s %s on %s)'
+                            % (g, HIST_CELLS, rgb.device, tuple(hist.shape), hist.dtype, hist.device))
+    check(lib.kpx_color_hist_add_u32(rgb.data_ptr(), g, n, hist.data_ptr(), _stream()), 'kpx_color_hist_add_u32')
+    return hist
+
+
+def palette_map(rgb, palette, sizes, dither=0, pmax=256, out=None):
+    """The nearest palette entry of every pixel.  rgb: contiguous uint8 [G,T,H,Wc,3]; palette: contiguous uint8
+    [G,256,3]; sizes: contiguous int32 [G] ON THE DEVICE, each in [1, pmax] (clamped into it) -> idx uint8 [G,T,H,Wc] = the smallest
+    j < sizes[g] that minimises the squared RGB distance (int32).  ``dither`` A in [0, 64]: the 4 x 4 ordered dither of ``kpx_amd.gif.BAYER4``
+    added to every channel before the search, A = 0 the plain search.  Any width and storage offset.  One launch."""
+    _u8_gpu('palette_map', 'rgb', rgb, 5)
+    _u8_gpu('palette_map', 'palette', palette, 3)
+    if not isinstance(sizes, torch.Tensor) or not sizes.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (palette_map\'s sizes live on the device); there is no CPU fallback')
+    g, t, h, w = (int(v) for v in rgb.shape[:4])
+    if rgb.shape[4] != 3 or min(g, t, h, w) < 1 or g > 65535 or t * h * w > 0x7fffffff:
+        raise _lib.KpxError('palette_map: rgb must be [G,T,H,Wc,3] with 1 <= G <= 65535 and T H Wc < 2^31 (got %s)' % (tuple(rgb.shape),))
+    if tuple(palette.shape) != (g, 256, 3) or palette.device != rgb.device:
+        raise _lib.KpxError('palette_map: palette must be [%d, 256, 3] on %s (got %s on %s)' % (g, rgb.device, tuple(palette.shape), palette.device))
+    if sizes.dtype != torch.int32 or not sizes.is_contiguous() or tuple(sizes.shape) != (g,) or sizes.device != rgb.device:
+        raise _lib.KpxError('palette_map: sizes must be a contiguous int32 [%d] tensor on %s (got %s %s)' % (g, rgb.device, tuple(sizes.shape), sizes.dtype))
+    if isinstance(dither, bool) or not isinstance(dither, int) or not 0 <= dither <= GIF_MAX_DITHER:
+        raise _lib.KpxError('palette_map: dither is an integer in [0, %d] (got %r)' % (GIF_MAX_DITHER, dither))
+    if isinstance(pmax, bool) or not isinstance(pmax, int) or not 1 <= pmax <= 256:
+        raise _lib.KpxError('palette_map: pmax is an integer in [1, 256] (got %r)' % (pmax,))
+    if out is None:
+        out = torch.empty((g, t, h, w), dtype=torch.uint8, device=rgb.device)
+    else:
+        _u8_gpu('palette_map', 'out', out, 4)
+        if tuple(out.shape) != (g, t, h, w) or out.device != rgb.device:
+            raise _lib.KpxError('palette_map: out must be [%d,%d,%d,%d] on %s (got %s)' % (g, t, h, w, rgb.device, tuple(out.shape)))
+    check(lib.kpx_palette_map_u8(rgb.data_ptr(), g, t, h, w, palette.data_ptr(), sizes.data_ptr(), pmax, dither, out.data_ptr(), _stream()),
+          'kpx_palette_map_u8')
+    return out
+
+
+def gif_indices(canvas, dither=0):
+    """An 8-bit canvas to palette indices, one palette per group from all its frames.  canvas: contiguous uint8
+    [G,T,H,Wc,3] with T H Wc <= 2^24 -> (idx uint8 [G,T,H,Wc] on the device, palettes uint8 numpy [G,256,3] zero-padded, sizes int numpy [G]).
+    ``color_hist_add`` on the device, ``kpx_amd.gif.median_cut`` on the host (512 KB per group cross over), ``palette_map`` on the device."""
+    from . import gif as _gif
+    import numpy as _np
+    _u8_gpu('gif_indices', 'canvas', canvas, 5)
+    g = int(canvas.shape[0])
+    hist = torch.zeros((g, HIST_CELLS, 4), dtype=torch.int32, device=canvas.device)
+    color_hist_add(canvas.view(g, -1, 3), hist)
+    host = hist.cpu().numpy().view(_np.uint32)
+    palettes, sizes = _np.zeros((g, 256, 3), _np.uint8), _np.zeros((g,), _np.int32)
+    for i in range(g):
+        pal = _gif.median_cut(host[i])
+        palettes[i, :pal.shape[0]], sizes[i] = pal, pal.shape[0]
+    idx = palette_map(canvas, torch.from_numpy(palettes).to(canvas.device), torch.from_numpy(sizes).to(canvas.device), dither)
+    return idx, palettes, sizes
+
+
+RETARGET_MODES ={'hold': 0, 'absolute': 1, 'relative': 2}                        # = KPX_RETARGET_* of include/kpx.h ('relative' + scaled: 3)
 RETARGET_MAX_POINTS = 1024
 
 
