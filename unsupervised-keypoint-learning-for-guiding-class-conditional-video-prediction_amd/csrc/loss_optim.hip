@@ -102,7 +102,12 @@ extern "C" int kpx_sigmoid_xent_bwd_f32(const float* logits, size_t n0, float la
     return kpx_launch_status();
 }
 
-// ApplyAdam (TF 1.12): m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= m*alpha/(sqrt(v)+eps)
+// ApplyAdam (TF 1.12): m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= m*alpha/(sqrt(v)+eps), with g = gs * gradient.
+// Not op-for-op ApplyAdam rounding, whatever the _rn intrinsics suggest: for gfx950 the chain is contracted into fused multiply-adds
+// (gs*g - m, m + (..)(1-b1), g*g - v and v + (..)(1-b2) round once each) and the square root is the hardware's 1-ulp one.  What holds is
+// a bound around the exact step (tests/loss_optim_ref.py): m' within 16 ulps of |m|+|g|, v' of |v|+g*g, p' within 2 ulps of |p| plus 16
+// of the update's magnitude alpha(|m|+|g|)/(sqrt(v')+eps); and g = m = v = 0 leaves p, m and v bit-unchanged.  The dev-alpha kernel
+// below repeats this body and must stay bit-identical to it (graph replay against the eager step rests on that).
 __global__ __launch_bounds__(256) void adam_tf_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                       float* __restrict__ v, size_t n, float alpha, float omb1, float omb2, float eps, float gs) {
     const size_t n4 = n / 4;

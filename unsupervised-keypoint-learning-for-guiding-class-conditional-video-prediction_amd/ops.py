@@ -1151,44 +1151,6 @@ def upsample2x_concat(x, skip=None):
     return UpsampleConcatFn.apply(x, skip)
 
 
-class ConcatChannelsFn(torch.autograd.Function):
-    """tf.concat([a, b], axis=-1) for two NHWC tensors (batch-norm'd feature + skip) without resize."""
-
-    @staticmethod
-    def forward(ctx, a, b):
-        a, b = a.contiguous(), b.contiguous()
-        _require_gpu(a)
-        n, h, w, c1 = a.shape
-        c2 = b.shape[3]
-        out = torch.empty((n, h, w, c1 + c2), dtype=a.dtype, device=a.device)
-        if a.dtype == BF16:
-            cast_channels_raw(a.data_ptr(), c1, out.data_ptr(), c1 + c2, n * h * w, c1, 2)
-            cast_channels_raw(cast(b, BF16).data_ptr(), c2, out.data_ptr() + 2 * c1, c1 + c2, n * h * w, c2, 2)
-        else:
-            copy_channels_raw(a.data_ptr(), c1, out.data_ptr(), c1 + c2, n * h * w, c1)
-            copy_channels_raw(cast(b, torch.float32).data_ptr(), c2, out.data_ptr() + 4 * c1, c1 + c2, n * h * w, c2)
-        ctx.dims = (n, h, w, c1, c2)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        n, h, w, c1, c2 = ctx.dims
-        dout = dout.contiguous()
-        da = torch.empty((n, h, w, c1), dtype=dout.dtype, device=dout.device)
-        db = torch.empty((n, h, w, c2), dtype=dout.dtype, device=dout.device)
-        if dout.dtype == BF16:
-            cast_channels_raw(dout.data_ptr(), c1 + c2, da.data_ptr(), c1, n * h * w, c1, 2)
-            cast_channels_raw(dout.data_ptr() + 2 * c1, c1 + c2, db.data_ptr(), c2, n * h * w, c2, 2)
-        else:
-            copy_channels_raw(dout.data_ptr(), c1 + c2, da.data_ptr(), c1, n * h * w, c1)
-            copy_channels_raw(dout.data_ptr() + 4 * c1, c1 + c2, db.data_ptr(), c2, n * h * w, c2)
-        return da, db
-
-
-def concat_channels(a, b):
-    return ConcatChannelsFn.apply(a, b)
-
-
 class ConcatBatchFn(torch.autograd.Function):
     """tf.concat([a, b], axis=0): used to run the two pose_encoder calls / the real+fake discriminator passes batched."""
 
