@@ -1,0 +1,263 @@
+"""Animate your own stills: every image rolled out under each action class, or along the motion of your own video, as animated GIFs.
+
+    python animate.py --config C --checkpoint_stage1 S1 [--checkpoint_stage2 S2] --images PATH [PATH ...]
+                      [--box x0,y0,x1,y1] [--actions all|i,j,k] [--samples S] [--seed N] [--overlay R] [--sheet-frames i,j,k]
+                      [--driver DIR [--driver-mode relative|absolute] [--driver-scaled] [--driver-box x0,y0,x1,y1]]
+                      [--gif-fps N] [--gif-dither A] [--png] [--batch B] [--colors_seed S] [--save_dir D]
+
+Inputs (``kpx_amd.stills``): each PATH is an image file, a directory (its .jpg .jpeg .png .bmp files in sorted name order) or a .txt manifest
+(one ``path [x0,y0,x1,y1]`` per line, relative to the manifest).  Decoding is PIL's on the host: EXIF orientation applied, then
+``convert('RGB')`` -- an alpha channel is dropped, not composited.  ``--box`` crops in pixels of the upright image (a manifest's box wins);
+the fit to 128 x 128 is the sequence loader's start-frame arithmetic, so a still reaches the networks as a Penn frame of the same pixels.
+
+Rollouts (``--checkpoint_stage2``): every still under each class of ``--actions`` (default all) for each of ``--samples`` draws; draw s
+uses row s of ``numpy.random.RandomState(seed).randn(S, vae_dim).astype(float32)``, shared by all stills and all classes.
+Driver (``--driver DIR``, stage 2 not needed): DIR holds N >= 33 frames of a video; frames i * (N // 33) are fitted like stills, the stage-1
+detector finds their key points, and every still is rolled out on them (``FinalModel.run(drive=...)``, default mode ``relative``).
+
+Files, under <save_dir>/%04d/ per still in input order: input_im.png and current_points.png as evaluate.py writes them; classes.gif, the
+animated grid (row = draw, column = class, 33 frames, frame 0 = the still) with ONE palette over all cells and frames; with ``--overlay R``
+classes_overlay.gif, the same grid with the key points marked on the frames (a disc of radius R - 1 with a one-pixel outline,
+``kpx_amd.ops.cell_frames``), and overlay.png, its first cell at frame 0; classes.png and classes_points.png, the contact sheets of
+evaluate.py --actions for draw 0; with ``--driver`` driven.gif (driver | pred) and driven_overlay.gif; with ``--png`` the frames of every
+rollout as evaluate.py writes them.  <save_dir>/animate.json records the inputs and the settings.  No quality claim is made for images
+outside the training distribution: the overlay is there to judge that.
+"""
+import json
+import os
+import os.path as osp
+import sys
+from argparse import ArgumentParser
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+N_FRAMES = 33                          # the still, then the 32 predicted frames
+PNG_FOLDERS = (('pred_seq', 'pred_im_seq', True), ('mask', 'mask', False), ('crude', 'pred_im_crude', True), ('pred_points', 'future_points', False))
+
+
+class _Tap:
+    """a FinalModel whose run() hands every output to ``consume`` before the caller (evaluate._ClassSweep) sees it: the outputs live in graph
+    buffers that the next run() overwrites"""
+
+    def __init__(self, model, consume):
+        self.model, self.consume = model, consume
+
+    def __getattr__(self, name):
+        return getattr(self.model, name)
+
+    def run(self, sess, feed_dict, z=None, drive=None):
+        out = self.model.run(sess, feed_dict, z=z, drive=drive)
+        self.consume(out)
+        return out
+
+
+def _write_rollout_pngs(evaluate, folder, out, batch_idx):
+    for name, key, rescale in PNG_FOLDERS:
+        evaluate._save_img_sequence(osp.join(folder, name), out[key][batch_idx], rescale=rescale)
+
+
+def main(argv=None):
+    parser = ArgumentParser(description='animate stills by action class or by a driving video')
+    parser.add_argument('--config', type=str, required=True, help='path of the configuration file')
+    parser.add_argument('--checkpoint_stage1', type=str, required=True, help='path of the stage1 checkpoint')
+    parser.add_argument('--checkpoint_stage2', type=str, default=None, help='path of the stage2 checkpoint (class rollouts need it)')
+    parser.add_argument('--images', type=str, nargs='+', required=True, help='image files, directories or .txt manifests')
+    parser.add_argument('--box', type=str, default=None, help='x0,y0,x1,y1: crop every still, in pixels of the upright image')
+    parser.add_argument('--actions', type=str, default=None, help="'all' (default) or i,j,k: the classes, one column each")
+    parser.add_argument('--samples', type=int, default=None, help='draws of z, one row each (default 1)')
+    parser.add_argument('--seed', type=int, default=None, help='seed of the draws (default 0)')
+    parser.add_argument('--overlay', type=int, default=0, help='radius 1..16 of the key-point markers of the *_overlay files (default 0: none)')
+    parser.add_argument('--sheet-frames', type=str, default=None, help='the predicted frames of classes.png (default 3,7,...,31)')
+    parser.add_argument('--driver', type=str, default=None, help='a directory of >= 33 frames of a video whose motion drives every still')
+    parser.add_argument('--driver-mode', type=str, default=None, help='relative (default) or absolute')
+    parser.add_argument('--driver-scaled', action='store_true', help="with --driver-mode relative: scale the motion by the constellations' spreads")
+    parser.add_argument('--driver-box', type=str, default=None, help='x0,y0,x1,y1: crop every driver frame')
+    parser.add_argument('--gif-fps', type=int, default=10, help='frames per second, 1..50 (default 10)')
+    parser.add_argument('--gif-dither', type=int, default=0, help='amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
+    parser.add_argument('--png', action='store_true', help='also the frames of every rollout as PNGs')
+    parser.add_argument('--batch', type=int, default=8)
+    parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette')
+    parser.add_argument('--save_dir', type=str, default='results/animate')
+    args = parser.parse_args(argv)
+
+    import evaluate
+    from train import load_config
+    from kpx_amd import stills
+    from kpx_amd.gif import DITHER_RANGE, FPS_RANGE, delay_of_fps
+
+    # ---- everything that can be refused is refused here, before the device is touched
+    if args.checkpoint_stage2 is None and args.driver is None:
+        parser.error('at least one of --checkpoint_stage2 (class rollouts) and --driver (driven rollouts) must be given')
+    if args.driver is None:
+        for flag, given in (('--driver-mode', args.driver_mode is not None), ('--driver-scaled', args.driver_scaled),
+                            ('--driver-box', args.driver_box is not None)):
+            if given:
+                parser.error('%s shapes the rollout of --driver and needs it' % flag)
+    driver_mode = args.driver_mode or 'relative'
+    if driver_mode not in ('relative', 'absolute'):
+        parser.error('--driver-mode takes relative or absolute (got %r)' % args.driver_mode)
+    if args.driver_scaled and driver_mode != 'relative':
+        parser.error('--driver-scaled goes with --driver-mode relative alone')
+    if not FPS_RANGE[0] <= args.gif_fps <= FPS_RANGE[1]:
+        parser.error('--gif-fps takes %d..%d frames per second (got %d)' % (FPS_RANGE + (args.gif_fps,)))
+    if not DITHER_RANGE[0] <= args.gif_dither <= DITHER_RANGE[1]:
+        parser.error('--gif-dither takes an amplitude in %d..%d (got %d)' % (DITHER_RANGE + (args.gif_dither,)))
+    if not 0 <= args.overlay <= stills.MAX_RADIUS:
+        parser.error('--overlay takes a marker radius in 1..%d, or 0 for none (got %d)' % (stills.MAX_RADIUS, args.overlay))
+    if args.batch < 1:
+        parser.error('--batch must be >= 1 (got %d)' % args.batch)
+    samples = 1 if args.samples is None else args.samples
+    seed = 0 if args.seed is None else args.seed
+    if not 0 <= seed < 2 ** 32:
+        parser.error('--seed takes a numpy RandomState seed in [0, 2^32) (got %d)' % seed)
+    config = load_config(args.config)
+    n_action, size = config['model'].get('n_action', 9), stills.IMAGE_SIZE
+    actions = sheet_frames = None
+    try:
+        if args.checkpoint_stage2 is not None:
+            text = 'all' if args.actions is None else args.actions.strip()
+            actions = list(range(n_action)) if text == 'all' else evaluate._parse_index_list(text, '--actions', n_action)
+            stills.check_grid(samples, len(actions), size, size)
+            sheet_frames = list(evaluate.SHEET_FRAMES_DEFAULT)
+            if args.sheet_frames is not None:
+                sheet_frames = evaluate._parse_index_list(args.sheet_frames, '--sheet-frames', evaluate.N_FUTURE_FRAMES)
+                if sheet_frames != sorted(sheet_frames) or len(sheet_frames) > 63:
+                    raise ValueError('--sheet-frames takes at most 63 increasing frame indices (got %r)' % args.sheet_frames)
+        box = stills.parse_box(args.box, '--box') if args.box is not None else None
+        listed = stills.list_images(args.images, box)
+        fitted, records = [], []
+        for path, own in listed:                         # decoded on the host, once: the decode is what a still costs
+            u8, info = stills.fit(path, own, what='--box' if own is box else 'the manifest box')
+            fitted.append(u8)
+            records.append(info)
+        driver = None
+        if args.driver is not None:
+            driver_box = stills.parse_box(args.driver_box, '--driver-box') if args.driver_box is not None else None
+            paths, idx, n_found = stills.driver_frames(args.driver)
+            driver = {'paths': paths, 'frames': idx, 'n_found': n_found,
+                      'u8': np.stack([stills.fit(p, driver_box, what='--driver-box')[0] for p in paths])}
+    except ValueError as e:                              # (StillsError is one)
+        parser.error(str(e))
+    checkpoints = [args.checkpoint_stage1] + ([args.checkpoint_stage2] if args.checkpoint_stage2 is not None else [])
+    for p in checkpoints:
+        if not (osp.exists(p) or osp.exists(p + '.index')):
+            raise Exception('checkpoint not found at %s' % p)
+
+    # ---- the device
+    import torch
+    import kpx_amd
+    from kpx_amd.data import _to_device_unit
+    ops = kpx_amd.ops
+    dev = torch.device('cuda', 0)
+    model = kpx_amd.FinalModel(config, device=dev, point_maps=True, colors_seed=args.colors_seed)
+    model.build(None)
+    for p in checkpoints:
+        model.restore(None, p)
+    k, radius = model.n_points, args.overlay
+    if radius and k > ops.CELL_MAX_POINTS:
+        raise Exception('--overlay marks at most %d key points (the model has %d)' % (ops.CELL_MAX_POINTS, k))
+    colors = torch.from_numpy(stills.marker_colors(model.colors)).to(dev) if radius else None
+    gifs = kpx_amd.gif.RolloutGifs(args.gif_fps, args.gif_dither)
+    n_cls = len(actions) if actions else 0
+    layers = 2 if radius else 1
+    per_still = N_FRAMES * size * size * 3 * layers * ((samples * n_cls if actions else 0) + (2 if driver else 0))
+    batch = stills.batch_under(args.batch, per_still)
+    zs = None
+    if actions:
+        zs = torch.from_numpy(np.random.RandomState(seed).randn(samples, model.vae_dim).astype(np.float32)).to(dev)
+    drv = None
+    if driver is not None:
+        frames = _to_device_unit(driver['u8'], dev)                                        # [33,R,R,3]
+        pts = model.detect(frames)                                                         # [33,K,2]
+        drv = {'image': frames[:1], 'seq': frames[1:].unsqueeze(0), 'first_pt': pts[:1].contiguous(), 'seq_pt': pts[1:].unsqueeze(0).contiguous()}
+    palette_sizes = {name: [] for name in (['classes'] if actions else []) + (['classes_overlay'] if actions and radius else [])
+                     + (['driven'] if driver else []) + (['driven_overlay'] if driver and radius else [])}
+    from PIL import Image
+
+    for start in range(0, len(fitted), batch):
+        bsz = min(batch, len(fitted) - start)
+        image = _to_device_unit(np.stack(fitted[start:start + bsz]), dev)
+        dirs = [osp.join(args.save_dir, '%04d' % (start + i)) for i in range(bsz)]
+        for d in dirs:
+            os.makedirs(d, exist_ok=True)
+        state = {'inputs': False}
+
+        def write_inputs(out):
+            if not state['inputs']:
+                state['inputs'] = True
+                im, cur = out['im'].cpu().numpy(), out['current_points'].cpu().numpy()
+                for i, d in enumerate(dirs):
+                    evaluate._save_img(osp.join(d, 'input_im.png'), im[i], rescale=True)
+                    evaluate._save_img(osp.join(d, 'current_points.png'), cur[i], rescale=False)
+
+        def marks(out):
+            return out['first_pt'].reshape(bsz, k, 2).contiguous(), out['fut_pt_raw'].reshape(bsz, N_FRAMES - 1, k, 2).contiguous()
+
+        if actions:
+            grid = torch.empty((bsz, N_FRAMES, samples * size, n_cls * size, 3), dtype=torch.uint8, device=dev)
+            over = torch.empty_like(grid) if radius else None
+
+            def consume(out):                            # one rollout: its cell of the grids, before the next run() replays the graph
+                s, a = state['draw'], state['a']
+                pred = out['pred_im_seq'].contiguous()
+                ops.cell_frames(grid, image, pred, s, a, 'unit')
+                if over is not None:
+                    ops.cell_frames(over, image, pred, s, a, 'unit', *marks(out), colors=colors, radius=radius)
+                write_inputs(out)
+                if args.png:
+                    host = {key: out[key].cpu().numpy() for _, key, _ in PNG_FOLDERS}
+                    for i, d in enumerate(dirs):
+                        _write_rollout_pngs(evaluate, osp.join(d, 'draw_%02d' % s, 'class_%02d' % actions[a]), host, i)
+                state['a'] = a + 1
+
+            sweep = evaluate._ClassSweep(kpx_amd, _Tap(model, consume), actions, n_action, sheet_frames, image, None, True, samples, None, dev)
+            for s in range(samples):
+                state.update(draw=s, a=0)
+                sweep.run(s, zs[s:s + 1].expand(bsz, -1).contiguous())
+            sweep.write_sheets(args.save_dir, start)
+            palette_sizes['classes'] += stills.write_grid_gifs(gifs, grid, [osp.join(d, 'classes.gif') for d in dirs])
+            if over is not None:
+                palette_sizes['classes_overlay'] += stills.write_grid_gifs(gifs, over, [osp.join(d, 'classes_overlay.gif') for d in dirs])
+                first = over[:, 0, :size, :size].contiguous().cpu().numpy()
+                for i, d in enumerate(dirs):
+                    Image.fromarray(first[i]).save(osp.join(d, 'overlay.png'))
+        if drv is not None:
+            tile = lambda t: t.expand((bsz,) + tuple(t.shape[1:])).contiguous()
+            out = model.run(None, {'image': image}, drive={'mode': driver_mode, 'first': tile(drv['first_pt']), 'seq': tile(drv['seq_pt']),
+                                                           'shift': 0, 'scaled': bool(args.driver_scaled)})
+            pred = out['pred_im_seq'].contiguous()
+            d_first, d_seq = tile(drv['image']), tile(drv['seq'])
+            pair = torch.empty((bsz, N_FRAMES, size, 2 * size, 3), dtype=torch.uint8, device=dev)
+            ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit')
+            ops.cell_frames(pair, image, pred, 0, 1, 'unit')
+            palette_sizes['driven'] += stills.write_grid_gifs(gifs, pair, [osp.join(d, 'driven.gif') for d in dirs])
+            if radius:                                   # the driver's own key points on its cell, the retargeted ones on the rollout
+                ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit', tile(drv['first_pt']), tile(drv['seq_pt']), colors=colors, radius=radius)
+                ops.cell_frames(pair, image, pred, 0, 1, 'unit', *marks(out), colors=colors, radius=radius)
+                palette_sizes['driven_overlay'] += stills.write_grid_gifs(gifs, pair, [osp.join(d, 'driven_overlay.gif') for d in dirs])
+            write_inputs(out)
+            if args.png:
+                host = {key: out[key].cpu().numpy() for _, key, _ in PNG_FOLDERS}
+                for i, d in enumerate(dirs):
+                    _write_rollout_pngs(evaluate, osp.join(d, 'driven'), host, i)
+    torch.cuda.synchronize()
+    meta = {'stills': records, 'cell': [size, size], 'frames': N_FRAMES, 'fps': gifs.fps, 'delay_cs': delay_of_fps(gifs.fps), 'dither': gifs.dither,
+            'overlay': radius, 'batch': batch, 'palette_sizes': palette_sizes}
+    if actions:
+        meta.update({'actions': actions, 'draws': samples, 'seed': seed, 'grid': [samples, n_cls], 'sheet_frames': sheet_frames})
+    if driver is not None:
+        meta['driver'] = {'dir': args.driver, 'n_found': driver['n_found'], 'frames': driver['frames'], 'files': driver['paths'],
+                          'mode': driver_mode, 'scaled': bool(args.driver_scaled),
+                          'box': None if args.driver_box is None else list(stills.parse_box(args.driver_box, '--driver-box'))}
+    os.makedirs(args.save_dir, exist_ok=True)
+    with open(osp.join(args.save_dir, 'animate.json'), 'w') as f:
+        json.dump(meta, f, indent=1)
+    print('animated %d stills: %s' % (len(fitted), ', '.join('%s.gif' % name for name in palette_sizes)))
+
+
+if __name__ == '__main__':
+    main()

@@ -88,6 +88,15 @@
    and written as 128 GIF files), alternated in one process; ms per rollout of each, and the flag's cost split into the device part (through
    the copy of the indices) and the host part (median cut, LZW, files).
 
+``--animate`` measures the animated grids of stills (animate.py) instead:
+
+20. kpx_cell_frames_u8_f32 alone on a 64-still batch (frame 0 and 32 predicted frames of 128 x 128 x 3 into one cell: 415 MB of fp32 in,
+   104 MB out) without markers and with 15 key points at radius 3, beside a device copy of the frames in the same process, and the route
+   the kernel replaces without markers (``RolloutGifs._canvas``: a staging stack, two copies and kpx_sheet_paste_u8_f32); device-event
+   time after warm-up, median us, GB/s of the bytes each moves and the kernel's rate as a fraction of the copy's.
+21. animate.py's loop for 8 stills under 9 classes x 1 draw with --overlay 3 (random weights): the rollouts alone, with both grids
+   composed, quantised and copied, and with the host GIF work (LZW, 16 files); ms per still of each part.
+
 Prints one JSON line.
 """
 import argparse
@@ -997,6 +1006,101 @@ def gif_rollout_leg(dev, rollouts):
             'device_ms_all': [round(v, 1) for v in ms['device']], 'on_ms_all': [round(v, 1) for v in ms['on']]}
 
 
+def animate_kernel_leg(dev, launches):
+    from kpx_amd import gif, ops
+    t, k = 32, 15
+    g = torch.Generator(device=dev).manual_seed(21)
+    first = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    seq = torch.rand((B, t, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    pts_first = torch.rand((B, k, 2), generator=g, device=dev) * 1.8 - 0.9
+    pts_seq = torch.rand((B, t, k, 2), generator=g, device=dev) * 1.8 - 0.9
+    colors = torch.randint(0, 256, (k, 3), generator=g, device=dev, dtype=torch.uint8)
+    canvas = torch.empty((B, t + 1, RES, RES, 3), dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(seq)
+    gifs = gif.RolloutGifs(10, 0)
+    legs = (('device_copy', lambda: dst.copy_(seq)),
+            ('cell_frames_r0', lambda: ops.cell_frames(canvas, first, seq, 0, 0, 'unit')),
+            ('cell_frames_r3', lambda: ops.cell_frames(canvas, first, seq, 0, 0, 'unit', pts_first, pts_seq, colors, 3)),
+            ('stack_copies_sheet_paste', lambda: gifs._canvas([(first, seq, 'unit')])))
+    values = first.numel() + seq.numel()
+    moved = {'device_copy': 8 * seq.numel(), 'cell_frames_r0': 5 * values, 'cell_frames_r3': 5 * values,
+             'stack_copies_sheet_paste': 8 * values + 5 * values}           # the staging stack is written and read again
+    res = {'first': list(first.shape), 'seq': list(seq.shape), 'canvas': list(canvas.shape), 'key_points': k}
+    for name, fn in legs:
+        us = _event_times(fn, launches, dev)
+        med = statistics.median(us)
+        res[name] = {'launches': launches, 'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                     'mb_moved': round(moved[name] / 1e6, 1), 'gb_per_s': round(moved[name] / (med * 1e-6) / 1e9, 1)}
+    copy = res['device_copy']['gb_per_s']
+    for name, _ in legs[1:3]:
+        res[name]['fraction_of_copy_rate'] = round(res[name]['gb_per_s'] / copy, 3)
+    res['cell_frames_r0']['over_existing_route'] = round(res['cell_frames_r0']['median_us'] / res['stack_copies_sheet_paste']['median_us'], 3)
+    res['cell_frames_r3']['over_r0'] = round(res['cell_frames_r3']['median_us'] / res['cell_frames_r0']['median_us'], 3)
+    return res
+
+
+def animate_stills_leg(dev, rollouts):
+    """animate.py's loop for a batch of 8 stills, 9 classes x 1 draw, overlay radius 3: the rollouts alone, with the canvases (both grids
+    composed, quantised, the indices copied), and with the host GIF work (LZW, files); ms per still"""
+    import shutil
+    import tempfile
+    import kpx_amd
+    from kpx_amd import stills
+    n, classes, radius = 8, 9, 3
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': classes}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(8)
+    low = torch.rand((n, 3, 8, 8), generator=g, device=dev)
+    im = (torch.nn.functional.interpolate(low, size=(RES, RES), mode='bilinear', align_corners=False).permute(0, 2, 3, 1) * 2 - 1).contiguous()
+    codes = torch.eye(classes, device=dev)
+    z = torch.randn((1, 64), generator=g, device=dev).expand(n, -1).contiguous()
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256, point_maps=True)
+    fm.build()
+    ops = kpx_amd.ops
+    colors = torch.from_numpy(stills.marker_colors(fm.colors)).to(dev)
+    gifs = kpx_amd.gif.RolloutGifs(10, 0)
+    grid = torch.empty((n, 33, RES, classes * RES, 3), dtype=torch.uint8, device=dev)
+    over = torch.empty_like(grid)
+    out_dir = tempfile.mkdtemp(prefix='kpx_animate_bench_')
+    paths = {name: [os.path.join(out_dir, '%s_%d.gif' % (name, i)) for i in range(n)] for name in ('classes', 'overlay')}
+
+    def run(mode):
+        for a in range(classes):
+            o = fm.run(None, {'image': im, 'action_code': codes[a:a + 1].expand(n, -1).contiguous()}, z=z)
+            if mode != 'off':
+                pred = o['pred_im_seq'].contiguous()
+                ops.cell_frames(grid, im, pred, 0, a, 'unit')
+                ops.cell_frames(over, im, pred, 0, a, 'unit', o['first_pt'].reshape(n, 15, 2).contiguous(), o['fut_pt_raw'].contiguous(), colors, radius)
+        if mode == 'device':
+            for canvas in (grid, over):
+                gifs._host(ops.gif_indices(canvas, 0)[0])
+        elif mode == 'on':
+            stills.write_grid_gifs(gifs, grid, paths['classes'])
+            stills.write_grid_gifs(gifs, over, paths['overlay'])
+
+    try:
+        for _ in range(3):                                # eager, capture, one replay
+            run('off')
+        run('on')
+        torch.cuda.synchronize(dev)
+        modes = ('off', 'device', 'on')
+        ms = {m: [] for m in modes}
+        for _ in range(max(1, min(rollouts, 3))):
+            for m in modes:
+                t0 = time.perf_counter()
+                run(m)
+                torch.cuda.synchronize(dev)
+                ms[m].append((time.perf_counter() - t0) * 1e3)
+        size = sum(os.path.getsize(os.path.join(d, f)) for d, _, names in os.walk(out_dir) for f in names)
+    finally:
+        shutil.rmtree(out_dir, ignore_errors=True)
+    off, device, on = (statistics.median(ms[m]) for m in modes)
+    return {'stills': n, 'classes': classes, 'draws': 1, 'overlay_radius': radius, 'grid': list(grid.shape), 'gif_files': 2 * n,
+            'gif_mb': round(size / 1e6, 1), 'rollouts_ms_per_still': round(off / n, 2),
+            'canvases_quantised_and_copied_ms_per_still': round((device - off) / n, 2), 'host_lzw_and_files_ms_per_still': round((on - device) / n, 2),
+            'total_ms_per_still': round(on / n, 2), 'off_ms_all': [round(v, 1) for v in ms['off']],
+            'device_ms_all': [round(v, 1) for v in ms['device']], 'on_ms_all': [round(v, 1) for v in ms['on']]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -1014,12 +1118,22 @@ def main():
                     help='measure the landmark regression (its three launches, the cost of JointRegression per video) instead')
     ap.add_argument('--gif', action='store_true',
                     help='measure the animated GIFs (the colour histogram and palette-map kernels, the host route, the cost of --gif per rollout) instead')
+    ap.add_argument('--animate', action='store_true',
+                    help="measure animate.py's grids (the cell kernel without and with markers, the route it replaces, the cost per still) instead")
     args = ap.parse_args()
-    if args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability + args.joints + args.gif > 1:
-        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier, --stability, --joints and --gif are nine measurements: pass one')
+    if (args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability + args.joints + args.gif
+            + args.animate > 1):
+        ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier, --stability, --joints, --gif and --animate are ten '
+                 'measurements: pass one')
     if not torch.cuda.is_available():
         raise SystemExit('bench_metrics.py needs the MI355X')
     dev = torch.device('cuda:0')
+    if args.animate:
+        res = {'animate_kernels': animate_kernel_leg(dev, args.launches)}
+        torch.cuda.empty_cache()
+        res['animate_stills'] = animate_stills_leg(dev, args.rollouts)
+        print(json.dumps(res))
+        return
     if args.gif:
         res = {'gif_kernels': gif_kernel_leg(dev, args.launches)}
         torch.cuda.empty_cache()

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 20
+#define KPX_ABI_VERSION 21
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -418,6 +418,32 @@ int kpx_moments_add_f64(const double* x /*[M,D]*/, int M, int D, double* sum /*[
 enum { KPX_SHEET_UNIT = 0, KPX_SHEET_RAW = 1 };
 int kpx_sheet_paste_u8_f32(const float* src /*[B,F,H,W,C]*/, int B, int F, int H, int W, int C, const int* frames /*host [J]*/, int J,
                            uint8_t* canvas /*[B,rows*H,cols*W,3]*/, int rows, int cols, int row, int col, int premap, void* stream);
+
+/* ---- animated grids (animate.py), DESIGN.md sections 2 and 4.4: one cell of a time-major canvas of rows x cols cells, T + 1 frames deep,
+ * composed in one launch, optionally with key-point markers drawn on the frames.
+ *   first fp32 [B,H,W,C] and seq fp32 [B,T,H,W,C] contiguous, C in {1,3} (C = 1 is written to the three channels); canvas uint8
+ *   [B, T+1, rows*H, cols*W, 3] contiguous, any byte alignment.
+ *   Pixels: canvas[b, 0, row*H + y, col*W + x, :] = q(first[b,y,x,:]) and canvas[b, t+1, row*H + y, col*W + x, :] = q(seq[b,t,y,x,:]) with
+ *   q = KPX_SHEET_UNIT or KPX_SHEET_RAW exactly as kpx_sheet_paste_u8_f32 defines them (NaN -> 0).  Nothing outside the cell is written.
+ *   Markers (radius r >= 1): pts_first fp32 [B,K,2] belongs to frame 0 and pts_seq fp32 [B,T,K,2] to frames 1..T; (x, y) = p[0], p[1] in the
+ *   convention of kpx_gaussian_maps_fwd_f32 (index 0 is x -> columns; pixel i of n sits at -1 + 2 i / (n - 1)).  The centre in 1/16 pixel
+ *   is cx = (int) rint(fl(fl(fl(x + 1) * 0.5f) * (float)(16 * (W - 1)))) and cy likewise with H: every step rounded to fp32, ties to even,
+ *   none contracted into an fma.  A key point with a non-finite coordinate or with |x| > 4 or |y| > 4 draws nothing.  With
+ *   d2 = (16 px - cx)^2 + (16 py - cy)^2 in exact integers, pixel (px, py) of the cell is covered by k iff d2 <= (16 r)^2; it takes
+ *   colors[k] (device uint8 [K,3], any alignment) iff d2 <= (16 (r - 1))^2 and (0,0,0) otherwise: a one-pixel outline.  A pixel covered by
+ *   several key points takes the marker of the LOWEST k.  Markers are clipped to their cell.  r = 0 reads neither the points nor the
+ *   colours: those pointers may be NULL and K is ignored.
+ *   Limits: B, T >= 1, B (T+1) < 2^31, H and W in [1,1024], C in {1,3}, rows and cols in [1,64], 0 <= row < rows, 0 <= col < cols, r in
+ *   [0,16], K in [1,64] when r >= 1.  KPX_EINVAL before any device call for anything else, a null required pointer, an fp32 pointer that is
+ *   not 4-byte aligned or an unknown premap.
+ * One launch; a workgroup takes rows of one frame at a time and stages that frame's K centres and colours in LDS once.  The vector paths
+ * are kpx_sheet_paste_u8_f32's (16 values per lane when W % 16 == 0 and first, seq and canvas are 16-byte aligned; 4 when W % 4 == 0, first
+ * and seq are 16-byte and canvas 4-byte aligned; one otherwise) -- the same bytes on every path.  No allocation, copy, synchronisation or
+ * atomics (capturable).  Added in ABI version 21. */
+int kpx_cell_frames_u8_f32(const float* first /*[B,H,W,C]*/, const float* seq /*[B,T,H,W,C]*/, int B, int T, int H, int W, int C,
+                           const float* pts_first /*[B,K,2]*/, const float* pts_seq /*[B,T,K,2]*/, int K,
+                           const uint8_t* colors /*device [K,3]*/, int radius,
+                           uint8_t* canvas /*[B,T+1,rows*H,cols*W,3]*/, int rows, int cols, int row, int col, int premap, void* stream);
 
 /* ---- animated GIFs (evaluate.py --gif), DESIGN.md sections 2 and 4.4: 8-bit RGB canvases to palette indices on the device, and GIF's LZW on
  * the host.  Integer arithmetic throughout: the same bits in any order of execution.  Added in ABI version 20.

@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/kpx.h one to one (tests/test_abi.py checks header vs this table)
-ABI_VERSION = 20      # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
+ABI_VERSION = 21     # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
 SIGNATURES = {
     'kpx_abi_version': (c_int, []),
     'kpx_reload_env': (c_int, []),
@@ -125,6 +125,7 @@ SIGNATURES = {
     'kpx_feature_pool_f64': (c_int, [P, c_int, c_int, c_int, c_int, P, P, P]),
     'kpx_moments_add_f64': (c_int, [P, c_int, c_int, P, P, P]),
     'kpx_sheet_paste_u8_f32': (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
+    'kpx_cell_frames_u8_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
     'kpx_color_hist_add_u32': (c_int, [P, c_int, c_size_t, P, P]),
     'kpx_palette_map_u8': (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, c_int, P, P]),
     'kpx_gif_lzw_bound': (c_size_t, [c_size_t]),

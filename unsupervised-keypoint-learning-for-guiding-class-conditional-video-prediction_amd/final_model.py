@@ -115,6 +115,12 @@ class FinalModel(BaseModel):
         res['real_im_seq'] = feed_dict.get('real_im_seq')
         return res
 
+    def detect(self, image):
+        """The detector alone (animate.py --driver): image [B,R,R,3] in [-1,1] -> its key points [B,K,2] as (x, y), the ``first_pt`` of run()."""
+        im = image.contiguous()
+        with variables.as_default(self.store), torch.no_grad():
+            return networks.pose_encoder(im, self.n_points, False, final_res=self.image_size).reshape(im.shape[0], self.n_points, 2)
+
     def _check_drive(self, im, drive):
         """-> (mode, shift, scaled, {'first' / 'seq': contiguous tensors the mode reads}); everything ops.points_retarget would refuse is
         refused here, before any copy into a graph's static buffers"""

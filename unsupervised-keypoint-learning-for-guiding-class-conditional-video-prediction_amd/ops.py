@@ -1635,7 +1635,72 @@ def sheet_paste(canvas, src, frames, row, col, premap):
     return canvas
 
 
-HIST_CELLS = 32768                                                                # 5-5-5 colour cells
+CELL_MAX_POINTS = 64                                                              # markers per frame of kpx_cell_frames_u8_f32
+CELL_MAX_RADIUS = 16
+
+
+def cell_frames(canvas, first, seq, row, col, premap, pts_first=None, pts_seq=None, colors=None, radius=0):
+    """One cell of an animated grid, optionally with key-point markers (DESIGN.md sections 2 and 4.4).  canvas: contiguous uint8
+    [B, T+1, rows*H, cols*W, 3]; first: contiguous fp32 [B,H,W,C] and seq: contiguous fp32 [B,T,H,W,C], C in (1, 3), on canvas's device.
+    canvas[b, 0, cell] = q(first[b]) and canvas[b, t+1, cell] = q(seq[b, t]) with ``premap`` as in ``sheet_paste``; nothing outside cell
+    (row, col) is written.  ``radius`` r in [1, 16]: pts_first fp32 [B,K,2] and pts_seq fp32 [B,T,K,2] (x, y in [-1, 1], the convention of
+    ``gaussian_maps``), 1 <= K <= 64, and colors uint8 [K,3] on the device draw a disc of radius r - 1 in colors[k] with a one-pixel black
+    outline at every key point (centres in 1/16 pixel, integer distances, the lowest k on top, clipped to the cell; a non-finite point or
+    one beyond +-4 draws nothing).  r = 0 draws none and takes no points.  rows and cols (from the canvas shape) in [1, 64], H and W in
+    [1, 1024].  One launch on the current stream; capturable."""
+    for name, t, dtype, dim in (('canvas', canvas, torch.uint8, 5), ('first', first, torch.float32, 4), ('seq', seq, torch.float32, 5)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.KpxError('kpx ops run on MI355X only (got %s for cell_frames\'s %s); there is no CPU fallback'
+                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
+        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
+            raise _lib.KpxError('cell_frames: %s must be a contiguous %s tensor of %d dimensions (got %s %s, contiguous=%s)'
+                                % (name, dtype, dim, tuple(t.shape), t.dtype, t.is_contiguous()))
+    if canvas.device != seq.device or first.device != seq.device:
+        raise _lib.KpxError('cell_frames: canvas, first and seq must be on one device (got %s, %s and %s)'
+                            % (canvas.device, first.device, seq.device))
+    if premap not in SHEET_PREMAPS:
+        raise _lib.KpxError('cell_frames: premap must be one of %s (got %r)' % (sorted(SHEET_PREMAPS), premap))
+    b, t_, h, w, c = seq.shape
+    if b < 1 or t_ < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
+        raise _lib.KpxError('cell_frames: seq needs B, T >= 1, H and W in [1, 1024] and C in (1, 3) (got %s)' % (tuple(seq.shape),))
+    if tuple(first.shape) != (b, h, w, c):
+        raise _lib.KpxError('cell_frames: first must be %s, one frame per sample of seq (got %s)' % ([b, h, w, c], tuple(first.shape)))
+    if canvas.shape[0] != b or canvas.shape[1] != t_ + 1 or canvas.shape[4] != 3 or canvas.shape[2] % h or canvas.shape[3] % w:
+        raise _lib.KpxError('cell_frames: canvas must be [%d, %d, rows * %d, cols * %d, 3] (got %s)' % (b, t_ + 1, h, w, tuple(canvas.shape)))
+    rows, cols = canvas.shape[2] // h, canvas.shape[3] // w
+    if not (1 <= rows <= 64 and 1 <= cols <= 64):
+        raise _lib.KpxError('cell_frames: a grid has 1 to 64 rows and columns of cells (got %d x %d)' % (rows, cols))
+    if any(isinstance(v, bool) or not isinstance(v, int) for v in (row, col, radius)):
+        raise _lib.KpxError('cell_frames: row, col and radius are integers (got %r, %r, %r)' % (row, col, radius))
+    if not (0 <= row < rows and 0 <= col < cols):
+        raise _lib.KpxError('cell_frames: cell (row %d, col %d) is outside a grid of %d x %d cells' % (row, col, rows, cols))
+    if not 0 <= radius <= CELL_MAX_RADIUS:
+        raise _lib.KpxError('cell_frames: radius must be in [0, %d] (got %d)' % (CELL_MAX_RADIUS, radius))
+    k = 0
+    if radius == 0:
+        if pts_first is not None or pts_seq is not None or colors is not None:
+            raise _lib.KpxError('cell_frames: radius 0 draws no markers and takes no points or colours')
+    else:
+        for name, t, dim in (('pts_first', pts_first, 3), ('pts_seq', pts_seq, 4)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise _lib.KpxError('kpx ops run on MI355X only (got %s for cell_frames\'s %s); there is no CPU fallback'
+                                    % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
+            if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous() or t.shape[-1] != 2 or t.device != seq.device:
+                raise _lib.KpxError('cell_frames: %s must be a contiguous fp32 tensor of %d dimensions ending in 2 on %s (got %s %s on %s, '
+                                    'contiguous=%s)' % (name, dim, seq.device, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
+        k = int(pts_first.shape[1])
+        if not 1 <= k <= CELL_MAX_POINTS or tuple(pts_first.shape) != (b, k, 2) or tuple(pts_seq.shape) != (b, t_, k, 2):
+            raise _lib.KpxError('cell_frames: pts_first must be [%d, K, 2] and pts_seq [%d, %d, K, 2] with 1 <= K <= %d (got %s and %s)'
+                                % (b, b, t_, CELL_MAX_POINTS, tuple(pts_first.shape), tuple(pts_seq.shape)))
+        _u8_gpu('cell_frames', 'colors', colors, 2)
+        if tuple(colors.shape) != (k, 3) or colors.device != seq.device:
+            raise _lib.KpxError('cell_frames: colors must be uint8 [%d, 3] on %s (got %s on %s)' % (k, seq.device, tuple(colors.shape), colors.device))
+    check(lib.kpx_cell_frames_u8_f32(first.data_ptr(), seq.data_ptr(), b, t_, h, w, c, _ptr(pts_first), _ptr(pts_seq), k, _ptr(colors), radius,
+                                     canvas.data_ptr(), rows, cols, row, col, SHEET_PREMAPS[premap], _stream()), 'kpx_cell_frames_u8_f32')
+    return canvas
+
+
+HIST_CELLS = 32768                                                          # 5-5-5 colour cells
 HIST_MAX_PIXELS = 1 << 24                                                         # per group and call: the uint32 sums cannot overflow
 GIF_MAX_DITHER = 64
 
