@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif | --animate | --guard]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -96,6 +96,15 @@
    time after warm-up, median us, GB/s of the bytes each moves and the kernel's rate as a fraction of the copy's.
 21. animate.py's loop for 8 stills under 9 classes x 1 draw with --overlay 3 (random weights): the rollouts alone, with both grids
    composed, quantised and copied, and with the host GIF work (LZW, 16 files); ms per still of each part.
+
+``--guard`` measures the step guard (train.py --guard) instead:
+
+22. kpx_grad_health_f32 (its two launches), kpx_adam_tf_flat_guarded_f32 beside kpx_adam_tf_flat_dev_alpha_f32, and kpx_guard_restore_f32
+   on a dirty record, on the two flat buckets of the configs[1] model (their real sizes, read from a built model), each beside a device copy
+   of the same number of floats in the same process; device-event time of each call after warm-up, median us, bytes/s of what each moves
+   (health 4n read; Adam 16n read + 12n written; copy and restore 4n + 4n) and the rate as a fraction of the copy's.
+23. The configs[1] train step (128x128, K = 15, B = 32, replayed HIP graph) through the model API with guard off and on, two models in one
+   process, alternated in blocks; median ms per step of each and the difference in ms and %.
 
 Prints one JSON line.
 """
@@ -1101,6 +1110,74 @@ def animate_stills_leg(dev, rollouts):
             'device_ms_all': [round(v, 1) for v in ms['device']], 'on_ms_all': [round(v, 1) for v in ms['on']]}
 
 
+def _c1_model(dev, guard):
+    import kpx_amd
+    cfg = {'training': {'lr': {'start_val': 1e-4, 'step': 20000, 'decay': 0.95}, 'batch_size': 32},
+           'model': {'n_pts': 15}, 'paths': {'log_dir': '/tmp/kpx_bench', 'vggnet': None}}
+    vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(seed=19), device=dev)
+    model = kpx_amd.DetectorTranslatorModel(cfg, device=dev, vgg=vgg, image_size=RES, **({'guard': True} if guard else {}))
+    model.build()
+    return model
+
+
+def guard_kernel_leg(dev, launches, sizes):
+    from kpx_amd import ops
+    res = {}
+    for which, n in sizes.items():
+        g = torch.randn(n, device=dev) * 1e-3
+        p, m, v, dst = torch.randn(n, device=dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.empty(n, device=dev)
+        clean, dirty = ops.new_guard_health(dev), ops.new_guard_health(dev)
+        work = ops.grad_health_workspace(n, dev)
+        ops.grad_health(torch.full((4,), float('inf'), device=dev), dirty)
+        alpha = torch.full((1,), 1e-4, device=dev)
+        legs = (('device_copy', lambda: dst.copy_(g), 8 * n),
+                ('grad_health', lambda: ops.grad_health(g, clean, work), 4 * n),
+                ('adam_dev_alpha', lambda: ops.adam_tf_flat_dev_alpha_(p, g, m, v, alpha, 0.5, 0.999, 1e-8), 28 * n),
+                ('adam_guarded_clean', lambda: ops.adam_tf_flat_guarded_(p, g, m, v, alpha, 0.5, 0.999, 1e-8, clean), 28 * n),
+                ('adam_guarded_skipped', lambda: ops.adam_tf_flat_guarded_(p, g, m, v, alpha, 0.5, 0.999, 1e-8, dirty), 0),
+                ('guard_restore_dirty', lambda: ops.guard_restore_(dst, g, dirty), 8 * n))
+        out = {'floats': n, 'mb': round(4 * n / 1e6, 1)}
+        for name, fn, moved in legs:
+            us = _event_times(fn, launches, dev)
+            med = statistics.median(us)
+            out[name] = {'launches': launches, 'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                         'gb_per_s': round(moved / (med * 1e-6) / 1e9, 1)}
+        copy = out['device_copy']['gb_per_s']
+        for name in ('grad_health', 'adam_dev_alpha', 'adam_guarded_clean', 'guard_restore_dirty'):
+            out[name]['fraction_of_copy_rate'] = round(out[name]['gb_per_s'] / copy, 3)
+        assert ops.read_guard_health(clean)['nonfinite'] == 0 and ops.read_guard_health(dirty)['skipped_total'] >= launches
+        res[which] = out
+        del g, p, m, v, dst
+        torch.cuda.empty_cache()
+    return res
+
+
+def guard_step_leg(dev, steps):
+    """The configs[1] train step with guard off and on: two models, blocks of ``steps`` replayed steps each, alternated three times."""
+    from kpx_amd.synthetic import synthetic_pair
+    models = {'off': _c1_model(dev, False), 'on': _c1_model(dev, True)}
+    feed = {k: torch.from_numpy(v).to(dev) for k, v in synthetic_pair(32, res=RES, seed0=0, seed1=1).items()}
+    for m in models.values():
+        for i in range(4):                                # eager, capture, replays
+            m.train_step(None, feed, i, 32)
+    torch.cuda.synchronize(dev)
+    ms = {k: [] for k in models}
+    for _ in range(3):
+        for k, m in models.items():
+            t0 = time.perf_counter()
+            for i in range(steps):
+                m.train_step(None, feed, 4 + i, 32)
+            torch.cuda.synchronize(dev)
+            ms[k].append((time.perf_counter() - t0) * 1e3 / steps)
+    off, on = statistics.median(ms['off']), statistics.median(ms['on'])
+    rep = models['on'].guard_report()
+    return {'batch': 32, 'steps_per_block': steps, 'graph_replay': all(len(m._graphs) == 1 and not m._graph_failed for m in models.values()),
+            'off_ms_per_step': round(off, 3), 'on_ms_per_step': round(on, 3), 'guard_ms_per_step': round(on - off, 3),
+            'guard_percent': round(100.0 * (on - off) / off, 2), 'off_ms_all': [round(v, 3) for v in ms['off']],
+            'on_ms_all': [round(v, 3) for v in ms['on']], 'moving_statistics_floats': {k: v.numel() for k, v in models['on'].store.moving.items()},
+            'skipped': {k: r['skipped_total'] for k, r in rep.items()}}, {k: b.grads.numel() for k, b in models['on'].store.buckets.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -1120,7 +1197,18 @@ def main():
                     help='measure the animated GIFs (the colour histogram and palette-map kernels, the host route, the cost of --gif per rollout) instead')
     ap.add_argument('--animate', action='store_true',
                     help="measure animate.py's grids (the cell kernel without and with markers, the route it replaces, the cost per still) instead")
+    ap.add_argument('--guard', action='store_true',
+                    help="measure the step guard (the health pass, the guarded update and the restore on the two real buckets, the configs[1] train "
+                         'step with guard off and on) instead')
     args = ap.parse_args()
+    if args.guard:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        step, sizes = guard_step_leg(dev, max(args.rollouts, 10))
+        torch.cuda.empty_cache()
+        print(json.dumps({'guard_kernels': guard_kernel_leg(dev, args.launches, sizes), 'guard_step_c1': step}))
+        return
     if (args.vgg + args.motion + args.actions + args.drive + args.frechet + args.classifier + args.stability + args.joints + args.gif
             + args.animate > 1):
         ap.error('--vgg, --motion, --actions, --drive, --frechet, --classifier, --stability, --joints, --gif and --animate are ten '

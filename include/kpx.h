@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 21
+#define KPX_ABI_VERSION 22
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -533,6 +533,35 @@ int kpx_adam_tf_flat_f32(float* p, const float* g, float* m, float* v, size_t n,
  * capture time while alpha (learning-rate decay :193-195, bias correction) changes every step; the caller refreshes *alpha_dev before each replay. */
 int kpx_adam_tf_flat_dev_alpha_f32(float* p, const float* g, float* m, float* v, size_t n,
                                    const float* alpha_dev, float beta1, float beta2, float eps, float gscale, void* stream);
+
+/* ---- the step guard (train.py --guard), DESIGN.md section 4.4: a bucket whose gradient holds a NaN or an Inf skips its update.  The
+ * verdict is a record in DEVICE memory, one per bucket, written by the health pass and read by the update and the restore themselves, so
+ * the captured step needs no host synchronisation.  All three entries: no allocation, copy or synchronisation (capturable); no atomics;
+ * KPX_EINVAL before any device call for a null or misaligned pointer or n == 0.  Added in ABI version 22. */
+typedef struct KpxGuardHealth {      /* 32 bytes, 8-byte aligned */
+    uint32_t nonfinite;              /* this step's gradient values that are NaN or +-Inf (saturates at 2^32 - 1) */
+    uint32_t skipped_total;          /* updates skipped so far */
+    uint32_t skipped_run;            /* consecutive skips; a clean update resets it to 0 */
+    uint32_t updates;                /* guarded updates so far, skipped ones included */
+    double sumsq;                    /* sum of g^2 over the finite values */
+    float maxabs;                    /* max |g| over the finite values */
+    float pad_;
+} KpxGuardHealth;
+/* kpx_grad_health_f32: one read pass over g fp32 [n] (4-byte aligned, n >= 1; sizes beyond 2^31 are fine) -> health->nonfinite, ->sumsq
+ *   and ->maxabs; the four counters are left alone, a second call overwrites the first call's result.  Two launches: per-slab partials into
+ *   `work` (kpx_grad_health_workspace_bytes(n) bytes, 8-byte aligned), then a one-workgroup fold.  Every value is converted to fp64 before
+ *   it is squared (the square is exact), a slab is 16384 consecutive elements whatever the grid, and the order of every addition depends
+ *   on n alone: the record is bitwise the same from run to run and whether g is 16-byte aligned (16-byte loads) or not (4-byte loads).
+ * kpx_adam_tf_flat_guarded_f32: with health->nonfinite == 0, kpx_adam_tf_flat_dev_alpha_f32 bit for bit (one shared definition of the
+ *   arithmetic); otherwise p, m and v are left bitwise untouched.  One lane bumps ->updates and either ->skipped_total and ->skipped_run,
+ *   or clears ->skipped_run.  p, g, m, v 16-byte aligned, n >= 1.
+ * kpx_guard_restore_f32: dst[0:n] = src[0:n] bit for bit if health->nonfinite != 0, nothing otherwise (4-byte aligned pointers; 16-byte
+ *   accesses when both are 16-byte aligned). */
+size_t kpx_grad_health_workspace_bytes(size_t n);
+int kpx_grad_health_f32(const float* g, size_t n, void* work, KpxGuardHealth* health, void* stream);
+int kpx_adam_tf_flat_guarded_f32(float* p, const float* g, float* m, float* v, size_t n, const float* alpha_dev,
+                                 float beta1, float beta2, float eps, float gscale, KpxGuardHealth* health, void* stream);
+int kpx_guard_restore_f32(float* dst, const float* src, size_t n, const KpxGuardHealth* health, void* stream);
 
 /* ---- evaluate.py / FinalModel rollout (forward only).  Dense layers run as 1x1 kpx_conv2d_fwd_f32.
  * LSTMCell pointwise part (models/networks/layers.py:17-21): gates [B,4U] = (i,j,f,o) pre-activations. */

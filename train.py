@@ -19,6 +19,13 @@ PIL call or numpy work per step; the start frames, which only the image summary 
 ``action_classifier`` reads the batches ``motion_generator`` reads (``--resident-labels`` included) and uses their ``real_seq`` and
 ``action_code``; its ``--synthetic`` feeds a planted problem in which the class decides the direction the points drift in
 (kpx_amd.synthetic.planted_action_batch).
+
+Long runs, all three modes: ``--resume latest|PATH`` continues from a checkpoint (variables, Adam slots, beta powers, global_step; stage 2 also
+its noise generator's state from the side file model.ckpt-N.rng-RANK.npz; ``latest`` = the newest complete checkpoint of the log directory,
+or a start from scratch when there is none), ``--keep N`` prunes older checkpoints after each save, and ``--guard`` skips the update of a
+bucket whose gradient holds a NaN or an Inf, decided on the device inside the step (``--guard-max-skips N`` stops a run that only skips).
+Checkpoints are written under temporary names and renamed into place.  Real data loaders are reseeded on a resume, not continued sample
+for sample.
 """
 import logging
 import os
@@ -27,6 +34,8 @@ from argparse import ArgumentParser
 
 import torch
 import yaml
+
+log = logging.getLogger('kpx')
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -56,6 +65,88 @@ def _get_model_by_mode(mode, config, global_step, **kw):
     raise Exception('unknown model %s' % mode)
 
 
+def _guard_kw(args):
+    """guard=True only under --guard: without the flag the constructors are called exactly as before."""
+    return {'guard': True} if args.guard else {}
+
+
+def _resume_seed(rank, step):
+    """One integer per (data-parallel rank, step resumed at): what the streams that are not continued sample for sample are reseeded from."""
+    return ((1000 + rank) << 32) | int(step)
+
+
+def _resume(args, model, log_dir, rank, world, dev):
+    """--resume latest|PATH, after build() and before initialize_loggers and the first step: restore the checkpoint strictly (model.resume),
+    continue this rank's torch generators from the checkpoint's side file where the model draws on the device, and hold the ranks to one
+    global_step.  -> True when a checkpoint was restored (False: --resume latest on a log directory without one)."""
+    path = args.resume
+    if path == 'latest':
+        found = model.latest_checkpoint(log_dir)
+        if found is None:
+            log.info('--resume latest: no complete checkpoint under %s, starting from scratch', os.path.join(str(log_dir), model.name))
+            return False
+        path = found[0]
+    step, n_vars, n_slots = model.resume(None, path)
+    log.info('resumed from %s: global_step %d, %d variables and %d Adam slots restored', path, step, n_vars, n_slots)
+    if getattr(model, 'draws_on_device', False):
+        saved, beside = step - 1, os.path.dirname(os.path.abspath(path))     # the checkpoint written after step s holds global_step s + 1
+        if not model.load_rng_state(saved, rank, beside):
+            log.warning('no generator state %s (another world size?): rank %d reseeds its noise from (%d, %d)',
+                        model.rng_state_path(saved, rank, beside), rank, 1000 + rank, step)
+            torch.manual_seed(_resume_seed(rank, step))
+    if world > 1:
+        # every rank read the same file; one all-reduce (max of [step, -step]) holds them to it before the first step
+        both = torch.tensor([step, -step], dtype=torch.int64, device=dev)
+        torch.distributed.all_reduce(both, op=torch.distributed.ReduceOp.MAX)
+        hi, lo = int(both[0]), -int(both[1])
+        if hi != lo:
+            raise Exception('--resume: the ranks restored different steps (global_step %d .. %d; this rank %d): every rank must read the '
+                            'same checkpoint' % (lo, hi, step))
+    return True
+
+
+def _reseed_loaders(rank, step):
+    """Real data loaders are not continued sample for sample (threads, prefetch, shuffle buffer): a run resumed at ``step`` draws from
+    streams reseeded from (1000 + rank, step) -- a deterministic function of where it resumed."""
+    import random
+    import numpy as np
+    random.seed(_resume_seed(rank, step)); np.random.seed([1000 + rank, int(step)])
+
+
+class _GuardLog(object):
+    """--guard at a log point (rank 0): one line when a count moved, the guard/* scalars with the summaries, and the end of a run in which a
+    bucket has skipped --guard-max-skips updates in a row."""
+
+    def __init__(self, max_skips):
+        self.max_skips, self.seen = max_skips, None
+
+    def __call__(self, model, step, should_write_summary):
+        report = model.guard_report()
+        counts = {b: (r['skipped_total'], r['skipped_run']) for b, r in report.items()}
+        if counts != self.seen and (self.seen is not None or any(c != (0, 0) for c in counts.values())):
+            log.info('guard: step %d: %s', step, ', '.join(
+                '%s skipped %d of %d updates (%d in a row; %d non-finite gradient values in the last step, grad norm %.4g, max |g| %.4g)'
+                % (b, r['skipped_total'], r['updates'], r['skipped_run'], r['nonfinite'], r['grad_norm'], r['max_abs']) for b, r in report.items()))
+        self.seen = counts
+        if should_write_summary and model.train_writer is not None:
+            from kpx_amd import summary
+            model.train_writer.add_summary([summary.scalar_value('guard/%s_%s' % (key, b), float(r[field])) for b, r in report.items()
+                                            for key, field in (('skipped', 'skipped_total'), ('grad_norm', 'grad_norm'))], step)
+        stuck = [b for b, r in report.items() if r['skipped_run'] >= self.max_skips]
+        if stuck:
+            raise Exception('--guard: bucket %s has skipped %d updates in a row at step %d (--guard-max-skips %d): every gradient is '
+                            'non-finite, the run is not training' % (', '.join(stuck), max(report[b]['skipped_run'] for b in stuck), step, self.max_skips))
+
+
+def _save(args, model, step, rank):
+    """The checkpoint of ``step``: rank 0 writes (and prunes under --keep); every rank of a model that draws on the device writes its
+    generator states beside it."""
+    if getattr(model, 'draws_on_device', False):
+        model.save_rng_state(step, rank)
+    if rank == 0:
+        model.save_checkpoint(None, step, fmt=args.ckpt_format, **({'keep': args.keep} if args.keep is not None else {}))
+
+
 def _train_motion_generator(args, config, dev, rank, world):
     """reference train.py:136-147 (SequenceDataLoader, is_train -> random_order + randomness) + the common loop (:84-113).  The
     action_classifier mode runs the same loop over the same loaders; it writes no image summary, so it asks for no start frames."""
@@ -63,16 +154,19 @@ def _train_motion_generator(args, config, dev, rank, world):
     import kpx_amd
     paths_config, train_config, model_config = config['paths'], config['training'], config['model']
     classifier = args.mode == 'action_classifier'
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed)
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed, **_guard_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']
     n_steps = args.steps if args.steps is not None else train_config['n_steps']
     k, a = model_config['n_pts'], model_config['n_action']
     train_it = test_batches = None
+    resumed = args.resume is not None and _resume(args, model, paths_config['log_dir'], rank, world, dev)
     if not args.synthetic:
         import random
         random.seed(1000 + rank); np.random.seed(1000 + rank)
+        if resumed:
+            _reseed_loaders(rank, model.global_step)
         mk = lambda subset, train: kpx_amd.SequenceDataLoader(paths_config['data_dir'], subset, n_points=k, n_action=a,
                                                               random_order=train, randomness=train)
         train_it = mk('train', True).batches(batch_size, dev, repeat=True, resident=args.resident_labels)
@@ -96,6 +190,7 @@ def _train_motion_generator(args, config, dev, rank, world):
              'action_code': np.eye(a)[rs.randint(0, a, size=batch_size)]}
         return {n: torch.from_numpy(v.astype(np.float32)).to(dev) for n, v in d.items()}
     model.initialize_loggers(paths_config['log_dir'], None)
+    guard_log = _GuardLog(args.guard_max_skips) if args.guard else None
     print('training start')
     for step in range(model.global_step, n_steps):
         feed = next(train_it) if train_it is not None else synthetic(step * world + rank)
@@ -104,8 +199,10 @@ def _train_motion_generator(args, config, dev, rank, world):
             feed = dict(feed, image=train_it.start_images(2))
         model.train_step(None, feed, step, batch_size, should_write_log=step % train_config['log_interval'] == 0 and rank == 0,
                          should_write_summary=should_write_summary)
-        if step % train_config['checkpoint_interval'] == 0 and rank == 0:
-            model.save_checkpoint(None, step, fmt=args.ckpt_format)
+        if guard_log is not None and step % train_config['log_interval'] == 0 and rank == 0:
+            guard_log(model, step, should_write_summary)
+        if step % train_config['checkpoint_interval'] == 0:
+            _save(args, model, step, rank)
         if step % train_config['test_interval'] == 0 and rank == 0:
             feeds = test_feeds(test_batches()) if test_batches is not None else [synthetic(10 ** 6)]
             model.collect_test_results([model.test_step(None, f, step, i, f['keypoints'].shape[0]) for i, f in enumerate(feeds)], step)
@@ -144,7 +241,25 @@ def main(argv=None):
                              'step with a shared generator forward')
     parser.add_argument('--colors_seed', type=int, default=0,
                         help='seed of the key-point palette of the image summaries (the reference draws it from the unseeded random module)')
+    parser.add_argument('--resume', type=str, default=None, metavar='latest|PATH',
+                        help="continue from a checkpoint (an .npz or a bundle prefix): variables, Adam slots, beta powers and global_step; 'latest' = "
+                             'the complete checkpoint with the highest step under <log_dir>/<mode>/, or a start from scratch when there is none, so '
+                             'that one command line serves the first start and every restart.  Every trainable variable must be in it')
+    parser.add_argument('--keep', type=int, default=None, metavar='N',
+                        help='after each save, delete this mode\'s checkpoints beyond the newest N (default: keep all)')
+    parser.add_argument('--guard', action='store_true',
+                        help='skip the update of a bucket whose gradient holds a NaN or an Inf (parameters, Adam slots and batch-norm moving '
+                             'statistics keep their bits) instead of writing it into every parameter; decided on the device, inside the captured step')
+    parser.add_argument('--guard-max-skips', type=int, default=100, metavar='N',
+                        help='--guard: stop the run when a bucket has skipped N updates in a row at a log point (default 100)')
     args = parser.parse_args(argv)
+    if args.keep is not None and args.keep < 1:
+        parser.error('--keep N keeps the newest N checkpoints: N must be at least 1')
+    if args.guard_max_skips < 1:
+        parser.error('--guard-max-skips N: N must be at least 1')
+    if args.resume is not None and args.resume != 'latest':
+        if not (os.path.isfile(args.resume) or os.path.isfile(args.resume + '.index')):
+            parser.error('--resume %s: no such checkpoint (an .npz file, the prefix of a bundle, or the word latest)' % args.resume)
     if args.resident_data and (args.mode != 'detector_translator' or args.synthetic):
         parser.error('--resident-data keeps JPEG frames in HBM: the motion_generator and action_classifier modes read key-point files and '
                      '--synthetic reads no frames')
@@ -172,11 +287,12 @@ def main(argv=None):
         if not args.synthetic_vgg:
             raise Exception('file of pretrained vgg19 does not exist at: %s (pass --synthetic-vgg for benchmarking)' % paths_config.get('vggnet'))
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev)
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed)
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, **_guard_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']          # per process, like the reference's single-device batch
     train_it = test_it = None
+    resumed = args.resume is not None and _resume(args, model, paths_config['log_dir'], rank, world, dev)
     if not args.synthetic:                           # reference train.py:125-135, 60-70: is_train -> random_order + randomness
         data_dir = paths_config['data_dir']
         if not os.path.exists(os.path.join(str(data_dir), 'train_set.txt')):
@@ -184,6 +300,8 @@ def main(argv=None):
         import random
         import numpy as np
         random.seed(1000 + rank); np.random.seed(1000 + rank)          # different sample streams per data-parallel rank
+        if resumed:
+            _reseed_loaders(rank, model.global_step)
         train_it = iter(kpx_amd.ImagePairDataLoader(data_dir, 'train', random_order=True, randomness=True)
                         .batches(batch_size, dev, repeat=True, shuffle=True, resident=args.resident_data))
         if os.path.exists(os.path.join(str(data_dir), 'test_set.txt')):
@@ -191,6 +309,7 @@ def main(argv=None):
             test_it = lambda: iter(test_loader.batches(batch_size, dev, repeat=False, shuffle=False, resident=args.resident_data))
     n_steps = args.steps if args.steps is not None else train_config['n_steps']
     model.initialize_loggers(paths_config['log_dir'], None)
+    guard_log = _GuardLog(args.guard_max_skips) if args.guard else None
     print('training start')
     for step in range(model.global_step, n_steps):   # reference train.py:84-113
         should_write_log = step % train_config['log_interval'] == 0
@@ -205,10 +324,13 @@ def main(argv=None):
                 s2 = 10 ** 7 + 2 * (step * world + rank)
                 pair = synthetic_pair(batch_size, res=model.image_size, seed0=s2, seed1=s2 + 1)
                 feed_dict.update({k + '_G': torch.from_numpy(v).to(dev) for k, v in pair.items()})
+        should_write_summary = _should_write_summary(train_config, step, rank)
         model.train_step(None, feed_dict, step, batch_size, should_write_log=should_write_log and rank == 0,
-                         should_write_summary=_should_write_summary(train_config, step, rank))
-        if step % train_config['checkpoint_interval'] == 0 and rank == 0:
-            model.save_checkpoint(None, step, fmt=args.ckpt_format)
+                         should_write_summary=should_write_summary)
+        if guard_log is not None and should_write_log and rank == 0:
+            guard_log(model, step, should_write_summary)
+        if step % train_config['checkpoint_interval'] == 0:
+            _save(args, model, step, rank)
         if step % train_config['test_interval'] == 0 and rank == 0:
             if test_it is not None:                  # reference train.py:97-110: one pass over the test subset
                 results = [model.test_step(None, fd, step, i, fd['image'].shape[0]) for i, fd in enumerate(test_it())]

@@ -24,8 +24,9 @@ DEFAULT_CELLS = (256, 256)      # model.classifier_cells when the config has non
 class ActionClassifierModel(BaseModel):
     name = 'action_classifier'         # checkpoint / summary sub-directory
 
-    def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777):
+    def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777, guard=False):
         super(ActionClassifierModel, self).__init__(is_training)
+        self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
         self.batch_size = train_config['batch_size']
@@ -46,7 +47,8 @@ class ActionClassifierModel(BaseModel):
     def build(self, inputs=None):
         with variables.as_default(self.store):
             networks.seq_classifier(Sym(2, N_FUTURE_FRAMES, self.n_points * 2), self.n_action, self.cells)
-        self.store.materialise()             # every variable lands in the 'G' bucket; 'D' stays empty and is never stepped
+        self.store.materialise(guard=self.guard)     # every variable lands in the 'G' bucket; 'D' stays empty and is never stepped
+        self._guard_init(('G',))
         if self.device.type == 'cuda':
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
 
@@ -82,8 +84,11 @@ class ActionClassifierModel(BaseModel):
             torch.distributed.all_reduce(bucket.grads, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
         b1p, b2p = self.beta_power
         alpha = np.float32(np.float32(lr) * np.sqrt(np.float32(1) - b2p) / (np.float32(1) - b1p))
-        ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha, self.beta1, self.beta2, self.adam_eps,
-                          gscale=1.0 / self.world_size)
+        if self.guard:                               # (after the exchange: every rank judges the same summed gradient)
+            self._guarded_adam('G', alpha, gscale=1.0 / self.world_size)
+        else:
+            ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha, self.beta1, self.beta2, self.adam_eps,
+                              gscale=1.0 / self.world_size)
         self.store.touch()
         self.beta_power = [np.float32(b1p * self.beta1), np.float32(b2p * self.beta2)]
 

@@ -6,11 +6,17 @@ names, in an ``.npz`` container (default) or as a TensorFlow
 ``KPX_CKPT_FORMAT=tf``).
 """
 import os
+import re
 from abc import ABC, abstractmethod
 from os import path as osp
 
 import numpy as np
 import torch
+
+TMP_SUFFIX = '.tmp'                # a checkpoint file being written; renamed into place when it is whole (tf_bundle.TMP_SUFFIX)
+_CKPT_FILE = re.compile(r'^model\.ckpt-(\d+)\.(npz|index)$')
+_RNG_FILE = re.compile(r'^model\.ckpt-(\d+)\.rng-(\d+)\.npz$')
+_COUNTERS = ('global_step', 'beta1_power', 'beta2_power', 'beta1_power_1', 'beta2_power_1')
 
 
 class BaseModel(ABC):
@@ -67,13 +73,74 @@ class BaseModel(ABC):
             for values in summaries:
                 writer.add_summary(values, step)
 
+    # ---- the step guard (guard=True of the training models, train.py --guard) -------------------------------------------------------
+    # A bucket whose exchanged gradient holds a NaN or an Inf skips its update: parameters, Adam slots and the batch-norm moving
+    # statistics the bucket owns keep the bits they had before the step.  The verdict is one KpxGuardHealth record per bucket in device
+    # memory, written by the health pass and read by the update and the restore themselves, so every launch is part of the captured step
+    # and the host never learns of a skip: beta powers and global_step advance as on any other step (the bias correction then runs a few
+    # steps ahead of the slots, which is harmless).  Only guard_report() reads the records back.
+    guard = False
+    draws_on_device = False            # a model whose train step draws from torch's device generator (stage 2): see save_rng_state
+
+    def _guard_init(self, buckets):
+        """After store.materialise(): the health record, the health pass's workspace and the device-side step size of every non-empty bucket."""
+        self._guard_health, self._guard_work, self._guard_alpha = {}, {}, {}
+        if not self.guard:
+            return
+        from . import ops
+        for which in buckets:
+            bucket = self.store.buckets[which]
+            if bucket.size:
+                self._guard_health[which] = ops.new_guard_health(self.device)
+                self._guard_work[which] = ops.grad_health_workspace(bucket.grads.numel(), self.device)
+                self._guard_alpha[which] = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    def _guard_shadow_moving(self):
+        """Before the forward: the moving statistics as they stand, into their shadows (one copy per owner bucket; nothing without guard)."""
+        if self.guard:
+            from . import ops
+            for which, live in self.store.moving.items():
+                ops.flat_copy_raw(live.data_ptr(), self.store.moving_shadow[which].data_ptr(), live.numel())
+
+    def _guarded_adam(self, which, alpha=None, alpha_dev=None, gscale=1.0):
+        """Health pass over the bucket's (exchanged) gradient, the guarded update in the place of the plain one, and the restore of the
+        moving statistics the bucket owns.  ``alpha``: the step size as a host number, written into the device float first (the eager
+        form); None when the caller has refreshed ``alpha_dev`` itself (a captured launch, whose arguments are frozen)."""
+        from . import ops
+        bucket, health = self.store.buckets[which], self._guard_health[which]
+        alpha_dev = self._guard_alpha[which] if alpha_dev is None else alpha_dev
+        if alpha is not None:
+            ops.fill_raw_(alpha_dev, float(alpha))
+        ops.grad_health(bucket.grads, health, self._guard_work[which])
+        ops.adam_tf_flat_guarded_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha_dev, self.beta1, self.beta2, self.adam_eps, health,
+                                  gscale=gscale)
+        live = self.store.moving.get(which)
+        if live is not None:
+            ops.guard_restore_(live, self.store.moving_shadow[which], health)
+
+    def guard_report(self):
+        """{bucket: skipped_total, skipped_run, updates, and of the last step nonfinite, grad_norm = gscale * sqrt(sum g^2) and max_abs over the
+        finite gradient values}.  Synchronises; nothing else reads the health records from the host."""
+        if not self.guard:
+            raise ValueError('%s was built without guard=True: there is nothing to report' % self.__class__.name)
+        from . import ops
+        gscale = 1.0 / float(getattr(self, 'world_size', 1))
+        out = {}
+        for which, health in self._guard_health.items():
+            h = ops.read_guard_health(health)
+            out[which] = dict(skipped_total=h['skipped_total'], skipped_run=h['skipped_run'], updates=h['updates'], nonfinite=h['nonfinite'],
+                              grad_norm=gscale * float(np.sqrt(h['sumsq'])), max_abs=h['maxabs'])
+        return out
+
     def checkpoint_arrays(self):
         """Everything tf.train.Saver(tf.global_variables()) would hold (reference :74)."""
         return self.store.export_numpy(include_slots=self.is_training)
 
-    def save_checkpoint(self, sess, step, fmt=None):
+    def save_checkpoint(self, sess, step, fmt=None, keep=None):
         """reference :77-81 -> <log_dir>/<name>/model.ckpt-<step>.  ``fmt`` (or $KPX_CKPT_FORMAT): 'npz' (default, one file) or
-        'tf' = a TensorFlow V2 bundle (.index + .data-00000-of-00001 + ``checkpoint``) that tf.train.Saver can restore."""
+        'tf' = a TensorFlow V2 bundle (.index + .data-00000-of-00001 + ``checkpoint``) that tf.train.Saver can restore.  Either container is
+        written under a temporary name in the same directory and renamed into place: a write that fails or is killed leaves the checkpoint
+        before it the newest one latest_checkpoint finds.  ``keep``: after the save, prune_checkpoints(keep)."""
         fmt = fmt or os.environ.get('KPX_CKPT_FORMAT', 'npz')
         if fmt not in ('npz', 'tf', 'bundle'):           # ('bundle' = 'tf'; anything else is a typo that must not silently write the other container)
             raise ValueError("checkpoint format %r: expected 'npz', 'tf' or 'bundle' (KPX_CKPT_FORMAT / --ckpt-format)" % (fmt,))
@@ -81,9 +148,141 @@ class BaseModel(ABC):
         if fmt in ('tf', 'bundle'):
             from . import tf_bundle
             tf_bundle.write_bundle(prefix, self.checkpoint_arrays())
-            return prefix
-        np.savez(prefix + '.npz', **{k.replace('/', '|'): v for k, v in self.checkpoint_arrays().items()})
-        return prefix + '.npz'
+            path = prefix
+        else:
+            path = prefix + '.npz'
+            tmp = path + TMP_SUFFIX
+            try:
+                with open(tmp, 'wb') as f:
+                    np.savez(f, **{k.replace('/', '|'): v for k, v in self.checkpoint_arrays().items()})
+                    f.flush()
+                    os.fsync(f.fileno())
+                os.replace(tmp, path)
+            except BaseException:
+                if osp.exists(tmp):
+                    os.remove(tmp)
+                raise
+        if keep is not None:
+            self.prune_checkpoints(keep)
+        return path
+
+    # ---- finding, pruning and resuming ----------------------------------------------------------------------------------------------
+    @classmethod
+    def list_checkpoints(cls, log_dir):
+        """[(step, path, container)] of the COMPLETE checkpoints under <log_dir>/<name>/, ascending by step (numpy and the standard library
+        only).  An .npz is complete when it opens as a zip archive and lists global_step; a bundle when its .index parses and its data file
+        has the length the index implies (tf_bundle.bundle_complete).  Anything else -- temporary files of a write in progress, truncated
+        files, other models' files -- is neither listed nor touched."""
+        import zipfile
+        from . import tf_bundle
+        directory = osp.join(str(log_dir), cls.name)
+        if not osp.isdir(directory):
+            return []
+        found = []
+        for f in sorted(os.listdir(directory)):
+            m = _CKPT_FILE.match(f)
+            if m is None:
+                continue
+            step, path = int(m.group(1)), osp.join(directory, f)
+            if m.group(2) == 'npz':
+                try:
+                    with zipfile.ZipFile(path) as z:
+                        whole = 'global_step.npy' in z.namelist()
+                except (OSError, zipfile.BadZipFile):
+                    whole = False
+                if whole:
+                    found.append((step, path, 'npz'))
+            elif tf_bundle.bundle_complete(path[:-len('.index')]):
+                found.append((step, path[:-len('.index')], 'tf'))
+        return sorted(found)
+
+    @classmethod
+    def latest_checkpoint(cls, log_dir):
+        """(path, step) of the complete checkpoint with the highest step under <log_dir>/<name>/, in either container, or None."""
+        found = cls.list_checkpoints(log_dir)
+        return (found[-1][1], found[-1][0]) if found else None
+
+    def rng_state_path(self, step, rank, directory=None):
+        return osp.join(directory or osp.join(self.log_dir, self.__class__.name), 'model.ckpt-%d.rng-%d.npz' % (step, rank))
+
+    def prune_checkpoints(self, keep):
+        """Delete this model's complete checkpoints beyond the newest ``keep`` (by step, either container) with their generator-state side
+        files, and list the surviving bundles in the ``checkpoint`` state file if there is one.  Only what list_checkpoints recognises as a
+        whole checkpoint of this model is ever deleted.  -> the paths deleted."""
+        from . import tf_bundle
+        if int(keep) < 1:
+            raise ValueError('keep must be at least 1 (got %r)' % (keep,))
+        directory = osp.join(self.log_dir, self.__class__.name)
+        found = self.list_checkpoints(self.log_dir)
+        steps = sorted({step for step, _, _ in found})
+        doomed = set(steps[:-int(keep)])
+        removed = []
+        for step, path, container in found:
+            if step not in doomed:
+                continue
+            files = [path] if container == 'npz' else [path + '.index', path + '.data-00000-of-00001']     # the index first: no longer a checkpoint
+            files += [osp.join(directory, f) for f in sorted(os.listdir(directory)) if _RNG_FILE.match(f) and int(_RNG_FILE.match(f).group(1)) == step]
+            for f in files:
+                if osp.exists(f):
+                    os.remove(f)
+                    removed.append(f)
+        bundles = [osp.basename(path) for step, path, container in found if container == 'tf' and step not in doomed]
+        if doomed and bundles and osp.exists(osp.join(directory, 'checkpoint')):
+            tf_bundle.write_checkpoint_state(directory, bundles)
+        return removed
+
+    def trainable_names(self):
+        return [n for n, (shape, kind) in self.store.specs.items() if self.store.is_trainable(kind)]
+
+    def resume(self, sess, checkpoint_path):
+        """train.py --resume: restore() made strict.  Every trainable variable of the model must be in the checkpoint with the model's
+        shape (the fused translator head counts through its two reference variables); otherwise nothing is restored and the exception names
+        the variables.  -> (restored global_step, variables restored, Adam slots restored)."""
+        arrays = self.read_checkpoint(checkpoint_path)
+        bad = []
+        for name in self.trainable_names():
+            want = tuple(self.store.vars[name].shape)
+            if '_0+1/' in name:
+                parts = [(name.replace('_0+1/', '_0/'), want[:-1] + (3,)), (name.replace('_0+1/', '_1/'), want[:-1] + (want[-1] - 3,))]
+            else:
+                parts = [(name, want)]
+            for n, shape in parts:
+                if n not in arrays:
+                    bad.append('%s: missing' % n)
+                elif tuple(arrays[n].shape) != shape:
+                    bad.append('%s: checkpoint %s, model %s' % (n, tuple(arrays[n].shape), shape))
+        if bad:
+            raise Exception('cannot resume %s from %s: %d trainable variable(s) do not match: %s'
+                            % (self.__class__.name, checkpoint_path, len(bad), '; '.join(bad)))
+        self.store.load_numpy(arrays, strict=False)
+        self._restore_extra(arrays)
+        n_vars = sum(1 for n in arrays if not n.endswith(('/Adam', '/Adam_1')) and n not in _COUNTERS)
+        n_slots = sum(1 for n in arrays if n.endswith(('/Adam', '/Adam_1')))
+        return int(getattr(self, 'global_step', 0)), n_vars, n_slots
+
+    def save_rng_state(self, step, rank):
+        """The torch CPU and device generator states of this rank beside checkpoint ``step`` (model.ckpt-<step>.rng-<rank>.npz): what a
+        model that draws on the device (stage 2's eps_D / eps_G) needs to continue its noise stream bit for bit."""
+        path = self.rng_state_path(step, rank)
+        state = {'cpu': torch.get_rng_state().numpy()}
+        if self.device.type == 'cuda':
+            state['device'] = torch.cuda.get_rng_state(self.device).numpy()
+        with open(path + TMP_SUFFIX, 'wb') as f:
+            np.savez(f, **state)
+        os.replace(path + TMP_SUFFIX, path)
+        return path
+
+    def load_rng_state(self, step, rank, directory=None):
+        """-> True when this rank's side file of checkpoint ``step`` was there (in ``directory``, by default this model's checkpoint
+        directory) and the generators continue from it."""
+        path = self.rng_state_path(step, rank, directory)
+        if not osp.exists(path):
+            return False
+        with np.load(path) as data:
+            torch.set_rng_state(torch.from_numpy(data['cpu'].copy()))
+            if 'device' in data.files and self.device.type == 'cuda':
+                torch.cuda.set_rng_state(torch.from_numpy(data['device'].copy()), self.device)
+        return True
 
     def restore(self, sess, checkpoint_path):
         """reference :83-91: restore the intersection of checkpoint variables and model variables, by name.  Accepts the .npz

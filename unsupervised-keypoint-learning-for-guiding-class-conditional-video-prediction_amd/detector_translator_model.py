@@ -71,8 +71,9 @@ class DetectorTranslatorModel(BaseModel):
     name = 'detector_translator'       # reference :15 (checkpoint sub-directory)
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', vgg=None, process_group=None,
-                 image_size=128, seed=1234, colors_seed=0):
+                 image_size=128, seed=1234, colors_seed=0, guard=False):
         super(DetectorTranslatorModel, self).__init__(is_training)
+        self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None      # reference :24-27
         self.batch_size = train_config['batch_size']
@@ -119,8 +120,11 @@ class DetectorTranslatorModel(BaseModel):
         with variables.as_default(self.store):
             self._define_forward_pass(Sym(b, r, r, 3), Sym(b, r, r, 3))
             networks.img_discr(Sym(b, r, r, 3))
-        self.store.materialise()
+        self.store.materialise(guard=self.guard)
         dev = self.device
+        self._guard_init(('D', 'G'))
+        if self.guard and dev.type == 'cuda':
+            self._ensure_alpha_dev()        # the guarded update reads its step size from device memory in every form of the step
         if dev.type == 'cuda':
             self._e0 = torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32, device=dev)
             self._one = torch.ones(1, dtype=torch.float32, device=dev)
@@ -242,7 +246,13 @@ class DetectorTranslatorModel(BaseModel):
             pending.wait()                      # stream-level wait for the asynchronous all-reduce
         elif not exchanged:
             self.exchange_gradients(which)
-        if self._capturing:
+        if self.guard:
+            # the gradient is the exchanged sum here (the bf16 form has widened it back): every rank judges the same values
+            self._guarded_adam(which, None if self._capturing else self._adam_alpha(which, lr), alpha_dev=self._alpha_dev[which],
+                               gscale=1.0 / self.world_size)
+            if not self._capturing:
+                self._advance_beta_powers(which)
+        elif self._capturing:
             # a captured launch replays with frozen arguments: the step size lives in device memory and is refreshed before each replay
             ops.adam_tf_flat_dev_alpha_(bucket.params, bucket.grads, bucket.m, bucket.v, self._alpha_dev[which], self.beta1, self.beta2,
                                         self.adam_eps, gscale=1.0 / self.world_size)
@@ -251,6 +261,10 @@ class DetectorTranslatorModel(BaseModel):
                               gscale=1.0 / self.world_size)
             self._advance_beta_powers(which)
         self.store.touch(which)                 # the filters changed: their Winograd forms are re-derived before the next use
+
+    def _ensure_alpha_dev(self):
+        if self._alpha_dev is None:
+            self._alpha_dev = {w: torch.zeros(1, dtype=torch.float32, device=self.device) for w in ('D', 'G')}
 
     def _adam_alpha(self, which, lr):
         """lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t) in fp32, like tf.train.AdamOptimizer._prepare / _apply_dense."""
@@ -349,8 +363,7 @@ class DetectorTranslatorModel(BaseModel):
     def _capture_step(self, key, im, fut):
         self._quiesce_collectives()
         dev = self.device
-        if self._alpha_dev is None:
-            self._alpha_dev = {w: torch.zeros(1, dtype=torch.float32, device=dev) for w in ('D', 'G')}
+        self._ensure_alpha_dev()
         static = {'image': torch.empty_like(im, memory_format=torch.contiguous_format),
                   'future_image': torch.empty_like(fut, memory_format=torch.contiguous_format)}
         saved = (dict(self.beta_power), self.global_step, self.last)
@@ -418,7 +431,12 @@ class DetectorTranslatorModel(BaseModel):
 
         def adam(which):
             bucket = self.store.buckets[which]
-            if device_alpha:
+            if self.guard:
+                self._guarded_adam(which, None if device_alpha else self._adam_alpha(which, lr), alpha_dev=self._alpha_dev[which],
+                                   gscale=1.0 / self.world_size)
+                if not device_alpha:
+                    self._advance_beta_powers(which)
+            elif device_alpha:
                 ops.adam_tf_flat_dev_alpha_(bucket.params, bucket.grads, bucket.m, bucket.v, self._alpha_dev[which], self.beta1, self.beta2,
                                             self.adam_eps, gscale=1.0 / self.world_size)
             else:
@@ -429,6 +447,7 @@ class DetectorTranslatorModel(BaseModel):
 
         with variables.as_default(self.store):
             # ---- A
+            self._guard_shadow_moving()
             fwd = self._define_forward_pass(im, future_im)
             final = fwd['final_output']
             final_d = final.detach()
@@ -520,8 +539,7 @@ class DetectorTranslatorModel(BaseModel):
         collective is issued; the first real execution is the first replay."""
         self._quiesce_collectives()
         dev = self.device
-        if self._alpha_dev is None:
-            self._alpha_dev = {w: torch.zeros(1, dtype=torch.float32, device=dev) for w in ('D', 'G')}
+        self._ensure_alpha_dev()
         static = {'image': torch.empty_like(im, memory_format=torch.contiguous_format),
                   'future_image': torch.empty_like(fut, memory_format=torch.contiguous_format)}
         saved = (dict(self.beta_power), self.global_step, self.last)
@@ -587,6 +605,7 @@ class DetectorTranslatorModel(BaseModel):
         separate = 'image_G' in feed_dict
         lr = self.current_lr()
         with variables.as_default(self.store):
+            self._guard_shadow_moving()             # (guard only) the moving statistics as they stand, before any forward overwrites them
             # ---- D run (:93)
             if separate:
                 with torch.no_grad():

@@ -25,10 +25,12 @@ N_FUTURE_FRAMES = 32       # reference :9
 
 class MotionGeneratorModel(BaseModel):
     name = 'motion_generator'          # reference :16 (checkpoint sub-directory)
+    draws_on_device = True             # eps_D / eps_G come from torch's device generator: checkpoints carry its state in a side file
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777,
-                 discr_cells=(1024, 1024), colors_seed=0):
+                 discr_cells=(1024, 1024), colors_seed=0, guard=False):
         super(MotionGeneratorModel, self).__init__(is_training)
+        self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
         self.batch_size = train_config['batch_size']
@@ -57,7 +59,8 @@ class MotionGeneratorModel(BaseModel):
             networks.vae_encoder(Sym(b, N_FUTURE_FRAMES, k2), Sym(b, k2), Sym(b, self.n_action), self.cell_info, self.vae_dim)
             networks.vae_decoder(Sym(b, self.vae_dim), Sym(b, k2), Sym(b, self.n_action), self.cell_info, self.vae_dim, self.n_points)
             networks.seq_discr(Sym(b, N_FUTURE_FRAMES, k2), self.discr_cells)
-        self.store.materialise()
+        self.store.materialise(guard=self.guard)
+        self._guard_init(('D', 'G'))
         if self.device.type == 'cuda':
             self._e0 = torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32, device=self.device)
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
@@ -106,8 +109,11 @@ class MotionGeneratorModel(BaseModel):
             torch.distributed.all_reduce(bucket.grads, op=torch.distributed.ReduceOp.SUM, group=self.process_group)
         b1p, b2p = self.beta_power[which]
         alpha = np.float32(np.float32(lr) * np.sqrt(np.float32(1) - b2p) / (np.float32(1) - b1p))
-        ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha, self.beta1, self.beta2, self.adam_eps,
-                          gscale=1.0 / self.world_size)
+        if self.guard:                               # (after the exchange: every rank judges the same summed gradient)
+            self._guarded_adam(which, alpha, gscale=1.0 / self.world_size)
+        else:
+            ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha, self.beta1, self.beta2, self.adam_eps,
+                              gscale=1.0 / self.world_size)
         self.store.touch()
         self.beta_power[which] = [np.float32(b1p * self.beta1), np.float32(b2p * self.beta2)]
 
@@ -223,3 +229,10 @@ class MotionGeneratorModel(BaseModel):
         for which, suffix in (('D', ''), ('G', '_1')):
             if 'beta1_power' + suffix in arrays:
                 self.beta_power[which] = [np.float32(arrays['beta1_power' + suffix]), np.float32(arrays['beta2_power' + suffix])]
+        if self.is_training:                 # the Adam slots, as the other two training models restore theirs: training continues bit for bit
+            with torch.no_grad():
+                for b in self.store.buckets.values():
+                    for name in b.entries:
+                        for slot, flat in (('/Adam', b.m), ('/Adam_1', b.v)):
+                            if name + slot in arrays:
+                                b.view(flat, name).copy_(torch.from_numpy(np.ascontiguousarray(arrays[name + slot], np.float32)).to(flat.device))

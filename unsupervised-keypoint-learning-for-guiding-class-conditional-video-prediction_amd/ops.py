@@ -2268,6 +2268,80 @@ def adam_tf_flat_dev_alpha_(p, g, m, v, alpha_dev, beta1, beta2, eps, gscale=1.0
                                              float(beta1), float(beta2), float(eps), float(gscale), _stream()), 'kpx_adam_tf_flat_dev_alpha_f32')
 
 
+# ----------------------------------------------------------------------------------------------- step guard (train.py --guard)
+GUARD_HEALTH_BYTES = 32          # sizeof(KpxGuardHealth), include/kpx.h
+
+
+def new_guard_health(device):
+    """One zeroed KpxGuardHealth record in device memory (an int64 [4] tensor: 32 bytes, 8-byte aligned)."""
+    return torch.zeros(GUARD_HEALTH_BYTES // 8, dtype=torch.int64, device=device)
+
+
+def grad_health_workspace(n, device):
+    """The workspace one health pass over n floats needs (fp64 elements: 8-byte aligned)."""
+    return torch.empty(max(int(lib.kpx_grad_health_workspace_bytes(int(n))) // 8, 1), dtype=torch.float64, device=device)
+
+
+def _require_flat_f32(what, t, n=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(t, 'device', type(t)))
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0 or (n is not None and t.numel() != n):
+        raise _lib.KpxError('%s must be a contiguous non-empty fp32 tensor%s (got %s %s)'
+                            % (what, '' if n is None else ' of %d elements' % n, t.dtype, tuple(t.shape)))
+
+
+def _require_health(what, health, dev):
+    if not isinstance(health, torch.Tensor) or not health.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(health, 'device', type(health)))
+    if health.dtype != torch.int64 or not health.is_contiguous() or health.numel() * 8 != GUARD_HEALTH_BYTES or health.device != dev:
+        raise _lib.KpxError('%s: health must be the int64 [4] record of ops.new_guard_health on %s (got %s %s on %s)'
+                            % (what, dev, health.dtype, tuple(health.shape), health.device))
+
+
+def grad_health(g, health, work=None):
+    """Count the NaN / Inf values of the flat gradient ``g`` and sum the squares (fp64) and the largest magnitude of the finite ones into the
+    device record ``health`` (kpx_grad_health_f32: two launches, one read of g).  ``work``: grad_health_workspace(g.numel()) or larger."""
+    _require_flat_f32('grad_health: g', g)
+    _require_health('grad_health', health, g.device)
+    need = int(lib.kpx_grad_health_workspace_bytes(g.numel()))
+    if work is None:
+        work = grad_health_workspace(g.numel(), g.device)
+    if (not isinstance(work, torch.Tensor) or not work.is_cuda or work.device != g.device or not work.is_contiguous()
+            or work.numel() * work.element_size() < need or work.data_ptr() % 8):
+        raise _lib.KpxError('grad_health: work must be a contiguous 8-byte aligned tensor of at least %d bytes on %s' % (need, g.device))
+    check(lib.kpx_grad_health_f32(g.data_ptr(), g.numel(), work.data_ptr(), health.data_ptr(), _stream()), 'kpx_grad_health_f32')
+    return health
+
+
+def adam_tf_flat_guarded_(p, g, m, v, alpha_dev, beta1, beta2, eps, health, gscale=1.0):
+    """adam_tf_flat_dev_alpha_ when ``health`` counts no non-finite gradient value (bit for bit), nothing otherwise; the record's counters
+    are advanced either way."""
+    _require_flat_f32('adam_tf_flat_guarded_: p', p)
+    for name, t in (('g', g), ('m', m), ('v', v)):
+        _require_flat_f32('adam_tf_flat_guarded_: ' + name, t, p.numel())
+    _require_flat_f32('adam_tf_flat_guarded_: alpha_dev', alpha_dev, 1)
+    _require_health('adam_tf_flat_guarded_', health, p.device)
+    check(lib.kpx_adam_tf_flat_guarded_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), alpha_dev.data_ptr(),
+                                           float(beta1), float(beta2), float(eps), float(gscale), health.data_ptr(), _stream()),
+          'kpx_adam_tf_flat_guarded_f32')
+
+
+def guard_restore_(dst, src, health):
+    """dst = src (bit for bit) when ``health`` counts a non-finite gradient value, nothing otherwise."""
+    _require_flat_f32('guard_restore_: dst', dst)
+    _require_flat_f32('guard_restore_: src', src, dst.numel())
+    _require_health('guard_restore_', health, dst.device)
+    check(lib.kpx_guard_restore_f32(dst.data_ptr(), src.data_ptr(), dst.numel(), health.data_ptr(), _stream()), 'kpx_guard_restore_f32')
+
+
+def read_guard_health(health):
+    """Host copy of a KpxGuardHealth record (synchronises)."""
+    import struct
+    raw = health.cpu().numpy().tobytes()
+    nonfinite, skipped_total, skipped_run, updates, sumsq, maxabs, _ = struct.unpack('<IIIIdff', raw)
+    return dict(nonfinite=nonfinite, skipped_total=skipped_total, skipped_run=skipped_run, updates=updates, sumsq=sumsq, maxabs=maxabs)
+
+
 # ----------------------------------------------------------------------------------------------- rollout (forward only)
 def dense(x, w, b, act=ACT_NONE):
     """act(x @ w + b) for x [B,In], w [In,Out]: a 1x1 convolution over a [B,1,1,In] tensor on the implicit-GEMM kernel

@@ -180,12 +180,14 @@ def read_events(path):
 
 
 def scalars(path):
-    """{tag: [(step, value), ...]} of every scalar in an event file."""
+    """{tag: [(step, value), ...]} of every scalar in an event file, or -- given a directory -- in all its event files, oldest first
+    (a run resumed with train.py --resume opens new files beside those of the runs before it)."""
     out = {}
-    for e in read_events(path):
-        for v in e['values']:
-            if 'simple_value' in v:
-                out.setdefault(v['tag'], []).append((e['step'], v['simple_value']))
+    for p in (event_files(path) if os.path.isdir(path) else [path]):
+        for e in read_events(p):
+            for v in e['values']:
+                if 'simple_value' in v:
+                    out.setdefault(v['tag'], []).append((e['step'], v['simple_value']))
     return out
 
 

@@ -254,25 +254,80 @@ def read_table(path):
 
 
 # ------------------------------------------------------------------------------------------------ bundles
+TMP_SUFFIX = '.tmp'               # files being written carry it until they are renamed into place; no reader looks at such a name
+
+
+def _replace(tmp, final):
+    os.replace(tmp, final)
+
+
+def write_checkpoint_state(directory, names):
+    """The ``checkpoint`` text file (CheckpointState proto) of ``directory``: the last of ``names`` is the newest checkpoint.  Written
+    under a temporary name and renamed into place."""
+    path = os.path.join(directory, 'checkpoint')
+    with open(path + TMP_SUFFIX, 'w') as f:
+        f.write('model_checkpoint_path: "%s"\n' % names[-1] + ''.join('all_model_checkpoint_paths: "%s"\n' % n for n in names))
+        f.flush()
+        os.fsync(f.fileno())
+    _replace(path + TMP_SUFFIX, path)
+
+
 def write_bundle(prefix, arrays):
-    """arrays: {variable name: numpy array}.  Writes <prefix>.index, <prefix>.data-00000-of-00001 and the ``checkpoint`` state file."""
-    os.makedirs(os.path.dirname(os.path.abspath(prefix)) or '.', exist_ok=True)
+    """arrays: {variable name: numpy array}.  Writes <prefix>.index, <prefix>.data-00000-of-00001 and the ``checkpoint`` state file.
+    Every file is written under a temporary name in the same directory and renamed into place -- the data file first, the index and the
+    state file last --, so a write that fails or is killed leaves no file under a final name that bundle_complete would accept, and the
+    checkpoint before it stays the newest."""
+    directory = os.path.dirname(os.path.abspath(prefix))
+    os.makedirs(directory or '.', exist_ok=True)
+    data, index = prefix + '.data-00000-of-00001', prefix + '.index'
     items, offset = [(b'', encode_header())], 0
-    with open(prefix + '.data-00000-of-00001', 'wb') as f:
-        for name in sorted(arrays):                       # BundleWriter keeps a sorted map; data follows the same order
-            a = np.asarray(arrays[name])               # (ascontiguousarray would turn a scalar into shape [1])
-            if a.dtype.byteorder == '>':
-                a = a.astype(a.dtype.newbyteorder('<'))
-            if a.dtype not in DTYPE_IDS:
-                raise ValueError('variable %s: dtype %s has no TensorFlow bundle mapping here' % (name, a.dtype))
-            raw = a.tobytes()                          # C order
-            f.write(raw)
-            items.append((name.encode(), encode_entry(DTYPE_IDS[a.dtype], a.shape, offset, len(raw), mask_crc(crc32c(raw)))))
-            offset += len(raw)
-    write_table(prefix + '.index', items)
-    with open(os.path.join(os.path.dirname(os.path.abspath(prefix)), 'checkpoint'), 'w') as f:      # CheckpointState text proto
-        base = os.path.basename(prefix)
-        f.write('model_checkpoint_path: "%s"\nall_model_checkpoint_paths: "%s"\n' % (base, base))
+    try:
+        with open(data + TMP_SUFFIX, 'wb') as f:
+            for name in sorted(arrays):                       # BundleWriter keeps a sorted map; data follows the same order
+                a = np.asarray(arrays[name])               # (ascontiguousarray would turn a scalar into shape [1])
+                if a.dtype.byteorder == '>':
+                    a = a.astype(a.dtype.newbyteorder('<'))
+                if a.dtype not in DTYPE_IDS:
+                    raise ValueError('variable %s: dtype %s has no TensorFlow bundle mapping here' % (name, a.dtype))
+                raw = a.tobytes()                          # C order
+                f.write(raw)
+                items.append((name.encode(), encode_entry(DTYPE_IDS[a.dtype], a.shape, offset, len(raw), mask_crc(crc32c(raw)))))
+                offset += len(raw)
+            f.flush()
+            os.fsync(f.fileno())
+        write_table(index + TMP_SUFFIX, items)
+        _replace(data + TMP_SUFFIX, data)
+        _replace(index + TMP_SUFFIX, index)
+    except BaseException:
+        for tmp in (data + TMP_SUFFIX, index + TMP_SUFFIX):
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        raise
+    write_checkpoint_state(directory, [os.path.basename(prefix)])
+
+
+def bundle_complete(prefix):
+    """True when <prefix>.index parses as a bundle index (every block checksum included) and the data file has exactly the length its
+    entries imply.  The tensors' own checksums are left to read_bundle: this is the cheap question `is this checkpoint whole`."""
+    try:
+        items = read_table(prefix + '.index')
+        if not items or items[0][0] != b'':
+            return False
+        num_shards = 1
+        for field, _, v in _pb_fields(items[0][1]):
+            if field == 1:
+                num_shards = v
+        if num_shards != 1:
+            return False
+        end = 0
+        for _, value in items[1:]:
+            e = decode_entry(value)
+            if e['shard_id'] != 0:
+                return False
+            end = max(end, e['offset'] + e['size'])
+        return os.path.getsize(prefix + '.data-00000-of-00001') == end
+    except (OSError, ValueError, IndexError, struct.error):
+        return False
 
 
 def is_bundle(prefix):

@@ -119,13 +119,28 @@ class VariableStore:
     def is_trainable(kind):
         return not kind.startswith('moving')
 
-    def materialise(self):
-        """Allocate the buckets on the device and turn every variable into a view of them."""
+    def materialise(self, guard=False):
+        """Allocate the buckets on the device and turn every variable into a view of them.  ``guard`` (the step guard of the training
+        models): the NON-trainable variables -- batch-norm moving statistics -- are laid into one flat buffer per owner bucket as well (the
+        same 'discr' rule, every view 16-byte aligned), each with a shadow of the same size that the step copies them into before the
+        forward and restores them from when the owner's update is skipped (self.moving / self.moving_shadow).  Without it they are
+        separate tensors, as ever."""
         for name, (shape, kind) in self.specs.items():
             if self.is_trainable(kind):
                 self.buckets['D' if 'discr' in name else 'G'].add(name, shape)   # reference :191-192 ('discr' in var.name: img_discr, seq_discr)
         for b in self.buckets.values():
             b.allocate(self.device)
+        self.moving, self.moving_shadow, moving_layout = {}, {}, {}
+        if guard:
+            layouts = OrderedDict((k, Bucket(k)) for k in self.buckets)
+            for name, (shape, kind) in self.specs.items():
+                if not self.is_trainable(kind):
+                    layouts['D' if 'discr' in name else 'G'].add(name, shape)
+            for k, lay in layouts.items():
+                if lay.size:
+                    self.moving[k] = torch.zeros(lay.size, dtype=torch.float32, device=self.device)
+                    self.moving_shadow[k] = torch.zeros(lay.size, dtype=torch.float32, device=self.device)
+                    moving_layout[k] = lay
         for name, (shape, kind) in self.specs.items():
             val = torch.from_numpy(self.init_values[name])
             if self.is_trainable(kind):
@@ -135,6 +150,11 @@ class VariableStore:
                 v.requires_grad_(True)
                 self.vars[name] = v
                 self.grad_views[name] = b.view(b.grads, name)
+            elif guard:
+                k = 'D' if 'discr' in name else 'G'
+                v = moving_layout[k].view(self.moving[k], name)
+                v.copy_(val)
+                self.vars[name] = v
             else:
                 self.vars[name] = val.to(self.device)
         self.init_values.clear()
