@@ -81,6 +81,8 @@ def main(argv=None):
     parser.add_argument('--png', action='store_true', help='also the frames of every rollout as PNGs')
     parser.add_argument('--batch', type=int, default=8)
     parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette')
+    parser.add_argument('--ema', action='store_true',
+                        help="read every checkpoint given under its averaged weights (train.py --ema: the <name>/ExponentialMovingAverage entries take their variables' places); a checkpoint without them is refused")
     parser.add_argument('--save_dir', type=str, default='results/animate')
     args = parser.parse_args(argv)
 
@@ -156,7 +158,7 @@ def main(argv=None):
     model = kpx_amd.FinalModel(config, device=dev, point_maps=True, colors_seed=args.colors_seed)
     model.build(None)
     for p in checkpoints:
-        model.restore(None, p)
+        model.restore(None, p, **({'ema': True} if args.ema else {}))
     k, radius = model.n_points, args.overlay
     if radius and k > ops.CELL_MAX_POINTS:
         raise Exception('--overlay marks at most %d key points (the model has %d)' % (ops.CELL_MAX_POINTS, k))

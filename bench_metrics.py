@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif | --animate | --guard]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif | --animate | --guard | --ema]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -105,6 +105,15 @@
    (health 4n read; Adam 16n read + 12n written; copy and restore 4n + 4n) and the rate as a fraction of the copy's.
 23. The configs[1] train step (128x128, K = 15, B = 32, replayed HIP graph) through the model API with guard off and on, two models in one
    process, alternated in blocks; median ms per step of each and the difference in ms and %.
+
+``--ema`` measures the averaged generator (train.py --ema) instead:
+
+24. kpx_ema_flat_f32 (without a health record and with a clean one) and kpx_swap_flat_f32 on the 'G' bucket of the configs[1] model (its real
+   size, read from a built model), beside a device copy of the same number of floats in the same process; device-event time of each call
+   after warm-up, median us, bytes/s of what each moves (the average 8n read + 4n written; the swap 8n + 8n; the copy 4n + 4n) and the rate
+   as a fraction of the copy's.
+25. The configs[1] train step through the model API with ema off and on (ema=0.999), two models in one process, alternated in blocks; median
+   ms per step of each and the difference in ms and %.
 
 Prints one JSON line.
 """
@@ -1110,12 +1119,12 @@ def animate_stills_leg(dev, rollouts):
             'device_ms_all': [round(v, 1) for v in ms['device']], 'on_ms_all': [round(v, 1) for v in ms['on']]}
 
 
-def _c1_model(dev, guard):
+def _c1_model(dev, guard, **kw):
     import kpx_amd
     cfg = {'training': {'lr': {'start_val': 1e-4, 'step': 20000, 'decay': 0.95}, 'batch_size': 32},
            'model': {'n_pts': 15}, 'paths': {'log_dir': '/tmp/kpx_bench', 'vggnet': None}}
     vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(seed=19), device=dev)
-    model = kpx_amd.DetectorTranslatorModel(cfg, device=dev, vgg=vgg, image_size=RES, **({'guard': True} if guard else {}))
+    model = kpx_amd.DetectorTranslatorModel(cfg, device=dev, vgg=vgg, image_size=RES, **({'guard': True} if guard else {}), **kw)
     model.build()
     return model
 
@@ -1178,6 +1187,50 @@ def guard_step_leg(dev, steps):
             'skipped': {k: r['skipped_total'] for k, r in rep.items()}}, {k: b.grads.numel() for k, b in models['on'].store.buckets.items()}
 
 
+def ema_kernel_leg(dev, launches, n):
+    from kpx_amd import ops
+    p, e, dst = torch.randn(n, device=dev), torch.randn(n, device=dev), torch.empty(n, device=dev)
+    rate, clean = torch.full((1,), 1e-3, device=dev), ops.new_guard_health(dev)
+    legs = (('device_copy', lambda: dst.copy_(p), 8 * n),
+            ('ema_flat', lambda: ops.ema_flat_(e, p, rate), 12 * n),
+            ('ema_flat_clean_health', lambda: ops.ema_flat_(e, p, rate, clean), 12 * n),
+            ('swap_flat', lambda: ops.swap_flat_(e, dst), 16 * n))
+    out = {'floats': n, 'mb': round(4 * n / 1e6, 1)}
+    for name, fn, moved in legs:
+        us = _event_times(fn, launches, dev)
+        med = statistics.median(us)
+        out[name] = {'launches': launches, 'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                     'gb_per_s': round(moved / (med * 1e-6) / 1e9, 1)}
+    for name in ('ema_flat', 'ema_flat_clean_health', 'swap_flat'):
+        out[name]['fraction_of_copy_rate'] = round(out[name]['gb_per_s'] / out['device_copy']['gb_per_s'], 3)
+    return {'G': out}
+
+
+def ema_step_leg(dev, steps):
+    """The configs[1] train step with ema off and on: two models, blocks of ``steps`` replayed steps each, alternated three times."""
+    from kpx_amd.synthetic import synthetic_pair
+    models = {'off': _c1_model(dev, False), 'on': _c1_model(dev, False, ema=0.999)}
+    feed = {k: torch.from_numpy(v).to(dev) for k, v in synthetic_pair(32, res=RES, seed0=0, seed1=1).items()}
+    for m in models.values():
+        for i in range(4):                                # eager, capture, replays
+            m.train_step(None, feed, i, 32)
+    torch.cuda.synchronize(dev)
+    ms = {k: [] for k in models}
+    for _ in range(3):
+        for k, m in models.items():
+            t0 = time.perf_counter()
+            for i in range(steps):
+                m.train_step(None, feed, 4 + i, 32)
+            torch.cuda.synchronize(dev)
+            ms[k].append((time.perf_counter() - t0) * 1e3 / steps)
+    off, on = statistics.median(ms['off']), statistics.median(ms['on'])
+    return {'batch': 32, 'steps_per_block': steps, 'decay': 0.999,
+            'graph_replay': all(len(m._graphs) == 1 and not m._graph_failed for m in models.values()),
+            'off_ms_per_step': round(off, 3), 'on_ms_per_step': round(on, 3), 'ema_ms_per_step': round(on - off, 3),
+            'ema_percent': round(100.0 * (on - off) / off, 2), 'off_ms_all': [round(v, 3) for v in ms['off']],
+            'on_ms_all': [round(v, 3) for v in ms['on']]}, models['on'].store.buckets['G'].ema.numel()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -1200,7 +1253,18 @@ def main():
     ap.add_argument('--guard', action='store_true',
                     help="measure the step guard (the health pass, the guarded update and the restore on the two real buckets, the configs[1] train "
                          'step with guard off and on) instead')
+    ap.add_argument('--ema', action='store_true',
+                    help="measure the averaged generator (the update and the swap on the real 'G' bucket beside a device copy, the configs[1] "
+                         'train step with ema off and on) instead')
     args = ap.parse_args()
+    if args.ema:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        step, n = ema_step_leg(dev, max(args.rollouts, 10))
+        torch.cuda.empty_cache()
+        print(json.dumps({'ema_kernels': ema_kernel_leg(dev, args.launches, n), 'ema_step_c1': step}))
+        return
     if args.guard:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

@@ -367,11 +367,11 @@ class _ActionAccuracy:
     """--action-accuracy: the recogniser, its scores per batch (device tensors until the end) and the moments of its features."""
     SETS = ('real_even', 'real_odd', 'pred', 'pred_draw0')
 
-    def __init__(self, kpx_amd, config, checkpoint, dev, samples, actions):
+    def __init__(self, kpx_amd, config, checkpoint, dev, samples, actions, ema=False):
         self.ops, self.F, self.dev, self.samples, self.actions = kpx_amd.ops, kpx_amd.frechet, dev, samples, actions
         self.model = kpx_amd.ActionClassifierModel(config, is_training=False, device=dev)
         self.model.build(None)
-        self.model.restore(None, checkpoint, strict=True)
+        self.model.restore(None, checkpoint, strict=True, **({'ema': True} if ema else {}))
         a, u = self.model.n_action, self.model.cells[-1]
         self.n_action, self.dim = a, u
         zi = lambda: torch.zeros((a, a), dtype=torch.int32, device=dev)
@@ -858,6 +858,10 @@ def main(argv=None):
                              'predicted key points (with --actions: every class rollout against the commanded class) and gives a Frechet '
                              "distance in its feature space.  This project's own key-point-space quantity: not comparable with published "
                              'action-recognition or FVD figures')
+    parser.add_argument('--action-accuracy-ema', action='store_true',
+                        help='with --action-accuracy: read the recogniser under its averaged weights (it was trained with train.py --ema)')
+    parser.add_argument('--ema', action='store_true',
+                        help="read every checkpoint given under its averaged weights (train.py --ema: the <name>/ExponentialMovingAverage entries take their variables' places); a checkpoint without them is refused")
     parser.add_argument('--gif', action='store_true',
                         help='per sample pred.gif (the input image, then the predicted frames of draw 0) and compare.gif (real | pred | '
                              'points side by side), quantised to one palette per GIF on the device; <save_dir>/gif.json')
@@ -915,6 +919,8 @@ def main(argv=None):
     if args.action_accuracy is not None and args.synthetic:
         parser.error('--action-accuracy classifies the pseudo labels of the real frames and the rollouts of their classes, and --synthetic '
                      'inputs have neither')
+    if args.action_accuracy_ema and args.action_accuracy is None:
+        parser.error('--action-accuracy-ema reads the checkpoint of --action-accuracy and needs it')
     if args.action_accuracy is not None and not args.metrics:
         parser.error('--action-accuracy adds to the scores of --metrics and needs it')
     if args.metrics and args.synthetic:
@@ -954,7 +960,7 @@ def main(argv=None):
     print('model initialized')
     model.build(None)
     for p in checkpoints:                                            # reference :76-77: two partial restores by name
-        model.restore(None, p)
+        model.restore(None, p, **({'ema': True} if args.ema else {}))
     n_action = config['model']['n_action']
     gifs = kpx_amd.gif.RolloutGifs(gif_fps, gif_dither) if args.gif else None
     sample_idx, frames, t0 = 0, 0, time.time()
@@ -977,7 +983,7 @@ def main(argv=None):
             motion_scores = {'kp_l2': []} if args.samples < 2 else {'kp_l2': [], 'kp_div': [], 'div_mse': []}
         drive_scores = {m: [] for m in drive_modes if m != 'transfer'} if drive_modes and args.metrics else None
         n_self_driven = 0
-        accuracy = _ActionAccuracy(kpx_amd, config, args.action_accuracy, dev, args.samples, actions) if args.action_accuracy is not None else None
+        accuracy = _ActionAccuracy(kpx_amd, config, args.action_accuracy, dev, args.samples, actions, ema=args.action_accuracy_ema) if args.action_accuracy is not None else None
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
             if args.drive_only:              # the driven rollouts alone: no own rollout, so no draws and nothing of what they write

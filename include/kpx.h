@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 22
+#define KPX_ABI_VERSION 23
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -562,6 +562,18 @@ int kpx_grad_health_f32(const float* g, size_t n, void* work, KpxGuardHealth* he
 int kpx_adam_tf_flat_guarded_f32(float* p, const float* g, float* m, float* v, size_t n, const float* alpha_dev,
                                  float beta1, float beta2, float eps, float gscale, KpxGuardHealth* health, void* stream);
 int kpx_guard_restore_f32(float* dst, const float* src, size_t n, const KpxGuardHealth* health, void* stream);
+
+/* ---- the averaged generator (train.py --ema), DESIGN.md section 4.4: an exponential moving average of a bucket's parameters, kept beside
+ * training and read only for inference.  Both entries: no allocation, copy or synchronisation (capturable); no atomics; the result is a
+ * function of the operands alone.  They return KPX_EINVAL before any device call on a null or misaligned pointer or n == 0.
+ * kpx_ema_flat_f32: ema[i] += (p[i] - ema[i]) * *rate_dev for i < n (tf assign_moving_average with rate = 1 - decay), computed as
+ *   d = p - ema (one rounding), ema = fma(d, rate, ema) (one rounding).  rate_dev is read on the device.  health may be NULL; otherwise the
+ *   launch writes nothing when health->nonfinite != 0 (the guarded update was skipped).  health is only read, p is never written.
+ *   ema, p 16-byte aligned, rate_dev 4-byte, health 8-byte aligned, n >= 1 (sizes beyond 2^31 are fine).
+ * kpx_swap_flat_f32: exchanges a[0:n] and b[0:n] word for word (NaN payloads and -0 survive).  a, b 16-byte aligned, a != b, n >= 1; the
+ *   ranges must not overlap. */
+int kpx_ema_flat_f32(float* ema, const float* p, size_t n, const float* rate_dev, const KpxGuardHealth* health /* may be NULL */, void* stream);
+int kpx_swap_flat_f32(float* a, float* b, size_t n, void* stream);
 
 /* ---- evaluate.py / FinalModel rollout (forward only).  Dense layers run as 1x1 kpx_conv2d_fwd_f32.
  * LSTMCell pointwise part (models/networks/layers.py:17-21): gates [B,4U] = (i,j,f,o) pre-activations. */

@@ -209,6 +209,8 @@ def main(argv=None):
     parser.add_argument('--joints-pck', type=str, default=None, help='PCK thresholds, comma separated, at most 8 in (0, 1] (default 0.05,0.1,0.2)')
     parser.add_argument('--joints-norm', type=str, default=None, choices=('bbox', 'image'), help='PCK normaliser (default bbox)')
     parser.add_argument('--joints-sheets', action='store_true', help='one contact sheet per video for its first frame')
+    parser.add_argument('--ema', action='store_true',
+                        help="read the checkpoint under its averaged weights (train.py --ema: the <name>/ExponentialMovingAverage entries take their variables' places); a checkpoint without them is refused")
     args = parser.parse_args(argv)
     if not args.joints and (args.joints_dir is not None or args.joints_ridge is not None or args.joints_pck is not None
                             or args.joints_norm is not None or args.joints_sheets):
@@ -245,7 +247,7 @@ def main(argv=None):
     model = kpx_amd.KeypointModel(config, device=dev)
     print('model initialized')
     model.build(None)
-    restored = model.restore(None, args.checkpoint)
+    restored = model.restore(None, args.checkpoint, **({'ema': True} if args.ema else {}))
     print('restored %d arrays' % len(restored))
     stab = None
     if args.stability:

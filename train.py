@@ -24,6 +24,10 @@ Long runs, all three modes: ``--resume latest|PATH`` continues from a checkpoint
 its noise generator's state from the side file model.ckpt-N.rng-RANK.npz; ``latest`` = the newest complete checkpoint of the log directory,
 or a start from scratch when there is none), ``--keep N`` prunes older checkpoints after each save, and ``--guard`` skips the update of a
 bucket whose gradient holds a NaN or an Inf, decided on the device inside the step (``--guard-max-skips N`` stops a run that only skips).
+``--ema DECAY`` keeps an exponential moving average of the generator's weights (the 'G' bucket) inside the step, one HIP launch behind the
+generator's Adam update; checkpoints carry the averages as ``<name>/ExponentialMovingAverage``, ``--resume`` continues them, ``--ema-test``
+runs each test pass a second time under them (``<log_dir>/<mode>/test_ema``), and evaluate.py / animate.py / make_pseudo_labels.py ``--ema``
+read a checkpoint under them (``python -m kpx_amd.ema IN OUT`` writes them out as a plain inference checkpoint).
 Checkpoints are written under temporary names and renamed into place.  Real data loaders are reseeded on a resume, not continued sample
 for sample.
 """
@@ -68,6 +72,25 @@ def _get_model_by_mode(mode, config, global_step, **kw):
 def _guard_kw(args):
     """guard=True only under --guard: without the flag the constructors are called exactly as before."""
     return {'guard': True} if args.guard else {}
+
+
+def _ema_kw(args):
+    """ema=DECAY (and ema_warmup=False) only under --ema (--ema-no-warmup), as _guard_kw."""
+    kw = {'ema': args.ema} if args.ema is not None else {}
+    if args.ema is not None and args.ema_no_warmup:
+        kw['ema_warmup'] = False
+    return kw
+
+
+def _test_under_ema(model, test_pass, step):
+    """--ema-test: the test pass once more inside ema_weights(), its summaries and collect_test_results through the third writer."""
+    with model.ema_weights():
+        writer, model.test_writer = model.test_writer, model.test_ema_writer
+        try:
+            log.info('test under the averaged weights (step %d):', step)
+            return model.collect_test_results(test_pass(), step)
+        finally:
+            model.test_writer = writer
 
 
 def _resume_seed(rank, step):
@@ -154,7 +177,7 @@ def _train_motion_generator(args, config, dev, rank, world):
     import kpx_amd
     paths_config, train_config, model_config = config['paths'], config['training'], config['model']
     classifier = args.mode == 'action_classifier'
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed, **_guard_kw(args))
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']
@@ -204,8 +227,12 @@ def _train_motion_generator(args, config, dev, rank, world):
         if step % train_config['checkpoint_interval'] == 0:
             _save(args, model, step, rank)
         if step % train_config['test_interval'] == 0 and rank == 0:
-            feeds = test_feeds(test_batches()) if test_batches is not None else [synthetic(10 ** 6)]
-            model.collect_test_results([model.test_step(None, f, step, i, f['keypoints'].shape[0]) for i, f in enumerate(feeds)], step)
+            def test_pass():
+                feeds = test_feeds(test_batches()) if test_batches is not None else [synthetic(10 ** 6)]
+                return [model.test_step(None, f, step, i, f['keypoints'].shape[0]) for i, f in enumerate(feeds)]
+            model.collect_test_results(test_pass(), step)
+            if args.ema_test:
+                _test_under_ema(model, test_pass, step)
     model.close_loggers()
     if world > 1:
         torch.distributed.destroy_process_group()
@@ -252,7 +279,19 @@ def main(argv=None):
                              'statistics keep their bits) instead of writing it into every parameter; decided on the device, inside the captured step')
     parser.add_argument('--guard-max-skips', type=int, default=100, metavar='N',
                         help='--guard: stop the run when a bucket has skipped N updates in a row at a log point (default 100)')
+    parser.add_argument('--ema', type=float, default=None, metavar='DECAY',
+                        help="keep an exponential moving average of the generator's weights (0 < DECAY < 1, e.g. 0.999), updated on the device "
+                             'inside the step; checkpoints carry it as <name>/ExponentialMovingAverage and --resume continues it')
+    parser.add_argument('--ema-no-warmup', action='store_true',
+                        help='--ema: the rate is 1 - DECAY from the first step (default: 1 - min(DECAY, (1 + step) / (10 + step)))')
+    parser.add_argument('--ema-test', action='store_true',
+                        help='--ema: at each test interval run the test pass a second time under the averaged weights and write it to '
+                             '<log_dir>/<mode>/test_ema')
     args = parser.parse_args(argv)
+    if args.ema is not None and not (0.0 < args.ema < 1.0):
+        parser.error('--ema DECAY: DECAY must lie strictly between 0 and 1 (got %r)' % args.ema)
+    if (args.ema_test or args.ema_no_warmup) and args.ema is None:
+        parser.error('--ema-test and --ema-no-warmup need --ema DECAY')
     if args.keep is not None and args.keep < 1:
         parser.error('--keep N keeps the newest N checkpoints: N must be at least 1')
     if args.guard_max_skips < 1:
@@ -287,7 +326,7 @@ def main(argv=None):
         if not args.synthetic_vgg:
             raise Exception('file of pretrained vgg19 does not exist at: %s (pass --synthetic-vgg for benchmarking)' % paths_config.get('vggnet'))
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev)
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, **_guard_kw(args))
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']          # per process, like the reference's single-device batch
@@ -332,12 +371,14 @@ def main(argv=None):
         if step % train_config['checkpoint_interval'] == 0:
             _save(args, model, step, rank)
         if step % train_config['test_interval'] == 0 and rank == 0:
-            if test_it is not None:                  # reference train.py:97-110: one pass over the test subset
-                results = [model.test_step(None, fd, step, i, fd['image'].shape[0]) for i, fd in enumerate(test_it())]
-            else:
+            def test_pass():
+                if test_it is not None:              # reference train.py:97-110: one pass over the test subset
+                    return [model.test_step(None, fd, step, i, fd['image'].shape[0]) for i, fd in enumerate(test_it())]
                 tp = synthetic_pair(batch_size, res=model.image_size, seed0=10 ** 6, seed1=10 ** 6 + 1)
-                results = [model.test_step(None, {k: torch.from_numpy(v).to(dev) for k, v in tp.items()}, step, 0, batch_size)]
-            model.collect_test_results(results, step)
+                return [model.test_step(None, {k: torch.from_numpy(v).to(dev) for k, v in tp.items()}, step, 0, batch_size)]
+            model.collect_test_results(test_pass(), step)
+            if args.ema_test:
+                _test_under_ema(model, test_pass, step)
     model.close_loggers()
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -24,8 +24,9 @@ DEFAULT_CELLS = (256, 256)      # model.classifier_cells when the config has non
 class ActionClassifierModel(BaseModel):
     name = 'action_classifier'         # checkpoint / summary sub-directory
 
-    def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777, guard=False):
+    def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777, guard=False, ema=None, ema_warmup=True):
         super(ActionClassifierModel, self).__init__(is_training)
+        self._ema_config(ema, ema_warmup)                  # train.py --ema: the averaged weights (BaseModel._ema_*)
         self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
@@ -47,8 +48,9 @@ class ActionClassifierModel(BaseModel):
     def build(self, inputs=None):
         with variables.as_default(self.store):
             networks.seq_classifier(Sym(2, N_FUTURE_FRAMES, self.n_points * 2), self.n_action, self.cells)
-        self.store.materialise(guard=self.guard)     # every variable lands in the 'G' bucket; 'D' stays empty and is never stepped
+        self.store.materialise(guard=self.guard, **({'ema': True} if self.ema is not None else {}))     # every variable lands in the 'G' bucket; 'D' stays empty and is never stepped
         self._guard_init(('G',))
+        self._ema_init()
         if self.device.type == 'cuda':
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
 
@@ -89,6 +91,7 @@ class ActionClassifierModel(BaseModel):
         else:
             ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha, self.beta1, self.beta2, self.adam_eps,
                               gscale=1.0 / self.world_size)
+        self._ema_update('G', self.global_step, self._ema_health('G'))     # (global_step before its increment: the update's index)
         self.store.touch()
         self.beta_power = [np.float32(b1p * self.beta1), np.float32(b2p * self.beta2)]
 
@@ -101,6 +104,7 @@ class ActionClassifierModel(BaseModel):
     # ------------------------------------------------------------------------------------------------ model surface
     def train_step(self, sess, feed_dict, step, batch_size, should_write_log=False, should_write_summary=False):
         """feed_dict: 'real_seq' [B,32,K,2] and 'action_code' [B,A] (the SequenceDataLoader batch; other keys are ignored)."""
+        self._ema_forbid_training()
         start_time = time.time()
         lr = self.current_lr()
         with variables.as_default(self.store):
@@ -111,7 +115,8 @@ class ActionClassifierModel(BaseModel):
         self.global_step += 1
         self.last = dict(loss=loss.detach(), logits=logits.detach(), target=target, lr=float(lr))
         if should_write_summary and self.train_writer is not None:
-            self._write_summaries(self.train_writer, step, self._summaries(self.loss_values()) + [[summary.scalar_value('lr', self.last['lr'])]])
+            self._write_summaries(self.train_writer, step, self._summaries(self.loss_values()) + [[summary.scalar_value('lr', self.last['lr'])]]
+                                  + self._ema_summary())
         if should_write_log:
             v = self.loss_values()
             duration = time.time() - start_time
@@ -156,18 +161,19 @@ class ActionClassifierModel(BaseModel):
             arrays.update({'beta1_power': self.beta_power[0], 'beta2_power': self.beta_power[1]})
         return arrays
 
-    def restore(self, sess, checkpoint_path, strict=False):
+    def restore(self, sess, checkpoint_path, strict=False, ema=False):
         """BaseModel.restore; ``strict`` (evaluate.py --action-accuracy): every seq_classifier variable must be in the checkpoint with this
-        model's shape -- a recogniser trained at another width cannot score anything."""
+        model's shape -- a recogniser trained at another width cannot score anything.  ``ema``: read it under its averages (BaseModel.restore)."""
         if strict:
-            arrays = self.read_checkpoint(checkpoint_path)
+            from .ema import read_selected
+            arrays = read_selected(checkpoint_path) if ema else self.read_checkpoint(checkpoint_path)
             bad = ['%s: %s' % (n, 'missing' if n not in arrays else 'checkpoint %s, model %s' % (tuple(arrays[n].shape), tuple(v.shape)))
                    for n, v in self.store.vars.items() if n not in arrays or tuple(arrays[n].shape) != tuple(v.shape)]
             if bad:
                 raise Exception('%s is not an action_classifier checkpoint for model.classifier_cells = %s, n_pts = %d, n_action = %d '
                                 '(train.py --mode action_classifier writes one; the config must name the cells it was trained with): %s'
                                 % (checkpoint_path, list(self.cells), self.n_points, self.n_action, '; '.join(bad)))
-        return super(ActionClassifierModel, self).restore(sess, checkpoint_path)
+        return super(ActionClassifierModel, self).restore(sess, checkpoint_path, ema=ema)
 
     def _restore_extra(self, arrays):
         if 'global_step' in arrays:

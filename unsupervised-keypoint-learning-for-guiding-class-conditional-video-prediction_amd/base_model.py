@@ -5,6 +5,8 @@ current HIP stream).  Checkpoints keep the reference's location ``<log_dir>/<nam
 names (SURVEY Appendix B), in an ``.npz`` container (default) or as a TensorFlow V2 checkpoint bundle (``tf_bundle.py``, SURVEY 8f-2;
 ``KPX_CKPT_FORMAT=tf``).
 """
+import contextlib
+import logging
 import os
 import re
 from abc import ABC, abstractmethod
@@ -16,6 +18,7 @@ import torch
 TMP_SUFFIX = '.tmp'                # a checkpoint file being written; renamed into place when it is whole (tf_bundle.TMP_SUFFIX)
 _CKPT_FILE = re.compile(r'^model\.ckpt-(\d+)\.(npz|index)$')
 _RNG_FILE = re.compile(r'^model\.ckpt-(\d+)\.rng-(\d+)\.npz$')
+log = logging.getLogger('kpx')
 _COUNTERS = ('global_step', 'beta1_power', 'beta2_power', 'beta1_power_1', 'beta2_power_1')
 
 
@@ -30,6 +33,7 @@ class BaseModel(ABC):
         self.store = None
         self.train_writer = None
         self.test_writer = None
+        self.test_ema_writer = None
 
     @abstractmethod
     def build(self, inputs):
@@ -60,12 +64,14 @@ class BaseModel(ABC):
             self.close_loggers()
             self.train_writer = EventFileWriter(osp.join(log_dir, name, 'train'))
             self.test_writer = EventFileWriter(osp.join(log_dir, name, 'test'))
+            if self.ema is not None:       # train.py --ema-test: the test pass under the averages, <log_dir>/<name>/test_ema
+                self.test_ema_writer = EventFileWriter(osp.join(log_dir, name, 'test_ema'))
 
     def close_loggers(self):
-        for w in (self.train_writer, self.test_writer):
+        for w in (self.train_writer, self.test_writer, self.test_ema_writer):
             if w is not None:
                 w.close()
-        self.train_writer = self.test_writer = None
+        self.train_writer = self.test_writer = self.test_ema_writer = None
 
     def _write_summaries(self, writer, step, summaries):
         """One add_summary per merged summary, in order (the reference's add_summary calls)."""
@@ -131,6 +137,104 @@ class BaseModel(ABC):
             out[which] = dict(skipped_total=h['skipped_total'], skipped_run=h['skipped_run'], updates=h['updates'], nonfinite=h['nonfinite'],
                               grad_norm=gscale * float(np.sqrt(h['sumsq'])), max_abs=h['maxabs'])
         return out
+
+    # ---- the averaged generator (ema=DECAY of the training models, train.py --ema) --------------------------------------------------
+    # Bucket 'G' -- the bucket inference reads in every mode -- keeps an exponential moving average of its parameters in a fifth flat buffer
+    # (Bucket.ema): ema += (p - ema) * rate after every 'G' Adam update, one kpx_ema_flat_f32 launch behind the Adam launch on its stream.
+    # The rate lives in a [1] device float that is refreshed on the host where the Adam step size is (before each eager launch, before each
+    # graph or segment replay, never inside a capture), so the launch is part of the captured step.  With guard=True the launch reads the
+    # bucket's health record and a skipped update is no step for the average either; the schedule's index t = global_step before its
+    # increment advances on a skipped step all the same, as beta powers and global_step do (the warm-up then runs a few steps ahead of the
+    # average, which is harmless).  'D' is never averaged; batch-norm moving statistics are not trainable and are not averaged either:
+    # inference under the averages reads the live ones.
+    ema = None                         # the decay, a float in (0, 1); None: no averages (nothing below allocates or launches anything)
+    ema_warmup = True                  # rate = 1 - min(decay, (1 + t) / (10 + t)), tf.train.ExponentialMovingAverage(decay, num_updates=t)
+    _ema_active = False                # inside ema_weights()
+
+    def _ema_config(self, ema, ema_warmup=True):
+        """Constructor half: check and keep the decay (training models only)."""
+        if ema is not None and self.is_training:
+            if not (isinstance(ema, (int, float, np.floating)) and 0.0 < float(ema) < 1.0):
+                raise ValueError('ema must be a decay with 0 < ema < 1 (got %r)' % (ema,))
+            self.ema, self.ema_warmup = float(ema), bool(ema_warmup)
+
+    def _ema_init(self):
+        """After store.materialise(ema=...): the device float the launches read their rate from."""
+        self._ema_rate_dev = self._ema_last_rate = None
+        if self.ema is not None and self.device.type == 'cuda':
+            self._ema_rate_dev = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    def ema_rate(self, step):
+        """The float32 step of the average at update index ``step`` (ema.rate, the one definition)."""
+        from . import ema
+        return ema.rate(self.ema, step, self.ema_warmup)
+
+    def _ema_refresh(self, step):
+        """The rate of update index ``step`` into the device float (host side: before an eager launch or a replay, never in a capture)."""
+        from . import ops
+        self._ema_last_rate = float(self.ema_rate(step))
+        ops.fill_raw_(self._ema_rate_dev, self._ema_last_rate)
+
+    def _ema_update(self, which, step, health=None):
+        """Behind the Adam launch of bucket ``which``: nothing unless the bucket is averaged.  ``step``: the update's index (global_step
+        before the increment), written into the device float first; None when the caller refreshes it itself (a captured launch, whose
+        arguments are frozen).  ``health``: the bucket's guard record, or None."""
+        bucket = self.store.buckets[which]
+        if self.ema is None or bucket.ema is None:
+            return
+        from . import ops
+        if step is not None:
+            self._ema_refresh(step)
+        ops.ema_flat_(bucket.ema, bucket.params, self._ema_rate_dev, health)
+
+    def _ema_health(self, which):
+        return self._guard_health.get(which) if self.guard else None
+
+    def _ema_summary(self):
+        """The train summaries' one more scalar, ema/rate of the step just taken ([] without ema)."""
+        if self.ema is None or self._ema_last_rate is None:
+            return []
+        from . import summary
+        return [[summary.scalar_value('ema/rate', self._ema_last_rate)]]
+
+    def _ema_forbid_training(self):
+        if self._ema_active:
+            raise RuntimeError('train_step inside ema_weights(): the parameters are the averages there; leave the context first')
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's 'G' variables ARE the averages (and Bucket.ema holds the parameters): one swap launch in place,
+        so no address changes and captured graphs stay valid.  Leaving -- also by an exception -- swaps back.  Not reentrant; train_step
+        inside is an error.  The batch-norm moving statistics are the live ones either way."""
+        if self.ema is None:
+            raise ValueError('%s was built without ema=DECAY: there are no averaged weights' % self.__class__.name)
+        if self._ema_active:
+            raise RuntimeError('ema_weights() is already active: the context does not nest')
+        from . import ops
+        bucket = self.store.buckets['G']
+        ops.swap_flat_(bucket.params, bucket.ema)
+        self.store.touch('G')
+        self._ema_active = True
+        try:
+            yield self
+        finally:
+            ops.swap_flat_(bucket.params, bucket.ema)
+            self.store.touch('G')
+            self._ema_active = False
+
+    def _restore_ema(self, arrays, checkpoint_path):
+        """The averages' half of restore / resume, after the parameters are in place.  -> shadow keys in the checkpoint."""
+        from .ema import SUFFIX
+        n_shadows = sum(1 for n in arrays if n.endswith(SUFFIX))
+        if self.ema is not None:
+            found, missing = self.store.load_ema_numpy(arrays)
+            if found == 0:
+                log.info('%s holds no averaged weights: the averages start as the restored parameters', checkpoint_path)
+            elif missing:
+                log.info('%s holds averages of %d of %d variables: the others start as the restored parameters', checkpoint_path, found, found + missing)
+        elif n_shadows and self.is_training:
+            log.info('%s holds %d averaged weights, which this run (without ema) ignores: the next checkpoint will not carry them', checkpoint_path, n_shadows)
+        return n_shadows
 
     def checkpoint_arrays(self):
         """Everything tf.train.Saver(tf.global_variables()) would hold (reference :74)."""
@@ -256,7 +360,11 @@ class BaseModel(ABC):
                             % (self.__class__.name, checkpoint_path, len(bad), '; '.join(bad)))
         self.store.load_numpy(arrays, strict=False)
         self._restore_extra(arrays)
-        n_vars = sum(1 for n in arrays if not n.endswith(('/Adam', '/Adam_1')) and n not in _COUNTERS)
+        from .ema import SUFFIX
+        n_shadows = self._restore_ema(arrays, checkpoint_path)
+        if n_shadows and self.ema is not None:
+            log.info('%d averaged weights restored from %s', n_shadows, checkpoint_path)
+        n_vars = sum(1 for n in arrays if not n.endswith(('/Adam', '/Adam_1', SUFFIX)) and n not in _COUNTERS)     # (shadows are not variables)
         n_slots = sum(1 for n in arrays if n.endswith(('/Adam', '/Adam_1')))
         return int(getattr(self, 'global_step', 0)), n_vars, n_slots
 
@@ -284,12 +392,18 @@ class BaseModel(ABC):
                 torch.cuda.set_rng_state(torch.from_numpy(data['device'].copy()), self.device)
         return True
 
-    def restore(self, sess, checkpoint_path):
+    def restore(self, sess, checkpoint_path, ema=False):
         """reference :83-91: restore the intersection of checkpoint variables and model variables, by name.  Accepts the .npz
-        container or the prefix of a TensorFlow V2 bundle (e.g. the published stage-1 / stage-2 checkpoints)."""
-        arrays = self.read_checkpoint(checkpoint_path)
+        container or the prefix of a TensorFlow V2 bundle (e.g. the published stage-1 / stage-2 checkpoints).  ``ema`` (the --ema of the
+        inference tools): read the checkpoint under its averages (ema.select); one without averages is refused by name."""
+        if ema:
+            from .ema import read_selected
+            arrays = read_selected(checkpoint_path)
+        else:
+            arrays = self.read_checkpoint(checkpoint_path)
         self.store.load_numpy(arrays, strict=False)
         self._restore_extra(arrays)
+        self._restore_ema(arrays, checkpoint_path)
         return sorted(arrays)
 
     @staticmethod

@@ -71,8 +71,9 @@ class DetectorTranslatorModel(BaseModel):
     name = 'detector_translator'       # reference :15 (checkpoint sub-directory)
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', vgg=None, process_group=None,
-                 image_size=128, seed=1234, colors_seed=0, guard=False):
+                 image_size=128, seed=1234, colors_seed=0, guard=False, ema=None, ema_warmup=True):
         super(DetectorTranslatorModel, self).__init__(is_training)
+        self._ema_config(ema, ema_warmup)                  # train.py --ema: the averaged generator (BaseModel._ema_*)
         self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None      # reference :24-27
@@ -120,9 +121,10 @@ class DetectorTranslatorModel(BaseModel):
         with variables.as_default(self.store):
             self._define_forward_pass(Sym(b, r, r, 3), Sym(b, r, r, 3))
             networks.img_discr(Sym(b, r, r, 3))
-        self.store.materialise(guard=self.guard)
+        self.store.materialise(guard=self.guard, **({'ema': True} if self.ema is not None else {}))
         dev = self.device
         self._guard_init(('D', 'G'))
+        self._ema_init()
         if self.guard and dev.type == 'cuda':
             self._ensure_alpha_dev()        # the guarded update reads its step size from device memory in every form of the step
         if dev.type == 'cuda':
@@ -260,6 +262,9 @@ class DetectorTranslatorModel(BaseModel):
             ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, self._adam_alpha(which, lr), self.beta1, self.beta2, self.adam_eps,
                               gscale=1.0 / self.world_size)
             self._advance_beta_powers(which)
+        if which == 'G':
+            # the average follows the generator's update on its stream; a captured launch reads the rate its replay refreshes
+            self._ema_update('G', None if self._capturing else self.global_step, self._ema_health('G'))
         self.store.touch(which)                 # the filters changed: their Winograd forms are re-derived before the next use
 
     def _ensure_alpha_dev(self):
@@ -283,6 +288,7 @@ class DetectorTranslatorModel(BaseModel):
         convention).  The reference's input node hands a NEW batch to each sess.run (train.py:46-50):
         pass that second batch as 'image_G' / 'future_image_G' and the G-run recomputes the forward on it, exactly like the
         reference's second sess.run (BN moving statistics then come from the G-run's batch only, :199-202)."""
+        self._ema_forbid_training()
         start_time = time.time()
         if self.distributed and self.dp_graph == 'segments' and self._phased_eligible(feed_dict):
             self._train_step_dp(feed_dict)
@@ -295,7 +301,7 @@ class DetectorTranslatorModel(BaseModel):
             g_feed = ('image_G', 'future_image_G') if 'image_G' in feed_dict else ('image', 'future_image')
             vals = self.loss_values()
             self._write_summaries(self.train_writer, step, self._summaries(vals, self.last['fwd'], feed_dict[g_feed[0]], feed_dict[g_feed[1]])
-                                  + [[summary.scalar_value('lr', self.last['lr'])]])
+                                  + [[summary.scalar_value('lr', self.last['lr'])]] + self._ema_summary())
         if should_write_log:
             vals = self.loss_values()
             duration = time.time() - start_time
@@ -334,6 +340,8 @@ class DetectorTranslatorModel(BaseModel):
         ops.flat_copy_raw(fut.contiguous().data_ptr(), static['future_image'].data_ptr(), fut.numel())
         for which in ('D', 'G'):
             ops.fill_raw_(self._alpha_dev[which], float(self._adam_alpha(which, lr)))
+        if self.ema is not None:
+            self._ema_refresh(self.global_step)
         graph.replay()
         for which in ('D', 'G'):
             self._advance_beta_powers(which)
@@ -443,6 +451,8 @@ class DetectorTranslatorModel(BaseModel):
                 ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, self._adam_alpha(which, lr), self.beta1, self.beta2,
                                   self.adam_eps, gscale=1.0 / self.world_size)
                 self._advance_beta_powers(which)
+            if which == 'G':
+                self._ema_update('G', None if device_alpha else self.global_step, self._ema_health('G'))
             self.store.touch(which)
 
         with variables.as_default(self.store):
@@ -523,6 +533,8 @@ class DetectorTranslatorModel(BaseModel):
         ops.flat_copy_raw(fut.contiguous().data_ptr(), static['future_image'].data_ptr(), fut.numel())
         for which in ('D', 'G'):
             ops.fill_raw_(self._alpha_dev[which], float(self._adam_alpha(which, lr)))
+        if self.ema is not None:
+            self._ema_refresh(self.global_step)
         state = {}
         for graph, tag in zip(graphs, ('exchange_D', 'wait_D', 'exchange_G', None)):
             graph.replay()
@@ -585,7 +597,7 @@ class DetectorTranslatorModel(BaseModel):
         group_src = torch.distributed.get_global_rank(self.process_group, src) if self.process_group is not None else src
         with torch.no_grad():
             for b in self.store.buckets.values():
-                for flat in (b.params, b.m, b.v):
+                for flat in (b.params, b.m, b.v, b.ema):
                     if flat is not None:
                         torch.distributed.broadcast(flat, group_src, group=self.process_group)
             for name, (shape, kind) in self.store.specs.items():

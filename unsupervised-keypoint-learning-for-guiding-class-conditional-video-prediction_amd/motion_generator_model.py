@@ -28,8 +28,9 @@ class MotionGeneratorModel(BaseModel):
     draws_on_device = True             # eps_D / eps_G come from torch's device generator: checkpoints carry its state in a side file
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777,
-                 discr_cells=(1024, 1024), colors_seed=0, guard=False):
+                 discr_cells=(1024, 1024), colors_seed=0, guard=False, ema=None, ema_warmup=True):
         super(MotionGeneratorModel, self).__init__(is_training)
+        self._ema_config(ema, ema_warmup)                  # train.py --ema: the averaged generator (BaseModel._ema_*)
         self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
@@ -59,8 +60,9 @@ class MotionGeneratorModel(BaseModel):
             networks.vae_encoder(Sym(b, N_FUTURE_FRAMES, k2), Sym(b, k2), Sym(b, self.n_action), self.cell_info, self.vae_dim)
             networks.vae_decoder(Sym(b, self.vae_dim), Sym(b, k2), Sym(b, self.n_action), self.cell_info, self.vae_dim, self.n_points)
             networks.seq_discr(Sym(b, N_FUTURE_FRAMES, k2), self.discr_cells)
-        self.store.materialise(guard=self.guard)
+        self.store.materialise(guard=self.guard, **({'ema': True} if self.ema is not None else {}))
         self._guard_init(('D', 'G'))
+        self._ema_init()
         if self.device.type == 'cuda':
             self._e0 = torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32, device=self.device)
             self._one = torch.ones(1, dtype=torch.float32, device=self.device)
@@ -114,6 +116,8 @@ class MotionGeneratorModel(BaseModel):
         else:
             ops.adam_tf_flat_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha, self.beta1, self.beta2, self.adam_eps,
                               gscale=1.0 / self.world_size)
+        if which == 'G':
+            self._ema_update('G', self.global_step, self._ema_health('G'))     # (global_step before its increment: the update's index)
         self.store.touch()
         self.beta_power[which] = [np.float32(b1p * self.beta1), np.float32(b2p * self.beta2)]
 
@@ -125,6 +129,7 @@ class MotionGeneratorModel(BaseModel):
     def train_step(self, sess, feed_dict, step, batch_size, should_write_log=False, should_write_summary=False):
         """reference train_step (:68-104).  feed_dict: 'keypoints' [B,K,2], 'real_seq' [B,32,K,2], 'action_code' [B,A]
         (the SequenceDataLoader batch); optional 'eps_D' / 'eps_G' [B,vae_dim] pin the two random_normal draws."""
+        self._ema_forbid_training()
         kp, rs, ac = feed_dict['keypoints'], feed_dict['real_seq'], feed_dict['action_code']
         b = kp.shape[0]
         start_time = time.time()
@@ -147,7 +152,7 @@ class MotionGeneratorModel(BaseModel):
         self.last = dict(d_losses=d_losses.detach(), recon=recon.detach(), kl=kl.detach(), adv=adv.detach(), lr=float(lr), pred_seq=pred.detach())
         if should_write_summary and self.train_writer is not None:
             self._write_summaries(self.train_writer, step, self._summaries(self.loss_values(), self.last['pred_seq'], feed_dict)
-                                  + [[summary.scalar_value('lr', self.last['lr'])]])
+                                  + [[summary.scalar_value('lr', self.last['lr'])]] + self._ema_summary())
         if should_write_log:
             v = self.loss_values()
             duration = time.time() - start_time

@@ -2342,6 +2342,32 @@ def read_guard_health(health):
     return dict(nonfinite=nonfinite, skipped_total=skipped_total, skipped_run=skipped_run, updates=updates, sumsq=sumsq, maxabs=maxabs)
 
 
+# ----------------------------------------------------------------------------------------------- averaged generator (train.py --ema)
+def ema_flat_(ema, p, rate_dev, health=None):
+    """ema += (p - ema) * rate over one flat bucket, ``rate_dev`` a [1] fp32 device tensor read by the launch (kpx_ema_flat_f32).  With a
+    ``health`` record that counts a non-finite gradient value the launch writes nothing; the record is only read."""
+    _require_flat_f32('ema_flat_: ema', ema)
+    _require_flat_f32('ema_flat_: p', p, ema.numel())
+    _require_flat_f32('ema_flat_: rate_dev', rate_dev, 1)
+    if p.device != ema.device or rate_dev.device != ema.device:
+        raise _lib.KpxError('ema_flat_: ema, p and rate_dev must be on one device (got %s, %s, %s)' % (ema.device, p.device, rate_dev.device))
+    if health is not None:
+        _require_health('ema_flat_', health, ema.device)
+    check(lib.kpx_ema_flat_f32(ema.data_ptr(), p.data_ptr(), ema.numel(), rate_dev.data_ptr(), _ptr(health), _stream()), 'kpx_ema_flat_f32')
+
+
+def swap_flat_(a, b):
+    """Exchange two flat fp32 ranges of equal size bit for bit (kpx_swap_flat_f32); the two must not overlap."""
+    _require_flat_f32('swap_flat_: a', a)
+    _require_flat_f32('swap_flat_: b', b, a.numel())
+    if b.device != a.device:
+        raise _lib.KpxError('swap_flat_: a and b must be on one device (got %s, %s)' % (a.device, b.device))
+    lo, hi = sorted((a.data_ptr(), b.data_ptr()))
+    if lo + a.numel() * 4 > hi:
+        raise _lib.KpxError('swap_flat_: the two ranges overlap')
+    check(lib.kpx_swap_flat_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), 'kpx_swap_flat_f32')
+
+
 # ----------------------------------------------------------------------------------------------- rollout (forward only)
 def dense(x, w, b, act=ACT_NONE):
     """act(x @ w + b) for x [B,In], w [In,Out]: a 1x1 convolution over a [B,1,1,In] tensor on the implicit-GEMM kernel

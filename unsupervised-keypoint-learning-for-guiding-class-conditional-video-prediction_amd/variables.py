@@ -14,6 +14,8 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
+from .ema import SUFFIX as EMA_SUFFIX      # '<name>/ExponentialMovingAverage': tf.train.ExponentialMovingAverage's shadow naming
+
 
 class Bucket:
     """One flat parameter bucket with matching flat gradient and Adam-slot buffers."""
@@ -23,6 +25,7 @@ class Bucket:
         self.entries = OrderedDict()     # var name -> (offset, shape)
         self.size = 0
         self.params = self.grads = self.m = self.v = None
+        self.ema = None                  # (materialise(ema=True), bucket 'G' only) the averages of params, same layout
 
     def add(self, name, shape):
         n = int(np.prod(shape))
@@ -119,12 +122,13 @@ class VariableStore:
     def is_trainable(kind):
         return not kind.startswith('moving')
 
-    def materialise(self, guard=False):
+    def materialise(self, guard=False, ema=False):
         """Allocate the buckets on the device and turn every variable into a view of them.  ``guard`` (the step guard of the training
         models): the NON-trainable variables -- batch-norm moving statistics -- are laid into one flat buffer per owner bucket as well (the
         same 'discr' rule, every view 16-byte aligned), each with a shadow of the same size that the step copies them into before the
         forward and restores them from when the owner's update is skipped (self.moving / self.moving_shadow).  Without it they are
-        separate tensors, as ever."""
+        separate tensors, as ever.  ``ema`` (the averaged generator of the training models): bucket 'G' -- the bucket inference reads in
+        every mode -- gets a fifth flat buffer ``Bucket.ema`` of the bucket's size, a copy of ``params`` as initialised; 'D' never has one."""
         for name, (shape, kind) in self.specs.items():
             if self.is_trainable(kind):
                 self.buckets['D' if 'discr' in name else 'G'].add(name, shape)   # reference :191-192 ('discr' in var.name: img_discr, seq_discr)
@@ -159,6 +163,8 @@ class VariableStore:
                 self.vars[name] = val.to(self.device)
         self.init_values.clear()
         self.materialised = True
+        if ema:
+            self.buckets['G'].ema = self.buckets['G'].params.detach().clone()
         if self.device.type == 'cuda':
             from . import ops                            # pre-transformed Winograd filters of every trainable 3x3 kernel
             # (only filters a Winograd kernel can ever take: >= 4 produced channels in at least one direction; the discriminator's single
@@ -271,9 +277,36 @@ class VariableStore:
                 for name in b.entries:
                     put(name, b.view(b.m, name), '/Adam')
                     put(name, b.view(b.v, name), '/Adam_1')
+        for b in self.buckets.values():                   # the averages under TF's shadow naming, through the same put (fused head split)
+            if b.ema is not None:
+                for name in b.entries:
+                    put(name, b.view(b.ema, name), EMA_SUFFIX)
         if beta_powers:
             out.update(beta_powers)
         return out
+
+    def load_ema_numpy(self, arrays):
+        """The averages of every bucket that keeps them, from the ``<name>/ExponentialMovingAverage`` keys of ``arrays`` (the fused head from
+        its two); a variable without one starts its average at the parameter's current value.  -> (restored, started at the parameter)."""
+        found = missing = 0
+        with torch.no_grad():
+            for b in self.buckets.values():
+                if b.ema is None:
+                    continue
+                for name in b.entries:
+                    dst = b.view(b.ema, name)
+                    if '_0+1/' in name:
+                        parts = [arrays.get(name.replace('_0+1/', '_%d/' % i) + EMA_SUFFIX) for i in (0, 1)]
+                        src = None if any(a is None for a in parts) else np.concatenate([np.asarray(a) for a in parts], axis=-1)
+                    else:
+                        src = arrays.get(name + EMA_SUFFIX)
+                    if src is None:
+                        dst.copy_(b.view(b.params, name).detach())
+                        missing += 1
+                    else:
+                        dst.copy_(torch.from_numpy(np.ascontiguousarray(src, dtype=np.float32)).to(dst.device))
+                        found += 1
+        return found, missing
 
 
 _default_store = []
