@@ -412,7 +412,11 @@ extern "C" int kpx_keypoint_head_proj_bwd_f32(const float* dmu, const float* mu,
 // ------------------------------------------------------------------------------------------ Gaussian maps
 // ONE definition of a heat-map element for every renderer and for the backward: the reference's rounding sequence
 // square(y - mu_y) + square(x - mu_x), times float32(inv_std**2), negate, exp (utils/model.py:56-59); exp is the hardware
-// exp2 path (__expf: |err| <= ~2 ulp of a result in [0,1], inside the 2e-6 absolute budget).  Because both renderers call
+// exp2 path (__expf = v_exp_f32 of fl(-dist * log2 e)).  That product rounds the ARGUMENT, so the relative error of the result is not a
+// fixed number of ulps: it grows like dist * 2^-24 on top of the instruction's own ulp (measured against exp of the same fp32 dist at
+// inv_std = 1: 6 ulp for dist < 1, 17 for dist in [1,4), 29 for [4,16)); the absolute error stays below 2^-24 (dist * e^-dist <= 1/e),
+// inside the 2e-6 absolute budget.  A result below 2^-126 comes back as +0, never as a denormal.  tests/keypoints_ref.py bounds both
+// (e * dist in the exponent, 1.2e-38 absolute).  Because both renderers call
 // this function, a map element has the same bits whether it is rendered contiguously or into a channel slice.
 // The operations go through kpx_*_rn (kpx_common.h): hipcc contracts the __f*_rn intrinsics like plain operators, and the fixed-column loop
 // of gauss_fwd_reg_kernel was compiled to fma(dy, dy, dx2), an ulp of dist away from the other renderers.
