@@ -1069,9 +1069,12 @@ __global__ __launch_bounds__(256) void bn_apply_strip_bf16_kernel(const bf16_t* 
     const int cg = blockIdx.y * Gb + cgl;
     if (prow >= PPB || cg >= G) return;
     x += (size_t)blockIdx.z * P * ldx; mean += blockIdx.z * C; invstd += blockIdx.z * C;
-    float sc[8], sh[8];                                   // y = x * sc + sh with sc = invstd * gamma, sh = beta - mean * sc: the fp32 kernel's value up to one rounding
+    // y = (x - mean) * sc + beta with sc = invstd * gamma: the mean is subtracted first, so the error stays relative to |xhat gamma| + |beta|
+    // as in the fp32 kernel.  (x * sc + (beta - mean * sc) saves the subtraction, but its error is relative to |x sc| + |mean sc|: a constant
+    // channel came out u |x| gamma / sqrt(eps) away from beta, and an element near y = 0 could pass this ReLU and be masked by the backward.)
+    float mu[8], sc[8], be[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { const int c = cg * 8 + j; sc[j] = invstd[c] * gamma[c]; sh[j] = fmaf(-mean[c], sc[j], beta[c]); }
+    for (int j = 0; j < 8; ++j) { const int c = cg * 8 + j; mu[j] = mean[c]; sc[j] = invstd[c] * gamma[c]; be[j] = beta[c]; }
     const size_t step = (size_t)gridDim.x * PPB;
     for (size_t p0 = (size_t)blockIdx.x * PPB + prow; p0 < P; p0 += step * 4) {
         float v[4][8];
@@ -1083,7 +1086,7 @@ __global__ __launch_bounds__(256) void bn_apply_strip_bf16_kernel(const bf16_t* 
             if (p >= P) break;
             float r[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { r[j] = fmaf(v[u][j], sc[j], sh[j]); if (act == KPX_ACT_RELU) r[j] = fmaxf(r[j], 0.f); }
+            for (int j = 0; j < 8; ++j) { r[j] = fmaf(v[u][j] - mu[j], sc[j], be[j]); if (act == KPX_ACT_RELU) r[j] = fmaxf(r[j], 0.f); }
             if (OUTF32) {
                 float* o = reinterpret_cast<float*>(yv) + ((size_t)blockIdx.z * P + p) * ldy + cg * 8;
                 *reinterpret_cast<f32x4*>(o) = f32x4{r[0], r[1], r[2], r[3]}; *reinterpret_cast<f32x4*>(o + 4) = f32x4{r[4], r[5], r[6], r[7]};
