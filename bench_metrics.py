@@ -1231,6 +1231,73 @@ def ema_step_leg(dev, steps):
             'on_ms_all': [round(v, 3) for v in ms['on']]}, models['on'].store.buckets['G'].ema.numel()
 
 
+def clip_kernel_leg(dev, launches, model):
+    """The clipped update beside the guarded update and a device copy, and the per-variable statistics beside the copy, on the two real
+    buckets (the sizes and the segment tables of ``model``)."""
+    from kpx_amd import ops
+    res = {}
+    for which, bucket in model.store.buckets.items():
+        n = bucket.grads.numel()
+        g = torch.randn(n, device=dev) * 1e-3
+        p, m, v, dst = torch.randn(n, device=dev), torch.zeros(n, device=dev), torch.zeros(n, device=dev), torch.empty(n, device=dev)
+        health, clip = ops.new_guard_health(dev), ops.new_clip_state(dev)
+        ops.grad_health(g, health)
+        norm = float(ops.read_guard_health(health)['sumsq']) ** 0.5
+        alpha = torch.full((1,), 1e-4, device=dev)
+        table = ops.grad_segment_table(bucket, dev)
+        work, out = ops.grad_segment_workspace(table, dev)
+        legs = (('device_copy', lambda: dst.copy_(g), 8 * n),
+                ('adam_guarded_clean', lambda: ops.adam_tf_flat_guarded_(p, g, m, v, alpha, 0.5, 0.999, 1e-8, health), 28 * n),
+                ('adam_clipped_below_bound', lambda: ops.adam_tf_flat_clipped_(p, g, m, v, alpha, 0.5, 0.999, 1e-8, health, clip, 4 * norm), 28 * n),
+                ('adam_clipped_above_bound', lambda: ops.adam_tf_flat_clipped_(p, g, m, v, alpha, 0.5, 0.999, 1e-8, health, clip, norm / 4), 28 * n),
+                ('segment_stats_g', lambda: ops.grad_segment_stats(g, None, table, work, out), 4 * table.size),
+                ('segment_stats_g_and_p', lambda: ops.grad_segment_stats(g, p, table, work, out), 8 * table.size))
+        o = {'floats': n, 'mb': round(4 * n / 1e6, 1), 'variables': table.n_segs, 'chunks': table.n_chunks}
+        for name, fn, moved in legs:
+            us = _event_times(fn, launches, dev)
+            med = statistics.median(us)
+            o[name] = {'launches': launches, 'median_us': round(med, 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1),
+                       'gb_per_s': round(moved / (med * 1e-6) / 1e9, 1)}
+        for name, _, _ in legs[1:]:
+            o[name]['fraction_of_copy_rate'] = round(o[name]['gb_per_s'] / o['device_copy']['gb_per_s'], 3)
+        o['clipped_over_guarded'] = round(o['adam_clipped_above_bound']['median_us'] / o['adam_guarded_clean']['median_us'], 3)
+        assert ops.read_clip_state(clip)['clipped_total'] >= launches and ops.read_guard_health(health)['skipped_total'] == 0
+        res[which] = o
+        del g, p, m, v, dst
+        torch.cuda.empty_cache()
+    return res
+
+
+def clip_step_leg(dev, steps):
+    """The configs[1] train step guarded, and guarded with clip_norm (a bound every step exceeds): two models in one process, blocks of
+    ``steps`` replayed steps each, alternated three times."""
+    from kpx_amd.synthetic import synthetic_pair
+    models = {'off': _c1_model(dev, True), 'on': _c1_model(dev, True, clip_norm=1e-3, grad_stats=True)}
+    feed = {k: torch.from_numpy(v).to(dev) for k, v in synthetic_pair(32, res=RES, seed0=0, seed1=1).items()}
+    for m in models.values():
+        for i in range(4):                                # eager, capture, replays
+            m.train_step(None, feed, i, 32)
+    torch.cuda.synchronize(dev)
+    ms = {k: [] for k in models}
+    for _ in range(3):
+        for k, m in models.items():
+            t0 = time.perf_counter()
+            for i in range(steps):
+                m.train_step(None, feed, 4 + i, 32)
+            torch.cuda.synchronize(dev)
+            ms[k].append((time.perf_counter() - t0) * 1e3 / steps)
+    off, on = statistics.median(ms['off']), statistics.median(ms['on'])
+    t0 = time.perf_counter()
+    models['on'].grad_stats()
+    stats_ms = (time.perf_counter() - t0) * 1e3
+    return {'batch': 32, 'steps_per_block': steps, 'clip_norm': 1e-3,
+            'graph_replay': all(len(m._graphs) == 1 and not m._graph_failed for m in models.values()),
+            'guarded_ms_per_step': round(off, 3), 'clipped_ms_per_step': round(on, 3), 'clip_ms_per_step': round(on - off, 3),
+            'clip_percent': round(100.0 * (on - off) / off, 2), 'guarded_ms_all': [round(v, 3) for v in ms['off']],
+            'clipped_ms_all': [round(v, 3) for v in ms['on']], 'grad_stats_call_ms': round(stats_ms, 2),
+            'clip_report': models['on'].clip_report()}, models['on']
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -1256,7 +1323,18 @@ def main():
     ap.add_argument('--ema', action='store_true',
                     help="measure the averaged generator (the update and the swap on the real 'G' bucket beside a device copy, the configs[1] "
                          'train step with ema off and on) instead')
+    ap.add_argument('--clip', action='store_true',
+                    help='measure gradient clipping (the clipped update beside the guarded update and a device copy, the per-variable statistics '
+                         'on the two real buckets, the configs[1] train step guarded without and with clip_norm, all in this process) instead')
     args = ap.parse_args()
+    if args.clip:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        step, model = clip_step_leg(dev, max(args.rollouts, 10))
+        torch.cuda.empty_cache()
+        print(json.dumps({'clip_kernels': clip_kernel_leg(dev, args.launches, model), 'clip_step_c1': step}))
+        return
     if args.ema:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 23
+#define KPX_ABI_VERSION 24
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -562,6 +562,57 @@ int kpx_grad_health_f32(const float* g, size_t n, void* work, KpxGuardHealth* he
 int kpx_adam_tf_flat_guarded_f32(float* p, const float* g, float* m, float* v, size_t n, const float* alpha_dev,
                                  float beta1, float beta2, float eps, float gscale, KpxGuardHealth* health, void* stream);
 int kpx_guard_restore_f32(float* dst, const float* src, size_t n, const KpxGuardHealth* health, void* stream);
+
+/* ---- gradient norms (train.py --clip-norm / --grad-stats), DESIGN.md section 4.4.  Added in ABI version 24.
+ * kpx_adam_tf_flat_clipped_f32: kpx_adam_tf_flat_guarded_f32 with tf.clip_by_global_norm over the bucket.  The launch reads the record the
+ *   health pass wrote: N = (double)gscale * sqrt(health->sumsq) in fp64 (gscale = 1 / world, so every rank derives the same N from the
+ *   exchanged sum).  health->nonfinite != 0: the guarded kernel's skip bit for bit (counters bumped; p, m, v and *clip untouched).
+ *   N <= clip_norm (N == clip_norm, sumsq == 0 and clip_norm = +Inf included): the guarded update bit for bit, clip->scale = 1.  Otherwise
+ *   the walk runs with gs = (float)((double)gscale * ((double)clip_norm / N)), clip->scale = (float)(clip_norm / N) and
+ *   clip->clipped_total += 1.  Every lane derives gs from the same record; one lane writes clip->norm = (float)N, ->scale and the counters.
+ *   No allocation, copy, synchronisation or atomics (capturable).  p, g, m, v 16-byte aligned, alpha_dev and clip 4-byte, health 8-byte,
+ *   n >= 1, clip_norm > 0 (+Inf allowed); KPX_EINVAL before any device call for anything else (a NaN clip_norm included). */
+typedef struct KpxClipState {        /* 16 bytes */
+    float norm;                      /* N of the last update that was not skipped */
+    float scale;                     /* what that update multiplied the gradient by on top of gscale: 1, or clip_norm / N < 1 */
+    uint32_t clipped_total;          /* updates so far with N > clip_norm */
+    uint32_t pad_;
+} KpxClipState;
+int kpx_adam_tf_flat_clipped_f32(float* p, const float* g, float* m, float* v, size_t n, const float* alpha_dev,
+                                 float beta1, float beta2, float eps, float gscale, float clip_norm,
+                                 KpxGuardHealth* health, KpxClipState* clip, void* stream);
+
+/* kpx_grad_segment_stats_f32: per-variable statistics of a flat bucket, one deterministic segmented reduction (csrc/grad_stats.hip).
+ *   The caller cuts every variable [offset, offset + numel) of the bucket into chunks of at most KPX_SEG_CHUNK elements, counted from the
+ *   variable's own start, and lists them in DEVICE memory: chunks[c] = (start, len, seg) in ascending order of (seg, start), and
+ *   ranges[s] = (first chunk, chunk count) of variable s.  Launch 1 takes one chunk per workgroup and writes one partial per chunk into
+ *   `work` (kpx_grad_segment_stats_workspace_bytes(n_chunks) bytes, 8-byte aligned); launch 2 folds each variable's partials in ascending
+ *   order with a fixed tree into out[s].  Every value is converted to fp64 before it is squared; which lane owns an element is counted
+ *   from the chunk's start, so the result is a function of the values and the table alone: bitwise the same from run to run and whether a
+ *   chunk starts 16-byte aligned (16-byte loads) or only 4-byte aligned (4-byte loads).  Elements outside every chunk are never read.
+ *   The kernels clamp every table entry to [0, n) and KPX_SEG_CHUNK, so a wrong table gives wrong numbers, never an access outside g[0:n].
+ *   p may be NULL (sumsq_p = 0).  No allocation, copy, synchronisation or atomics (capturable).  g, p 4-byte aligned, chunks 8-byte,
+ *   ranges 4-byte, work and out 8-byte; n, n_chunks, n_segs >= 1, n_chunks and n_segs < 2^31; KPX_EINVAL before any device call otherwise. */
+#define KPX_SEG_CHUNK 16384
+typedef struct KpxSegChunk {         /* 16 bytes */
+    uint64_t start;                  /* first element, an index into the bucket */
+    uint32_t len;                    /* 1 .. KPX_SEG_CHUNK */
+    uint32_t seg;                    /* the variable it belongs to */
+} KpxSegChunk;
+typedef struct KpxSegRange {         /* 8 bytes */
+    uint32_t first;                  /* the variable's first chunk */
+    uint32_t count;                  /* and how many it has */
+} KpxSegRange;
+typedef struct KpxSegStats {         /* 32 bytes */
+    double sumsq_g;                  /* sum of g^2 over the variable's finite gradient values */
+    double sumsq_p;                  /* sum of p^2 over its finite parameter values; 0 when p == NULL */
+    float maxabs_g;                  /* max |g| over the finite values */
+    uint32_t nonfinite_g;            /* gradient values that are NaN or +-Inf (saturates at 2^32 - 1) */
+    uint32_t pad_[2];
+} KpxSegStats;
+size_t kpx_grad_segment_stats_workspace_bytes(size_t n_chunks);
+int kpx_grad_segment_stats_f32(const float* g, const float* p /* may be NULL */, size_t n, const KpxSegChunk* chunks, size_t n_chunks,
+                               const KpxSegRange* ranges, size_t n_segs, void* work, KpxSegStats* out, void* stream);
 
 /* ---- the averaged generator (train.py --ema), DESIGN.md section 4.4: an exponential moving average of a bucket's parameters, kept beside
  * training and read only for inference.  Both entries: no allocation, copy or synchronisation (capturable); no atomics; the result is a

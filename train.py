@@ -28,6 +28,12 @@ bucket whose gradient holds a NaN or an Inf, decided on the device inside the st
 generator's Adam update; checkpoints carry the averages as ``<name>/ExponentialMovingAverage``, ``--resume`` continues them, ``--ema-test``
 runs each test pass a second time under them (``<log_dir>/<mode>/test_ema``), and evaluate.py / animate.py / make_pseudo_labels.py ``--ema``
 read a checkpoint under them (``python -m kpx_amd.ema IN OUT`` writes them out as a plain inference checkpoint).
+``--clip-norm C`` is tf.clip_by_global_norm per optimiser: a bucket whose exchanged gradient has a norm above C is scaled down to norm C inside
+the Adam launch, from the fp64 sum of squares the guard's health pass already leaves on the device (so it turns ``--guard`` on).
+``--grad-stats [N]`` prints, at each log point, the N variables of largest gradient norm per bucket (one segmented reduction in HIP, run
+between steps) and names every variable that holds a non-finite gradient value when the guard counted one; at summary steps the scalars
+``clip/*``, ``grad_norm/<variable>`` and ``update_ratio/<variable>`` are written.  Neither is written into checkpoints: the clip counters
+restart on ``--resume``.
 Checkpoints are written under temporary names and renamed into place.  Real data loaders are reseeded on a resume, not continued sample
 for sample.
 """
@@ -72,6 +78,14 @@ def _get_model_by_mode(mode, config, global_step, **kw):
 def _guard_kw(args):
     """guard=True only under --guard: without the flag the constructors are called exactly as before."""
     return {'guard': True} if args.guard else {}
+
+
+def _clip_kw(args):
+    """clip_norm=C only under --clip-norm and grad_stats=True only under --grad-stats, as _guard_kw."""
+    kw = {'clip_norm': args.clip_norm} if args.clip_norm is not None else {}
+    if args.grad_stats is not None:
+        kw['grad_stats'] = True
+    return kw
 
 
 def _ema_kw(args):
@@ -161,6 +175,41 @@ class _GuardLog(object):
                             'non-finite, the run is not training' % (', '.join(stuck), max(report[b]['skipped_run'] for b in stuck), step, self.max_skips))
 
 
+class _ClipLog(object):
+    """--clip-norm / --grad-stats at a log point (rank 0): the clip line, the per-variable line of each bucket, the names of the variables
+    that hold a non-finite gradient value when the last step's health record counts one, and the scalars with the summaries."""
+
+    def __init__(self, top):
+        self.top = top                      # --grad-stats N, or None without the flag
+
+    def __call__(self, model, step, should_write_summary):
+        from kpx_amd import summary
+        values = []
+        if model.clip_norm is not None:
+            report = model.clip_report()
+            log.info('clip: step %d: %s', step, ', '.join('%s norm %.4g scale %.4g (%d clipped so far, bound %.4g)'
+                                                          % (b, r['norm'], r['scale'], r['clipped_total'], model.clip_norm)
+                                                          for b, r in sorted(report.items())))
+            for b, r in sorted(report.items()):
+                values += [summary.scalar_value('clip/norm_%s' % b, r['norm']), summary.scalar_value('clip/scale_%s' % b, r['scale']),
+                           summary.scalar_value('clip/clipped_%s' % b, float(r['clipped_total']))]
+        if self.top is not None:
+            stats = model.grad_stats()
+            lr = float(model.current_lr())
+            for b, per_var in sorted(stats.items()):
+                first = sorted(per_var.items(), key=lambda kv: -kv[1]['grad_norm'])[:self.top]
+                log.info('grad-stats: step %d: %s: %s', step, b, ', '.join('%s %.4g' % (name, r['grad_norm']) for name, r in first))
+                bad = [(name, r['nonfinite']) for name, r in per_var.items() if r['nonfinite'] > 0]
+                if bad:         # the same buffer the guard's health pass judged: its record counts what these add up to
+                    log.info('grad-stats: step %d: %s: non-finite gradient values in %s', step, b, ', '.join('%s (%d)' % nb for nb in bad))
+                for name, r in per_var.items():
+                    values.append(summary.scalar_value('grad_norm/%s' % name, r['grad_norm']))
+                    if r['param_norm'] > 0.0:
+                        values.append(summary.scalar_value('update_ratio/%s' % name, lr * r['grad_norm'] / r['param_norm']))
+        if should_write_summary and model.train_writer is not None and values:
+            model.train_writer.add_summary(values, step)
+
+
 def _save(args, model, step, rank):
     """The checkpoint of ``step``: rank 0 writes (and prunes under --keep); every rank of a model that draws on the device writes its
     generator states beside it."""
@@ -177,7 +226,7 @@ def _train_motion_generator(args, config, dev, rank, world):
     import kpx_amd
     paths_config, train_config, model_config = config['paths'], config['training'], config['model']
     classifier = args.mode == 'action_classifier'
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args))
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args), **_clip_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']
@@ -214,6 +263,7 @@ def _train_motion_generator(args, config, dev, rank, world):
         return {n: torch.from_numpy(v.astype(np.float32)).to(dev) for n, v in d.items()}
     model.initialize_loggers(paths_config['log_dir'], None)
     guard_log = _GuardLog(args.guard_max_skips) if args.guard else None
+    clip_log = _ClipLog(args.grad_stats) if (args.clip_norm is not None or args.grad_stats is not None) else None
     print('training start')
     for step in range(model.global_step, n_steps):
         feed = next(train_it) if train_it is not None else synthetic(step * world + rank)
@@ -224,6 +274,8 @@ def _train_motion_generator(args, config, dev, rank, world):
                          should_write_summary=should_write_summary)
         if guard_log is not None and step % train_config['log_interval'] == 0 and rank == 0:
             guard_log(model, step, should_write_summary)
+        if clip_log is not None and step % train_config['log_interval'] == 0 and rank == 0:
+            clip_log(model, step, should_write_summary)
         if step % train_config['checkpoint_interval'] == 0:
             _save(args, model, step, rank)
         if step % train_config['test_interval'] == 0 and rank == 0:
@@ -244,7 +296,8 @@ def _should_write_summary(train_config, step, rank):
     return bool(interval) and step % int(interval) == 0 and rank == 0
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line, checked: a bad value ends in parser.error (exit status 2) before anything is built."""
     parser = ArgumentParser()
     parser.add_argument('--mode', type=str, choices=['detector_translator', 'motion_generator', 'action_classifier'],
                         help='which mode to train: stage 1, stage 2, or the key-point action recogniser evaluate.py --action-accuracy reads')
@@ -287,7 +340,21 @@ def main(argv=None):
     parser.add_argument('--ema-test', action='store_true',
                         help='--ema: at each test interval run the test pass a second time under the averaged weights and write it to '
                              '<log_dir>/<mode>/test_ema')
+    parser.add_argument('--clip-norm', type=float, default=None, metavar='C',
+                        help='clip each optimiser\'s gradient to global norm C (tf.clip_by_global_norm per bucket, C > 0), inside the Adam launch; '
+                             'turns --guard on: a norm over non-finite values has no meaning, and the guard costs +0.08 %% of a step '
+                             '(profiles/guard.txt).  The counters are not checkpointed and restart on --resume')
+    parser.add_argument('--grad-stats', type=int, nargs='?', const=5, default=None, metavar='N',
+                        help='at each log point, print the N (default 5) variables of largest gradient norm per bucket and, when the guard '
+                             'counted a non-finite value in the last step, the name of every variable that holds one; at summary steps write '
+                             'grad_norm/<variable> and update_ratio/<variable> = lr * grad_norm / param_norm')
     args = parser.parse_args(argv)
+    if args.clip_norm is not None:
+        if not args.clip_norm > 0.0:
+            parser.error('--clip-norm C: C must be a number greater than 0 (got %r)' % args.clip_norm)
+        args.guard = True
+    if args.grad_stats is not None and args.grad_stats < 1:
+        parser.error('--grad-stats N: N must be at least 1')
     if args.ema is not None and not (0.0 < args.ema < 1.0):
         parser.error('--ema DECAY: DECAY must lie strictly between 0 and 1 (got %r)' % args.ema)
     if (args.ema_test or args.ema_no_warmup) and args.ema is None:
@@ -305,6 +372,11 @@ def main(argv=None):
     if args.resident_labels and (args.mode not in ('motion_generator', 'action_classifier') or args.synthetic):
         parser.error('--resident-labels keeps pseudo labels in HBM: the detector_translator mode reads frames (see --resident-data) and '
                      '--synthetic reads no label files')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     logging.basicConfig(level=logging.INFO, format='%(message)s')
 
     config = load_config(args.config)
@@ -326,7 +398,7 @@ def main(argv=None):
         if not args.synthetic_vgg:
             raise Exception('file of pretrained vgg19 does not exist at: %s (pass --synthetic-vgg for benchmarking)' % paths_config.get('vggnet'))
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev)
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args))
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args), **_clip_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']          # per process, like the reference's single-device batch
@@ -349,6 +421,7 @@ def main(argv=None):
     n_steps = args.steps if args.steps is not None else train_config['n_steps']
     model.initialize_loggers(paths_config['log_dir'], None)
     guard_log = _GuardLog(args.guard_max_skips) if args.guard else None
+    clip_log = _ClipLog(args.grad_stats) if (args.clip_norm is not None or args.grad_stats is not None) else None
     print('training start')
     for step in range(model.global_step, n_steps):   # reference train.py:84-113
         should_write_log = step % train_config['log_interval'] == 0
@@ -368,6 +441,8 @@ def main(argv=None):
                          should_write_summary=should_write_summary)
         if guard_log is not None and should_write_log and rank == 0:
             guard_log(model, step, should_write_summary)
+        if clip_log is not None and step % train_config['log_interval'] == 0 and rank == 0:
+            clip_log(model, step, should_write_summary)
         if step % train_config['checkpoint_interval'] == 0:
             _save(args, model, step, rank)
         if step % train_config['test_interval'] == 0 and rank == 0:

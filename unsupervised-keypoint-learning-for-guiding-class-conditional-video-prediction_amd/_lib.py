@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/kpx.h one to one (tests/test_abi.py checks header vs this table)
-ABI_VERSION = 23     # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
+ABI_VERSION = 24    # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
 SIGNATURES = {
     'kpx_abi_version': (c_int, []),
     'kpx_reload_env': (c_int, []),
@@ -149,6 +149,9 @@ SIGNATURES = {
     'kpx_grad_health_f32': (c_int, [P, c_size_t, P, P, P]),
     'kpx_adam_tf_flat_guarded_f32': (c_int, [P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, P, P]),
     'kpx_guard_restore_f32': (c_int, [P, P, c_size_t, P, P]),
+    'kpx_adam_tf_flat_clipped_f32': (c_int, [P, P, P, P, c_size_t, P, c_float, c_float, c_float, c_float, c_float, P, P, P]),
+    'kpx_grad_segment_stats_workspace_bytes': (c_size_t, [c_size_t]),
+    'kpx_grad_segment_stats_f32': (c_int, [P, P, c_size_t, P, c_size_t, P, c_size_t, P, P, P]),
     'kpx_ema_flat_f32': (c_int, [P, P, c_size_t, P, P, P]),
     'kpx_swap_flat_f32': (c_int, [P, P, c_size_t, P]),
     'kpx_lstm_pointwise_f32': (c_int, [P, P, c_float, P, P, c_int, c_int, P]),

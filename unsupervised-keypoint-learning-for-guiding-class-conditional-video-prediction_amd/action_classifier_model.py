@@ -24,10 +24,12 @@ DEFAULT_CELLS = (256, 256)      # model.classifier_cells when the config has non
 class ActionClassifierModel(BaseModel):
     name = 'action_classifier'         # checkpoint / summary sub-directory
 
-    def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777, guard=False, ema=None, ema_warmup=True):
+    def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777, guard=False, ema=None, ema_warmup=True,
+                 clip_norm=None, grad_stats=False):
         super(ActionClassifierModel, self).__init__(is_training)
         self._ema_config(ema, ema_warmup)                  # train.py --ema: the averaged weights (BaseModel._ema_*)
-        self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
+        self._clip_config(clip_norm, grad_stats)           # train.py --clip-norm / --grad-stats: gradient norms (BaseModel._clip_*)
+        self.guard = (bool(guard) or self.clip_norm is not None) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*); clipping reads its record
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
         self.batch_size = train_config['batch_size']

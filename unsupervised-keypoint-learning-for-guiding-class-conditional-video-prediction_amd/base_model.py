@@ -90,7 +90,8 @@ class BaseModel(ABC):
 
     def _guard_init(self, buckets):
         """After store.materialise(): the health record, the health pass's workspace and the device-side step size of every non-empty bucket."""
-        self._guard_health, self._guard_work, self._guard_alpha = {}, {}, {}
+        self._guard_health, self._guard_work, self._guard_alpha, self._clip_state = {}, {}, {}, {}
+        self._grad_stats_init(buckets)
         if not self.guard:
             return
         from . import ops
@@ -100,6 +101,8 @@ class BaseModel(ABC):
                 self._guard_health[which] = ops.new_guard_health(self.device)
                 self._guard_work[which] = ops.grad_health_workspace(bucket.grads.numel(), self.device)
                 self._guard_alpha[which] = torch.zeros(1, dtype=torch.float32, device=self.device)
+                if self.clip_norm is not None:
+                    self._clip_state[which] = ops.new_clip_state(self.device)
 
     def _guard_shadow_moving(self):
         """Before the forward: the moving statistics as they stand, into their shadows (one copy per owner bucket; nothing without guard)."""
@@ -118,8 +121,12 @@ class BaseModel(ABC):
         if alpha is not None:
             ops.fill_raw_(alpha_dev, float(alpha))
         ops.grad_health(bucket.grads, health, self._guard_work[which])
-        ops.adam_tf_flat_guarded_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha_dev, self.beta1, self.beta2, self.adam_eps, health,
-                                  gscale=gscale)
+        if self.clip_norm is not None:      # clip_norm=C: the same launch geometry, the gradient scaled down when its norm exceeds C
+            ops.adam_tf_flat_clipped_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha_dev, self.beta1, self.beta2, self.adam_eps, health,
+                                      self._clip_state[which], self.clip_norm, gscale=gscale)
+        else:
+            ops.adam_tf_flat_guarded_(bucket.params, bucket.grads, bucket.m, bucket.v, alpha_dev, self.beta1, self.beta2, self.adam_eps, health,
+                                      gscale=gscale)
         live = self.store.moving.get(which)
         if live is not None:
             ops.guard_restore_(live, self.store.moving_shadow[which], health)
@@ -137,6 +144,65 @@ class BaseModel(ABC):
             out[which] = dict(skipped_total=h['skipped_total'], skipped_run=h['skipped_run'], updates=h['updates'], nonfinite=h['nonfinite'],
                               grad_norm=gscale * float(np.sqrt(h['sumsq'])), max_abs=h['maxabs'])
         return out
+
+    # ---- gradient norms (clip_norm=C and grad_stats=True of the training models, train.py --clip-norm / --grad-stats) -----------------
+    # clip_norm=C is tf.clip_by_global_norm over each bucket, per optimiser ('D' and 'G' clip separately): the guarded update's launch reads
+    # the sum of squares the health pass already left in the bucket's record and scales the gradient by C / norm when norm > C
+    # (kpx_adam_tf_flat_clipped_f32).  It needs the guard -- a norm over non-finite values has no meaning --, so clip_norm turns guard on.
+    # One KpxClipState record per bucket in device memory holds the last norm, the last scale and the count of clipped updates; only
+    # clip_report() reads it back.  grad_stats=True builds the segment table of every bucket once; grad_stats() then runs eagerly, outside
+    # any capture, over bucket.grads, which still hold the step's exchanged gradient after train_step returns (no model clears them).
+    # Neither is written into checkpoints: the counters restart on resume.
+    clip_norm = None                   # the bound on gscale * ||g||, a float > 0; None: the guarded (or plain) update, exactly as before
+    grad_stats_on = False
+
+    def _clip_config(self, clip_norm, grad_stats=False):
+        """Constructor half, before ``self.guard`` is set: check and keep the bound (training models only; a model that never steps has no
+        gradient to clip, so the keyword is refused there)."""
+        if clip_norm is not None:
+            if not self.is_training:
+                raise ValueError('clip_norm is for training models: %s with is_training=False never takes a step' % self.__class__.name)
+            if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float, np.floating, np.integer)) or not float(clip_norm) > 0.0:
+                raise ValueError('clip_norm must be a number > 0 (got %r)' % (clip_norm,))
+            self.clip_norm = float(clip_norm)
+        if grad_stats and not self.is_training:
+            raise ValueError('grad_stats is for training models: %s with is_training=False has no gradients' % self.__class__.name)
+        self.grad_stats_on = bool(grad_stats)
+
+    def _grad_stats_init(self, buckets):
+        """The segment table, workspace and result records of every non-empty bucket (grad_stats=True only)."""
+        self._seg = {}
+        if not self.grad_stats_on or self.device.type != 'cuda':
+            return
+        from . import ops
+        for which in buckets:
+            bucket = self.store.buckets[which]
+            if bucket.size:
+                table = ops.grad_segment_table(bucket, self.device)
+                self._seg[which] = (table,) + ops.grad_segment_workspace(table, self.device)
+
+    def clip_report(self):
+        """{bucket: norm = gscale * ||g|| and scale of the last update that was not skipped, clipped_total}.  Synchronises."""
+        if self.clip_norm is None:
+            raise ValueError('%s was built without clip_norm=C: there is nothing to report' % self.__class__.name)
+        from . import ops
+        return {which: ops.read_clip_state(clip) for which, clip in self._clip_state.items()}
+
+    def grad_stats(self):
+        """{bucket: {variable: grad_norm (gscale * ||g|| over the finite values), param_norm, max_abs, nonfinite}} of the gradient the last
+        train_step left in the buckets.  Eager (two launches per bucket) and synchronising: call it between steps, never inside a capture."""
+        if not self.grad_stats_on:
+            raise ValueError('%s was built without grad_stats=True: there is no segment table' % self.__class__.name)
+        from . import ops
+        gscale = 1.0 / float(getattr(self, 'world_size', 1))
+        report = {}
+        for which, (table, work, out) in self._seg.items():
+            bucket = self.store.buckets[which]
+            rec = ops.read_segment_stats(ops.grad_segment_stats(bucket.grads, bucket.params, table, work, out))
+            report[which] = {name: dict(grad_norm=gscale * float(np.sqrt(rec['sumsq_g'][i])), param_norm=float(np.sqrt(rec['sumsq_p'][i])),
+                                        max_abs=float(rec['maxabs_g'][i]), nonfinite=int(rec['nonfinite_g'][i]))
+                             for i, name in enumerate(table.names)}
+        return report
 
     # ---- the averaged generator (ema=DECAY of the training models, train.py --ema) --------------------------------------------------
     # Bucket 'G' -- the bucket inference reads in every mode -- keeps an exponential moving average of its parameters in a fifth flat buffer

@@ -1,13 +1,16 @@
 // The step guard (train.py --guard): a non-finite gradient costs one skipped update instead of the run.
 //   health  : one read pass over a bucket's flat gradient -> count of NaN / +-Inf values, sum of squares (fp64) and max |g| of the finite ones
 //   adam    : the fused Adam update of loss_optim.hip (kpx_adam.h), taken only when the health record counts no non-finite value
+//   clipped : the same update with the gradient scaled to a global norm of at most clip_norm, from the record's sum of squares (--clip-norm)
 //   restore : dst = src when the record counts one (the batch-norm moving statistics the forward already overwrote)
 // The verdict lives in device memory (KpxGuardHealth) and is read by the launches themselves, like the step size of the device-alpha
 // Adam: the step is one captured HIP graph and the host never learns of a skip.  No atomics; every result is bitwise reproducible.
 #include "kpx_common.h"
 #include "kpx_adam.h"
+#include "kpx_health.h"
 
 static_assert(sizeof(KpxGuardHealth) == 32, "KpxGuardHealth is 32 bytes");
+static_assert(sizeof(KpxClipState) == 16, "KpxClipState is 16 bytes");
 
 // The gradient is cut into slabs of HEALTH_SLAB elements by element index alone: lane t of the workgroup that takes a slab owns the elements
 // base + k*1024 + 4*t + j (k < 16, j < 4) and adds them in ascending (k, j).  Which workgroup takes a slab, and whether the four elements
@@ -15,21 +18,6 @@ static_assert(sizeof(KpxGuardHealth) == 32, "KpxGuardHealth is 32 bytes");
 #define HEALTH_LANES 256
 #define HEALTH_ITERS 16
 #define HEALTH_SLAB (HEALTH_LANES * 4 * HEALTH_ITERS)      // 16384 elements = 64 KiB
-
-struct HealthAcc {
-    double s;
-    float mx;
-    unsigned bad;
-};
-__device__ __forceinline__ void health_add(HealthAcc& a, float x) {
-    if ((__float_as_uint(x) & 0x7f800000u) == 0x7f800000u) {     // exponent all ones: NaN or +-Inf
-        a.bad += 1u;
-    } else {
-        const double d = (double)x;                               // exact; d*d is exact in fp64 (24-bit significand): the addition alone rounds
-        a.s = fma(d, d, a.s);
-        a.mx = fmaxf(a.mx, fabsf(x));
-    }
-}
 
 template <bool VEC>
 __device__ __forceinline__ void health_slab(const float* __restrict__ g, size_t base, size_t n, HealthAcc& a) {
@@ -158,6 +146,43 @@ extern "C" int kpx_adam_tf_flat_guarded_f32(float* p, const float* g, float* m, 
         return KPX_EINVAL;
     hipLaunchKernelGGL(adam_tf_guarded_kernel, dim3(kpx_adam_tf_blocks(n)), dim3(256), 0, kpx_stream(stream), p, g, m, v, n, alpha_dev,
                        1.0f - beta1, 1.0f - beta2, eps, gscale, health);
+    return kpx_launch_status();
+}
+
+// The guarded update with tf.clip_by_global_norm over the bucket (train.py --clip-norm).  Every lane derives the norm and the scale from
+// health->sumsq and the launch's own arguments, none of which this launch writes: the two branches and gs are uniform across the launch.
+// With N <= clip_norm the walk gets gscale itself, the guarded kernel's operand.  Lane 0 of workgroup 0 alone writes the counters and *clip.
+__global__ __launch_bounds__(256) void adam_tf_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, size_t n, const float* __restrict__ alpha_dev,
+                                                              float omb1, float omb2, float eps, float gscale, float clip_norm,
+                                                              KpxGuardHealth* health, KpxClipState* clip) {
+    const bool skip = health->nonfinite != 0u;
+    const double norm = (double)gscale * sqrt(health->sumsq);
+    const bool clipped = norm > (double)clip_norm;
+    const double ratio = clipped ? (double)clip_norm / norm : 1.0;
+    const float gs = clipped ? (float)((double)gscale * ratio) : gscale;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        health->updates += 1u;
+        if (skip) { health->skipped_total += 1u; health->skipped_run += 1u; }
+        else {
+            health->skipped_run = 0u;
+            clip->norm = (float)norm;
+            clip->scale = (float)ratio;
+            if (clipped) clip->clipped_total += 1u;
+        }
+    }
+    if (skip) return;
+    kpx_adam_tf_walk(p, g, m, v, n, *alpha_dev, omb1, omb2, eps, gs);
+}
+extern "C" int kpx_adam_tf_flat_clipped_f32(float* p, const float* g, float* m, float* v, size_t n, const float* alpha_dev,
+                                            float beta1, float beta2, float eps, float gscale, float clip_norm,
+                                            KpxGuardHealth* health, KpxClipState* clip, void* stream) {
+    if (!p || !g || !m || !v || !alpha_dev || !health || !clip || n == 0 || !(clip_norm > 0.0f)) return KPX_EINVAL;      // (a NaN fails the comparison)
+    if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) || ((((uintptr_t)alpha_dev) | ((uintptr_t)clip)) & 3) ||
+        (((uintptr_t)health) & 7))
+        return KPX_EINVAL;
+    hipLaunchKernelGGL(adam_tf_clipped_kernel, dim3(kpx_adam_tf_blocks(n)), dim3(256), 0, kpx_stream(stream), p, g, m, v, n, alpha_dev,
+                       1.0f - beta1, 1.0f - beta2, eps, gscale, clip_norm, health, clip);
     return kpx_launch_status();
 }
 

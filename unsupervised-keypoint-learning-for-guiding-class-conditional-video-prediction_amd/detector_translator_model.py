@@ -71,10 +71,12 @@ class DetectorTranslatorModel(BaseModel):
     name = 'detector_translator'       # reference :15 (checkpoint sub-directory)
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', vgg=None, process_group=None,
-                 image_size=128, seed=1234, colors_seed=0, guard=False, ema=None, ema_warmup=True):
+                 image_size=128, seed=1234, colors_seed=0, guard=False, ema=None, ema_warmup=True,
+                 clip_norm=None, grad_stats=False):
         super(DetectorTranslatorModel, self).__init__(is_training)
         self._ema_config(ema, ema_warmup)                  # train.py --ema: the averaged generator (BaseModel._ema_*)
-        self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
+        self._clip_config(clip_norm, grad_stats)           # train.py --clip-norm / --grad-stats: gradient norms (BaseModel._clip_*)
+        self.guard = (bool(guard) or self.clip_norm is not None) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*); clipping reads its record
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None      # reference :24-27
         self.batch_size = train_config['batch_size']

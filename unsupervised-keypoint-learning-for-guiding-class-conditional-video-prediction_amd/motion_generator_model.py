@@ -28,10 +28,12 @@ class MotionGeneratorModel(BaseModel):
     draws_on_device = True             # eps_D / eps_G come from torch's device generator: checkpoints carry its state in a side file
 
     def __init__(self, config, global_step=None, is_training=True, device='cuda', process_group=None, seed=777,
-                 discr_cells=(1024, 1024), colors_seed=0, guard=False, ema=None, ema_warmup=True):
+                 discr_cells=(1024, 1024), colors_seed=0, guard=False, ema=None, ema_warmup=True,
+                 clip_norm=None, grad_stats=False):
         super(MotionGeneratorModel, self).__init__(is_training)
         self._ema_config(ema, ema_warmup)                  # train.py --ema: the averaged generator (BaseModel._ema_*)
-        self.guard = bool(guard) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*)
+        self._clip_config(clip_norm, grad_stats)           # train.py --clip-norm / --grad-stats: gradient norms (BaseModel._clip_*)
+        self.guard = (bool(guard) or self.clip_norm is not None) and self.is_training      # train.py --guard: the step guard (BaseModel._guard_*); clipping reads its record
         train_config, model_config, paths_config = config['training'], config['model'], config['paths']
         self.lr = train_config['lr'] if self.is_training else None
         self.batch_size = train_config['batch_size']

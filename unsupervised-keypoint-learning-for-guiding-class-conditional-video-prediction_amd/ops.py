@@ -14,6 +14,7 @@ import struct as _struct
 import weakref as _weakref
 from fractions import Fraction
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2340,6 +2341,130 @@ def read_guard_health(health):
     raw = health.cpu().numpy().tobytes()
     nonfinite, skipped_total, skipped_run, updates, sumsq, maxabs, _ = struct.unpack('<IIIIdff', raw)
     return dict(nonfinite=nonfinite, skipped_total=skipped_total, skipped_run=skipped_run, updates=updates, sumsq=sumsq, maxabs=maxabs)
+
+
+# ----------------------------------------------------------------------------------------------- gradient norms (train.py --clip-norm / --grad-stats)
+CLIP_STATE_BYTES = 16            # sizeof(KpxClipState), include/kpx.h
+SEG_CHUNK = 16384                # KPX_SEG_CHUNK
+SEG_STATS_BYTES = 32             # sizeof(KpxSegStats)
+
+
+def new_clip_state(device):
+    """One zeroed KpxClipState record in device memory (an int32 [4] tensor: 16 bytes)."""
+    return torch.zeros(CLIP_STATE_BYTES // 4, dtype=torch.int32, device=device)
+
+
+def _require_clip_state(what, clip, dev):
+    if not isinstance(clip, torch.Tensor) or not clip.is_cuda:
+        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(clip, 'device', type(clip)))
+    if clip.dtype != torch.int32 or not clip.is_contiguous() or clip.numel() * 4 != CLIP_STATE_BYTES or clip.device != dev:
+        raise _lib.KpxError('%s: clip must be the int32 [4] record of ops.new_clip_state on %s (got %s %s on %s)'
+                            % (what, dev, clip.dtype, tuple(clip.shape), clip.device))
+
+
+def read_clip_state(clip):
+    """Host copy of a KpxClipState record (synchronises)."""
+    import struct
+    norm, scale, clipped_total, _ = struct.unpack('<ffII', clip.cpu().numpy().tobytes())
+    return dict(norm=norm, scale=scale, clipped_total=clipped_total)
+
+
+def adam_tf_flat_clipped_(p, g, m, v, alpha_dev, beta1, beta2, eps, health, clip, clip_norm, gscale=1.0):
+    """adam_tf_flat_guarded_ with tf.clip_by_global_norm over the bucket: with N = gscale * sqrt(health.sumsq) <= clip_norm the guarded update
+    bit for bit; otherwise the gradient is scaled by clip_norm / N on top of gscale.  ``clip`` (ops.new_clip_state) receives N, the scale and
+    the count of clipped updates; a skipped update leaves it alone."""
+    _require_flat_f32('adam_tf_flat_clipped_: p', p)
+    for name, t in (('g', g), ('m', m), ('v', v)):
+        _require_flat_f32('adam_tf_flat_clipped_: ' + name, t, p.numel())
+    _require_flat_f32('adam_tf_flat_clipped_: alpha_dev', alpha_dev, 1)
+    _require_health('adam_tf_flat_clipped_', health, p.device)
+    _require_clip_state('adam_tf_flat_clipped_', clip, p.device)
+    clip_norm = float(clip_norm)
+    if not clip_norm > 0.0:
+        raise _lib.KpxError('adam_tf_flat_clipped_: clip_norm must be a number > 0 (got %r)' % (clip_norm,))
+    check(lib.kpx_adam_tf_flat_clipped_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), alpha_dev.data_ptr(),
+                                           float(beta1), float(beta2), float(eps), float(gscale), clip_norm, health.data_ptr(),
+                                           clip.data_ptr(), _stream()),
+          'kpx_adam_tf_flat_clipped_f32')
+
+
+def grad_segment_chunks(bucket):
+    """The host half of the segment table of a flat bucket (anything with ``entries``: name -> (offset, shape), and ``size``): every variable
+    [offset, offset + numel) cut into chunks of at most SEG_CHUNK elements counted from the variable's own start.
+    -> (names, chunks int64 [C, 3] of (start, len, seg) ascending in (seg, start), ranges int64 [S, 2] of (first chunk, chunk count))."""
+    names, chunks, ranges = [], [], []
+    for seg, (name, (offset, shape)) in enumerate(bucket.entries.items()):
+        numel = int(np.prod(shape, dtype=np.int64))
+        offset = int(offset)
+        if numel < 1 or offset < 0 or offset + numel > int(bucket.size):
+            raise _lib.KpxError('grad_segment_chunks: variable %s [%d, %d) does not lie in a bucket of %d floats' % (name, offset, offset + numel, bucket.size))
+        names.append(name)
+        ranges.append((len(chunks), (numel + SEG_CHUNK - 1) // SEG_CHUNK))
+        chunks.extend((offset + at, min(SEG_CHUNK, numel - at), seg) for at in range(0, numel, SEG_CHUNK))
+    return names, np.asarray(chunks, dtype=np.int64).reshape(-1, 3), np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+
+
+class SegmentTable:
+    """grad_segment_table's result: ``names`` (bucket order), ``numel`` per variable, ``size`` of the bucket, and on ``device`` the KpxSegChunk
+    [n_chunks] and KpxSegRange [n_segs] records as int64 [n_chunks, 2] and int32 [n_segs, 2] tensors."""
+
+    def __init__(self, names, numel, size, chunks, ranges):
+        self.names, self.numel, self.size, self.chunks, self.ranges = names, numel, size, chunks, ranges
+        self.n_chunks, self.n_segs = int(chunks.shape[0]), int(ranges.shape[0])
+
+
+def grad_segment_table(bucket, device):
+    """The segment table of ``bucket`` in ``device`` memory, built once (BaseModel._grad_stats_init does it at build())."""
+    names, chunks, ranges = grad_segment_chunks(bucket)
+    if not names:
+        raise _lib.KpxError('grad_segment_table: the bucket holds no variable')
+    packed = np.stack([chunks[:, 0], chunks[:, 1] | (chunks[:, 2] << 32)], axis=1)          # (uint64 start, uint32 len, uint32 seg), little-endian
+    numel = [int(n) for n in np.add.reduceat(chunks[:, 1], ranges[:, 0])]
+    return SegmentTable(names, numel, int(bucket.size), torch.from_numpy(np.ascontiguousarray(packed)).to(device),
+                        torch.from_numpy(ranges.astype(np.int32)).to(device))
+
+
+def grad_segment_workspace(table, device):
+    """(work, out) of one grad_segment_stats call over ``table``: the partials' workspace and the KpxSegStats [n_segs] records (int64 [n_segs, 4])."""
+    need = int(lib.kpx_grad_segment_stats_workspace_bytes(table.n_chunks))
+    return (torch.empty(max(need // 8, 1), dtype=torch.float64, device=device),
+            torch.zeros((table.n_segs, SEG_STATS_BYTES // 8), dtype=torch.int64, device=device))
+
+
+def grad_segment_stats(grads, params, table, work=None, out=None):
+    """Per-variable sum of g^2 and of p^2 (fp64), largest finite |g| and count of non-finite g over the flat bucket ``grads`` (and ``params``, or
+    None: sumsq_p = 0), by ``table`` (kpx_grad_segment_stats_f32: two launches, no atomics, bitwise reproducible).  -> ``out``, the device
+    records; read_segment_stats makes them host numbers."""
+    _require_flat_f32('grad_segment_stats: grads', grads)
+    if params is not None:
+        _require_flat_f32('grad_segment_stats: params', params, grads.numel())
+        if params.device != grads.device:
+            raise _lib.KpxError('grad_segment_stats: grads and params must be on one device (got %s, %s)' % (grads.device, params.device))
+    if not isinstance(table, SegmentTable) or table.chunks.device != grads.device or table.ranges.device != grads.device:
+        raise _lib.KpxError('grad_segment_stats: table must be the ops.grad_segment_table of the bucket on %s' % (grads.device,))
+    if table.size > grads.numel():
+        raise _lib.KpxError('grad_segment_stats: the table describes a bucket of %d floats, grads holds %d' % (table.size, grads.numel()))
+    if work is None or out is None:
+        w, o = grad_segment_workspace(table, grads.device)
+        work, out = (w if work is None else work), (o if out is None else out)
+    need = int(lib.kpx_grad_segment_stats_workspace_bytes(table.n_chunks))
+    if (not isinstance(work, torch.Tensor) or not work.is_cuda or work.device != grads.device or not work.is_contiguous()
+            or work.numel() * work.element_size() < need or work.data_ptr() % 8):
+        raise _lib.KpxError('grad_segment_stats: work must be a contiguous 8-byte aligned tensor of at least %d bytes on %s' % (need, grads.device))
+    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != grads.device or out.dtype != torch.int64 or not out.is_contiguous()
+            or out.numel() * 8 != table.n_segs * SEG_STATS_BYTES):
+        raise _lib.KpxError('grad_segment_stats: out must be the int64 [%d, 4] records of ops.grad_segment_workspace on %s' % (table.n_segs, grads.device))
+    check(lib.kpx_grad_segment_stats_f32(grads.data_ptr(), _ptr(params), grads.numel(), table.chunks.data_ptr(), table.n_chunks,
+                                         table.ranges.data_ptr(), table.n_segs, work.data_ptr(), out.data_ptr(), _stream()),
+          'kpx_grad_segment_stats_f32')
+    return out
+
+
+def read_segment_stats(out):
+    """Host copy of KpxSegStats records (synchronises) -> dict of arrays sumsq_g, sumsq_p (float64), maxabs_g (float32), nonfinite_g (uint32)."""
+    rec = np.frombuffer(out.cpu().numpy().tobytes(), dtype=np.dtype([('sumsq_g', '<f8'), ('sumsq_p', '<f8'), ('maxabs_g', '<f4'),
+                                                                      ('nonfinite_g', '<u4'), ('pad_', '<u4', (2,))]))
+    return {k: rec[k].copy() for k in ('sumsq_g', 'sumsq_p', 'maxabs_g', 'nonfinite_g')}
 
 
 # ----------------------------------------------------------------------------------------------- averaged generator (train.py --ema)
