@@ -715,6 +715,8 @@ int kpx_conv3x3_wgrad_bf16(const void* x, int N, int H, int W, int Cin, int ldx,
  * kind 3 = f32 -> bf16 into a contiguous 8-channel tensor (lddst = 8, C <= 8) whose channels C .. 7 are written as zeros. */
 int kpx_cast_channels(const void* src, int ldsrc, void* dst, int lddst, size_t P, int C, int kind, void* stream);
 int kpx_chan_sum_bf16(const void* x, size_t P, int C, int ldx, float* sum_out, void* scratch, void* stream);
+/* dz = dy * act'(y) on bf16 tensors, n % 8 == 0; act in {KPX_ACT_NONE, KPX_ACT_RELU, KPX_ACT_LRELU}.  Unlike kpx_act_bwd_f32 it has no tanh
+ * backward: KPX_ACT_TANH and any other value are refused with KPX_EINVAL (nothing is written). */
 int kpx_act_bwd_bf16(const void* dy, const void* y, void* dz, size_t n, int act, void* stream);
 int kpx_resize2x_fwd_bf16(const void* x, int N, int H, int W, int C, int ldx, void* y, int ldy, void* stream);
 int kpx_resize2x_bwd_bf16(const void* dy, int N, int H, int W, int C, int lddy, void* dx, int lddx, void* stream);

@@ -1181,7 +1181,8 @@ extern "C" int kpx_bn_train_bwd_bf16(const void* dy, int lddy, int dy_f32, const
     return kpx_launch_status();
 }
 
-// ---- activation backward: dz = dy * act'(y) on bf16 tensors (n multiple of 8)
+// ---- activation backward: dz = dy * act'(y) on bf16 tensors (n multiple of 8); act none / relu / leaky_relu only: kpx_act_grad_from_y has no
+//      tanh (it would come out as the identity), so the entry refuses it
 __global__ __launch_bounds__(256) void act_bwd_bf16_kernel(const bf16_t* dy, const bf16_t* y, bf16_t* dz, size_t n8, int act) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
         float g[8], v[8];
@@ -1192,7 +1193,7 @@ __global__ __launch_bounds__(256) void act_bwd_bf16_kernel(const bf16_t* dy, con
     }
 }
 extern "C" int kpx_act_bwd_bf16(const void* dy, const void* y, void* dz, size_t n, int act, void* stream) {
-    if (!dy || !y || !dz || n % 8 || !kpx_aligned16(dy, y, dz)) return KPX_EINVAL;
+    if (!dy || !y || !dz || n % 8 || act < KPX_ACT_NONE || act > KPX_ACT_LRELU || !kpx_aligned16(dy, y, dz)) return KPX_EINVAL;
     if (n == 0) return 0;
     hipLaunchKernelGGL(act_bwd_bf16_kernel, dim3(grid_for(n / 8)), dim3(256), 0, kpx_stream(stream), (const bf16_t*)dy, (const bf16_t*)y, (bf16_t*)dz, n / 8, act);
     return kpx_launch_status();
