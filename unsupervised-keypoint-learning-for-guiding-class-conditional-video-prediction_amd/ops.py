@@ -7,6 +7,10 @@ library fails at import (``_lib``) and a failed launch raises ``KpxError``.
 Weight / bias / gamma / beta gradients are written by the kernels straight into caller-provided views of the
 flat gradient bucket (``*_grad_out``), so the RCCL all-reduce and the fused Adam step run on one contiguous buffer
 without a gather pass.
+
+This module holds what runs inside a train step.  The forward-only wrappers of the evaluation tools live in ``tool_ops`` and are
+re-exported here (``ops.sheet_paste`` ...); the stream, the scratch buffers and the argument checker of the per-batch wrappers live in
+``_args``.  The wrappers that run once per launch (convolutions, batch norm, losses) check their tensors by hand: DESIGN.md section 1.
 """
 import collections as _collections
 import os as _os
@@ -19,26 +23,12 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
+from ._args import OPTIONAL, _Scratch, _ptr, _stream, _workspace, check_tensors, scratch      # noqa: F401 (ops._stream, ops.scratch ... are public)
+from .tool_ops import *      # noqa: F401,F403 -- the forward-only wrappers of the evaluation tools and their constants: ops.sheet_paste, ops.MAX_DRAWS ...
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 BN_EPS = 1e-5        # reference: models/networks/layers.py:14
 BN_DECAY = 0.999     # tf.contrib.layers.batch_norm default
-
-
-# raw handle of torch's current HIP stream on the current device: the private accessors are ~10x cheaper than
-# torch.cuda.current_stream().cuda_stream, which was 2 x 2 ms of host time per train step (one lookup per kernel launch)
-_raw_stream = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-_cur_device = getattr(torch._C, '_cuda_getDevice', None)
-
-
-def _stream():
-    if _raw_stream is not None and _cur_device is not None:
-        return _raw_stream(_cur_device())
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _require_gpu(t):
@@ -67,33 +57,6 @@ def _nhwc(t):
         t = t.contiguous()
         ld = c
     return t, ld
-
-
-class _Scratch:
-    """Per-device, per-stream scratch buffers; kernels on one stream are ordered, so consecutive ops may share them."""
-
-    def __init__(self):
-        self._bufs = {}
-
-    def get(self, key, nbytes, device):
-        k = (key, device, _stream())
-        b = self._bufs.get(k)
-        if b is None or b.numel() < nbytes:
-            b = torch.empty(int(max(nbytes, 1 << 16)), dtype=torch.uint8, device=device)
-            self._bufs[k] = b
-        return b
-
-    def reduce(self, c, device):
-        return self.get('reduce', lib.kpx_chan_reduce_scratch_bytes(int(c)), device)
-
-
-scratch = _Scratch()
-
-
-def _workspace(key, nbytes, device):
-    """The (workspace, workspace_bytes) arguments of an entry whose *_workspace_bytes query answered ``nbytes``: the scratch buffer ``key``
-    of the current stream, or (None, 0) where the launch needs none."""
-    return (scratch.get(key, nbytes, device).data_ptr() if nbytes else None), nbytes
 
 
 def _took(rc, entry):
@@ -1309,726 +1272,6 @@ def gaussian_maps(mu, h, w, inv_std=14.3):
     return GaussianMapsFn.apply(mu, h, w, inv_std)
 
 
-def point_maps_rgb(mu, h, w, colors, inv_std=14.3, out=None):
-    """colorize_point_maps(get_gaussian_maps(mu, [h, w], inv_std), colors) (reference utils/model.py:42-60) in one launch, forward only:
-    mu [N,K,2] (x,y), colors [K,3] fp32 on mu's device -> [N,h,w,3].  The Gaussian factor has the bits of ``gaussian_maps``."""
-    _require_gpu(mu)
-    _require_gpu(colors)
-    mu = mu.contiguous()
-    colors = colors.contiguous()
-    n, k, _ = mu.shape
-    if mu.dtype != torch.float32 or colors.dtype != torch.float32 or tuple(colors.shape) != (k, 3) or colors.device != mu.device:
-        raise _lib.KpxError('point_maps_rgb: mu [N,K,2] and colors [K,3], fp32 on one device (got %s %s, %s %s)'
-                            % (tuple(mu.shape), mu.dtype, tuple(colors.shape), colors.dtype))
-    if out is None:
-        out = torch.empty((n, h, w, 3), dtype=torch.float32, device=mu.device)
-    elif tuple(out.shape) != (n, h, w, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != mu.device:
-        raise _lib.KpxError('point_maps_rgb: out must be a contiguous fp32 [%d,%d,%d,3] tensor on %s' % (n, h, w, mu.device))
-    check(lib.kpx_point_maps_rgb_f32(mu.data_ptr(), n, k, int(h), int(w), float(inv_std), colors.data_ptr(), out.data_ptr(), _stream()),
-          'kpx_point_maps_rgb_f32')
-    return out
-
-
-def point_seq_strip_rgb(mu, h, w, colors, recolour=True, inv_std=14.3, max_outputs=None):
-    """The reference's pose-sequence strip (motion_generator_model.py:225-248, 258-263) in one launch, forward only: mu [N,T,K,2] (x,y)
-    -> [N,h,T*w,3], frame t (= ``point_maps_rgb`` of mu[:, t], same bits) in columns [t*w, (t+1)*w).  ``recolour``: the summary's second
-    colorize_point_maps over the 3-channel strip, out[...,c] = max_{i<3} strip[...,i] * colors[i][c] (K >= 3).  ``max_outputs``: render
-    only the first images."""
-    _require_gpu(mu)
-    _require_gpu(colors)
-    if mu.dim() != 4 or mu.shape[3] != 2:
-        raise _lib.KpxError('point_seq_strip_rgb: mu must be [N,T,K,2] (got %s)' % (tuple(mu.shape),))
-    if max_outputs is not None:
-        mu = mu[:max_outputs]
-    mu = mu.contiguous()
-    colors = colors.contiguous()
-    n, t, k, _ = mu.shape
-    if mu.dtype != torch.float32 or colors.dtype != torch.float32 or tuple(colors.shape) != (k, 3) or colors.device != mu.device:
-        raise _lib.KpxError('point_seq_strip_rgb: mu [N,T,K,2] and colors [K,3], fp32 on one device (got %s %s, %s %s)'
-                            % (tuple(mu.shape), mu.dtype, tuple(colors.shape), colors.dtype))
-    if recolour and k < 3:
-        raise _lib.KpxError('point_seq_strip_rgb: the recolour reads colors[0:3] and needs K >= 3 (got K = %d)' % k)
-    out = torch.empty((n, h, t * w, 3), dtype=torch.float32, device=mu.device)
-    check(lib.kpx_point_seq_strip_rgb_f32(mu.data_ptr(), n, t, k, int(h), int(w), float(inv_std), colors.data_ptr(), 1 if recolour else 0,
-                                          out.data_ptr(), _stream()), 'kpx_point_seq_strip_rgb_f32')
-    return out
-
-
-SUMMARY_PREMAPS = {'identity': 0, 'x255': 1, 'unit255': 2, 'unit255_clip': 3}   # = KPX_PREMAP_* of include/kpx.h
-SUMMARY_SLICES = 64                                                               # = KPX_SUMMARY_SLICES
-
-
-def summary_image_u8(x, premap='identity', max_outputs=2):
-    """tf.summary.image's float -> uint8 conversion (TF 1.12 SummaryImageOp / NormalizeFloatImage) of the first ``max_outputs`` images of
-    x [N,H,W,C] fp32 (C in 1, 3, 4), after the pre-map ``premap``: 'identity' x, 'x255' x*255 (the mask), 'unit255' (x+1)/2*255 (the
-    input frames), 'unit255_clip' clip((x+1)/2*255, 0, 255) (the predictions).  -> uint8 [min(N, max_outputs),H,W,C] on x's device."""
-    _require_gpu(x)
-    if premap not in SUMMARY_PREMAPS:
-        raise _lib.KpxError('summary_image_u8: premap must be one of %s (got %r)' % (sorted(SUMMARY_PREMAPS), premap))
-    if x.dim() != 4 or x.dtype != torch.float32 or x.shape[3] not in (1, 3, 4) or x.shape[0] < 1 or x.shape[1] < 1 or x.shape[2] < 1:
-        raise _lib.KpxError('summary_image_u8: x must be a non-empty fp32 [N,H,W,C] tensor with C in (1, 3, 4) (got %s %s)'
-                            % (tuple(x.shape), x.dtype))
-    if int(max_outputs) < 1:
-        raise _lib.KpxError('summary_image_u8: max_outputs must be >= 1 (got %r)' % (max_outputs,))
-    x = x[:int(max_outputs)].contiguous()
-    n, h, w, c = x.shape
-    work = torch.empty(2 * SUMMARY_SLICES * n, dtype=torch.float32, device=x.device)
-    out = torch.empty((n, h, w, c), dtype=torch.uint8, device=x.device)
-    check(lib.kpx_summary_image_u8_f32(x.data_ptr(), n, h, w, c, SUMMARY_PREMAPS[premap], work.data_ptr(), out.data_ptr(), _stream()),
-          'kpx_summary_image_u8_f32')
-    return out
-
-
-def frame_metrics(a, b, max_val=1.0, png8=False, out=None):
-    """Per-frame SSIM, MSE and PSNR (TF 1.12 tf.image.ssim / tf.image.psnr) of a against b, both contiguous fp32
-    [N,H,W,C] on one device, C in (1, 3), H and W in [11, 1024], dynamic range ``max_val`` > 0 -> fp32 [N,3] = (ssim, mse, psnr) on that
-    device, in one launch.  ``png8``: score the 8-bit frames evaluate.py writes (each value quantised as ``_save_img(rescale=True)``,
-    scored as q / 255 with max_val 1).  ``out``: a contiguous fp32 [N,3] tensor to write into."""
-    for t in (a, b):
-        _require_gpu(t)
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.KpxError('frame_metrics: a and b must be contiguous fp32 tensors (got %s, contiguous=%s)' % (t.dtype, t.is_contiguous()))
-    if a.dim() != 4 or tuple(a.shape) != tuple(b.shape) or a.device != b.device:
-        raise _lib.KpxError('frame_metrics: a and b must be [N,H,W,C] of one shape on one device (got %s on %s, %s on %s)'
-                            % (tuple(a.shape), a.device, tuple(b.shape), b.device))
-    n, h, w, c = a.shape
-    if n < 1 or not (11 <= h <= 1024 and 11 <= w <= 1024) or c not in (1, 3):
-        raise _lib.KpxError('frame_metrics: needs N >= 1, H and W in [11, 1024] and C in (1, 3) (got %s)' % (tuple(a.shape),))
-    L = float(max_val)
-    if not (0.0 < L < float('inf')):
-        raise _lib.KpxError('frame_metrics: max_val must be a finite value > 0 (got %r)' % (max_val,))
-    if out is None:
-        out = torch.empty((n, 3), dtype=torch.float32, device=a.device)
-    elif tuple(out.shape) != (n, 3) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a.device:
-        raise _lib.KpxError('frame_metrics: out must be a contiguous fp32 [%d,3] tensor on %s' % (n, a.device))
-    check(lib.kpx_frame_metrics_f32(a.data_ptr(), b.data_ptr(), n, h, w, c, L, 1 if png8 else 0, out.data_ptr(), _stream()),
-          'kpx_frame_metrics_f32')
-    return out
-
-
-def feature_pair_metrics(fa, fb, out=None):
-    """Per-frame VGG feature-space metrics of one layer's features fa against fb, both contiguous fp32 [N,H,W,C] on
-    one device at 16-byte aligned addresses, C a multiple of 4 in [4, 512], H and W in [1, 1024] -> fp32 [N,2] = (cos_layer, l1_layer): the
-    mean over positions of the channel cosine (1 where both sides are zero, 0 where one is) and the mean of |a - b|.  ``out``: a contiguous
-    fp32 [N,2] tensor to write into.  Two launches on the current stream; frame n's result is bitwise independent of the batch."""
-    for t in (fa, fb):
-        _require_gpu(t)
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.KpxError('feature_pair_metrics: fa and fb must be contiguous fp32 tensors (got %s, contiguous=%s)'
-                                % (t.dtype, t.is_contiguous()))
-    if fa.dim() != 4 or tuple(fa.shape) != tuple(fb.shape) or fa.device != fb.device:
-        raise _lib.KpxError('feature_pair_metrics: fa and fb must be [N,H,W,C] of one shape on one device (got %s on %s, %s on %s)'
-                            % (tuple(fa.shape), fa.device, tuple(fb.shape), fb.device))
-    n, h, w, c = fa.shape
-    if n < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c % 4 or not 4 <= c <= 512:
-        raise _lib.KpxError('feature_pair_metrics: needs N >= 1, H and W in [1, 1024] and C a multiple of 4 in [4, 512] (got %s)'
-                            % (tuple(fa.shape),))
-    if fa.data_ptr() % 16 or fb.data_ptr() % 16:
-        raise _lib.KpxError('feature_pair_metrics: fa and fb must start on 16-byte boundaries')
-    if out is None:
-        out = torch.empty((n, 2), dtype=torch.float32, device=fa.device)
-    elif tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != fa.device:
-        raise _lib.KpxError('feature_pair_metrics: out must be a contiguous fp32 [%d,2] tensor on %s' % (n, fa.device))
-    work = scratch.get('feature_pair', lib.kpx_feature_pair_metrics_workspace_bytes(n, h, w, c), fa.device)
-    check(lib.kpx_feature_pair_metrics_f32(fa.data_ptr(), fb.data_ptr(), n, h, w, c, work.data_ptr(), out.data_ptr(), _stream()),
-          'kpx_feature_pair_metrics_f32')
-    return out
-
-
-def feature_pool(f, out=None):
-    """The mean over the H * W positions of one layer's features (the Fréchet distance): f contiguous fp32 [N,H,W,C]
-    at a 16-byte aligned address, C a multiple of 4 in [4, 512], H and W in [1, 1024] -> fp64 [N,C], every value converted to fp64 before
-    its first addition.  ``out``: a contiguous fp64 [N,C] tensor to write into.  Two launches on the current stream; frame n's row is
-    bitwise independent of the batch."""
-    if not f.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % f.device)
-    if f.dtype != torch.float32 or not f.is_contiguous():
-        raise _lib.KpxError('feature_pool: f must be a contiguous fp32 tensor (got %s, contiguous=%s)' % (f.dtype, f.is_contiguous()))
-    if f.dim() != 4:
-        raise _lib.KpxError('feature_pool: f must be [N,H,W,C] (got %s)' % (tuple(f.shape),))
-    n, h, w, c = f.shape
-    if n < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c % 4 or not 4 <= c <= 512:
-        raise _lib.KpxError('feature_pool: needs N >= 1, H and W in [1, 1024] and C a multiple of 4 in [4, 512] (got %s)' % (tuple(f.shape),))
-    if f.data_ptr() % 16:
-        raise _lib.KpxError('feature_pool: f must start on a 16-byte boundary')
-    if out is None:
-        out = torch.empty((n, c), dtype=torch.float64, device=f.device)
-    elif tuple(out.shape) != (n, c) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != f.device:
-        raise _lib.KpxError('feature_pool: out must be a contiguous fp64 [%d,%d] tensor on %s' % (n, c, f.device))
-    work = scratch.get('feature_pool', lib.kpx_feature_pool_workspace_bytes(n, h, w, c), f.device)
-    check(lib.kpx_feature_pool_f64(f.data_ptr(), n, h, w, c, work.data_ptr(), out.data_ptr(), _stream()), 'kpx_feature_pool_f64')
-    return out
-
-
-MAX_MOMENT_ROWS, MAX_MOMENT_DIM = 1 << 20, 1024                                   # kpx_moments_add_f64's limits on M and D
-
-
-def moments_add(x, sum, outer):
-    """Rows into the moment accumulators of the Fréchet distance: x contiguous fp64 [M,D], 1 <= M <= 2^20,
-    1 <= D <= 1024; sum [D] += the column sums, outer [D,D] += x^T x, both contiguous fp64 on x's device, zeroed by the caller before the
-    first call.  One launch on the current stream; each element adds the rows in ascending order, so the result is bitwise reproducible
-    and ``outer`` stays bitwise symmetric.  -> (sum, outer)."""
-    for t in (x, sum, outer):
-        if not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % t.device)
-        if t.dtype != torch.float64 or not t.is_contiguous():
-            raise _lib.KpxError('moments_add: x, sum and outer must be contiguous fp64 tensors (got %s, contiguous=%s)'
-                                % (t.dtype, t.is_contiguous()))
-    if x.dim() != 2 or not 1 <= x.shape[0] <= MAX_MOMENT_ROWS or not 1 <= x.shape[1] <= MAX_MOMENT_DIM:
-        raise _lib.KpxError('moments_add: x must be [M,D] with 1 <= M <= %d and 1 <= D <= %d (got %s)'
-                            % (MAX_MOMENT_ROWS, MAX_MOMENT_DIM, tuple(x.shape)))
-    m, d = x.shape
-    if tuple(sum.shape) != (d,) or tuple(outer.shape) != (d, d) or sum.device != x.device or outer.device != x.device:
-        raise _lib.KpxError('moments_add: sum must be [%d] and outer [%d,%d] on %s (got %s on %s, %s on %s)'
-                            % (d, d, d, x.device, tuple(sum.shape), sum.device, tuple(outer.shape), outer.device))
-    if x.data_ptr() % 8 or sum.data_ptr() % 8 or outer.data_ptr() % 8:
-        raise _lib.KpxError('moments_add: x, sum and outer must start on 8-byte boundaries')
-    check(lib.kpx_moments_add_f64(x.data_ptr(), m, d, sum.data_ptr(), outer.data_ptr(), _stream()), 'kpx_moments_add_f64')
-    return sum, outer
-
-
-MAX_DRAWS = 4096                                                                 # draws of z the uint32 accumulators hold exactly
-
-
-def _draw_accumulators(what, sum, sumsq):
-    for t in (sum, sumsq):
-        if not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % t.device)
-        if t.dtype != torch.int32 or not t.is_contiguous():
-            raise _lib.KpxError('%s: sum and sumsq must be contiguous int32 tensors (got %s, contiguous=%s)' % (what, t.dtype, t.is_contiguous()))
-    if sum.numel() != sumsq.numel() or sum.device != sumsq.device:
-        raise _lib.KpxError('%s: sum and sumsq must have one size on one device (got %d on %s, %d on %s)'
-                            % (what, sum.numel(), sum.device, sumsq.numel(), sumsq.device))
-
-
-def draw_moments_add(x, sum, sumsq):
-    """One draw of z into the accumulators of the draw diversity: per value of x (contiguous fp32, any shape), the
-    8-bit value q evaluate.py writes (as ``frame_metrics(png8=True)``): sum += q, sumsq += q * q.  ``sum`` / ``sumsq``: contiguous int32
-    tensors (the bits of uint32) of x's size on x's device, zeroed before the first draw; exact for up to 4096 draws.  One launch."""
-    _require_gpu(x)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise _lib.KpxError('draw_moments_add: x must be a contiguous fp32 tensor (got %s, contiguous=%s)' % (x.dtype, x.is_contiguous()))
-    _draw_accumulators('draw_moments_add', sum, sumsq)
-    if sum.numel() != x.numel() or sum.device != x.device:
-        raise _lib.KpxError('draw_moments_add: the accumulators must have the size and device of x (got %d on %s for %d on %s)'
-                            % (sum.numel(), sum.device, x.numel(), x.device))
-    if sum.data_ptr() == sumsq.data_ptr() and x.numel():
-        raise _lib.KpxError('draw_moments_add: sum and sumsq must be two buffers')
-    check(lib.kpx_draw_moments_add_f32(x.data_ptr(), x.numel(), sum.data_ptr(), sumsq.data_ptr(), _stream()), 'kpx_draw_moments_add_f32')
-
-
-def draw_diversity(sum, sumsq, draws, frame_shape, std_map=False, out=None):
-    """The diversity of ``draws`` draws of z from the accumulators ``draw_moments_add`` filled.  ``frame_shape`` =
-    (H, W, C) of one frame, C in (1, 3), H and W in [1, 1024]; the accumulators hold N = numel / (H W C) >= 1 frames; 2 <= draws <= 4096.
-    -> div_mse fp32 [N]: per frame the mean over pairs of draws of the MSE between their 8-bit frames (q / 255 scale), exact up to its one
-    rounding.  ``std_map``: also the per-pixel spread uint8 [N,H,W] = floor(2 * sqrt(mean over channels of the variance of q)), capped at
-    255 -> (div_mse, std_map); True allocates it, a contiguous uint8 [N,H,W] tensor is written into.  ``out``: a contiguous fp32 [N]
-    tensor for div_mse.  One launch."""
-    _draw_accumulators('draw_diversity', sum, sumsq)
-    try:
-        h, w, c = (int(v) for v in frame_shape)
-        d = int(draws)
-    except (TypeError, ValueError):
-        raise _lib.KpxError('draw_diversity: frame_shape must be (H, W, C) and draws an integer (got %r, %r)' % (frame_shape, draws))
-    if not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
-        raise _lib.KpxError('draw_diversity: needs H and W in [1, 1024] and C in (1, 3) (got %r)' % (tuple(frame_shape),))
-    if not 2 <= d <= MAX_DRAWS:
-        raise _lib.KpxError('draw_diversity: needs 2 <= draws <= %d (got %d)' % (MAX_DRAWS, d))
-    n = sum.numel() // (h * w * c)
-    if n < 1 or n * h * w * c != sum.numel():
-        raise _lib.KpxError('draw_diversity: the accumulators must hold N >= 1 frames of %d x %d x %d (got %d values)' % (h, w, c, sum.numel()))
-    dev = sum.device
-    if out is None:
-        out = torch.empty((n,), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (n,) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
-        raise _lib.KpxError('draw_diversity: out must be a contiguous fp32 [%d] tensor on %s' % (n, dev))
-    smap = None
-    if isinstance(std_map, torch.Tensor):
-        smap = std_map
-        if tuple(smap.shape) != (n, h, w) or smap.dtype != torch.uint8 or not smap.is_contiguous() or smap.device != dev:
-            raise _lib.KpxError('draw_diversity: std_map must be a contiguous uint8 [%d,%d,%d] tensor on %s' % (n, h, w, dev))
-    elif std_map:
-        smap = torch.empty((n, h, w), dtype=torch.uint8, device=dev)
-    check(lib.kpx_draw_diversity_f32(sum.data_ptr(), sumsq.data_ptr(), n, h, w, c, d, out.data_ptr(), _ptr(smap), _stream()),
-          'kpx_draw_diversity_f32')
-    return out if smap is None else (out, smap)
-
-
-def keypoint_draw_metrics(pts, real, diversity=True, out=None):
-    """Key-point error and diversity of D draws of z: pts contiguous fp32 [D,N,T,K,2], real contiguous fp32 [N,T,K,2]
-    (the labels) on one device, D <= 4096 -> (l2, div): l2 fp32 [D,N,T] = the mean over the K points of the Euclidean distance to the label,
-    div fp32 [N,T] = the mean over pairs of draws and points of the distance between the draws (None with ``diversity=False``; needs
-    D >= 2).  fp64 arithmetic in a fixed order, rounded once.  ``out``: (l2, div) tensors to write into.  One launch."""
-    for t in (pts, real):
-        _require_gpu(t)
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.KpxError('keypoint_draw_metrics: pts and real must be contiguous fp32 tensors (got %s, contiguous=%s)'
-                                % (t.dtype, t.is_contiguous()))
-    if pts.dim() != 5 or real.dim() != 4 or tuple(pts.shape[1:]) != tuple(real.shape) or pts.shape[4] != 2 or pts.device != real.device:
-        raise _lib.KpxError('keypoint_draw_metrics: pts must be [D,N,T,K,2] and real [N,T,K,2] on one device (got %s on %s, %s on %s)'
-                            % (tuple(pts.shape), pts.device, tuple(real.shape), real.device))
-    d, n, t, k, _ = pts.shape
-    if min(d, n, t, k) < 1 or d > MAX_DRAWS:
-        raise _lib.KpxError('keypoint_draw_metrics: needs 1 <= D <= %d and N, T, K >= 1 (got %s)' % (MAX_DRAWS, tuple(pts.shape)))
-    if diversity and d < 2:
-        raise _lib.KpxError('keypoint_draw_metrics: the diversity needs D >= 2 draws (got %d); pass diversity=False' % d)
-    l2, div = out if out is not None else (None, None)
-    if l2 is None:
-        l2 = torch.empty((d, n, t), dtype=torch.float32, device=pts.device)
-    if diversity and div is None:
-        div = torch.empty((n, t), dtype=torch.float32, device=pts.device)
-    for name, o, shape in (('l2', l2, (d, n, t)), ('div', div, (n, t))):
-        if o is None:
-            continue
-        if name == 'div' and not diversity:
-            raise _lib.KpxError('keypoint_draw_metrics: out has a div tensor but diversity=False')
-        if tuple(o.shape) != shape or o.dtype != torch.float32 or not o.is_contiguous() or o.device != pts.device:
-            raise _lib.KpxError('keypoint_draw_metrics: out %s must be a contiguous fp32 %s tensor on %s' % (name, list(shape), pts.device))
-    check(lib.kpx_keypoint_draw_metrics_f32(pts.data_ptr(), real.data_ptr(), d, n, t, k, l2.data_ptr(), _ptr(div), _stream()),
-          'kpx_keypoint_draw_metrics_f32')
-    return l2, div
-
-
-SHEET_PREMAPS = {'unit': 0, 'raw': 1}                                             # = KPX_SHEET_* of include/kpx.h
-SHEET_MAX_FRAMES = 64                                                             # = KPX_SHEET_MAX_FRAMES
-
-
-def sheet_paste(canvas, src, frames, row, col, premap):
-    """Frames of a rollout into a contact sheet, as the bytes evaluate.py writes.  canvas: contiguous uint8
-    [B, rows*H, cols*W, 3]; src: contiguous fp32 [B,F,H,W,C], C in (1, 3) (C = 1 goes to the three channels), on canvas's device; frames:
-    1 <= J <= 64 ints in [0, F), any order, repeats allowed.  canvas[b, row*H:(row+1)*H, (col+j)*W:(col+j+1)*W] = q(src[b, frames[j]]) for
-    every b and j; nothing else is written.  ``premap``: 'unit' the bytes of ``_save_img(rescale=True)`` (``frame_metrics(png8=True)``'s
-    quantiser), 'raw' those of ``_save_img(rescale=False)`` for values in [0, 1]; both clamp to [0, 255] and send NaN to 0.  rows and cols
-    (from the canvas shape) in [1, 64], H and W in [1, 1024], row < rows, col + J <= cols.  One launch on the current stream; the frame
-    indices travel in the launch arguments (capturable)."""
-    for name, t, dtype, dim in (('canvas', canvas, torch.uint8, 4), ('src', src, torch.float32, 5)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got %s for sheet_paste\'s %s); there is no CPU fallback'
-                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
-        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
-            raise _lib.KpxError('sheet_paste: %s must be a contiguous %s tensor of %d dimensions (got %s %s, contiguous=%s)'
-                                % (name, dtype, dim, tuple(t.shape), t.dtype, t.is_contiguous()))
-    if canvas.device != src.device:
-        raise _lib.KpxError('sheet_paste: canvas and src must be on one device (got %s and %s)' % (canvas.device, src.device))
-    if premap not in SHEET_PREMAPS:
-        raise _lib.KpxError('sheet_paste: premap must be one of %s (got %r)' % (sorted(SHEET_PREMAPS), premap))
-    b, f, h, w, c = src.shape
-    if b < 1 or f < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
-        raise _lib.KpxError('sheet_paste: src needs B, F >= 1, H and W in [1, 1024] and C in (1, 3) (got %s)' % (tuple(src.shape),))
-    if canvas.shape[0] != b or canvas.shape[3] != 3 or canvas.shape[1] % h or canvas.shape[2] % w:
-        raise _lib.KpxError('sheet_paste: canvas must be [%d, rows * %d, cols * %d, 3] (got %s)' % (b, h, w, tuple(canvas.shape)))
-    rows, cols = canvas.shape[1] // h, canvas.shape[2] // w
-    if not (1 <= rows <= 64 and 1 <= cols <= 64):
-        raise _lib.KpxError('sheet_paste: a sheet has 1 to 64 rows and columns of cells (got %d x %d)' % (rows, cols))
-    try:
-        idx = [int(v) for v in frames]
-        row, col = int(row), int(col)
-    except (TypeError, ValueError):
-        raise _lib.KpxError('sheet_paste: frames must be a sequence of integers, row and col integers (got %r, %r, %r)' % (frames, row, col))
-    if any(i != v for i, v in zip(idx, frames)):
-        raise _lib.KpxError('sheet_paste: frames must be integers (got %r)' % (frames,))
-    if not 1 <= len(idx) <= SHEET_MAX_FRAMES or any(not 0 <= i < f for i in idx):
-        raise _lib.KpxError('sheet_paste: needs 1 to %d frame indices in [0, %d) (got %r)' % (SHEET_MAX_FRAMES, f, idx))
-    if not 0 <= row < rows or col < 0 or col + len(idx) > cols:
-        raise _lib.KpxError('sheet_paste: %d cells from (row %d, col %d) do not fit a sheet of %d x %d cells' % (len(idx), row, col, rows, cols))
-    check(lib.kpx_sheet_paste_u8_f32(src.data_ptr(), b, f, h, w, c, (_lib.c_int * len(idx))(*idx), len(idx), canvas.data_ptr(), rows, cols,
-                                     row, col, SHEET_PREMAPS[premap], _stream()), 'kpx_sheet_paste_u8_f32')
-    return canvas
-
-
-CELL_MAX_POINTS = 64                                                              # markers per frame of kpx_cell_frames_u8_f32
-CELL_MAX_RADIUS = 16
-
-
-def cell_frames(canvas, first, seq, row, col, premap, pts_first=None, pts_seq=None, colors=None, radius=0):
-    """One cell of an animated grid, optionally with key-point markers (DESIGN.md sections 2 and 4.4).  canvas: contiguous uint8
-    [B, T+1, rows*H, cols*W, 3]; first: contiguous fp32 [B,H,W,C] and seq: contiguous fp32 [B,T,H,W,C], C in (1, 3), on canvas's device.
-    canvas[b, 0, cell] = q(first[b]) and canvas[b, t+1, cell] = q(seq[b, t]) with ``premap`` as in ``sheet_paste``; nothing outside cell
-    (row, col) is written.  ``radius`` r in [1, 16]: pts_first fp32 [B,K,2] and pts_seq fp32 [B,T,K,2] (x, y in [-1, 1], the convention of
-    ``gaussian_maps``), 1 <= K <= 64, and colors uint8 [K,3] on the device draw a disc of radius r - 1 in colors[k] with a one-pixel black
-    outline at every key point (centres in 1/16 pixel, integer distances, the lowest k on top, clipped to the cell; a non-finite point or
-    one beyond +-4 draws nothing).  r = 0 draws none and takes no points.  rows and cols (from the canvas shape) in [1, 64], H and W in
-    [1, 1024].  One launch on the current stream; capturable."""
-    for name, t, dtype, dim in (('canvas', canvas, torch.uint8, 5), ('first', first, torch.float32, 4), ('seq', seq, torch.float32, 5)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got %s for cell_frames\'s %s); there is no CPU fallback'
-                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
-        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous():
-            raise _lib.KpxError('cell_frames: %s must be a contiguous %s tensor of %d dimensions (got %s %s, contiguous=%s)'
-                                % (name, dtype, dim, tuple(t.shape), t.dtype, t.is_contiguous()))
-    if canvas.device != seq.device or first.device != seq.device:
-        raise _lib.KpxError('cell_frames: canvas, first and seq must be on one device (got %s, %s and %s)'
-                            % (canvas.device, first.device, seq.device))
-    if premap not in SHEET_PREMAPS:
-        raise _lib.KpxError('cell_frames: premap must be one of %s (got %r)' % (sorted(SHEET_PREMAPS), premap))
-    b, t_, h, w, c = seq.shape
-    if b < 1 or t_ < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
-        raise _lib.KpxError('cell_frames: seq needs B, T >= 1, H and W in [1, 1024] and C in (1, 3) (got %s)' % (tuple(seq.shape),))
-    if tuple(first.shape) != (b, h, w, c):
-        raise _lib.KpxError('cell_frames: first must be %s, one frame per sample of seq (got %s)' % ([b, h, w, c], tuple(first.shape)))
-    if canvas.shape[0] != b or canvas.shape[1] != t_ + 1 or canvas.shape[4] != 3 or canvas.shape[2] % h or canvas.shape[3] % w:
-        raise _lib.KpxError('cell_frames: canvas must be [%d, %d, rows * %d, cols * %d, 3] (got %s)' % (b, t_ + 1, h, w, tuple(canvas.shape)))
-    rows, cols = canvas.shape[2] // h, canvas.shape[3] // w
-    if not (1 <= rows <= 64 and 1 <= cols <= 64):
-        raise _lib.KpxError('cell_frames: a grid has 1 to 64 rows and columns of cells (got %d x %d)' % (rows, cols))
-    if any(isinstance(v, bool) or not isinstance(v, int) for v in (row, col, radius)):
-        raise _lib.KpxError('cell_frames: row, col and radius are integers (got %r, %r, %r)' % (row, col, radius))
-    if not (0 <= row < rows and 0 <= col < cols):
-        raise _lib.KpxError('cell_frames: cell (row %d, col %d) is outside a grid of %d x %d cells' % (row, col, rows, cols))
-    if not 0 <= radius <= CELL_MAX_RADIUS:
-        raise _lib.KpxError('cell_frames: radius must be in [0, %d] (got %d)' % (CELL_MAX_RADIUS, radius))
-    k = 0
-    if radius == 0:
-        if pts_first is not None or pts_seq is not None or colors is not None:
-            raise _lib.KpxError('cell_frames: radius 0 draws no markers and takes no points or colours')
-    else:
-        for name, t, dim in (('pts_first', pts_first, 3), ('pts_seq', pts_seq, 4)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise _lib.KpxError('kpx ops run on MI355X only (got %s for cell_frames\'s %s); there is no CPU fallback'
-                                    % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
-            if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous() or t.shape[-1] != 2 or t.device != seq.device:
-                raise _lib.KpxError('cell_frames: %s must be a contiguous fp32 tensor of %d dimensions ending in 2 on %s (got %s %s on %s, '
-                                    'contiguous=%s)' % (name, dim, seq.device, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
-        k = int(pts_first.shape[1])
-        if not 1 <= k <= CELL_MAX_POINTS or tuple(pts_first.shape) != (b, k, 2) or tuple(pts_seq.shape) != (b, t_, k, 2):
-            raise _lib.KpxError('cell_frames: pts_first must be [%d, K, 2] and pts_seq [%d, %d, K, 2] with 1 <= K <= %d (got %s and %s)'
-                                % (b, b, t_, CELL_MAX_POINTS, tuple(pts_first.shape), tuple(pts_seq.shape)))
-        _u8_gpu('cell_frames', 'colors', colors, 2)
-        if tuple(colors.shape) != (k, 3) or colors.device != seq.device:
-            raise _lib.KpxError('cell_frames: colors must be uint8 [%d, 3] on %s (got %s on %s)' % (k, seq.device, tuple(colors.shape), colors.device))
-    check(lib.kpx_cell_frames_u8_f32(first.data_ptr(), seq.data_ptr(), b, t_, h, w, c, _ptr(pts_first), _ptr(pts_seq), k, _ptr(colors), radius,
-                                     canvas.data_ptr(), rows, cols, row, col, SHEET_PREMAPS[premap], _stream()), 'kpx_cell_frames_u8_f32')
-    return canvas
-
-
-HIST_CELLS = 32768                                                          # 5-5-5 colour cells
-HIST_MAX_PIXELS = 1 << 24                                                         # per group and call: the uint32 sums cannot overflow
-GIF_MAX_DITHER = 64
-
-
-def _u8_gpu(what, name, t, dims=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got %s for %s\'s %s); there is no CPU fallback'
-                            % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, what, name))
-    if t.dtype != torch.uint8 or not t.is_contiguous() or (dims is not None and t.dim() != dims):
-        raise _lib.KpxError('%s: %s must be a contiguous uint8 tensor%s (got %s %s, contiguous=%s)'
-                            % (what, name, '' if dims is None else ' of %d dimensions' % dims, tuple(t.shape), t.dtype, t.is_contiguous()))
-
-
-def color_hist_add(rgb, hist):
-    """Colour statistics of 8-bit RGB pixels (DESIGN.md section 4.4).  rgb: contiguous uint8 [G, n, 3] (any storage offset), 1 <= n <= 2^24;
-    hist: contiguous int32 [G, 32768, 4] (the bits of uint32) on rgb's device, updated in place: hist[g, cell] += (count, sum r, sum g,
-    sum b) over group g's pixels with cell = (r >> 3) << 10 | (g >> 3) << 5 | b >> 3.  Zero hist first (``hist.zero_()``: a memset node
-    under capture).  Integer adds: the same bits in any order.  One launch."""
-    _u8_gpu('color_hist_add', 'rgb', rgb, 3)
-    if not isinstance(hist, torch.Tensor) or not hist.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (color_hist_add\'s hist); there is no CPU fallback')
-    g, n = int(rgb.shape[0]), int(rgb.shape[1])
-    if rgb.shape[2] != 3 or g < 1 or g > 65535 or not 1 <= n <= HIST_MAX_PIXELS:
-        raise _lib.KpxError('color_hist_add: rgb must be [G, n, 3] with 1 <= G <= 65535 and 1 <= n <= 2^24 (got %s)' % (tuple(rgb.shape),))
-    if hist.dtype != torch.int32 or not hist.is_contiguous() or tuple(hist.shape) != (g, HIST_CELLS, 4) or hist.device != rgb.device:
-        raise _lib.KpxError('color_hist_add: hist must be a contiguous int32 [%d, %d, 4] tensor on %s (got %s %s on %s)'
-                            % (g, HIST_CELLS, rgb.device, tuple(hist.shape), hist.dtype, hist.device))
-    check(lib.kpx_color_hist_add_u32(rgb.data_ptr(), g, n, hist.data_ptr(), _stream()), 'kpx_color_hist_add_u32')
-    return hist
-
-
-def palette_map(rgb, palette, sizes, dither=0, pmax=256, out=None):
-    """The nearest palette entry of every pixel.  rgb: contiguous uint8 [G,T,H,Wc,3]; palette: contiguous uint8
-    [G,256,3]; sizes: contiguous int32 [G] ON THE DEVICE, each in [1, pmax] (clamped into it) -> idx uint8 [G,T,H,Wc] = the smallest
-    j < sizes[g] that minimises the squared RGB distance (int32).  ``dither`` A in [0, 64]: the 4 x 4 ordered dither of ``kpx_amd.gif.BAYER4``
-    added to every channel before the search, A = 0 the plain search.  Any width and storage offset.  One launch."""
-    _u8_gpu('palette_map', 'rgb', rgb, 5)
-    _u8_gpu('palette_map', 'palette', palette, 3)
-    if not isinstance(sizes, torch.Tensor) or not sizes.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (palette_map\'s sizes live on the device); there is no CPU fallback')
-    g, t, h, w = (int(v) for v in rgb.shape[:4])
-    if rgb.shape[4] != 3 or min(g, t, h, w) < 1 or g > 65535 or t * h * w > 0x7fffffff:
-        raise _lib.KpxError('palette_map: rgb must be [G,T,H,Wc,3] with 1 <= G <= 65535 and T H Wc < 2^31 (got %s)' % (tuple(rgb.shape),))
-    if tuple(palette.shape) != (g, 256, 3) or palette.device != rgb.device:
-        raise _lib.KpxError('palette_map: palette must be [%d, 256, 3] on %s (got %s on %s)' % (g, rgb.device, tuple(palette.shape), palette.device))
-    if sizes.dtype != torch.int32 or not sizes.is_contiguous() or tuple(sizes.shape) != (g,) or sizes.device != rgb.device:
-        raise _lib.KpxError('palette_map: sizes must be a contiguous int32 [%d] tensor on %s (got %s %s)' % (g, rgb.device, tuple(sizes.shape), sizes.dtype))
-    if isinstance(dither, bool) or not isinstance(dither, int) or not 0 <= dither <= GIF_MAX_DITHER:
-        raise _lib.KpxError('palette_map: dither is an integer in [0, %d] (got %r)' % (GIF_MAX_DITHER, dither))
-    if isinstance(pmax, bool) or not isinstance(pmax, int) or not 1 <= pmax <= 256:
-        raise _lib.KpxError('palette_map: pmax is an integer in [1, 256] (got %r)' % (pmax,))
-    if out is None:
-        out = torch.empty((g, t, h, w), dtype=torch.uint8, device=rgb.device)
-    else:
-        _u8_gpu('palette_map', 'out', out, 4)
-        if tuple(out.shape) != (g, t, h, w) or out.device != rgb.device:
-            raise _lib.KpxError('palette_map: out must be [%d,%d,%d,%d] on %s (got %s)' % (g, t, h, w, rgb.device, tuple(out.shape)))
-    check(lib.kpx_palette_map_u8(rgb.data_ptr(), g, t, h, w, palette.data_ptr(), sizes.data_ptr(), pmax, dither, out.data_ptr(), _stream()),
-          'kpx_palette_map_u8')
-    return out
-
-
-def gif_indices(canvas, dither=0):
-    """An 8-bit canvas to palette indices, one palette per group from all its frames.  canvas: contiguous uint8
-    [G,T,H,Wc,3] with T H Wc <= 2^24 -> (idx uint8 [G,T,H,Wc] on the device, palettes uint8 numpy [G,256,3] zero-padded, sizes int numpy [G]).
-    ``color_hist_add`` on the device, ``kpx_amd.gif.median_cut`` on the host (512 KB per group cross over), ``palette_map`` on the device."""
-    from . import gif as _gif
-    import numpy as _np
-    _u8_gpu('gif_indices', 'canvas', canvas, 5)
-    g = int(canvas.shape[0])
-    hist = torch.zeros((g, HIST_CELLS, 4), dtype=torch.int32, device=canvas.device)
-    color_hist_add(canvas.view(g, -1, 3), hist)
-    host = hist.cpu().numpy().view(_np.uint32)
-    palettes, sizes = _np.zeros((g, 256, 3), _np.uint8), _np.zeros((g,), _np.int32)
-    for i in range(g):
-        pal = _gif.median_cut(host[i])
-        palettes[i, :pal.shape[0]], sizes[i] = pal, pal.shape[0]
-    idx = palette_map(canvas, torch.from_numpy(palettes).to(canvas.device), torch.from_numpy(sizes).to(canvas.device), dither)
-    return idx, palettes, sizes
-
-
-RETARGET_MODES ={'hold': 0, 'absolute': 1, 'relative': 2}                        # = KPX_RETARGET_* of include/kpx.h ('relative' + scaled: 3)
-RETARGET_MAX_POINTS = 1024
-
-
-def points_retarget(src_first, mode, drv_first=None, drv_seq=None, shift=0, scaled=False, frames=None, out=None):
-    """The key-point sequence of a driven rollout (DESIGN.md section 2): src_first contiguous fp32 [B,K,2], the source images' key points;
-    drv_first [B,K,2] and drv_seq [B,T,K,2], the drivers' key points at frame 0 and at frames 1..T; sample b is driven by sample
-    (b + shift) mod B -> out fp32 [B,T,K,2]:
-      'hold'      out[b,t] = src_first[b] (T from ``frames``; takes no driver)
-      'absolute'  out[b,t] = drv_seq[j,t] (drv_first is not read and may be omitted)
-      'relative'  out[b,t] = src_first[b] + s_b * (drv_seq[j,t] - drv_first[j]); s_b = 1, or with ``scaled`` the ratio of the spreads of
-                  the two frame-0 constellations about their means (1 when either is 0 or non-finite)
-    'hold' and 'absolute' are bit copies, 'relative' is computed in fp64 and rounded once.  1 <= K <= 1024, 0 <= shift < B,
-    B*T*K*2 < 2^31.  One launch on the current stream; capturable."""
-    if mode not in RETARGET_MODES:
-        raise _lib.KpxError('points_retarget: mode must be one of %s (got %r)' % (sorted(RETARGET_MODES), mode))
-    if scaled and mode != 'relative':
-        raise _lib.KpxError("points_retarget: scaled belongs to mode 'relative' (got %r)" % (mode,))
-    if mode == 'hold':
-        if drv_first is not None or drv_seq is not None:
-            raise _lib.KpxError("points_retarget: mode 'hold' takes no driver")
-        drv_first = None
-    elif drv_seq is None or (mode == 'relative' and drv_first is None):
-        raise _lib.KpxError('points_retarget: mode %r needs %s' % (mode, 'drv_first and drv_seq' if mode == 'relative' else 'drv_seq'))
-    elif frames is not None:
-        raise _lib.KpxError("points_retarget: frames belongs to mode 'hold'; mode %r takes T from drv_seq" % (mode,))
-    for name, t, dim in (('src_first', src_first, 3), ('drv_first', drv_first, 3), ('drv_seq', drv_seq, 4), ('out', out, 4)):
-        if t is None:
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got %s for points_retarget\'s %s); there is no CPU fallback'
-                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, name))
-        if t.dtype != torch.float32 or t.dim() != dim or not t.is_contiguous() or t.shape[-1] != 2 or t.device != src_first.device:
-            raise _lib.KpxError('points_retarget: %s must be a contiguous fp32 tensor of %d dimensions ending in 2 on %s (got %s %s on %s, '
-                                'contiguous=%s)' % (name, dim, src_first.device, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
-    b, k, _ = src_first.shape
-    if mode == 'hold':
-        if isinstance(frames, bool) or not isinstance(frames, int):
-            raise _lib.KpxError("points_retarget: mode 'hold' takes the number of frames as frames= (got %r)" % (frames,))
-        t_ = frames
-    else:
-        t_ = drv_seq.shape[1]
-        if tuple(drv_seq.shape) != (b, t_, k, 2) or (drv_first is not None and tuple(drv_first.shape) != (b, k, 2)):
-            raise _lib.KpxError('points_retarget: src_first %s, drv_first %s and drv_seq %s must be [B,K,2], [B,K,2] and [B,T,K,2] of one B and K'
-                                % (tuple(src_first.shape), None if drv_first is None else tuple(drv_first.shape), tuple(drv_seq.shape)))
-    if b < 1 or t_ < 1 or not 1 <= k <= RETARGET_MAX_POINTS or b * t_ * k * 2 >= 2 ** 31:
-        raise _lib.KpxError('points_retarget: needs B, T >= 1, 1 <= K <= %d and B*T*K*2 < 2^31 (got B = %d, T = %d, K = %d)'
-                            % (RETARGET_MAX_POINTS, b, t_, k))
-    if isinstance(shift, bool) or not isinstance(shift, int) or not 0 <= shift < b:
-        raise _lib.KpxError('points_retarget: shift must be an integer in [0, B = %d) (got %r)' % (b, shift))
-    if out is None:
-        out = torch.empty((b, t_, k, 2), dtype=torch.float32, device=src_first.device)
-    elif tuple(out.shape) != (b, t_, k, 2):
-        raise _lib.KpxError('points_retarget: out must be %s (got %s)' % ([b, t_, k, 2], tuple(out.shape)))
-    check(lib.kpx_points_retarget_f32(src_first.data_ptr(), _ptr(drv_first) if mode == 'relative' else None, _ptr(drv_seq), b, t_, k, shift,
-                                      RETARGET_MODES[mode] + (1 if scaled else 0), out.data_ptr(), _stream()), 'kpx_points_retarget_f32')
-    return out
-
-
-WARP_MAX_ROWS = 1 << 16                                                           # = KPX_WARP_MAX_ROWS
-EQUIV_MAX_ROWS, EQUIV_MAX_POINTS = 1 << 20, 1024                                  # = KPX_EQUIV_MAX_ROWS; K of kpx_equivariance_scores_f32
-
-
-def _map_tables(what, rows, maps, maps_name, n, max_rows, dev, check_tables):
-    """The two tables the stability entries share: rows contiguous int32 [R] (every value in [0, n)) and maps contiguous fp64 [R,6] (finite)
-    on ``dev``, 1 <= R <= max_rows -> R.  The value checks read the tables back to the host; ``check_tables=False`` (or a stream that is
-    capturing, where nothing can be read back) skips them."""
-    for name, t, dtype, dim in (('rows', rows, torch.int32, 1), (maps_name, maps, torch.float64, 2)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got %s for %s\'s %s); there is no CPU fallback'
-                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, what, name))
-        if t.dtype != dtype or t.dim() != dim or not t.is_contiguous() or t.device != dev:
-            raise _lib.KpxError('%s: %s must be a contiguous %s tensor of %d dimension(s) on %s (got %s %s on %s, contiguous=%s)'
-                                % (what, name, dtype, dim, dev, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
-    r = rows.shape[0]
-    if not 1 <= r <= max_rows or tuple(maps.shape) != (r, 6):
-        raise _lib.KpxError('%s: needs 1 <= R <= %d rows and %s [R,6] (got rows %s, %s %s)'
-                            % (what, max_rows, maps_name, tuple(rows.shape), maps_name, tuple(maps.shape)))
-    if check_tables and not torch.cuda.is_current_stream_capturing():
-        lo, hi = (int(v) for v in torch.aminmax(rows))
-        if lo < 0 or hi >= n:
-            raise _lib.KpxError('%s: every frame number must lie in [0, %d) (got values from %d to %d)' % (what, n, lo, hi))
-        if not bool(torch.isfinite(maps).all()):
-            raise _lib.KpxError('%s: %s has a non-finite coefficient' % (what, maps_name))
-    return r
-
-
-def affine_warp(frames, rows, coef, out=None, check_tables=True):
-    """Frames resampled through affine maps (the detector's stability): frames contiguous fp32 [N,H,W,C], C in (1, 3),
-    H and W in [1, 1024], finite; rows contiguous int32 [R], the source frame of each output row (any order, repeats allowed); coef contiguous
-    fp64 [R,6], the INVERSE map of each row in pixel units: output pixel (x, y) reads the source at (c0 x + c1 y + c2, c3 x + c4 y + c5),
-    clamped to the frame (edge replication), bilinear -> fp32 [R,H,W,C].  fp64 arithmetic, nothing fused, one rounding: the bits of the numpy
-    float64 restatement; maps that send pixels to pixels copy input bits.  1 <= R <= 65536.  ``out``: a contiguous fp32 [R,H,W,C] tensor
-    to write into.  One launch on the current stream (capturable with ``check_tables=False``, which skips reading the tables back for the
-    range check of the frame numbers and the finiteness of the coefficients)."""
-    _require_gpu(frames)
-    if frames.dtype != torch.float32 or not frames.is_contiguous() or frames.dim() != 4:
-        raise _lib.KpxError('affine_warp: frames must be a contiguous fp32 [N,H,W,C] tensor (got %s %s, contiguous=%s)'
-                            % (tuple(frames.shape), frames.dtype, frames.is_contiguous()))
-    n, h, w, c = frames.shape
-    if n < 1 or not (1 <= h <= 1024 and 1 <= w <= 1024) or c not in (1, 3):
-        raise _lib.KpxError('affine_warp: needs N >= 1, H and W in [1, 1024] and C in (1, 3) (got %s)' % (tuple(frames.shape),))
-    dev = frames.device
-    r = _map_tables('affine_warp', rows, coef, 'coef', n, WARP_MAX_ROWS, dev, check_tables)
-    if out is None:
-        out = torch.empty((r, h, w, c), dtype=torch.float32, device=dev)
-    elif (not isinstance(out, torch.Tensor) or tuple(out.shape) != (r, h, w, c) or out.dtype != torch.float32 or not out.is_contiguous()
-          or out.device != dev):
-        raise _lib.KpxError('affine_warp: out must be a contiguous fp32 [%d,%d,%d,%d] tensor on %s' % (r, h, w, c, dev))
-    check(lib.kpx_affine_warp_f32(frames.data_ptr(), n, h, w, c, rows.data_ptr(), coef.data_ptr(), r, out.data_ptr(), _stream()),
-          'kpx_affine_warp_f32')
-    return out
-
-
-def equivariance_scores(pts, pts_w, rows, fwd, out=None, check_tables=True):
-    """The detector's equivariance error (DESIGN.md section 2): pts contiguous fp32 [N,K,2] (x, y), the key points of the original frames;
-    pts_w contiguous fp32 [R,K,2], those of the warped frames; rows contiguous int32 [R], the original frame of each row; fwd contiguous fp64
-    [R,6], the FORWARD map of each row in the key points' normalised coordinates -> (scores fp32 [R,K,2], valid uint8 [R,K], frame_mean fp32
-    [R,2], n_valid int32 [R]): scores = (err, moved) = (|pts_w - target|, |target - p|) with target = M p + t; valid = 1 where p, pts_w and
-    the target are finite and the target lies in [-1, 1]^2; frame_mean = the means of both over the row's valid points (NaN without any);
-    n_valid their number.  fp64 arithmetic in a fixed order, rounded once.  1 <= K <= 1024, 1 <= R <= 2^20.  ``out``: the four tensors to
-    write into.  One launch on the current stream (``check_tables`` as in ``affine_warp``)."""
-    for name, t in (('pts', pts), ('pts_w', pts_w)):
-        if not isinstance(t, torch.Tensor):
-            raise _lib.KpxError('equivariance_scores: %s must be a tensor (got %s)' % (name, type(t).__name__))
-        _require_gpu(t)
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 or t.shape[2] != 2:
-            raise _lib.KpxError('equivariance_scores: %s must be a contiguous fp32 [.,K,2] tensor (got %s %s, contiguous=%s)'
-                                % (name, tuple(t.shape), t.dtype, t.is_contiguous()))
-    n, k, _ = pts.shape
-    dev = pts.device
-    if n < 1 or not 1 <= k <= EQUIV_MAX_POINTS or pts_w.shape[1] != k or pts_w.device != dev:
-        raise _lib.KpxError('equivariance_scores: pts [N,K,2] and pts_w [R,K,2] need N >= 1 and one K in [1, %d] on one device (got %s on %s, '
-                            '%s on %s)' % (EQUIV_MAX_POINTS, tuple(pts.shape), dev, tuple(pts_w.shape), pts_w.device))
-    r = _map_tables('equivariance_scores', rows, fwd, 'fwd', n, EQUIV_MAX_ROWS, dev, check_tables)
-    if pts_w.shape[0] != r:
-        raise _lib.KpxError('equivariance_scores: pts_w must have one entry per row (got %s for %d rows)' % (tuple(pts_w.shape), r))
-    specs = (('scores', (r, k, 2), torch.float32), ('valid', (r, k), torch.uint8), ('frame_mean', (r, 2), torch.float32),
-             ('n_valid', (r,), torch.int32))
-    outs = list(out) if out is not None else [None] * 4
-    if len(outs) != 4:
-        raise _lib.KpxError('equivariance_scores: out must be (scores, valid, frame_mean, n_valid)')
-    for i, (name, shape, dtype) in enumerate(specs):
-        o = outs[i]
-        if o is not None and (not isinstance(o, torch.Tensor) or tuple(o.shape) != shape or o.dtype != dtype or not o.is_contiguous()
-                              or o.device != dev):
-            raise _lib.KpxError('equivariance_scores: out %s must be a contiguous %s %s tensor on %s' % (name, dtype, list(shape), dev))
-    outs = [torch.empty(shape, dtype=dtype, device=dev) if o is None else o for o, (_, shape, dtype) in zip(outs, specs)]
-    check(lib.kpx_equivariance_scores_f32(pts.data_ptr(), pts_w.data_ptr(), rows.data_ptr(), fwd.data_ptr(), r, k, outs[0].data_ptr(),
-                                          outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(), _stream()), 'kpx_equivariance_scores_f32')
-    return tuple(outs)
-
-
-JOINT_MAX_POINTS, JOINT_MAX_JOINTS, JOINT_MAX_FRAMES, JOINT_MAX_ALPHAS = 64, 32, 1 << 20, 8     # = KPX_JOINT_MAX_* of include/kpx.h
-
-
-def _joint_tensors(what, dev, specs):
-    """Every (name, tensor, dtype, shape) of specs is a contiguous tensor of that dtype and shape on ``dev`` (a GPU); a None in a shape
-    matches any size."""
-    for name, t, dtype, shape in specs:
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got %s for %s\'s %s); there is no CPU fallback'
-                                % ('a %s tensor' % t.device if isinstance(t, torch.Tensor) else type(t).__name__, what, name))
-        if (t.dtype != dtype or t.dim() != len(shape) or any(s is not None and s != g for s, g in zip(shape, t.shape)) or not t.is_contiguous()
-                or t.device != dev):
-            raise _lib.KpxError('%s: %s must be a contiguous %s %s tensor on %s (got %s %s on %s, contiguous=%s)'
-                                % (what, name, dtype, list(shape), dev, tuple(t.shape), t.dtype, t.device, t.is_contiguous()))
-
-
-def _joint_sizes(what, f, k, j):
-    if not (1 <= f <= JOINT_MAX_FRAMES and 1 <= k <= JOINT_MAX_POINTS and 1 <= j <= JOINT_MAX_JOINTS):
-        raise _lib.KpxError('%s: needs 1 <= F <= %d, 1 <= K <= %d and 1 <= J <= %d (got F = %d, K = %d, J = %d)'
-                            % (what, JOINT_MAX_FRAMES, JOINT_MAX_POINTS, JOINT_MAX_JOINTS, f, k, j))
-
-
-def joint_targets(xy, vis, bbox, crop_map):
-    """Annotated joints in the key points' coordinates (landmark regression): xy contiguous fp32 [F,J,2], the joints in
-    the original frame's pixels; vis contiguous uint8 [F,J]; bbox contiguous fp32 [F,4] = (x0, y0, x1, y1); crop_map contiguous fp64 [4] =
-    (ax, bx, ay, by) on the same device (``kpx_amd.joints.crop_map``) -> (target fp32 [F,J,2] = (ax x + bx, ay y + by) in fp64, rounded once;
-    mask uint8 [F,J] = visible, finite and inside [-1,1]^2; norm fp32 [F] = max(|ax| (x1 - x0), |ay| (y1 - y0)), NaN for a box that is not
-    finite or not positive).  1 <= F <= 2^20, 1 <= J <= 32.  One launch on the current stream."""
-    if not isinstance(xy, torch.Tensor) or xy.dim() != 3:
-        raise _lib.KpxError('joint_targets: xy must be a fp32 [F,J,2] tensor')
-    f, j, dev = xy.shape[0], xy.shape[1], xy.device
-    _joint_tensors('joint_targets', dev, (('xy', xy, torch.float32, (f, j, 2)), ('vis', vis, torch.uint8, (f, j)),
-                                          ('bbox', bbox, torch.float32, (f, 4)), ('crop_map', crop_map, torch.float64, (4,))))
-    _joint_sizes('joint_targets', f, 1, j)
-    target = torch.empty((f, j, 2), dtype=torch.float32, device=dev)
-    mask = torch.empty((f, j), dtype=torch.uint8, device=dev)
-    norm = torch.empty((f,), dtype=torch.float32, device=dev)
-    check(lib.kpx_joint_targets_f32(xy.data_ptr(), vis.data_ptr(), bbox.data_ptr(), crop_map.data_ptr(), f, j, target.data_ptr(), mask.data_ptr(),
-                                    norm.data_ptr(), _stream()), 'kpx_joint_targets_f32')
-    return target, mask, norm
-
-
-def joint_moments_add(pts, target, mask, g, bm, n):
-    """Frames into the masked normal equations of the landmark regression: pts contiguous fp32 [F,K,2]; target
-    contiguous fp32 [F,J,2]; mask contiguous uint8 [F,J]; in place g fp64 [J,D,D] += sum_f phi_f phi_f^T, bm fp64 [J,D,2] += sum_f phi_f
-    target[f,j]^T and n int64 [J] += the number of frames, over the frames with mask[f,j] set and finite key points, phi_f = (pts[f], 1),
-    D = 2K + 1; zeroed by the caller before the first call.  Every element takes its frames in ascending order with one fma each, so any
-    split of the frames into consecutive calls gives the same bits and g stays bitwise symmetric.  1 <= K <= 64, 1 <= J <= 32,
-    1 <= F <= 2^20.  One launch on the current stream.  -> (g, bm, n)."""
-    if not isinstance(pts, torch.Tensor) or pts.dim() != 3 or not isinstance(target, torch.Tensor) or target.dim() != 3:
-        raise _lib.KpxError('joint_moments_add: pts must be a fp32 [F,K,2] and target a fp32 [F,J,2] tensor')
-    f, k, j, dev = pts.shape[0], pts.shape[1], target.shape[1], pts.device
-    d = 2 * k + 1
-    _joint_tensors('joint_moments_add', dev, (('pts', pts, torch.float32, (f, k, 2)), ('target', target, torch.float32, (f, j, 2)),
-                                              ('mask', mask, torch.uint8, (f, j)), ('g', g, torch.float64, (j, d, d)),
-                                              ('bm', bm, torch.float64, (j, d, 2)), ('n', n, torch.int64, (j,))))
-    _joint_sizes('joint_moments_add', f, k, j)
-    check(lib.kpx_joint_moments_add_f64(pts.data_ptr(), target.data_ptr(), mask.data_ptr(), f, k, j, g.data_ptr(), bm.data_ptr(), n.data_ptr(),
-                                        _stream()), 'kpx_joint_moments_add_f64')
-    return g, bm, n
-
-
-def joint_scores(pts, target, mask, norm, w, alpha):
-    """The landmark regressor applied: pts contiguous fp32 [F,K,2]; target contiguous fp32 [F,J,2]; mask contiguous
-    uint8 [F,J]; norm contiguous fp32 [F]; w contiguous fp64 [J,D,2], D = 2K + 1; alpha contiguous fp64 [A], 1 <= A <= 8 -> (pred fp32
-    [F,J,2] = phi_f W[j], err fp32 [F,J] = |pred - target|, hits uint8 [F,J] with bit a set when the entry is valid, norm[f] is finite and
-    err <= alpha[a] norm[f]; per call sum_err fp64 [J] and count int64 [J] over the valid entries (mask set, finite key points) in ascending
-    f, pck_count int64 [J] those of them with a finite norm, hit_count int64 [J,A]).  fp64 arithmetic in a fixed order, nothing fused, each
-    stored value rounded once.  One launch on the current stream."""
-    if not isinstance(pts, torch.Tensor) or pts.dim() != 3 or not isinstance(target, torch.Tensor) or target.dim() != 3:
-        raise _lib.KpxError('joint_scores: pts must be a fp32 [F,K,2] and target a fp32 [F,J,2] tensor')
-    f, k, j, dev = pts.shape[0], pts.shape[1], target.shape[1], pts.device
-    d = 2 * k + 1
-    _joint_tensors('joint_scores', dev, (('pts', pts, torch.float32, (f, k, 2)), ('target', target, torch.float32, (f, j, 2)),
-                                         ('mask', mask, torch.uint8, (f, j)), ('norm', norm, torch.float32, (f,)),
-                                         ('w', w, torch.float64, (j, d, 2)), ('alpha', alpha, torch.float64, (None,))))
-    _joint_sizes('joint_scores', f, k, j)
-    a = alpha.shape[0]
-    if not 1 <= a <= JOINT_MAX_ALPHAS:
-        raise _lib.KpxError('joint_scores: needs 1 <= A <= %d thresholds (got %d)' % (JOINT_MAX_ALPHAS, a))
-    pred = torch.empty((f, j, 2), dtype=torch.float32, device=dev)
-    err = torch.empty((f, j), dtype=torch.float32, device=dev)
-    hits = torch.empty((f, j), dtype=torch.uint8, device=dev)
-    sum_err = torch.empty((j,), dtype=torch.float64, device=dev)
-    count = torch.empty((j,), dtype=torch.int64, device=dev)
-    pck_count = torch.empty((j,), dtype=torch.int64, device=dev)
-    hit_count = torch.empty((j, a), dtype=torch.int64, device=dev)
-    check(lib.kpx_joint_scores_f32(pts.data_ptr(), target.data_ptr(), mask.data_ptr(), norm.data_ptr(), w.data_ptr(), alpha.data_ptr(), f, k, j, a,
-                                   pred.data_ptr(), err.data_ptr(), hits.data_ptr(), sum_err.data_ptr(), count.data_ptr(), pck_count.data_ptr(),
-                                   hit_count.data_ptr(), _stream()), 'kpx_joint_scores_f32')
-    return pred, err, hits, sum_err, count, pck_count, hit_count
-
-
 class JointEmbeddingFn(torch.autograd.Function):
     """tf.concat([embedding, current_map, future_map], -1) (reference detector_translator_model.py:168-170) with the
     two heat-maps rendered straight into their channel slices.  Output pixel stride is padded to a multiple of 4
@@ -2166,34 +1409,17 @@ def sigmoid_xent(logits, n0, label0, n1=0, label1=0.0):
     return SigmoidXentFn.apply(logits, n0, float(label0), n1, float(label1))
 
 
-MAX_CLASS_ROWS, MAX_CLASSES = 1 << 20, 1024                                      # limits of the three classifier entries on B / M and A
-
-
-def _class_rows(what, logits):
-    """(rows, classes) of a logits tensor the classifier entries take: contiguous fp32 [rows, A] on the GPU within the limits."""
-    if not isinstance(logits, torch.Tensor) or not logits.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(logits, 'device', type(logits)))
-    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 2:
-        raise _lib.KpxError('%s: logits must be a contiguous fp32 [rows, classes] tensor (got %s %s, contiguous=%s)'
-                            % (what, logits.dtype, tuple(logits.shape), logits.is_contiguous()))
-    m, a = logits.shape
-    if not 1 <= m <= MAX_CLASS_ROWS or not 1 <= a <= MAX_CLASSES:
-        raise _lib.KpxError('%s: needs 1 <= rows <= %d and 1 <= classes <= %d (got %s)' % (what, MAX_CLASS_ROWS, MAX_CLASSES, tuple(logits.shape)))
-    return m, a
-
-
 class SoftmaxXentFn(torch.autograd.Function):
     """reduce_mean(tf.nn.softmax_cross_entropy_with_logits(labels, logits)) over logits [B,A] and label rows [B,A] -> loss [1].
     Differentiated with respect to the logits only (TensorFlow's gradient: exact when every label row sums to 1)."""
 
     @staticmethod
     def forward(ctx, logits, labels):
-        b, a = _class_rows('softmax_xent', logits)
-        if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
-            raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(labels, 'device', type(labels)))
-        if labels.dtype != torch.float32 or not labels.is_contiguous() or tuple(labels.shape) != (b, a) or labels.device != logits.device:
-            raise _lib.KpxError('softmax_xent: labels must be a contiguous fp32 %s tensor on %s (got %s %s on %s, contiguous=%s)'
-                                % ([b, a], logits.device, labels.dtype, tuple(labels.shape), labels.device, labels.is_contiguous()))
+        dev = check_tensors('softmax_xent', [('logits', logits, torch.float32, (None, None))])
+        b, a = logits.shape
+        if not 1 <= b <= MAX_CLASS_ROWS or not 1 <= a <= MAX_CLASSES:
+            raise _lib.KpxError('softmax_xent: needs 1 <= rows <= %d and 1 <= classes <= %d (got %s)' % (MAX_CLASS_ROWS, MAX_CLASSES, tuple(logits.shape)))
+        check_tensors('softmax_xent', [('labels', labels, torch.float32, (b, a))], dev)
         loss = torch.empty(1, dtype=torch.float32, device=logits.device)
         lse = torch.empty(b, dtype=torch.float32, device=logits.device)
         check(lib.kpx_softmax_xent_fwd_f32(logits.data_ptr(), labels.data_ptr(), b, a, loss.data_ptr(), lse.data_ptr(), _stream()),
@@ -2216,40 +1442,6 @@ class SoftmaxXentFn(torch.autograd.Function):
 def softmax_xent(logits, labels):
     """-> loss [1] (see SoftmaxXentFn); logits and labels contiguous fp32 [B,A] on one GPU, 1 <= B <= 2^20, 1 <= A <= 1024."""
     return SoftmaxXentFn.apply(logits, labels)[0]
-
-
-def class_scores(logits, target, confusion=None, out=None, check_target=True):
-    """Per row of logits (contiguous fp32 [M,A]) against target (contiguous int32 [M], every value in [0, A)) -> (pred int32 [M], rank
-    int32 [M], logp fp32 [M]): pred = the lowest index among the row's maxima, rank = 1 + the number of other
-    classes whose logit is >= the target's (a tie counts against the model), logp = the target's log-softmax.  ``confusion``: a contiguous
-    int32 [A,A] tensor, [target, pred] += 1 (zeroed by the caller before the first call).  A row with a non-finite logit gets pred = -1,
-    rank = A, logp = NaN and is left out of ``confusion``.  ``out``: (pred, rank, logp) tensors to write into.  One launch.  The range
-    check of the targets reads them back to the host before the launch; a caller that has checked them (or is capturing a graph, where
-    nothing can be read back) passes ``check_target=False``."""
-    m, a = _class_rows('class_scores', logits)
-    dev = logits.device
-    if not isinstance(target, torch.Tensor) or not target.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(target, 'device', type(target)))
-    if target.dtype != torch.int32 or not target.is_contiguous() or tuple(target.shape) != (m,) or target.device != dev:
-        raise _lib.KpxError('class_scores: target must be a contiguous int32 [%d] tensor on %s (got %s %s on %s)'
-                            % (m, dev, target.dtype, tuple(target.shape), target.device))
-    if confusion is not None and (not isinstance(confusion, torch.Tensor) or confusion.dtype != torch.int32 or not confusion.is_contiguous()
-                                  or tuple(confusion.shape) != (a, a) or confusion.device != dev):
-        raise _lib.KpxError('class_scores: confusion must be a contiguous int32 [%d,%d] tensor on %s' % (a, a, dev))
-    pred, rank, logp = out if out is not None else (None, None, None)
-    for name, o, dt in (('pred', pred, torch.int32), ('rank', rank, torch.int32), ('logp', logp, torch.float32)):
-        if o is not None and (not isinstance(o, torch.Tensor) or tuple(o.shape) != (m,) or o.dtype != dt or not o.is_contiguous() or o.device != dev):
-            raise _lib.KpxError('class_scores: out %s must be a contiguous %s [%d] tensor on %s' % (name, dt, m, dev))
-    if check_target and not torch.cuda.is_current_stream_capturing():
-        lo, hi = (int(v) for v in torch.aminmax(target))
-        if lo < 0 or hi >= a:
-            raise _lib.KpxError('class_scores: every target must lie in [0, %d) (got values from %d to %d)' % (a, lo, hi))
-    pred = torch.empty(m, dtype=torch.int32, device=dev) if pred is None else pred
-    rank = torch.empty(m, dtype=torch.int32, device=dev) if rank is None else rank
-    logp = torch.empty(m, dtype=torch.float32, device=dev) if logp is None else logp
-    check(lib.kpx_class_scores_f32(logits.data_ptr(), target.data_ptr(), m, a, pred.data_ptr(), rank.data_ptr(), logp.data_ptr(),
-                                   _ptr(confusion), _stream()), 'kpx_class_scores_f32')
-    return pred, rank, logp
 
 
 # ----------------------------------------------------------------------------------------------- optimiser
@@ -2283,27 +1475,27 @@ def grad_health_workspace(n, device):
     return torch.empty(max(int(lib.kpx_grad_health_workspace_bytes(int(n))) // 8, 1), dtype=torch.float64, device=device)
 
 
-def _require_flat_f32(what, t, n=None):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(t, 'device', type(t)))
-    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() == 0 or (n is not None and t.numel() != n):
-        raise _lib.KpxError('%s must be a contiguous non-empty fp32 tensor%s (got %s %s)'
-                            % (what, '' if n is None else ' of %d elements' % n, t.dtype, tuple(t.shape)))
+def _flat_f32(what, name, t):
+    """The flat bucket an op is sized by: a contiguous non-empty fp32 tensor of any shape -> (its element count, its device)."""
+    dev = check_tensors(what, [(name, t, torch.float32, None)])
+    if not t.numel():
+        raise _lib.KpxError('%s: %s is empty' % (what, name))
+    return t.numel(), dev
 
 
-def _require_health(what, health, dev):
-    if not isinstance(health, torch.Tensor) or not health.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(health, 'device', type(health)))
-    if health.dtype != torch.int64 or not health.is_contiguous() or health.numel() * 8 != GUARD_HEALTH_BYTES or health.device != dev:
-        raise _lib.KpxError('%s: health must be the int64 [4] record of ops.new_guard_health on %s (got %s %s on %s)'
-                            % (what, dev, health.dtype, tuple(health.shape), health.device))
+def _health_spec(health, *options):
+    return ('health (the record of ops.new_guard_health)', health, torch.int64, GUARD_HEALTH_BYTES // 8) + options
+
+
+def _adam_specs(n, g, m, v, alpha_dev):
+    return [('g', g, torch.float32, n), ('m', m, torch.float32, n), ('v', v, torch.float32, n), ('alpha_dev', alpha_dev, torch.float32, 1)]
 
 
 def grad_health(g, health, work=None):
     """Count the NaN / Inf values of the flat gradient ``g`` and sum the squares (fp64) and the largest magnitude of the finite ones into the
     device record ``health`` (kpx_grad_health_f32: two launches, one read of g).  ``work``: grad_health_workspace(g.numel()) or larger."""
-    _require_flat_f32('grad_health: g', g)
-    _require_health('grad_health', health, g.device)
+    _, dev = _flat_f32('grad_health', 'g', g)
+    check_tensors('grad_health', [_health_spec(health)], dev)
     need = int(lib.kpx_grad_health_workspace_bytes(g.numel()))
     if work is None:
         work = grad_health_workspace(g.numel(), g.device)
@@ -2317,11 +1509,8 @@ def grad_health(g, health, work=None):
 def adam_tf_flat_guarded_(p, g, m, v, alpha_dev, beta1, beta2, eps, health, gscale=1.0):
     """adam_tf_flat_dev_alpha_ when ``health`` counts no non-finite gradient value (bit for bit), nothing otherwise; the record's counters
     are advanced either way."""
-    _require_flat_f32('adam_tf_flat_guarded_: p', p)
-    for name, t in (('g', g), ('m', m), ('v', v)):
-        _require_flat_f32('adam_tf_flat_guarded_: ' + name, t, p.numel())
-    _require_flat_f32('adam_tf_flat_guarded_: alpha_dev', alpha_dev, 1)
-    _require_health('adam_tf_flat_guarded_', health, p.device)
+    n, dev = _flat_f32('adam_tf_flat_guarded_', 'p', p)
+    check_tensors('adam_tf_flat_guarded_', _adam_specs(n, g, m, v, alpha_dev) + [_health_spec(health)], dev)
     check(lib.kpx_adam_tf_flat_guarded_f32(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), alpha_dev.data_ptr(),
                                            float(beta1), float(beta2), float(eps), float(gscale), health.data_ptr(), _stream()),
           'kpx_adam_tf_flat_guarded_f32')
@@ -2329,17 +1518,15 @@ def adam_tf_flat_guarded_(p, g, m, v, alpha_dev, beta1, beta2, eps, health, gsca
 
 def guard_restore_(dst, src, health):
     """dst = src (bit for bit) when ``health`` counts a non-finite gradient value, nothing otherwise."""
-    _require_flat_f32('guard_restore_: dst', dst)
-    _require_flat_f32('guard_restore_: src', src, dst.numel())
-    _require_health('guard_restore_', health, dst.device)
+    n, dev = _flat_f32('guard_restore_', 'dst', dst)
+    check_tensors('guard_restore_', [('src', src, torch.float32, n), _health_spec(health)], dev)
     check(lib.kpx_guard_restore_f32(dst.data_ptr(), src.data_ptr(), dst.numel(), health.data_ptr(), _stream()), 'kpx_guard_restore_f32')
 
 
 def read_guard_health(health):
     """Host copy of a KpxGuardHealth record (synchronises)."""
-    import struct
     raw = health.cpu().numpy().tobytes()
-    nonfinite, skipped_total, skipped_run, updates, sumsq, maxabs, _ = struct.unpack('<IIIIdff', raw)
+    nonfinite, skipped_total, skipped_run, updates, sumsq, maxabs, _ = _struct.unpack('<IIIIdff', raw)
     return dict(nonfinite=nonfinite, skipped_total=skipped_total, skipped_run=skipped_run, updates=updates, sumsq=sumsq, maxabs=maxabs)
 
 
@@ -2354,18 +1541,9 @@ def new_clip_state(device):
     return torch.zeros(CLIP_STATE_BYTES // 4, dtype=torch.int32, device=device)
 
 
-def _require_clip_state(what, clip, dev):
-    if not isinstance(clip, torch.Tensor) or not clip.is_cuda:
-        raise _lib.KpxError('kpx ops run on MI355X only (got a %s tensor); there is no CPU fallback' % getattr(clip, 'device', type(clip)))
-    if clip.dtype != torch.int32 or not clip.is_contiguous() or clip.numel() * 4 != CLIP_STATE_BYTES or clip.device != dev:
-        raise _lib.KpxError('%s: clip must be the int32 [4] record of ops.new_clip_state on %s (got %s %s on %s)'
-                            % (what, dev, clip.dtype, tuple(clip.shape), clip.device))
-
-
 def read_clip_state(clip):
     """Host copy of a KpxClipState record (synchronises)."""
-    import struct
-    norm, scale, clipped_total, _ = struct.unpack('<ffII', clip.cpu().numpy().tobytes())
+    norm, scale, clipped_total, _ = _struct.unpack('<ffII', clip.cpu().numpy().tobytes())
     return dict(norm=norm, scale=scale, clipped_total=clipped_total)
 
 
@@ -2373,12 +1551,9 @@ def adam_tf_flat_clipped_(p, g, m, v, alpha_dev, beta1, beta2, eps, health, clip
     """adam_tf_flat_guarded_ with tf.clip_by_global_norm over the bucket: with N = gscale * sqrt(health.sumsq) <= clip_norm the guarded update
     bit for bit; otherwise the gradient is scaled by clip_norm / N on top of gscale.  ``clip`` (ops.new_clip_state) receives N, the scale and
     the count of clipped updates; a skipped update leaves it alone."""
-    _require_flat_f32('adam_tf_flat_clipped_: p', p)
-    for name, t in (('g', g), ('m', m), ('v', v)):
-        _require_flat_f32('adam_tf_flat_clipped_: ' + name, t, p.numel())
-    _require_flat_f32('adam_tf_flat_clipped_: alpha_dev', alpha_dev, 1)
-    _require_health('adam_tf_flat_clipped_', health, p.device)
-    _require_clip_state('adam_tf_flat_clipped_', clip, p.device)
+    n, dev = _flat_f32('adam_tf_flat_clipped_', 'p', p)
+    check_tensors('adam_tf_flat_clipped_', _adam_specs(n, g, m, v, alpha_dev) + [
+        _health_spec(health), ('clip (the record of ops.new_clip_state)', clip, torch.int32, CLIP_STATE_BYTES // 4)], dev)
     clip_norm = float(clip_norm)
     if not clip_norm > 0.0:
         raise _lib.KpxError('adam_tf_flat_clipped_: clip_norm must be a number > 0 (got %r)' % (clip_norm,))
@@ -2435,11 +1610,8 @@ def grad_segment_stats(grads, params, table, work=None, out=None):
     """Per-variable sum of g^2 and of p^2 (fp64), largest finite |g| and count of non-finite g over the flat bucket ``grads`` (and ``params``, or
     None: sumsq_p = 0), by ``table`` (kpx_grad_segment_stats_f32: two launches, no atomics, bitwise reproducible).  -> ``out``, the device
     records; read_segment_stats makes them host numbers."""
-    _require_flat_f32('grad_segment_stats: grads', grads)
-    if params is not None:
-        _require_flat_f32('grad_segment_stats: params', params, grads.numel())
-        if params.device != grads.device:
-            raise _lib.KpxError('grad_segment_stats: grads and params must be on one device (got %s, %s)' % (grads.device, params.device))
+    n, dev = _flat_f32('grad_segment_stats', 'grads', grads)
+    check_tensors('grad_segment_stats', [('params', params, torch.float32, n, *OPTIONAL)], dev)
     if not isinstance(table, SegmentTable) or table.chunks.device != grads.device or table.ranges.device != grads.device:
         raise _lib.KpxError('grad_segment_stats: table must be the ops.grad_segment_table of the bucket on %s' % (grads.device,))
     if table.size > grads.numel():
@@ -2451,9 +1623,7 @@ def grad_segment_stats(grads, params, table, work=None, out=None):
     if (not isinstance(work, torch.Tensor) or not work.is_cuda or work.device != grads.device or not work.is_contiguous()
             or work.numel() * work.element_size() < need or work.data_ptr() % 8):
         raise _lib.KpxError('grad_segment_stats: work must be a contiguous 8-byte aligned tensor of at least %d bytes on %s' % (need, grads.device))
-    if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != grads.device or out.dtype != torch.int64 or not out.is_contiguous()
-            or out.numel() * 8 != table.n_segs * SEG_STATS_BYTES):
-        raise _lib.KpxError('grad_segment_stats: out must be the int64 [%d, 4] records of ops.grad_segment_workspace on %s' % (table.n_segs, grads.device))
+    check_tensors('grad_segment_stats', [('out (the records of ops.grad_segment_workspace)', out, torch.int64, table.n_segs * SEG_STATS_BYTES // 8)], dev)
     check(lib.kpx_grad_segment_stats_f32(grads.data_ptr(), _ptr(params), grads.numel(), table.chunks.data_ptr(), table.n_chunks,
                                          table.ranges.data_ptr(), table.n_segs, work.data_ptr(), out.data_ptr(), _stream()),
           'kpx_grad_segment_stats_f32')
@@ -2471,22 +1641,15 @@ def read_segment_stats(out):
 def ema_flat_(ema, p, rate_dev, health=None):
     """ema += (p - ema) * rate over one flat bucket, ``rate_dev`` a [1] fp32 device tensor read by the launch (kpx_ema_flat_f32).  With a
     ``health`` record that counts a non-finite gradient value the launch writes nothing; the record is only read."""
-    _require_flat_f32('ema_flat_: ema', ema)
-    _require_flat_f32('ema_flat_: p', p, ema.numel())
-    _require_flat_f32('ema_flat_: rate_dev', rate_dev, 1)
-    if p.device != ema.device or rate_dev.device != ema.device:
-        raise _lib.KpxError('ema_flat_: ema, p and rate_dev must be on one device (got %s, %s, %s)' % (ema.device, p.device, rate_dev.device))
-    if health is not None:
-        _require_health('ema_flat_', health, ema.device)
+    n, dev = _flat_f32('ema_flat_', 'ema', ema)
+    check_tensors('ema_flat_', [('p', p, torch.float32, n), ('rate_dev', rate_dev, torch.float32, 1), _health_spec(health, *OPTIONAL)], dev)
     check(lib.kpx_ema_flat_f32(ema.data_ptr(), p.data_ptr(), ema.numel(), rate_dev.data_ptr(), _ptr(health), _stream()), 'kpx_ema_flat_f32')
 
 
 def swap_flat_(a, b):
     """Exchange two flat fp32 ranges of equal size bit for bit (kpx_swap_flat_f32); the two must not overlap."""
-    _require_flat_f32('swap_flat_: a', a)
-    _require_flat_f32('swap_flat_: b', b, a.numel())
-    if b.device != a.device:
-        raise _lib.KpxError('swap_flat_: a and b must be on one device (got %s, %s)' % (a.device, b.device))
+    n, dev = _flat_f32('swap_flat_', 'a', a)
+    check_tensors('swap_flat_', [('b', b, torch.float32, n)], dev)
     lo, hi = sorted((a.data_ptr(), b.data_ptr()))
     if lo + a.numel() * 4 > hi:
         raise _lib.KpxError('swap_flat_: the two ranges overlap')
