@@ -115,6 +115,17 @@
 25. The configs[1] train step through the model API with ema off and on (ema=0.999), two models in one process, alternated in blocks; median
    ms per step of each and the difference in ms and %.
 
+``--novelty`` measures the nearest-motion search (evaluate.py --novelty) instead:
+
+26. kpx_seq_nearest_f32 (its two launches) on a synthetic store of Penn's size -- 1 171 videos, lengths drawn from 18..663, K = 40, 9 classes,
+   mirror images searched -- for Q = 64 and Q = 1 024 queries; device-event time of each call after warm-up, min / median / max ms, and the
+   fp64 fmas per second of 4 fmas per point, candidate window and query.  Beside it, in the same process: (a) a device copy of the store's label
+   buffer; (b) the route the kernel replaces on the same device: every window gathered with ``MotionStore.gather`` (kpx_keypoint_seq_augment_f32)
+   and the distances formed in torch in fp64, in chunks, with a per-class ``amin`` (the distances alone: no argmin, no exclusion), whose
+   result is compared with the kernel's.
+27. The rollout of configs[4] (B = 64, replayed HIP graph) at n_pts = 40 without and with what --novelty adds per batch and draw (the copy of
+   the draw's key points and one search of the 64 real futures and 64 rollouts), alternated; median ms of each and the difference.
+
 Prints one JSON line.
 """
 import argparse
@@ -1297,6 +1308,112 @@ def clip_step_leg(dev, steps):
             'clipped_ms_all': [round(v, 3) for v in ms['on']], 'grad_stats_call_ms': round(stats_ms, 2),
             'clip_report': models['on'].clip_report()}, models['on']
 
+NOVELTY_VIDEOS, NOVELTY_K, NOVELTY_CLASSES = 1171, 40, 9
+
+
+def _novelty_store(dev):
+    import numpy as np
+    from kpx_amd import novelty, resident
+    rs = np.random.RandomState(5)
+    counts = [int(v) for v in rs.randint(18, 664, size=NOVELTY_VIDEOS)]
+    names = ['frames/%04d' % (v + 1) for v in range(NOVELTY_VIDEOS)]
+    arrays = [(rs.rand(n, NOVELTY_K, 2) * 2.0 - 1.0).astype(np.float32) for n in counts]
+    listing = ['%s %d' % (name, rs.randint(NOVELTY_CLASSES)) for name in names]
+    idx = resident.LabelIndex(names, counts, arrays, [line.split()[1] for line in listing], NOVELTY_K)
+    return novelty.MotionStore(None, listing, NOVELTY_K, NOVELTY_CLASSES, dev, index=idx)
+
+
+def _novelty_torch_route(store, queries, window_chunk=1024, query_chunk=16):
+    """The distances of the search by the route it replaces: gather every window, fp64 differences in torch, per-class amin.  -> d2 [Q, A]"""
+    import numpy as np
+    q, a, w = queries.shape[0], store.n_action, len(store.windows)
+    action = store.table[:, 3].long()
+    best = torch.full((q, a), float('inf'), dtype=torch.float64, device=queries.device)
+    q64 = queries.double().reshape(q, -1, 2)
+    n = q64.shape[1]
+    for lo in range(0, w, window_chunk):
+        hi = min(w, lo + window_chunk)
+        v = store.gather(2 * np.arange(lo, hi)).double().reshape(hi - lo, -1, 2)
+        cls = action[lo:hi]
+        for qlo in range(0, q, query_chunk):
+            qq = q64[qlo:qlo + query_chunk, None]
+            ey2 = (qq[..., 1] - v[None, ..., 1]) ** 2
+            d = torch.minimum(((qq[..., 0] - v[None, ..., 0]) ** 2 + ey2).sum(-1), ((qq[..., 0] + v[None, ..., 0]) ** 2 + ey2).sum(-1)) / n
+            best[qlo:qlo + query_chunk].scatter_reduce_(1, cls[None].expand(d.shape[0], -1), d, 'amin')
+    return best
+
+
+def novelty_kernel_leg(dev, launches):
+    store = _novelty_store(dev)
+    w, n = len(store.windows), 32 * NOVELTY_K
+    labels = store.labels.labels
+    copy = torch.empty_like(labels)
+    us = _event_times(lambda: copy.copy_(labels), launches, dev)
+    spread = lambda ms: {'median_ms': round(statistics.median(ms), 3), 'min_ms': round(min(ms), 3), 'max_ms': round(max(ms), 3)}
+    res = {'videos': NOVELTY_VIDEOS, 'n_points': NOVELTY_K, 'classes': NOVELTY_CLASSES, 'windows': w, 'candidates': 2 * w,
+           'label_rows': int(store.labels.index.label_rows.sum()), 'store_mb': round(labels.numel() * 4 / 1e6, 1),
+           'blocks_of_64': int(store.order.numel() // 64),
+           'device_copy_of_store': dict(spread([v / 1e3 for v in us]), launches=launches,
+                                        gb_per_s=round(2 * labels.numel() * 4 / (statistics.median(us) * 1e-6) / 1e9, 1))}
+    g = torch.Generator(device=dev).manual_seed(9)
+    for q, reps, torch_reps in ((64, launches, 3), (1024, max(3, launches // 4), 1)):
+        queries = torch.rand((q, 32, NOVELTY_K, 2), generator=g, device=dev) * 2 - 1
+        d2 = torch.empty((q, NOVELTY_CLASSES), dtype=torch.float64, device=dev)
+        code = torch.empty((q, NOVELTY_CLASSES), dtype=torch.int32, device=dev)
+        from kpx_amd import ops
+        search = lambda: ops.seq_nearest(labels, store.labels.label_off, store.table, store.order, store.group_first, queries, out=(d2, code))
+        ms = [v / 1e3 for v in _event_times(search, reps, dev)]
+        fmas = 4.0 * n * 2 * w * q / 2                   # per point, window and query: ex^2, ey^2 plain and mirrored
+        entry = {'queries': q, 'kernel': dict(spread(ms), launches=reps, fp64_tfma_per_s=round(fmas / (statistics.median(ms) * 1e-3) / 1e12, 2))}
+        _novelty_torch_route(store, queries[:16])
+        torch.cuda.synchronize(dev)
+        tms = []
+        for _ in range(torch_reps):
+            t0 = time.perf_counter()
+            ref = _novelty_torch_route(store, queries)
+            torch.cuda.synchronize(dev)
+            tms.append((time.perf_counter() - t0) * 1e3)
+        rel = float(((d2 - ref).abs() / ref).max())
+        assert rel <= 1e-12 and bool((code >= 0).all()), rel
+        entry['gather_and_torch_fp64'] = dict(spread(tms), runs=torch_reps, max_rel_difference_to_kernel=rel)
+        entry['torch_over_kernel'] = round(statistics.median(tms) / statistics.median(ms), 1)
+        res['q%d' % q] = entry
+    return res, store
+
+
+def novelty_rollout_leg(dev, rollouts, store):
+    import kpx_amd
+    from kpx_amd import ops
+    cfg = {'model': {'n_pts': NOVELTY_K, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    queries = torch.rand((2, B, 32, NOVELTY_K, 2), generator=g, device=dev) * 2 - 1          # slot 0: the real futures
+    exclude = torch.randint(0, NOVELTY_VIDEOS, (2 * B,), generator=g, device=dev).to(torch.int32)
+    feed = {'image': im, 'action_code': act}
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    for _ in range(3):                                    # eager, capture, one replay
+        o = fm.run(None, feed, z=z)
+    store.nearest(queries.view(2 * B, 32, NOVELTY_K, 2), True, exclude)
+    torch.cuda.synchronize(dev)
+    ms = {False: [], True: []}
+    for _ in range(rollouts):
+        for score in (False, True):
+            t0 = time.perf_counter()
+            o = fm.run(None, feed, z=z)
+            if score:
+                ops.flat_copy_tensor(o['fut_pt_raw'].contiguous(), queries[1].data_ptr())
+                d2, code = store.nearest(queries.view(2 * B, 32, NOVELTY_K, 2), True, exclude)
+            torch.cuda.synchronize(dev)
+            ms[score].append((time.perf_counter() - t0) * 1e3)
+    assert bool((code >= 0).all())
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    return {'batch': B, 'n_points': NOVELTY_K, 'queries_per_rollout': 2 * B, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 1,
+            'off_ms': round(off, 3), 'on_ms': round(on, 3), 'delta_ms': round(on - off, 3), 'overhead_pct': round(100 * (on - off) / off, 2),
+            'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -1326,7 +1443,18 @@ def main():
     ap.add_argument('--clip', action='store_true',
                     help='measure gradient clipping (the clipped update beside the guarded update and a device copy, the per-variable statistics '
                          'on the two real buckets, the configs[1] train step guarded without and with clip_norm, all in this process) instead')
+    ap.add_argument('--novelty', action='store_true',
+                    help='measure the nearest-motion search (the kernel on a Penn-sized synthetic store beside a device copy and the gather + torch '
+                         'fp64 route, the cost of --novelty per configs[4] rollout, all in this process) instead')
     args = ap.parse_args()
+    if args.novelty:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        kernels, store = novelty_kernel_leg(dev, args.launches)
+        torch.cuda.empty_cache()
+        print(json.dumps({'novelty_kernels': kernels, 'novelty_rollout_c4': novelty_rollout_leg(dev, args.rollouts, store)}))
+        return
     if args.clip:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

@@ -8,6 +8,7 @@
                        [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
                        [--metrics --action-accuracy CKPT]
                        [--gif [--gif-fps N] [--gif-dither A]]
+                       [--metrics --novelty [--novelty-sheets] [--novelty-no-mirror]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -90,6 +91,22 @@ crosses to the host, where ``kpx_amd.gif.write_gif`` packs it (LZW in the librar
 stored as the delay round(100 / N) centiseconds; ``--gif-dither A`` (0..64, default 0) adds a 4 x 4 ordered dither of that amplitude
 before the search.  ``<save_dir>/gif.json`` records the columns, fps, dither, the frame count and the palette size per sample.  DESIGN.md
 section 2 has the definition.  Without the flag every file keeps its bytes.
+
+``--novelty`` (with ``--metrics``; data path only) asks whether the motion generator invents motions or replays training sequences: the
+pseudo labels of ``train_set.txt`` are kept in HBM once (``kpx_amd.novelty.MotionStore``) and every draw's predicted key points, the pseudo
+labels of the real future and, with ``--actions``, every class rollout are searched in the set of sequences the stage-2 loader can draw
+without augmentation -- every legal start frame of every listed video at its own gap, and their mirror images unless
+``--novelty-no-mirror`` -- per action class, in fp64, by ``kpx_amd.ops.seq_nearest`` (two launches per batch).  A query never finds the
+windows of its own source video.  metrics.npz gains ``nov_d`` [samples, draws] (the RMS point distance to the nearest window, in label
+coordinates), ``nov_code`` (2 * window + mirrored, -1 when nothing was found), ``nov_class_d`` [samples, draws, A], ``nov_window`` [samples,
+draws, 4] = (listing line, im_idx, gap, mirrored), ``nov_real_d`` / ``nov_real_code`` / ``nov_real_class_d`` / ``nov_real_window`` for the
+real future, ``nov_own`` [samples], ``nov_window_action`` [W] and with ``--actions`` ``act_nov_d`` / ``act_nov_code`` [samples, classes,
+draws]; metrics.json a ``novelty`` block (``summarise_novelty``): the distances of the rollouts beside those of fresh real motion, their
+ratio, the share of rollouts closer than the closest 5 % of the real ones, and how often the nearest training motion belongs to the query's
+class.  ``--novelty-sheets`` (at most 31 ``--samples``; not with ``--no-save``) writes per sample ``nearest.png``: a row for the real future,
+then per draw the rollout and under it its nearest training window (``MotionStore.gather``), as colourised key points at the
+``--sheet-frames`` frames.  This is the project's own key-point-space quantity, not comparable with published figures.  Without the flags
+every output keeps its bytes.
 """
 import json
 import os
@@ -445,6 +462,157 @@ class _ActionAccuracy:
         return out
 
 
+NOVELTY_DEFINITION = (
+    'novelty: this project\'s own key-point-space quantity, not comparable with published figures. Candidates: every sequence the stage-2 '
+    'loader can draw from train_set.txt without augmentation (per listing line every legal start frame at the video\'s own gap = '
+    'int(n_files / 33), the interpolated form for videos shorter than 33 frames) and, when mirror is true, its mirror image (x negated). '
+    'd2(query, candidate) = the mean over the 32 frames and K points of the squared Euclidean distance in label coordinates, in fp64; a '
+    'query is every draw\'s predicted key points (pred), the pseudo labels of the real future frames (real) and with --actions every class '
+    'rollout (commanded); the candidates of the query\'s own source video are left out. d = sqrt of the minimum of d2 over all candidates: '
+    'an RMS point distance; ties go to the lowest code = 2 * window + mirrored. pred and real: mean, median and p05 (the 5th percentile, '
+    'linear interpolation) of d over the queries that found a candidate. ratio = median pred / median real: near 1 the rollouts lie as far '
+    'from the training set as fresh real motion does, well below 1 they replay it. copy_threshold = p05 of real, null below 20 real '
+    'queries; copied = the share of pred queries with d below it. nn_top1: the share of queries whose nearest candidate was listed under '
+    'the query\'s class (real: the sample\'s class, the ceiling; pred: the sample\'s class; commanded: the commanded class), chance = 1 / '
+    'the number of classes with a candidate. mirrored = the share of pred queries whose nearest candidate is a mirror image. n_nonfinite: '
+    'queries that found no candidate (a non-finite key point, or no candidate left); they enter no other figure.')
+
+
+def nearest_over_classes(d2, code):
+    """d2 float64 [..., A], code int [..., A] per class -> (d2 [...], code [...]) of the minimum over the classes, ties to the lowest code;
+    +inf and -1 where no class found a candidate.  numpy only."""
+    d2, code = np.asarray(d2, np.float64), np.asarray(code, np.int64)
+    low = d2.min(axis=-1) if d2.shape[-1] else np.full(d2.shape[:-1], np.inf)
+    at = (d2 == low[..., None]) & (code >= 0)
+    best = np.where(at, code, np.iinfo(np.int64).max).min(axis=-1) if d2.shape[-1] else np.full(d2.shape[:-1], -1, np.int64)
+    found = at.any(axis=-1) & np.isfinite(low)
+    return np.where(found, low, np.inf), np.where(found, best, -1).astype(np.int32)
+
+
+def summarise_novelty(arrays, mirror=True):
+    """The ``novelty`` block of metrics.json (NOVELTY_DEFINITION) from the arrays --novelty puts into metrics.npz: nov_d / nov_code [S, D],
+    nov_real_d / nov_real_code [S], nov_own [S], nov_window_action [W] and optionally actions [C] with act_nov_d / act_nov_code [S, C, D].
+    numpy only."""
+    win_action = np.asarray(arrays['nov_window_action'], np.int64)
+    own = np.asarray(arrays['nov_own'], np.int64)
+    n_cls = len(np.unique(win_action))
+    n_bad = [0]
+
+    def found(d, code):
+        d, code = np.asarray(d, np.float64), np.asarray(code, np.int64)
+        ok = (code >= 0) & np.isfinite(d)
+        n_bad[0] += int((~ok).sum())
+        return d, code, ok
+
+    def stats(x):
+        if not x.size:
+            return {'mean': None, 'median': None, 'p05': None}
+        return {'mean': _json_num(x.mean()), 'median': _json_num(np.median(x)), 'p05': _json_num(np.percentile(x, 5))}
+
+    def top1(code, ok, target):
+        hit = win_action[np.where(ok, code >> 1, 0)] == target
+        return _json_num(hit[ok].mean()) if ok.any() else None
+
+    pd, pc, pok = found(arrays['nov_d'], arrays['nov_code'])
+    rd, rc, rok = found(arrays['nov_real_d'], arrays['nov_real_code'])
+    out = {'definition': NOVELTY_DEFINITION, 'mirror': bool(mirror), 'n_windows': int(win_action.size), 'n_pred': int(pok.sum()),
+           'n_real': int(rok.sum()), 'pred': stats(pd[pok]), 'real': stats(rd[rok])}
+    pm, rm = out['pred']['median'], out['real']['median']
+    out['ratio'] = _json_num(pm / rm) if pm is not None and rm else None
+    out['copy_threshold'] = out['real']['p05'] if rok.sum() >= 20 else None
+    out['copied'] = _json_num((pd[pok] < out['copy_threshold']).mean()) if out['copy_threshold'] is not None and pok.any() else None
+    out['nn_top1'] = {'chance': 1.0 / n_cls if n_cls else None, 'real': top1(rc, rok, own), 'pred': top1(pc, pok, own[:, None])}
+    if 'act_nov_code' in arrays:
+        ad, ac, aok = found(arrays['act_nov_d'], arrays['act_nov_code'])
+        out['nn_top1']['commanded'] = top1(ac, aok, np.asarray(arrays['actions'], np.int64)[None, :, None])
+    out['mirrored'] = _json_num((pc[pok] & 1).mean()) if pok.any() else None
+    out['n_nonfinite'] = n_bad[0]
+    return out
+
+
+class _Novelty:
+    """--novelty: the store of training motions, the queries of a batch and their search; the results stay on the device until the end."""
+
+    def __init__(self, kpx_amd, config, dev, samples, actions, mirror, sheet_frames, colors):
+        data_dir = config['paths']['data_dir']
+        with open(osp.join(data_dir, 'train_set.txt')) as f:
+            listing = f.read().splitlines()
+        self.ops, self.dev, self.samples, self.actions, self.mirror = kpx_amd.ops, dev, samples, actions or [], mirror
+        self.store = kpx_amd.novelty.MotionStore(data_dir, listing, config['model']['n_pts'], config['model']['n_action'], dev)
+        self.sheet_frames = sheet_frames
+        self.colors = torch.tensor(colors, dtype=torch.float32, device=dev) if sheet_frames is not None else None
+        self.d2, self.code, self.own = [], [], []
+
+    def begin_batch(self, videos, batch):
+        """Slot 0 of the batch's queries holds the real future; 1 .. samples the draws; then draw-major the class rollouts."""
+        kp_real = batch['real_seq'].contiguous()
+        self.bsz = kp_real.shape[0]
+        n = 1 + self.samples * (1 + len(self.actions))
+        self.queries = torch.empty((n,) + tuple(kp_real.shape), dtype=torch.float32, device=self.dev)
+        self.ops.flat_copy_tensor(kp_real, self.queries[0].data_ptr())
+        self.exclude = torch.tensor([self.store.video(v) for v in videos], dtype=torch.int32, device=self.dev).repeat(n)
+        self.own.append(batch['action_code'].argmax(dim=1).to(torch.int32))
+
+    def own_draw(self, draw, fut_pt_raw):
+        self.ops.flat_copy_tensor(fut_pt_raw.contiguous(), self.queries[1 + draw].data_ptr())
+
+    def class_rollout(self, draw, a, fut_pt_raw):
+        self.ops.flat_copy_tensor(fut_pt_raw.contiguous(), self.queries[1 + self.samples + draw * len(self.actions) + a].data_ptr())
+
+    def end_batch(self, save_dir, first_sample):
+        q = self.queries.view((-1,) + tuple(self.queries.shape[2:]))
+        d2, code = self.store.nearest(q, self.mirror, self.exclude)
+        self.d2.append(d2.view(self.queries.shape[0], self.bsz, -1))
+        self.code.append(code.view(self.queries.shape[0], self.bsz, -1))
+        if self.sheet_frames is not None:
+            self._write_sheets(save_dir, first_sample)
+
+    def _write_sheets(self, save_dir, first_sample):
+        from PIL import Image
+        ops, frames, b, d = self.ops, self.sheet_frames, self.bsz, self.samples
+        _, code = nearest_over_classes(self.d2[-1][1:1 + d].cpu().numpy(), self.code[-1][1:1 + d].cpu().numpy())       # [D, B]
+        h = w = 128
+        canvas = torch.zeros((b, (1 + 2 * d) * h, len(frames) * w, 3), dtype=torch.uint8, device=self.dev)
+
+        def paste(row, seq, keep=None):
+            pts = seq[:, frames].contiguous()                                                             # [n, J, K, 2]
+            maps = ops.point_maps_rgb(pts.view((-1,) + tuple(pts.shape[2:])), h, w, self.colors).view(pts.shape[0], len(frames), h, w, 3)
+            if keep is None:
+                ops.sheet_paste(canvas, maps, list(range(len(frames))), row, 0, 'raw')
+            else:                            # the samples that found a window, one by one; the others keep their black row
+                for i, j in enumerate(keep):
+                    ops.sheet_paste(canvas[j:j + 1], maps[i:i + 1].contiguous(), list(range(len(frames))), row, 0, 'raw')
+        paste(0, self.queries[0])
+        for draw in range(d):
+            paste(1 + 2 * draw, self.queries[1 + draw])
+            keep = [j for j in range(b) if code[draw, j] >= 0]
+            if keep:
+                paste(2 + 2 * draw, self.store.gather(code[draw, keep]), keep)
+        host = _sheet_to_host(canvas)
+        for batch_idx in range(b):
+            dd = osp.join(save_dir, '%04d' % (first_sample + batch_idx))
+            os.makedirs(dd, exist_ok=True)
+            Image.fromarray(host[batch_idx]).save(osp.join(dd, 'nearest.png'))
+
+    def arrays(self):
+        """-> the nov_* arrays of metrics.npz (one copy to the host per kind)"""
+        d, c, a = self.samples, len(self.actions), self.store.n_action
+        cat = lambda ts, dt: torch.cat(ts, dim=1).cpu().numpy() if ts else np.zeros((1 + d * (1 + c), 0, a), dt)
+        d2, code = cat(self.d2, np.float64), cat(self.code, np.int32)                                   # [1 + D + D C, S, A]
+        win = self.store.windows
+        out = {'nov_own': torch.cat(self.own).cpu().numpy() if self.own else np.zeros((0,), np.int32), 'nov_window_action': win.table[:, 3].copy()}
+        low, best = nearest_over_classes(d2, code)
+        out.update(nov_real_d=np.sqrt(low[0]), nov_real_code=best[0], nov_real_class_d=np.sqrt(d2[0]), nov_real_window=win.describe(best[0]),
+                   nov_d=np.ascontiguousarray(np.sqrt(low[1:1 + d]).T), nov_code=np.ascontiguousarray(best[1:1 + d].T),
+                   nov_class_d=np.ascontiguousarray(np.sqrt(d2[1:1 + d]).transpose(1, 0, 2)))
+        out['nov_window'] = win.describe(out['nov_code'])
+        if c:
+            s = low.shape[1]
+            out['act_nov_d'] = np.ascontiguousarray(np.sqrt(low[1 + d:]).reshape(d, c, s).transpose(2, 1, 0))
+            out['act_nov_code'] = np.ascontiguousarray(best[1 + d:].reshape(d, c, s).transpose(2, 1, 0))
+        return out
+
+
 DRIVE_MODES = ('labels', 'hold', 'transfer')                                      # the order of the runs and of the sheet's rows
 DRIVE_METRICS = ('ssim', 'psnr', 'mse')
 DRIVE_DEFINITION = (
@@ -701,7 +869,7 @@ def _drive_line(blk):
 
 
 def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None,
-                   frechet=None, accuracy=None):
+                   frechet=None, accuracy=None, novelty=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
@@ -710,7 +878,7 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}.
     drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}.
     frechet (--frechet): the accumulators {'real_even', 'real_odd', 'pred', 'pred_draw0'}; also writes frechet.npz.
-    accuracy (--action-accuracy): the _ActionAccuracy of the run."""
+    accuracy (--action-accuracy): the _ActionAccuracy of the run.  novelty (--novelty): the _Novelty of the run."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -764,6 +932,10 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         np.savez(osp.join(save_dir, 'frechet.npz'), **stored)
     if accuracy is not None:
         arrays.update(accuracy.arrays())
+    if novelty is not None:
+        if act is None and novelty.actions:
+            arrays['actions'] = np.asarray(novelty.actions, np.int32)
+        arrays.update(novelty.arrays())
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
@@ -776,6 +948,9 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         res['drive'] = summarise_drive(drive, model={'ssim': ssim, 'psnr': psnr, 'mse': mse})
     if accuracy is not None:
         res['action_accuracy'] = summarise_action_accuracy(arrays)
+    if novelty is not None:
+        res['definition'] += ' ' + NOVELTY_DEFINITION
+        res['novelty'] = summarise_novelty(arrays, mirror=novelty.mirror)
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
@@ -805,6 +980,12 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
                  % (fmt(blk['real']['top1'], '%.4f'), fmt(blk['pred']['top1'], '%.4f'),
                     ', commanded %s' % fmt(blk['commanded']['top1'], '%.4f') if 'commanded' in blk else '', blk['real']['chance'],
                     fmt(blk['kp_fd']['kp_fd'], '%.4g'), fmt(blk['kp_fd']['kp_fd_floor'], '%.4g')))
+    if novelty is not None:
+        blk = res['novelty']
+        line += (', nearest training motion (own quantity, not comparable with published figures) median pred %s, real %s, ratio %s, '
+                 'copied %s, nn top-1 real %s, predicted %s'
+                 % (fmt(blk['pred']['median'], '%.4f'), fmt(blk['real']['median'], '%.4f'), fmt(blk['ratio'], '%.3f'), fmt(blk['copied'], '%.3f'),
+                    fmt(blk['nn_top1']['real'], '%.4f'), fmt(blk['nn_top1']['pred'], '%.4f')))
     print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
     if drive is not None:
         print(_drive_line(res['drive']))
@@ -867,7 +1048,27 @@ def main(argv=None):
                              'points side by side), quantised to one palette per GIF on the device; <save_dir>/gif.json')
     parser.add_argument('--gif-fps', type=int, default=None, help='with --gif: frames per second, 1..50 (default 10)')
     parser.add_argument('--gif-dither', type=int, default=None, help='with --gif: amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
+    parser.add_argument('--novelty', action='store_true',
+                        help='with --metrics: search every rollout and the real future in the training motions of train_set.txt (the nearest '
+                             "window per action class, in HIP) and report how far they lie.  This project's own key-point-space quantity: "
+                             'not comparable with published figures')
+    parser.add_argument('--novelty-sheets', action='store_true',
+                        help='with --novelty: per sample nearest.png, every rollout above its nearest training window (--sheet-frames picks the frames)')
+    parser.add_argument('--novelty-no-mirror', action='store_true', help='with --novelty: do not search the mirror images of the training motions')
     args = parser.parse_args(argv)
+    if (args.novelty_sheets or args.novelty_no_mirror) and not args.novelty:
+        parser.error('--novelty-sheets and --novelty-no-mirror shape the search of --novelty and need it')
+    if args.novelty and args.synthetic:
+        parser.error('--novelty searches the training motions for the rollouts of real videos and their pseudo labels, and --synthetic '
+                     'inputs have neither')
+    if args.novelty and not args.metrics:
+        parser.error('--novelty adds to the scores of --metrics and needs it')
+    if args.novelty and args.drive_only:
+        parser.error("--drive-only skips the model's own rollout, which --novelty is about")
+    if args.novelty_sheets and args.no_save:
+        parser.error('--novelty-sheets writes files, and --no-save writes none')
+    if args.novelty_sheets and args.samples > 31:
+        parser.error('--novelty-sheets draws two rows per draw and holds at most 31 --samples (got %d)' % args.samples)
     if (args.gif_fps is not None or args.gif_dither is not None) and not args.gif:
         parser.error('--gif-fps and --gif-dither shape the files of --gif and need it')
     if args.gif and args.no_save:
@@ -878,8 +1079,8 @@ def main(argv=None):
         parser.error('--gif-fps takes 1..50 frames per second (got %d)' % gif_fps)
     if not 0 <= gif_dither <= 64:
         parser.error('--gif-dither takes an amplitude in 0..64 (got %d)' % gif_dither)
-    if args.sheet_frames is not None and args.actions is None and args.drive is None:
-        parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive and needs it')
+    if args.sheet_frames is not None and args.actions is None and args.drive is None and not args.novelty_sheets:
+        parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive / --novelty-sheets and needs it')
     drive_modes = None
     if args.drive is not None:
         listed = [m.strip() for m in args.drive.split(',')] if args.drive.strip() else []
@@ -929,7 +1130,7 @@ def main(argv=None):
         parser.error('--samples must be >= 1 (got %d)' % args.samples)
     config = load_config(args.config)
     actions = sheet_frames = None
-    if args.actions is not None or drive_modes is not None:
+    if args.actions is not None or drive_modes is not None or args.novelty_sheets:
         n_cls_all = config['model'].get('n_action', 9)
         try:
             if args.actions is not None:
@@ -984,8 +1185,14 @@ def main(argv=None):
         drive_scores = {m: [] for m in drive_modes if m != 'transfer'} if drive_modes and args.metrics else None
         n_self_driven = 0
         accuracy = _ActionAccuracy(kpx_amd, config, args.action_accuracy, dev, args.samples, actions, ema=args.action_accuracy_ema) if args.action_accuracy is not None else None
+        novelty = None
+        if args.novelty:
+            novelty = _Novelty(kpx_amd, config, dev, args.samples, actions, not args.novelty_no_mirror,
+                               sheet_frames if args.novelty_sheets else None, model.colors)
+        n_read = 0                                                       # samples read so far: the listing line of a batch's first sample
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
+            n_read += bsz
             if args.drive_only:              # the driven rollouts alone: no own rollout, so no draws and nothing of what they write
                 real_flat = batch['real_im_seq'].reshape(bsz * n_frames, *batch['real_im_seq'].shape[2:]) if args.metrics else None
                 if not args.no_save:
@@ -1030,14 +1237,17 @@ def main(argv=None):
                         kpx_amd.ops.fill_raw_(moments, 0.0)
                 if accuracy is not None:
                     accuracy.begin_batch(batch)
+                if novelty is not None:
+                    novelty.begin_batch([line.split()[0] for line in loader._images[n_read - bsz:n_read]], batch)
             sweep = None
             if actions:
                 sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, batch['image'], batch['real_im_seq'], not args.no_save,
                                     args.samples, batch['real_seq'].contiguous() if args.metrics else None, dev)
                 if args.metrics:
                     action_scores['own'].append(batch['action_code'].clone())
-                if accuracy is not None:
-                    sweep.on_class = accuracy.class_rollout
+                hooks = [h.class_rollout for h in (accuracy, novelty) if h is not None]
+                if hooks:
+                    sweep.on_class = hooks[0] if len(hooks) == 1 else lambda *a: [h(*a) for h in hooks]
             for draw in range(args.samples):
                 # --actions: one z per batch and draw, drawn here, for the batch's own rollout and for every class of the sweep
                 z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None
@@ -1053,6 +1263,8 @@ def main(argv=None):
                         scorer(pred_flat, out=vgg_score[draw])
                     if accuracy is not None:
                         accuracy.own_draw(draw, outputs['fut_pt_raw'])
+                    if novelty is not None:
+                        novelty.own_draw(draw, outputs['fut_pt_raw'])
                     if args.motion_metrics:
                         kpx_amd.ops.flat_copy_tensor(outputs['fut_pt_raw'].contiguous(), kp_pred[draw].data_ptr())
                         if args.samples >= 2:
@@ -1104,6 +1316,8 @@ def main(argv=None):
                         sweep.write_sheets(args.save_dir, sample_idx - bsz)
                     if draw == args.samples - 1 and args.metrics:
                         sweep.scores(action_scores)
+            if novelty is not None:
+                novelty.end_batch(args.save_dir, n_read - bsz)
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
         if actions and not args.no_save:
@@ -1117,7 +1331,7 @@ def main(argv=None):
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
             _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores, frechet,
-                           accuracy)
+                           accuracy, novelty)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

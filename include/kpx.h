@@ -29,7 +29,7 @@ extern "C" {
 #endif
 
 #define KPX_EINVAL (-1)
-#define KPX_ABI_VERSION 24
+#define KPX_ABI_VERSION 25
 
 enum { KPX_ACT_NONE = 0, KPX_ACT_RELU = 1, KPX_ACT_LRELU = 2 /* slope 0.01 */, KPX_ACT_TANH = 3 /* forward only */ };
 
@@ -907,6 +907,45 @@ int kpx_joint_scores_f32(const float* pts /*[F,K,2]*/, const float* target /*[F,
                          const double* W /*[J,D,2]*/, const double* alpha /*[A]*/, int F, int K, int J, int A, float* pred /*[F,J,2]*/,
                          float* err /*[F,J]*/, uint8_t* hits /*[F,J]*/, double* sum_err /*[J]*/, int64_t* count /*[J]*/,
                          int64_t* pck_count /*[J]*/, int64_t* hit_count /*[J,A]*/, void* stream);
+
+/* ---- nearest training motion of a key-point sequence (csrc/novelty.hip; evaluate.py --novelty, kpx_amd/novelty.py), DESIGN.md section 2.
+ * No reference counterpart.  Added in ABI version 25.
+ *
+ *   labels, label_off   the resident label store of kpx_keypoint_seq_augment_f32
+ *   windows     int32 [W][KPX_NEAREST_ROW_INTS] = (video number, im_idx, gap, action index): the candidate windows, in listing order; the
+ *               window id w is the row number.  Frame t = 1..32 of window w is the loader's un-augmented real_seq[t - 1] in fp32: for gap >= 1
+ *               label row im_idx + gap * t, for gap == 0 rows im_idx + (t >> 1) with every odd t the float32 mean of its neighbours (float32
+ *               add, float32 halving) -- the values kpx_keypoint_seq_augment_f32 delivers with no flag set, bit for bit.
+ *   order       int32 [n_groups][KPX_NEAREST_GROUP]: the window ids grouped by action class, ascending inside a class, every class starting a
+ *               new block and its last block closed with -1 pads; group_first int32 [n_action + 1]: class a owns the blocks group_first[a] ..
+ *               group_first[a + 1] - 1 (kpx_amd.novelty.WindowIndex.plan builds both)
+ *   queries     fp32 [Q][32][n_points][2]; exclude int32 [Q] or NULL: the windows of that video number are skipped for the query (-1: none)
+ *   d2          double [Q][n_action], code int32 [Q][n_action]
+ *
+ * d2(q, w, m) = (sum_t sum_k ex^2 + ey^2) / (32 n_points), ex = (double)q.x - (double)v.x, ey = (double)q.y - (double)v.y, and for the mirrored
+ * candidate (m = 1, only with `mirror`) ex = (double)q.x + (double)v.x.  All in fp64: the conversions and differences are exact; lane l of one
+ * wavefront adds the points j = l, l + 64, ... (j = (t - 1) n_points + k) in ascending order with s = fma(ex, ex, s), s = fma(ey, ey, s) from
+ * s = 0, the 64 lane sums are added in the xor butterfly 32, 16, 8, 4, 2, 1, and the total is divided by 32 n_points once.  The bits of
+ * d2(q, w, m) therefore depend on the query's and the window's values and on n_points alone: not on w, q, Q, W or the grid.
+ * Per query and class a the result is the minimum of d2 over the candidates of class a and code = 2 w + m of the minimising one; ties go to the
+ * lowest code; a candidate whose d2 is not finite is never chosen; a class without a chosen candidate gets d2 = +inf and code = -1.
+ * Two launches on `stream`, no atomics: per block of `order` and query one partial (d2, code) goes into `workspace`, then one thread per (q, a)
+ * combines the class's blocks in ascending order.  workspace: kpx_seq_nearest_workspace_bytes(n_groups, Q) bytes (0 for sizes out of range),
+ * 8-byte aligned.  Capturable.
+ * Limits: 1 <= n_points <= KPX_SEQ_MAX_POINTS, 1 <= n_action <= KPX_SEQ_MAX_ACTIONS, 1 <= Q <= KPX_NEAREST_MAX_QUERIES, 1 <= W <=
+ * KPX_NEAREST_MAX_WINDOWS (W < 2^30: a code fits an int32), n_groups <= ceil(W / KPX_NEAREST_GROUP) + n_action; labels, label_off, queries,
+ * workspace and d2 8-byte aligned, the int32 tables 4-byte.  Anything else is KPX_EINVAL before any device call.  The kernel trusts the tables
+ * and clamps nothing: the HOST rejects, before the launch, a video number outside the store, a window that leaves its video's label rows and an
+ * action index outside 0..n_action-1 (kpx_amd.novelty.WindowIndex.check). */
+#define KPX_NEAREST_ROW_INTS 4
+#define KPX_NEAREST_GROUP 64
+#define KPX_NEAREST_MAX_QUERIES 4096
+#define KPX_NEAREST_MAX_WINDOWS ((1 << 30) - 1)
+size_t kpx_seq_nearest_workspace_bytes(int n_groups, int Q);
+int kpx_seq_nearest_f32(const float* labels, const int64_t* label_off, const int32_t* windows /*[W][4]*/, int W, const int32_t* order,
+                        const int32_t* group_first /*[n_action + 1]*/, int n_groups, const float* queries /*[Q,32,K,2]*/,
+                        const int32_t* exclude /*[Q] or NULL*/, int Q, int n_points, int n_action, int mirror, void* workspace,
+                        size_t workspace_bytes, double* d2 /*[Q,A]*/, int32_t* code /*[Q,A]*/, void* stream);
 
 #ifdef __cplusplus
 }

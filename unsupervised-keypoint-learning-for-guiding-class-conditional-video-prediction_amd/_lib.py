@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/kpx.h one to one (tests/test_abi.py checks header vs this table)
-ABI_VERSION = 24    # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
+ABI_VERSION = 25    # = KPX_ABI_VERSION of include/kpx.h (tests/test_abi.py holds the two equal); bumped whenever a signature changes
 SIGNATURES = {
     'kpx_abi_version': (c_int, []),
     'kpx_reload_env': (c_int, []),
@@ -169,6 +169,8 @@ SIGNATURES = {
     'kpx_augment_geometry_u8': (c_int, [P, P, P, c_int, P, c_int, P, P, P]),
     'kpx_augment_filter_f32': (c_int, [P, P, P, c_int, P, P, P]),
     'kpx_keypoint_seq_augment_f32': (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
+    'kpx_seq_nearest_workspace_bytes': (c_size_t, [c_int, c_int]),
+    'kpx_seq_nearest_f32': (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P]),
     'kpx_softmax_xent_fwd_f32': (c_int, [P, P, c_int, c_int, P, P, P]),
     'kpx_softmax_xent_bwd_f32': (c_int, [P, P, P, c_int, c_int, P, c_float, P, P]),
     'kpx_class_scores_f32': (c_int, [P, P, c_int, c_int, P, P, P, P, P]),

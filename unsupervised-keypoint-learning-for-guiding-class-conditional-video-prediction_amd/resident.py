@@ -572,12 +572,15 @@ class SequencePlanner(object):
 class ResidentLabels(SequencePlanner):
     """Every listed video's pseudo labels in ONE flat float32 device buffer, with the offsets and the trig table beside it."""
 
-    def __init__(self, data_dir, listing, n_points, n_action, device):
+    def __init__(self, data_dir, listing, n_points, n_action, device, index=None):
+        """``index``: a ``LabelIndex`` built by the caller (from arrays, say) takes the place of the scan of ``data_dir``."""
         import torch
         device = torch.device(device)
         if device.type != 'cuda':
             raise _error('resident labels live in HBM: device %s is not a GPU (the package has no CPU fallback)' % device)
-        super(ResidentLabels, self).__init__(LabelIndex.scan(data_dir, listing, n_points), n_action)      # raises before anything is allocated
+        if index is None:
+            index = LabelIndex.scan(data_dir, listing, n_points)
+        super(ResidentLabels, self).__init__(index, n_action)      # raises before anything is allocated
         self.device = device
         self.labels = torch.from_numpy(self.index.labels).to(device)
         self.label_off = torch.from_numpy(self.index.offsets).to(device)

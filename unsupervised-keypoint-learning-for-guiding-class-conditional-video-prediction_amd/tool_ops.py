@@ -1,7 +1,8 @@
 """Forward-only wrappers around the C ABI (include/kpx.h) for the tools around training: evaluate.py, animate.py, make_pseudo_labels.py
 and the summaries.  None of them runs inside a train step; each is called once per batch, so its tensors go through the spec checker of
 ``_args`` (one list of (name, tensor, dtype, shape) per op) and only what is specific to the op -- value ranges, mode rules, table
-read-backs -- is written out.  ``ops`` re-exports every name here: ``ops.sheet_paste``, ``ops.MAX_DRAWS`` ... are the public names.
+read-backs -- is written out.  ``ops`` re-exports every name here: ``ops.sheet_paste``, ``ops.MAX_DRAWS`` ... are the public names.  ``seq_nearest`` (evaluate.py --novelty)
+is written beside its tables in ``novelty`` and reaches ``tool_ops`` and ``ops`` by the import at the end of each.
 """
 import numpy as np
 import torch
@@ -589,3 +590,7 @@ def class_scores(logits, target, confusion=None, out=None, check_target=True):
     check(lib.kpx_class_scores_f32(logits.data_ptr(), target.data_ptr(), m, a, pred.data_ptr(), rank.data_ptr(), logp.data_ptr(),
                                    _ptr(confusion), _stream()), 'kpx_class_scores_f32')
     return pred, rank, logp
+
+
+# ----------------------------------------------------------------------------------------------- nearest training motion
+from .novelty import seq_nearest, NEAREST_GROUP, NEAREST_MAX_QUERIES, NEAREST_MAX_WINDOWS      # noqa: E402,F401
