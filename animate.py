@@ -3,6 +3,7 @@
     python animate.py --config C --checkpoint_stage1 S1 [--checkpoint_stage2 S2] --images PATH [PATH ...]
                       [--box x0,y0,x1,y1] [--actions all|i,j,k] [--samples S] [--seed N] [--overlay R] [--sheet-frames i,j,k]
                       [--driver DIR [--driver-mode relative|absolute] [--driver-scaled] [--driver-box x0,y0,x1,y1]]
+                      [--frames N] [--rate F] [--resample linear|cubic]
                       [--gif-fps N] [--gif-dither A] [--png] [--batch B] [--colors_seed S] [--save_dir D]
 
 Inputs (``kpx_amd.stills``): each PATH is an image file, a directory (its .jpg .jpeg .png .bmp files in sorted name order) or a .txt manifest
@@ -14,6 +15,13 @@ Rollouts (``--checkpoint_stage2``): every still under each class of ``--actions`
 uses row s of ``numpy.random.RandomState(seed).randn(S, vae_dim).astype(float32)``, shared by all stills and all classes.
 Driver (``--driver DIR``, stage 2 not needed): DIR holds N >= 33 frames of a video; frames i * (N // 33) are fitted like stills, the stage-1
 detector finds their key points, and every still is rolled out on them (``FinalModel.run(drive=...)``, default mode ``relative``).
+
+Longer and smoother (``FinalModel.run(frames=, rate=, resample=)``): ``--frames N`` (a multiple of 32) chains N / 32
+calls of the motion generator, each started from the last pose of the one before; segment i >= 1 of draw s uses row s of the i-th further
+``randn(S, vae_dim)`` of the same RandomState.  ``--rate F`` puts F - 1 frames between every two (``--resample``, default cubic) and plays
+the GIFs at F times ``--gif-fps``, so they last as long as before and only move more smoothly; set ``--gif-fps`` for slow motion.  The GIFs then
+hold 1 + N F frames and ``--sheet-frames`` indexes those.  With ``--driver`` only ``--rate`` applies: the driver's cell repeats each of its
+frames F times.
 
 Files, under <save_dir>/%04d/ per still in input order: input_im.png and current_points.png as evaluate.py writes them; classes.gif, the
 animated grid (row = draw, column = class, 33 frames, frame 0 = the still) with ONE palette over all cells and frames; with ``--overlay R``
@@ -43,14 +51,14 @@ class _Tap:
     """a FinalModel whose run() hands every output to ``consume`` before the caller (evaluate._ClassSweep) sees it: the outputs live in graph
     buffers that the next run() overwrites"""
 
-    def __init__(self, model, consume):
-        self.model, self.consume = model, consume
+    def __init__(self, model, consume, rollout=None):
+        self.model, self.consume, self.rollout = model, consume, dict(rollout or {})       # rollout: frames / rate / resample of every run()
 
     def __getattr__(self, name):
         return getattr(self.model, name)
 
     def run(self, sess, feed_dict, z=None, drive=None):
-        out = self.model.run(sess, feed_dict, z=z, drive=drive)
+        out = self.model.run(sess, feed_dict, z=z, drive=drive, **self.rollout)
         self.consume(out)
         return out
 
@@ -76,7 +84,10 @@ def main(argv=None):
     parser.add_argument('--driver-mode', type=str, default=None, help='relative (default) or absolute')
     parser.add_argument('--driver-scaled', action='store_true', help="with --driver-mode relative: scale the motion by the constellations' spreads")
     parser.add_argument('--driver-box', type=str, default=None, help='x0,y0,x1,y1: crop every driver frame')
-    parser.add_argument('--gif-fps', type=int, default=10, help='frames per second, 1..50 (default 10)')
+    parser.add_argument('--frames', type=int, default=None, help='predicted frames before resampling, a multiple of 32 (default 32): N / 32 chained motion-generator calls')
+    parser.add_argument('--rate', type=int, default=None, help='1..64 (default 1): F - 1 frames between every two predicted ones; the GIFs play at F x --gif-fps')
+    parser.add_argument('--resample', type=str, default=None, help='linear or cubic (default): how --rate places the key points in between')
+    parser.add_argument('--gif-fps', type=int, default=10, help='frames per second, 1..50 (default 10); with --rate F the GIFs play at F times this')
     parser.add_argument('--gif-dither', type=int, default=0, help='amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
     parser.add_argument('--png', action='store_true', help='also the frames of every rollout as PNGs')
     parser.add_argument('--batch', type=int, default=8)
@@ -106,6 +117,21 @@ def main(argv=None):
         parser.error('--driver-scaled goes with --driver-mode relative alone')
     if not FPS_RANGE[0] <= args.gif_fps <= FPS_RANGE[1]:
         parser.error('--gif-fps takes %d..%d frames per second (got %d)' % (FPS_RANGE + (args.gif_fps,)))
+    n_pred, rate, resample = 32 if args.frames is None else args.frames, 1 if args.rate is None else args.rate, args.resample or 'cubic'
+    if n_pred < 32 or n_pred % 32:
+        parser.error('--frames takes a positive multiple of 32 (got %d)' % n_pred)
+    if not 1 <= rate <= 64:
+        parser.error('--rate takes 1..64 (got %d)' % rate)
+    if resample not in ('linear', 'cubic'):
+        parser.error('--resample takes linear or cubic (got %r)' % args.resample)
+    if args.resample is not None and rate == 1:
+        parser.error('--resample chooses how --rate places the frames in between and needs --rate >= 2')
+    if args.driver is not None and args.frames is not None:
+        parser.error('--frames chains the motion generator; with --driver the motion is the 33 frames of the driver (only --rate applies)')
+    if args.gif_fps * rate > FPS_RANGE[1]:
+        parser.error('--gif-fps %d x --rate %d = %d frames per second, and a GIF plays at most %d: lower --gif-fps'
+                     % (args.gif_fps, rate, args.gif_fps * rate, FPS_RANGE[1]))
+    n_frames = 1 + n_pred * rate                           # the still, then T' = frames x rate predicted frames
     if not DITHER_RANGE[0] <= args.gif_dither <= DITHER_RANGE[1]:
         parser.error('--gif-dither takes an amplitude in %d..%d (got %d)' % (DITHER_RANGE + (args.gif_dither,)))
     if not 0 <= args.overlay <= stills.MAX_RADIUS:
@@ -123,10 +149,10 @@ def main(argv=None):
         if args.checkpoint_stage2 is not None:
             text = 'all' if args.actions is None else args.actions.strip()
             actions = list(range(n_action)) if text == 'all' else evaluate._parse_index_list(text, '--actions', n_action)
-            stills.check_grid(samples, len(actions), size, size)
+            stills.check_grid(samples, len(actions), size, size, frames=n_frames)
             sheet_frames = list(evaluate.SHEET_FRAMES_DEFAULT)
             if args.sheet_frames is not None:
-                sheet_frames = evaluate._parse_index_list(args.sheet_frames, '--sheet-frames', evaluate.N_FUTURE_FRAMES)
+                sheet_frames = evaluate._parse_index_list(args.sheet_frames, '--sheet-frames', n_frames - 1)
                 if sheet_frames != sorted(sheet_frames) or len(sheet_frames) > 63:
                     raise ValueError('--sheet-frames takes at most 63 increasing frame indices (got %r)' % args.sheet_frames)
         box = stills.parse_box(args.box, '--box') if args.box is not None else None
@@ -163,14 +189,16 @@ def main(argv=None):
     if radius and k > ops.CELL_MAX_POINTS:
         raise Exception('--overlay marks at most %d key points (the model has %d)' % (ops.CELL_MAX_POINTS, k))
     colors = torch.from_numpy(stills.marker_colors(model.colors)).to(dev) if radius else None
-    gifs = kpx_amd.gif.RolloutGifs(args.gif_fps, args.gif_dither)
+    gifs = kpx_amd.gif.RolloutGifs(args.gif_fps * rate, args.gif_dither)
+    rollout = {} if (n_pred, rate) == (32, 1) else {'frames': n_pred, 'rate': rate, 'resample': resample}
     n_cls = len(actions) if actions else 0
     layers = 2 if radius else 1
-    per_still = N_FRAMES * size * size * 3 * layers * ((samples * n_cls if actions else 0) + (2 if driver else 0))
+    per_still = n_frames * size * size * 3 * layers * ((samples * n_cls if actions else 0) + (2 if driver else 0))
     batch = stills.batch_under(args.batch, per_still)
     zs = None
     if actions:
-        zs = torch.from_numpy(np.random.RandomState(seed).randn(samples, model.vae_dim).astype(np.float32)).to(dev)
+        rs = np.random.RandomState(seed)                   # segment 0 first: a longer rollout begins as the 32-frame one of the same seed
+        zs = torch.from_numpy(np.stack([rs.randn(samples, model.vae_dim).astype(np.float32) for _ in range(n_pred // 32)], 1)).to(dev)   # [S, segments, V]
     drv = None
     if driver is not None:
         frames = _to_device_unit(driver['u8'], dev)                                        # [33,R,R,3]
@@ -197,10 +225,10 @@ def main(argv=None):
                     evaluate._save_img(osp.join(d, 'current_points.png'), cur[i], rescale=False)
 
         def marks(out):
-            return out['first_pt'].reshape(bsz, k, 2).contiguous(), out['fut_pt_raw'].reshape(bsz, N_FRAMES - 1, k, 2).contiguous()
+            return out['first_pt'].reshape(bsz, k, 2).contiguous(), out['fut_pt_raw'].reshape(bsz, n_frames - 1, k, 2).contiguous()
 
         if actions:
-            grid = torch.empty((bsz, N_FRAMES, samples * size, n_cls * size, 3), dtype=torch.uint8, device=dev)
+            grid = torch.empty((bsz, n_frames, samples * size, n_cls * size, 3), dtype=torch.uint8, device=dev)
             over = torch.empty_like(grid) if radius else None
 
             def consume(out):                            # one rollout: its cell of the grids, before the next run() replays the graph
@@ -216,10 +244,11 @@ def main(argv=None):
                         _write_rollout_pngs(evaluate, osp.join(d, 'draw_%02d' % s, 'class_%02d' % actions[a]), host, i)
                 state['a'] = a + 1
 
-            sweep = evaluate._ClassSweep(kpx_amd, _Tap(model, consume), actions, n_action, sheet_frames, image, None, True, samples, None, dev)
+            sweep = evaluate._ClassSweep(kpx_amd, _Tap(model, consume, rollout), actions, n_action, sheet_frames, image, None, True, samples, None, dev)
             for s in range(samples):
                 state.update(draw=s, a=0)
-                sweep.run(s, zs[s:s + 1].expand(bsz, -1).contiguous())
+                z = zs[s].unsqueeze(1).expand(-1, bsz, -1).contiguous()           # [segments, B, V]
+                sweep.run(s, z[0] if n_pred == 32 else z)
             sweep.write_sheets(args.save_dir, start)
             palette_sizes['classes'] += stills.write_grid_gifs(gifs, grid, [osp.join(d, 'classes.gif') for d in dirs])
             if over is not None:
@@ -230,15 +259,17 @@ def main(argv=None):
         if drv is not None:
             tile = lambda t: t.expand((bsz,) + tuple(t.shape[1:])).contiguous()
             out = model.run(None, {'image': image}, drive={'mode': driver_mode, 'first': tile(drv['first_pt']), 'seq': tile(drv['seq_pt']),
-                                                           'shift': 0, 'scaled': bool(args.driver_scaled)})
+                                                           'shift': 0, 'scaled': bool(args.driver_scaled)}, **rollout)
             pred = out['pred_im_seq'].contiguous()
-            d_first, d_seq = tile(drv['image']), tile(drv['seq'])
-            pair = torch.empty((bsz, N_FRAMES, size, 2 * size, 3), dtype=torch.uint8, device=dev)
+            d_first, d_seq, d_pts = tile(drv['image']), tile(drv['seq']), tile(drv['seq_pt'])
+            if rate > 1:                                 # the driver has the frames it has: each one stands for `rate` frames of the rollout
+                d_seq, d_pts = d_seq.repeat_interleave(rate, dim=1), d_pts.repeat_interleave(rate, dim=1)
+            pair = torch.empty((bsz, n_frames, size, 2 * size, 3), dtype=torch.uint8, device=dev)
             ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit')
             ops.cell_frames(pair, image, pred, 0, 1, 'unit')
             palette_sizes['driven'] += stills.write_grid_gifs(gifs, pair, [osp.join(d, 'driven.gif') for d in dirs])
             if radius:                                   # the driver's own key points on its cell, the retargeted ones on the rollout
-                ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit', tile(drv['first_pt']), tile(drv['seq_pt']), colors=colors, radius=radius)
+                ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit', tile(drv['first_pt']), d_pts, colors=colors, radius=radius)
                 ops.cell_frames(pair, image, pred, 0, 1, 'unit', *marks(out), colors=colors, radius=radius)
                 palette_sizes['driven_overlay'] += stills.write_grid_gifs(gifs, pair, [osp.join(d, 'driven_overlay.gif') for d in dirs])
             write_inputs(out)
@@ -247,8 +278,10 @@ def main(argv=None):
                 for i, d in enumerate(dirs):
                     _write_rollout_pngs(evaluate, osp.join(d, 'driven'), host, i)
     torch.cuda.synchronize()
-    meta = {'stills': records, 'cell': [size, size], 'frames': N_FRAMES, 'fps': gifs.fps, 'delay_cs': delay_of_fps(gifs.fps), 'dither': gifs.dither,
+    meta = {'stills': records, 'cell': [size, size], 'frames': n_frames, 'fps': gifs.fps, 'delay_cs': delay_of_fps(gifs.fps), 'dither': gifs.dither,
             'overlay': radius, 'batch': batch, 'palette_sizes': palette_sizes}
+    if rollout:
+        meta['rollout'] = dict(rollout, gif_fps=args.gif_fps)
     if actions:
         meta.update({'actions': actions, 'draws': samples, 'seed': seed, 'grid': [samples, n_cls], 'sheet_frames': sheet_frames})
     if driver is not None:

@@ -126,6 +126,13 @@
 27. The rollout of configs[4] (B = 64, replayed HIP graph) at n_pts = 40 without and with what --novelty adds per batch and draw (the copy of
    the draw's key points and one search of the 64 real futures and 64 rollouts), alternated; median ms of each and the difference.
 
+``--long`` measures the longer and smoother rollouts (FinalModel.run(frames=, rate=), evaluate.py / animate.py --frames --rate) instead:
+
+28. kpx_points_resample_f32 (linear and cubic) and kpx_points_speed_f64 at B = 64, N = 96, F = 4 for K = 15 and K = 40; device-event time of
+   each launch after warm-up, min / median / max us, beside a device copy of the resampler's output (B x 384 x K x 2 floats) in the same process.
+29. The rollout of configs[4] (B = 64, replayed HIP graphs) in one process, alternated: frames = 96 beside three 32-frame rollouts, and
+   frames = 32, rate = 4 beside four 32-frame rollouts; median ms of each and the quotient.
+
 Prints one JSON line.
 """
 import argparse
@@ -1415,6 +1422,61 @@ def novelty_rollout_leg(dev, rollouts, store):
             'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
 
 
+def long_kernel_leg(dev, launches):
+    from kpx_amd import ops
+    g = torch.Generator(device=dev).manual_seed(9)
+    n, f = 96, 4
+    res = {'batch': B, 'knots': n, 'rate': f, 'launches': launches}
+    stats = lambda us: {'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1)}
+    for k in (15, 40):
+        first = torch.rand((B, k, 2), generator=g, device=dev) * 1.6 - 0.8
+        seq = torch.rand((B, n, k, 2), generator=g, device=dev) * 1.6 - 0.8
+        out = torch.empty((B, n * f, k, 2), dtype=torch.float32, device=dev)
+        dst = torch.empty_like(out)
+        leg = {'out_shape': [B, n * f, k, 2], 'out_kb': round(out.numel() * 4 / 1e3, 1)}
+        for mode in ('linear', 'cubic'):
+            leg['resample_' + mode] = stats(_event_times(lambda: ops.points_resample(first, seq, f, mode, out=out), launches, dev))
+            assert bool(torch.isfinite(out).all())
+        leg['speed'] = stats(_event_times(lambda: ops.points_speed(first, out, float(f)), launches, dev))
+        leg['device_copy_of_out'] = stats(_event_times(lambda: dst.copy_(out), launches, dev))
+        res['k%d' % k] = leg
+    return res
+
+
+def long_rollout_leg(dev, rollouts):
+    import kpx_amd
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((3, B, 64), generator=g, device=dev)
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    feed = {'image': im, 'action_code': act}
+    plain = lambda: fm.run(None, feed, z=z[0])
+    runs = {'plain_x3': lambda: [plain() for _ in range(3)][-1], 'frames_96': lambda: fm.run(None, feed, z=z, frames=96),
+            'plain_x4': lambda: [plain() for _ in range(4)][-1], 'rate_4': lambda: fm.run(None, feed, z=z[0], rate=4)}
+    for fn in (plain, runs['frames_96'], runs['rate_4']):
+        for _ in range(3):                                # eager, capture, one replay
+            out = fn()
+        assert bool(torch.isfinite(out['pred_im_seq']).all())
+    torch.cuda.synchronize(dev)
+    ms = {name: [] for name in runs}
+    for _ in range(rollouts):
+        for name, fn in runs.items():
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    med = {name: statistics.median(v) for name, v in ms.items()}
+    res = {'batch': B, 'n_points': 15, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 3 and not fm._graph_failed}
+    for name in runs:
+        res[name] = {'ms': round(med[name], 3), 'ms_all': [round(v, 2) for v in ms[name]]}
+    res['frames_96_over_plain_x3'] = round(med['frames_96'] / med['plain_x3'], 4)
+    res['rate_4_over_plain_x4'] = round(med['rate_4'] / med['plain_x4'], 4)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -1446,7 +1508,17 @@ def main():
     ap.add_argument('--novelty', action='store_true',
                     help='measure the nearest-motion search (the kernel on a Penn-sized synthetic store beside a device copy and the gather + torch '
                          'fp64 route, the cost of --novelty per configs[4] rollout, all in this process) instead')
+    ap.add_argument('--long', action='store_true',
+                    help='measure the longer and smoother rollouts (the resample and speed launches beside a device copy, a 96-frame rollout beside '
+                         'three 32-frame ones and a rate-4 rollout beside four, all in this process) instead')
     args = ap.parse_args()
+    if args.long:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        kernels = long_kernel_leg(dev, args.launches)
+        print(json.dumps({'long_kernels': kernels, 'long_rollout_c4': long_rollout_leg(dev, args.rollouts)}))
+        return
     if args.novelty:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

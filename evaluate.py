@@ -7,7 +7,7 @@
                        [--actions all|i,j,k [--sheet-frames f,g,h]]
                        [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
                        [--metrics --action-accuracy CKPT]
-                       [--gif [--gif-fps N] [--gif-dither A]]
+                       [--gif [--gif-fps N] [--gif-dither A] [--frames N] [--rate F [--resample linear|cubic]]]
                        [--metrics --novelty [--novelty-sheets] [--novelty-no-mirror]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
@@ -91,6 +91,15 @@ crosses to the host, where ``kpx_amd.gif.write_gif`` packs it (LZW in the librar
 stored as the delay round(100 / N) centiseconds; ``--gif-dither A`` (0..64, default 0) adds a 4 x 4 ordered dither of that amplitude
 before the search.  ``<save_dir>/gif.json`` records the columns, fps, dither, the frame count and the palette size per sample.  DESIGN.md
 section 2 has the definition.  Without the flag every file keeps its bytes.
+
+``--frames N`` / ``--rate F`` (with ``--gif``; data path and ``--synthetic``) add a longer and smoother rollout beside the ordinary one, which
+is produced first and keeps every file, metric and byte.  Per batch a second rollout (``FinalModel.run(frames=N, rate=F, resample=...)``,
+DESIGN.md section 2) chains N / 32 calls of the motion generator -- segment 0 at draw 0's z, the later ones at z from
+``numpy.random.RandomState(first sample index of the batch)`` -- and puts F - 1 key-point frames between every two (``--resample``, default
+cubic).  Per sample ``long.gif`` (``pred | points``, 1 + N F frames, played at F x ``--gif-fps``; a product above 50 is refused) and
+``long_points.npy`` [N F, K, 2]; per run ``long.json``: ``speed``, the mean over all samples of the mean distance the key points move per
+source frame (``kpx_amd.ops.points_speed``), and ``seam_ratio``, the mean speed at the first frame of the segments after the first over the
+mean speed at all other frames (null for N = 32).  A chain whose seams jump shows up there as a number; no value is called good.
 
 ``--novelty`` (with ``--metrics``; data path only) asks whether the motion generator invents motions or replays training sequences: the
 pseudo labels of ``train_set.txt`` are kept in HBM once (``kpx_amd.novelty.MotionStore``) and every draw's predicted key points, the pseudo
@@ -991,6 +1000,49 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         print(_drive_line(res['drive']))
 
 
+class _LongRollout:
+    """--frames / --rate: after a batch's ordinary rollout a second one, chained to ``frames`` predicted frames and resampled by ``rate``
+    (FinalModel.run(frames=, rate=, resample=)), at the same z for segment 0 and seeded z for the later segments.  Per sample long.gif
+    (pred | points) and long_points.npy [T',K,2]; per run long.json: the mean speed curve and the seam ratio (kpx_amd.resample)."""
+
+    def __init__(self, kpx_amd, model, frames, rate, resample, fps, dither, dev):
+        self.kpx, self.model, self.frames, self.rate, self.resample, self.dev = kpx_amd, model, frames, rate, resample, dev
+        self.gifs = kpx_amd.gif.RolloutGifs(fps * rate, dither)        # F times the frames in the same time
+        self.speed_sum, self.n, self.sizes = np.zeros(frames * rate, np.float64), 0, []
+
+    def run(self, save_dir, first_sample, image, action_code, z):
+        """z: the [B,V] of the batch's ordinary rollout -> the number of frames predicted"""
+        ops, bsz, segments = self.kpx.ops, image.shape[0], self.frames // N_FUTURE_FRAMES
+        more = np.random.RandomState(first_sample).randn(segments - 1, bsz, self.model.vae_dim).astype(np.float32)
+        z_all = torch.cat([z.reshape(1, bsz, -1), torch.from_numpy(more).to(self.dev)])
+        out = self.model.run(None, {'image': image, 'action_code': action_code}, z=z_all, frames=self.frames, rate=self.rate, resample=self.resample)
+        pts = out['fut_pt_raw'].contiguous()
+        speed = ops.points_speed(out['first_pt'].reshape(bsz, -1, 2).contiguous(), pts, float(self.rate))
+        canvas = self.gifs._canvas([(out['im'], out['pred_im_seq'], 'unit'), (out['current_points'], out['future_points'], 'raw')])
+        idx, palettes, sizes = ops.gif_indices(canvas, self.gifs.dither)
+        host, pts_host = self.gifs._host(idx), pts.cpu().numpy()
+        for i in range(bsz):
+            d = osp.join(save_dir, '%04d' % (first_sample + i))
+            os.makedirs(d, exist_ok=True)
+            self.kpx.gif.write_gif(osp.join(d, 'long.gif'), host[i], palettes[i, :sizes[i]], self.gifs.delay)
+            np.save(osp.join(d, 'long_points.npy'), pts_host[i])
+            self.sizes.append(int(sizes[i]))
+        self.speed_sum += speed.cpu().numpy().sum(0)
+        self.n += bsz
+        return bsz * self.frames * self.rate
+
+    def write_json(self, save_dir):
+        from kpx_amd.resample import seam_ratio
+        speed = self.speed_sum / max(self.n, 1)
+        os.makedirs(save_dir, exist_ok=True)
+        with open(osp.join(save_dir, 'long.json'), 'w') as f:
+            json.dump({'frames': self.frames, 'rate': self.rate, 'resample': self.resample, 'n_frames': self.frames * self.rate,
+                       'columns': ['pred', 'points'], 'fps': self.gifs.fps, 'delay_cs': self.gifs.delay, 'n_samples': self.n,
+                       'speed_unit': 'mean key-point displacement per source frame, in the [-1, 1] coordinates',
+                       'speed': [_json_num(v) for v in speed], 'seam_ratio': seam_ratio(speed, self.frames, self.rate),
+                       'palette_sizes': self.sizes}, f, indent=1)
+
+
 def _save_img_sequence(output_dir, img_seq, rescale=False, raw=False):
     """reference :151-156"""
     os.makedirs(output_dir, exist_ok=True)
@@ -1055,7 +1107,29 @@ def main(argv=None):
     parser.add_argument('--novelty-sheets', action='store_true',
                         help='with --novelty: per sample nearest.png, every rollout above its nearest training window (--sheet-frames picks the frames)')
     parser.add_argument('--novelty-no-mirror', action='store_true', help='with --novelty: do not search the mirror images of the training motions')
+    parser.add_argument('--frames', type=int, default=None,
+                        help='with --gif: a second rollout per batch chained to this many predicted frames (a multiple of 32, default 32): '
+                             'per sample long.gif and long_points.npy, <save_dir>/long.json with the speed curve and the seam ratio')
+    parser.add_argument('--rate', type=int, default=None, help='with --gif: resample the second rollout to F = 1..64 times the frames (default 1); long.gif plays at F x --gif-fps')
+    parser.add_argument('--resample', type=str, default=None, help='with --rate: linear or cubic (default)')
     args = parser.parse_args(argv)
+    long_frames, long_rate = 32 if args.frames is None else args.frames, 1 if args.rate is None else args.rate
+    want_long = args.frames is not None or args.rate is not None
+    if args.resample is not None and args.rate is None:
+        parser.error('--resample chooses how --rate places the frames in between and needs it')
+    if want_long and not args.gif:
+        parser.error('--frames and --rate write long.gif beside the files of --gif and need it')
+    if want_long and args.drive_only:
+        parser.error("--drive-only skips the model's own rollout, which --frames and --rate lengthen")
+    if long_frames < 32 or long_frames % 32:
+        parser.error('--frames takes a positive multiple of 32 (got %d)' % long_frames)
+    if not 1 <= long_rate <= 64:
+        parser.error('--rate takes 1..64 (got %d)' % long_rate)
+    if (args.resample or 'cubic') not in ('linear', 'cubic'):
+        parser.error('--resample takes linear or cubic (got %r)' % args.resample)
+    if 2 * (1 + long_frames * long_rate) * 128 * 128 > 1 << 24:
+        parser.error('--frames x --rate: long.gif would hold %d frames of two 128 x 128 cells, and the colour histogram of one GIF counts '
+                     'at most 2^24 pixels (%d frames)' % (1 + long_frames * long_rate, (1 << 24) // (2 * 128 * 128)))
     if (args.novelty_sheets or args.novelty_no_mirror) and not args.novelty:
         parser.error('--novelty-sheets and --novelty-no-mirror shape the search of --novelty and need it')
     if args.novelty and args.synthetic:
@@ -1079,6 +1153,9 @@ def main(argv=None):
         parser.error('--gif-fps takes 1..50 frames per second (got %d)' % gif_fps)
     if not 0 <= gif_dither <= 64:
         parser.error('--gif-dither takes an amplitude in 0..64 (got %d)' % gif_dither)
+    if want_long and gif_fps * long_rate > 50:
+        parser.error('--gif-fps %d x --rate %d = %d frames per second, and a GIF plays at most 50: lower --gif-fps'
+                     % (gif_fps, long_rate, gif_fps * long_rate))
     if args.sheet_frames is not None and args.actions is None and args.drive is None and not args.novelty_sheets:
         parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive / --novelty-sheets and needs it')
     drive_modes = None
@@ -1164,6 +1241,7 @@ def main(argv=None):
         model.restore(None, p, **({'ema': True} if args.ema else {}))
     n_action = config['model']['n_action']
     gifs = kpx_amd.gif.RolloutGifs(gif_fps, gif_dither) if args.gif else None
+    long_run = _LongRollout(kpx_amd, model, long_frames, long_rate, args.resample or 'cubic', gif_fps, gif_dither, dev) if want_long else None
     sample_idx, frames, t0 = 0, 0, time.time()
     if not args.synthetic:                       # reference :43-51, :84-130: the test subset through the sequence loader
         loader = kpx_amd.data.SequenceDataLoader(config['paths']['data_dir'], 'test', n_points=config['model']['n_pts'], n_action=n_action,
@@ -1250,7 +1328,10 @@ def main(argv=None):
                     sweep.on_class = hooks[0] if len(hooks) == 1 else lambda *a: [h(*a) for h in hooks]
             for draw in range(args.samples):
                 # --actions: one z per batch and draw, drawn here, for the batch's own rollout and for every class of the sweep
-                z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None
+                # --frames / --rate: drawn here too -- the draw run() would make itself, so the ordinary rollout keeps its bits
+                z = torch.randn((bsz, model.vae_dim), device=dev) if actions or long_run is not None else None
+                if draw == 0:
+                    z_first = z
                 outputs = model.run(None, {'image': batch['image'], 'action_code': batch['action_code']}, z=z)
                 frames += bsz * 32
                 if args.metrics:             # enqueued before the next run() overwrites the graph's output buffers
@@ -1318,6 +1399,8 @@ def main(argv=None):
                         sweep.scores(action_scores)
             if novelty is not None:
                 novelty.end_batch(args.save_dir, n_read - bsz)
+            if long_run is not None:         # after everything of the ordinary rollout: its own graph, its own files
+                frames += long_run.run(args.save_dir, sample_idx - bsz, batch['image'], batch['action_code'], z_first)
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
         if actions and not args.no_save:
@@ -1327,6 +1410,8 @@ def main(argv=None):
                               (model.image_size, model.image_size), drive_modes, args.drive_scaled, n_self_driven)
         if gifs is not None:
             gifs.write_json(args.save_dir)
+        if long_run is not None:
+            long_run.write_json(args.save_dir)
         if args.metrics and args.drive_only:
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
@@ -1356,7 +1441,7 @@ def main(argv=None):
                                                        ('points', o['current_points'], o['future_points'], 'raw')])
             sample_idx += bsz
             continue
-        z = torch.randn((bsz, model.vae_dim), device=dev) if actions else None       # --actions: shared with the sweep below
+        z = torch.randn((bsz, model.vae_dim), device=dev) if actions or long_run is not None else None   # --actions: shared with the sweep below
         outputs = model.run(None, {'image': image, 'action_code': torch.from_numpy(act).to(dev)}, z=z)
         frames += bsz * 32
         if not args.no_save:
@@ -1388,6 +1473,8 @@ def main(argv=None):
             frames += sweep.run(0, z)
             if not args.no_save:
                 sweep.write_sheets(args.save_dir, sample_idx - bsz)
+        if long_run is not None:
+            frames += long_run.run(args.save_dir, sample_idx - bsz, image, torch.from_numpy(act).to(dev), z)
     if actions and not args.no_save:
         _write_actions_json(args.save_dir, actions, sheet_frames, False, (model.image_size, model.image_size))
     if drive_modes and not args.no_save:
@@ -1395,6 +1482,8 @@ def main(argv=None):
                           (model.image_size, model.image_size), drive_modes, False, 0)
     if gifs is not None:
         gifs.write_json(args.save_dir)
+    if long_run is not None:
+        long_run.write_json(args.save_dir)
     torch.cuda.synchronize()
     print('iteration through synthetic set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
 

@@ -488,6 +488,44 @@ enum { KPX_RETARGET_HOLD = 0, KPX_RETARGET_ABSOLUTE = 1, KPX_RETARGET_RELATIVE =
 int kpx_points_retarget_f32(const float* src_first /*[B,K,2]*/, const float* drv_first /*[B,K,2]*/, const float* drv_seq /*[B,T,K,2]*/,
                             int B, int T, int K, int shift, int mode, float* out /*[B,T,K,2]*/, void* stream);
 
+/* ---- key-point resampling in time and the speed of a key-point sequence (csrc/resample.hip; FinalModel.run(frames=, rate=), animate.py and
+ * evaluate.py --frames / --rate), DESIGN.md sections 2 and 4.4.  No reference counterpart.  Two entries added to ABI version 25: no existing
+ * signature changed, so the number stays.
+ *
+ * kpx_points_resample_f32: the knots P_0 = first fp32 [B,K,2] and P_1..P_N = seq fp32 [B,N,K,2] stand at the times 0..N.  Output frame
+ * j = 1..N*F stands at the time j / F and is stored at index j - 1 of out fp32 [B,N*F,K,2].  With i = j div F and r = j mod F, for every
+ * (b, k, axis):
+ *   r == 0                out = P_i                                                 (a bit copy: F = 1 is the identity, every knot survives,
+ *                                                                                    NaN payloads included)
+ *   KPX_RESAMPLE_LINEAR   out = P_i + s * (P_{i+1} - P_i),  s = (double)r / (double)F
+ *   KPX_RESAMPLE_CUBIC    out = h00 * P_i + h10 * m_i + h01 * P_{i+1} + h11 * m_{i+1}   (the cubic Hermite form, added from the left)
+ *                         s2 = s * s, s3 = s2 * s, h00 = (2 s3 - 3 s2) + 1, h10 = (s3 - 2 s2) + s, h01 = -2 s3 + 3 s2, h11 = s3 - s2;
+ *                         Catmull-Rom tangents m_i = (P_{i+1} - P_{i-1}) / 2 for 0 < i < N, one-sided at the ends: m_0 = P_1 - P_0,
+ *                         m_N = P_N - P_{N-1}.  A straight-line motion is reproduced on the whole range, a parabola on the interior
+ *                         intervals 1 <= i <= N - 2.
+ * In fp64 from the fp32 knots, every operation rounded once (no fma), in the order written, the result rounded to fp32 once, at the store.
+ * NOTHING IS CLAMPED: a cubic may overshoot [-1, 1] slightly between knots that touch the border; the Gaussian maps and the markers take any
+ * value.  An output reads the knots of its own sample, point and stencil alone (P_i, P_{i+1}; CUBIC also P_{i-1} and P_{i+2} where they
+ * exist): a non-finite knot reaches exactly the frames whose stencil holds it and no others.
+ *   Limits: B, N, K, F >= 1, K <= KPX_RESAMPLE_MAX_POINTS, F <= KPX_RESAMPLE_MAX_RATE, N >= 2 for CUBIC, B*N*F*K*2 < 2^31; the three pointers
+ *   4-byte aligned.  KPX_EINVAL before any device call for anything else, a null pointer or an unknown mode.
+ * One launch, one thread per output item; 16-byte accesses when K is even and the three pointers are 16-byte aligned, 4-byte accesses otherwise
+ * -- the same values on both paths.  No allocation, copy, synchronisation or atomics (capturable).
+ *
+ * kpx_points_speed_f64: speed[b,t] = scale * ((sum_k |P_t[k] - P_{t-1}[k]|) / K) for t = 1..T, stored at index t - 1 of speed double [B,T], with
+ * P_0 = first fp32 [B,K,2] and P_1..P_T = seq fp32 [B,T,K,2]: the mean distance the points move between consecutive frames.  In fp64: the
+ * differences dx, dy, then dx * dx + dy * dy, then sqrt, the terms added in the order k = 0..K-1, one division by K, one multiplication by
+ * `scale`, every operation rounded once.  `scale` is the rate F of a resampled sequence, so the unit stays "per source frame".
+ *   Limits: B, T >= 1, 1 <= K <= KPX_RESAMPLE_MAX_POINTS, B*T*K*2 < 2^31; first and seq 4-byte, speed 8-byte aligned; KPX_EINVAL before any
+ *   device call otherwise.  One launch, one thread per (b, t), no atomics (capturable). */
+enum { KPX_RESAMPLE_LINEAR = 0, KPX_RESAMPLE_CUBIC = 1 };
+#define KPX_RESAMPLE_MAX_POINTS 1024
+#define KPX_RESAMPLE_MAX_RATE 64
+int kpx_points_resample_f32(const float* first /*[B,K,2]*/, const float* seq /*[B,N,K,2]*/, int B, int N, int K, int F, int mode,
+                            float* out /*[B,N*F,K,2]*/, void* stream);
+int kpx_points_speed_f64(const float* first /*[B,K,2]*/, const float* seq /*[B,T,K,2]*/, int B, int T, int K, double scale,
+                         double* speed /*[B,T]*/, void* stream);
+
 /* ---- translator heads + blend: mask = sigmoid(raw[...,3]); final = im*mask + crude*(1-mask)
  *      (networks/__init__.py:87-89, detector_translator_model.py:174).  raw4 [P,4] = crude(3) ‖ mask logit(1). */
 int kpx_head_blend_fwd_f32(const float* im, const float* raw4, size_t P, float* final_out, float* crude_out, float* mask_out, void* stream);

@@ -10,6 +10,12 @@ palette after ``random.seed(s)``.  ``z`` can be injected for deterministic parit
 ``run(..., drive=...)`` is the driven rollout (not in the reference): the 32 key-point frames come from outside --
 ``ops.points_retarget`` on the detected key points and a driver's -- in the place of ``vae_decoder``, and everything after them is the same
 code.  It isolates the translator: no z is drawn or read and the stage-2 variables are not touched.
+
+``run(..., frames=32 S, rate=F, resample=...)`` is the long and the smooth rollout (not in the reference).  The motion
+generator is fed once and then free-runs for 32 steps, so S calls are chained: segment s >= 1 is ``vae_decoder`` on its own z with the pose
+of frame 32 s in the place of the detected one -- in distribution by construction, which free-running the LSTM past step 32 is not.  The 32 S
+key-point frames then go through ``ops.points_resample`` (F - 1 frames between every two) and everything downstream runs on T' = 32 S F
+frames.  ``frames=32, rate=1`` is the reference's rollout, on the code path it always had.
 """
 import logging
 import os
@@ -18,6 +24,7 @@ import random
 import torch
 
 from . import model_utils, networks, ops, variables
+from .resample import check_rollout_args
 from .base_model import BaseModel
 from .variables import Sym
 
@@ -62,15 +69,25 @@ class FinalModel(BaseModel):
             networks.translator(joint, False, final_res=r, cin=emb[-2].shape[-1] + 2 * k)
         self.store.materialise()
 
-    def run(self, sess, feed_dict, z=None, drive=None):
+    def run(self, sess, feed_dict, z=None, drive=None, frames=N_FUTURE_FRAMES, rate=1, resample='cubic'):
         """reference run (:124-125).  feed_dict: {'image': [B,H,W,3] in [-1,1], 'action_code': [B,n_action] one-hot,
         optional 'real_im_seq', 'real_seq'}.  z: the VAE latent [B, vae_dim]; drawn from N(0,1) when not given (:71).
         drive: {'mode': 'hold' | 'absolute' | 'relative', 'first': [B,K,2], 'seq': [B,32,K,2], 'shift': int, 'scaled': bool} -- the 32
         key-point frames come from ``ops.points_retarget`` on the detected key points instead of the motion generator ('first' and 'seq'
         are the driver's key points at frame 0 and at frames 1..32, absent for 'hold'; 'first' is read by 'relative' alone; sample b is
-        driven by sample (b + shift) mod B).  z and 'action_code' are then neither drawn nor read."""
+        driven by sample (b + shift) mod B).  z and 'action_code' are then neither drawn nor read.
+        frames: a positive multiple of 32; S = frames / 32 chained motion-generator segments, z then [S,B,vae_dim] ([B,vae_dim] serves S = 1),
+        drawn once as [S,B,vae_dim] when not given.  rate: F in [1, 64]; the frames * F key-point frames are ``ops.points_resample`` of the
+        frames knots in the mode ``resample`` ('linear' | 'cubic').  Every [B,32,...] output then has T' = frames * F frames.  A driven
+        rollout takes rate (the 32 retargeted frames are resampled) and refuses frames != 32: a driver has 33 frames."""
+        segments, _ = check_rollout_args('FinalModel.run', frames, rate, resample)
         if drive is not None:
-            return self._run_driven(feed_dict, drive)
+            if segments != 1:
+                raise ops._lib.KpxError('FinalModel.run: frames must be %d with drive= (got %r): a driver has %d frames and nothing chains it'
+                                        % (N_FUTURE_FRAMES, frames, N_FUTURE_FRAMES + 1))
+            return self._run_driven(feed_dict, drive, rate, resample)
+        if segments != 1 or rate != 1:
+            return self._run_long(feed_dict, z, segments, rate, resample)
         im, act = feed_dict['image'], feed_dict['action_code']
         if not (GRAPH and not self._graph_failed and im.is_cuda and im.dtype == torch.float32):
             return self._run_eager(feed_dict, z)
@@ -149,15 +166,17 @@ class FinalModel(BaseModel):
             tensors[name] = v.contiguous()
         return mode, shift, scaled, tensors
 
-    def _run_driven(self, feed_dict, drive):
+    def _run_driven(self, feed_dict, drive, rate=1, resample='cubic'):
         """run(drive=...): as run(), with the driver's key points in the place of z.  The scalars (mode, shift, scaled) are launch arguments
         of the captured points_retarget, so they are part of the graph's key."""
         im, act = feed_dict['image'], feed_dict.get('action_code')
         mode, shift, scaled, tensors = self._check_drive(im, drive)
-        eager = lambda image, ts: self._run_eager({'image': image}, drive=dict(ts, mode=mode, shift=shift, scaled=scaled))
+        eager = lambda image, ts: self._run_eager({'image': image}, drive=dict(ts, mode=mode, shift=shift, scaled=scaled), rate=rate, resample=resample)
         if not (GRAPH and not self._graph_failed and im.is_cuda and im.dtype == torch.float32):
             return dict(eager(im, tensors), real_im_seq=feed_dict.get('real_im_seq'))
         key = (tuple(im.shape), None if act is None else tuple(act.shape), im.device.index, mode, shift, scaled)
+        if rate != 1:                 # the rate and the mode are launch arguments of the captured points_resample
+            key += (rate, resample)
         feeds = dict(tensors, image=im)
         ent = self._graphs.get(key)
         if ent is not None and ent[3] != self.store.version:         # the parameters changed since the capture: as in run()
@@ -193,11 +212,80 @@ class FinalModel(BaseModel):
         res['real_im_seq'] = feed_dict.get('real_im_seq')
         return res
 
-    def _run_eager(self, feed_dict, z=None, drive=None):
-        """The rollout enqueued launch by launch (also the function a capture records).  ``drive``: a checked drive dict (_check_drive)."""
+    def _run_long(self, feed_dict, z, segments, rate, resample):
+        """run(frames=32 * segments, rate=, resample=) without a driver: as run(), with z [S,B,V] and (frames, rate, resample) in the graph's key
+        (they decide the launches a capture records)."""
+        im, act = feed_dict['image'], feed_dict['action_code']
+        b = im.shape[0]
+        if z is None:
+            z = torch.randn((segments, b, self.vae_dim), dtype=torch.float32, device=im.device)           # drawn once, outside the graph
+        elif isinstance(z, torch.Tensor) and z.dim() == 2 and segments == 1:
+            z = z.reshape(1, b, self.vae_dim)
+        if not isinstance(z, torch.Tensor) or z.dtype != torch.float32 or z.device != im.device or tuple(z.shape) != (segments, b, self.vae_dim):
+            raise ops._lib.KpxError('FinalModel.run: z must be an fp32 tensor %s on %s for frames = %d (got %s)'
+                                    % ([segments, b, self.vae_dim], im.device, N_FUTURE_FRAMES * segments,
+                                       '%s %s on %s' % (tuple(z.shape), z.dtype, z.device) if isinstance(z, torch.Tensor) else type(z).__name__))
+        frames = N_FUTURE_FRAMES * segments
+        eager = lambda image, action, z_: self._run_eager({'image': image, 'action_code': action}, z_, frames=frames, rate=rate, resample=resample)
+        if not (GRAPH and not self._graph_failed and im.is_cuda and im.dtype == torch.float32):
+            return dict(eager(im, act, z), real_im_seq=feed_dict.get('real_im_seq'))
+        key = (tuple(im.shape), tuple(act.shape), im.device.index, 'long', frames, rate, resample)
+        feeds = {'image': im, 'action_code': act, 'z': z}
+        ent = self._graphs.get(key)
+        if ent is not None and ent[3] != self.store.version:         # the parameters changed since the capture: as in run()
+            del self._graphs[key]
+            self._eager_runs[key] = 0
+            ent = None
+        if ent is None:
+            if self._eager_runs.get(key, 0) < 1:                     # one eager run first, as in run()
+                self._eager_runs[key] = 1
+                return dict(eager(im, act, z), real_im_seq=feed_dict.get('real_im_seq'))
+            static = {k_: torch.empty_like(v, memory_format=torch.contiguous_format) for k_, v in feeds.items()}
+            for k_, v in feeds.items():
+                static[k_].copy_(v)
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph):
+                    out = eager(static['image'], static['action_code'], static['z'])
+            except Exception as e:          # noqa: BLE001 -- whatever the runtime refuses: stay on the eager path
+                log.warning('HIP graph capture of the long rollout failed (%s: %s); continuing with eager launches', type(e).__name__, e)
+                self._graph_failed = True
+                torch.cuda.synchronize(im.device)
+                self.store.touch()
+                ops.reset_after_failed_capture()
+                return dict(eager(im, act, z), real_im_seq=feed_dict.get('real_im_seq'))
+            ent = self._graphs[key] = (graph, static, out, self.store.version)
+        graph, static, out, _ = ent
+        for k_, v in feeds.items():
+            v = v.contiguous()
+            ops.flat_copy_raw(v.data_ptr(), static[k_].data_ptr(), v.numel())
+        graph.replay()
+        res = dict(out)
+        res['im'] = im
+        res['real_im_seq'] = feed_dict.get('real_im_seq')
+        return res
+
+    def _chained_points(self, z, first_pt, act, segments):
+        """The key points of a chained rollout, fp32 [B, 32 S, 2K]: segment 0 is vae_decoder on the detected pose, segment s >= 1 on the pose of
+        frame 32 s, each with its own z[s] and the same action code.  Copies only between the calls (kpx_copy_channels)."""
+        b, k2, t = first_pt.shape[0], 2 * self.n_points, N_FUTURE_FRAMES
+        knots = torch.empty((b, segments * t, k2), dtype=torch.float32, device=first_pt.device)
+        f_pt = first_pt.reshape(b, k2)
+        for s in range(segments):
+            seg = networks.vae_decoder(z[s], f_pt, act, self.cell_info, self.vae_dim, self.n_points)          # [B,32,2K]
+            ops.copy_channels_raw(seg.data_ptr(), t * k2, knots.data_ptr() + 4 * s * t * k2, segments * t * k2, b, t * k2)
+            if s + 1 < segments:
+                f_pt = torch.empty((b, k2), dtype=torch.float32, device=first_pt.device)
+                ops.copy_channels_raw(seg.data_ptr() + 4 * (t - 1) * k2, t * k2, f_pt.data_ptr(), k2, b, k2)
+        return knots
+
+    def _run_eager(self, feed_dict, z=None, drive=None, frames=N_FUTURE_FRAMES, rate=1, resample='cubic'):
+        """The rollout enqueued launch by launch (also the function a capture records).  ``drive``: a checked drive dict (_check_drive).
+        ``frames``, ``rate``, ``resample``: checked by run(); z is [S,B,V] when frames > 32."""
         im = feed_dict['image'].contiguous()
         act = feed_dict['action_code'].contiguous() if drive is None else None
         b, r, k, t = im.shape[0], self.image_size, self.n_points, N_FUTURE_FRAMES
+        segments = frames // t
         dev = im.device
         with variables.as_default(self.store), torch.no_grad():
             emb = networks.image_encoder(im, False)[-2]                                          # :61-62
@@ -208,28 +296,40 @@ class FinalModel(BaseModel):
             else:
                 if z is None:
                     z = torch.randn((b, self.vae_dim), dtype=torch.float32, device=dev)          # :71
-                pred_seq = networks.vae_decoder(z, first_pt.reshape(b, 2 * k), act, self.cell_info, self.vae_dim, k)   # :72-77
+                if segments == 1:
+                    pred_seq = networks.vae_decoder(z if z.dim() == 2 else z[0], first_pt.reshape(b, 2 * k), act, self.cell_info, self.vae_dim, k)   # :72-77
+                else:
+                    if z.dim() == 2:
+                        raise ops._lib.KpxError('FinalModel: a rollout of %d frames takes z [%d, B, vae_dim]' % (frames, segments))
+                    pred_seq = self._chained_points(z, first_pt, act, segments)
+            if rate != 1:                     # F - 1 frames between every two knots; the knots themselves stay, bit for bit
+                pred_seq = ops.points_resample(first_pt.reshape(b, k, 2).contiguous(), pred_seq.reshape(b, frames, k, 2), rate, resample)
+            t = frames * rate                 # T': everything downstream runs on it
             pred_pts = pred_seq.reshape(b * t, k, 2)
             # joint embedding [B*T, h, h, C+2K (+pad)]: tiled image embedding ‖ tiled current map ‖ per-frame predicted map
             c = emb.shape[-1]
             ld = (c + 2 * k + 3) // 4 * 4
             hs = self.heat_size
             finals, crudes, masks = [], [], []
-            fpl = max(t, (self.frames_per_launch // t) * t)          # whole samples per slab
             first_tiled = ops.tile_batch(first_pt.reshape(b, 1, 2 * k), t).reshape(b * t, k, 2)   # :85-87 (points instead of maps)
-            for s in range(0, b * t, fpl):
-                e = min(b * t, s + fpl)
-                nb = (e - s) // t
+            if t <= max(self.frames_per_launch, N_FUTURE_FRAMES):
+                fpl = max(t, (self.frames_per_launch // t) * t)      # whole samples per slab
+                slabs = [(s, min(b * t, s + fpl), t) for s in range(0, b * t, fpl)]
+            else:                             # a long rollout: a sample's frames no longer fit one slab, so a slab is a run of one sample's frames
+                slabs = [(i * t + s, i * t + min(t, s + self.frames_per_launch), min(t, s + self.frames_per_launch) - s)
+                         for i in range(b) for s in range(0, t, self.frames_per_launch)]
+            for s, e, rep_ in slabs:          # rows s..e of the B*T' frames: (e - s) / rep_ samples, rep_ frames of each
+                nb = (e - s) // rep_
                 joint = torch.empty((e - s, hs, hs, ld), dtype=torch.float32, device=dev)
                 if ld > c + 2 * k:
                     ops.fill_raw_(joint, 0.0)
-                ops.tile_batch(emb[s // t:s // t + nb], t, out=joint, out_ld=ld, out_channel_offset=0)             # :63-66
+                ops.tile_batch(emb[s // t:s // t + nb], rep_, out=joint, out_ld=ld, out_channel_offset=0)          # :63-66
                 for i, pts in enumerate((first_tiled[s:e], pred_pts[s:e])):                                        # :79-92
                     ops.check(ops.lib.kpx_gaussian_maps_fwd_f32(pts.contiguous().data_ptr(), e - s, k, hs, hs, 14.3,
                                                                 joint.data_ptr() + 4 * (c + i * k), ld, ops._stream()),
                               'kpx_gaussian_maps_fwd_f32')
                 raw4 = networks.translator(joint, False, final_res=r, cin=c + 2 * k)                                # :95
-                f_, c_, m_ = ops.head_blend_tiled(im[s // t:s // t + nb], raw4, t, clip=True)                       # :96-99
+                f_, c_, m_ = ops.head_blend_tiled(im[s // t:s // t + nb], raw4, rep_, clip=True)                    # :96-99
                 finals.append(f_); crudes.append(c_); masks.append(m_)
             cat = lambda xs: xs[0] if len(xs) == 1 else torch.cat(xs, dim=0)
             out = {'im': im, 'real_im_seq': feed_dict.get('real_im_seq'),

@@ -126,18 +126,18 @@ def driver_frames(folder, what='--driver'):
     return [osp.join(folder, names[i]) for i in idx], idx, n
 
 
-def check_grid(samples, classes, h=IMAGE_SIZE, w=IMAGE_SIZE):
-    """the limits of classes.gif: a canvas grid holds at most 64 x 64 cells, and one palette is counted over 33 S A H W pixels, which the
-    uint32 histogram bounds by 2^24"""
+def check_grid(samples, classes, h=IMAGE_SIZE, w=IMAGE_SIZE, frames=N_SEQUENCE_LEN):
+    """the limits of classes.gif: a canvas grid holds at most 64 x 64 cells, and one palette is counted over ``frames`` S A H W pixels
+    (33 frames unless animate.py --frames / --rate ask for more), which the uint32 histogram bounds by 2^24"""
     if not 1 <= samples <= MAX_GRID:
         raise StillsError('--samples: a grid has 1 to %d rows of draws (got %d)' % (MAX_GRID, samples))
     if not 1 <= classes <= MAX_GRID:
         raise StillsError('--actions: a grid has 1 to %d columns of classes (got %d)' % (MAX_GRID, classes))
-    pixels = N_SEQUENCE_LEN * samples * classes * h * w
+    pixels = frames * samples * classes * h * w
     if pixels > HIST_MAX_PIXELS:
         raise StillsError('--samples x --actions: %d draws x %d classes x %d frames of %d x %d are %d pixels in one GIF, and the colour '
                           'histogram counts at most 2^24 = %d (%d cells of this size)'
-                          % (samples, classes, N_SEQUENCE_LEN, h, w, pixels, HIST_MAX_PIXELS, HIST_MAX_PIXELS // (N_SEQUENCE_LEN * h * w)))
+                          % (samples, classes, frames, h, w, pixels, HIST_MAX_PIXELS, HIST_MAX_PIXELS // (frames * h * w)))
 
 
 def batch_under(batch, bytes_per_still, limit=CANVAS_BYTES):

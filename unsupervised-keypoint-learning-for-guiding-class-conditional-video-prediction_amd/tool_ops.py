@@ -2,7 +2,8 @@
 and the summaries.  None of them runs inside a train step; each is called once per batch, so its tensors go through the spec checker of
 ``_args`` (one list of (name, tensor, dtype, shape) per op) and only what is specific to the op -- value ranges, mode rules, table
 read-backs -- is written out.  ``ops`` re-exports every name here: ``ops.sheet_paste``, ``ops.MAX_DRAWS`` ... are the public names.  ``seq_nearest`` (evaluate.py --novelty)
-is written beside its tables in ``novelty`` and reaches ``tool_ops`` and ``ops`` by the import at the end of each.
+is written beside its tables in ``novelty`` and reaches ``tool_ops`` and ``ops`` by the import at the end of each; so do ``points_resample``
+and ``points_speed`` of ``resample``.
 """
 import numpy as np
 import torch
@@ -594,3 +595,6 @@ def class_scores(logits, target, confusion=None, out=None, check_target=True):
 
 # ----------------------------------------------------------------------------------------------- nearest training motion
 from .novelty import seq_nearest, NEAREST_GROUP, NEAREST_MAX_QUERIES, NEAREST_MAX_WINDOWS      # noqa: E402,F401
+
+# ----------------------------------------------------------------------------------------------- key-point resampling in time
+from .resample import points_resample, points_speed, RESAMPLE_MODES, RESAMPLE_MAX_POINTS, RESAMPLE_MAX_RATE      # noqa: E402,F401
