@@ -9,7 +9,7 @@
 Inputs (``kpx_amd.stills``): each PATH is an image file, a directory (its .jpg .jpeg .png .bmp files in sorted name order) or a .txt manifest
 (one ``path [x0,y0,x1,y1]`` per line, relative to the manifest).  Decoding is PIL's on the host: EXIF orientation applied, then
 ``convert('RGB')`` -- an alpha channel is dropped, not composited.  ``--box`` crops in pixels of the upright image (a manifest's box wins);
-the fit to 128 x 128 is the sequence loader's start-frame arithmetic, so a still reaches the networks as a Penn frame of the same pixels.
+the fit to S x S (``model.image_size`` / ``--image-size``, default 128) is the sequence loader's start-frame arithmetic, so a still reaches the networks as a Penn frame of the same pixels.
 
 Rollouts (``--checkpoint_stage2``): every still under each class of ``--actions`` (default all) for each of ``--samples`` draws; draw s
 uses row s of ``numpy.random.RandomState(seed).randn(S, vae_dim).astype(float32)``, shared by all stills and all classes.
@@ -92,13 +92,16 @@ def main(argv=None):
     parser.add_argument('--png', action='store_true', help='also the frames of every rollout as PNGs')
     parser.add_argument('--batch', type=int, default=8)
     parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette')
+    parser.add_argument('--image-size', type=int, default=None, metavar='S',
+                        help='side S of the stills the networks see and of every cell written, a multiple of 16 in [32, 256]; overrides '
+                             'model.image_size of the configuration (default 128)')
     parser.add_argument('--ema', action='store_true',
                         help="read every checkpoint given under its averaged weights (train.py --ema: the <name>/ExponentialMovingAverage entries take their variables' places); a checkpoint without them is refused")
     parser.add_argument('--save_dir', type=str, default='results/animate')
     args = parser.parse_args(argv)
 
     import evaluate
-    from train import load_config
+    from train import config_image_size, load_config
     from kpx_amd import stills
     from kpx_amd.gif import DITHER_RANGE, FPS_RANGE, delay_of_fps
 
@@ -143,7 +146,7 @@ def main(argv=None):
     if not 0 <= seed < 2 ** 32:
         parser.error('--seed takes a numpy RandomState seed in [0, 2^32) (got %d)' % seed)
     config = load_config(args.config)
-    n_action, size = config['model'].get('n_action', 9), stills.IMAGE_SIZE
+    n_action, size = config['model'].get('n_action', 9), config_image_size(config, args.image_size)      # the model's size, and the stills'
     actions = sheet_frames = None
     try:
         if args.checkpoint_stage2 is not None:
@@ -159,7 +162,7 @@ def main(argv=None):
         listed = stills.list_images(args.images, box)
         fitted, records = [], []
         for path, own in listed:                         # decoded on the host, once: the decode is what a still costs
-            u8, info = stills.fit(path, own, what='--box' if own is box else 'the manifest box')
+            u8, info = stills.fit(path, own, what='--box' if own is box else 'the manifest box', image_size=size)
             fitted.append(u8)
             records.append(info)
         driver = None
@@ -167,7 +170,7 @@ def main(argv=None):
             driver_box = stills.parse_box(args.driver_box, '--driver-box') if args.driver_box is not None else None
             paths, idx, n_found = stills.driver_frames(args.driver)
             driver = {'paths': paths, 'frames': idx, 'n_found': n_found,
-                      'u8': np.stack([stills.fit(p, driver_box, what='--driver-box')[0] for p in paths])}
+                      'u8': np.stack([stills.fit(p, driver_box, what='--driver-box', image_size=size)[0] for p in paths])}
     except ValueError as e:                              # (StillsError is one)
         parser.error(str(e))
     checkpoints = [args.checkpoint_stage1] + ([args.checkpoint_stage2] if args.checkpoint_stage2 is not None else [])
@@ -181,7 +184,7 @@ def main(argv=None):
     from kpx_amd.data import _to_device_unit
     ops = kpx_amd.ops
     dev = torch.device('cuda', 0)
-    model = kpx_amd.FinalModel(config, device=dev, point_maps=True, colors_seed=args.colors_seed)
+    model = kpx_amd.FinalModel(config, device=dev, image_size=size, point_maps=True, colors_seed=args.colors_seed)
     model.build(None)
     for p in checkpoints:
         model.restore(None, p, **({'ema': True} if args.ema else {}))

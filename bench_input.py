@@ -6,7 +6,12 @@ Every window is warmed up and at least a second long.  KPX_DTYPE=bf16 selects th
 --motion measures stage 2 instead (kpx_amd.data.SequenceDataLoader, K = 40 pseudo labels on 480x270 videos of 40 / 70 / 100 frames, the
 motion generator at the reference's size): sequences/s at batch 16 and 64 of the loader alone -- the host threads, or with --resident
 the key-point kernel on labels kept in HBM -- of the train step on one fixed device batch, and of the train step fed by the loader.
-Run it once without and once with --resident in the same session to compare the two loaders."""
+Run it once without and once with --resident in the same session to compare the two loaders.
+
+--image-size S runs everything at S x S frames (default 128; --points K sets the model's key points, so --image-size 256 --points 40
+--batch 16 is the shape of bench.py --config c3).  --resident --launches times the two augmentation launches of one fixed batch by
+themselves, in alternating blocks: the entries that take the side as an argument, at 128 the compile-time entries of the same process
+beside them, and a device copy of their output for scale."""
 import argparse, io, os, sys, tempfile, time
 import numpy as np
 import torch
@@ -90,6 +95,41 @@ def motion(a):
                 print('stage-2 train step fed by the loader (%s) [%d]: %.0f sequences/s (batch %d)' % (what, rep, timed(fed, b, a.batches), b))
 
 
+def launches(a, loader, store, dev, blocks=5):
+    """--resident --launches: microseconds per batch of the geometry + filter launches on one fixed row table, per block."""
+    from kpx_amd import resident as R
+    from kpx_amd._lib import lib, check
+    s, n = store.image_size, 2 * a.batch
+    plans = [p for _ in range(a.batch // max(1, loader.length()) + 1) for p in loader.plans()][:a.batch]
+    rows_dev = torch.from_numpy(store.check_rows(store.rows_for_plans(plans, True))).to(dev)
+    out, out2 = (torch.empty((n, s, s, 3), dtype=torch.float32, device=dev) for _ in range(2))
+    tiles = torch.empty((n, s, s, 3), dtype=torch.uint8, device=dev)
+    lsum = torch.empty((n, R.BANDS), dtype=torch.int32, device=dev)
+
+    def by_argument(i):
+        store.augment(rows_dev, n, out=out)
+
+    def compile_time(i):                           # kpx_augment_geometry_u8 / kpx_augment_filter_f32: side 128 only
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib.kpx_augment_geometry_u8(store.frames.data_ptr(), store.frame_off.data_ptr(), rows_dev.data_ptr(), n, store.resize_tabs.data_ptr(),
+                                          store.band_rows_cap, tiles.data_ptr(), lsum.data_ptr(), stream), 'kpx_augment_geometry_u8')
+        check(lib.kpx_augment_filter_f32(tiles.data_ptr(), lsum.data_ptr(), rows_dev.data_ptr(), n, store.kernels.data_ptr(), out2.data_ptr(), stream),
+              'kpx_augment_filter_f32')
+
+    def copy(i):
+        out2.copy_(out)
+    forms = [('side as an argument', by_argument)] + ([('side 128 at compile time', compile_time)] if s == 128 else []) + [('device copy of the output', copy)]
+    for _, f in forms:
+        for i in range(20): f(i)
+    if s == 128:
+        torch.cuda.synchronize()
+        assert torch.equal(out, out2), 'the two forms of the launches disagree'
+    for block in range(blocks):
+        for name, f in forms:
+            print('launches of one batch of %d pairs at %d x %d, %s [%d]: %.1f us'
+                  % (a.batch, s, s, name, block, 1e6 * a.batch / timed(f, a.batch, 200, min_seconds=0.5)))
+
+
 def timed(step, batch, batches, min_seconds=1.0):
     """pairs/s of ``step(i)`` over a window of at least ``batches`` calls and ``min_seconds`` (the caller has warmed up)."""
     n = 0
@@ -107,6 +147,9 @@ def main():
     ap.add_argument('--frames', type=int, default=40, help='frames per synthetic video (8 videos)')
     ap.add_argument('--motion', action='store_true', help='stage 2: the sequence loader and the motion generator step (batch 16 and 64); '
                                                           'with --resident the key-point labels are kept in HBM')
+    ap.add_argument('--image-size', type=int, default=128, metavar='S', help='side of the frames (a multiple of 16 in [32, 256], default 128)')
+    ap.add_argument('--points', type=int, default=15, metavar='K', help='key points of the --train model (default 15; bench.py --config c3 has 40)')
+    ap.add_argument('--launches', action='store_true', help='with --resident: time the two augmentation launches of one fixed batch alone')
     a = ap.parse_args()
     if a.motion:
         return motion(a)
@@ -114,23 +157,26 @@ def main():
     dev = torch.device('cuda', 0)
     with tempfile.TemporaryDirectory() as root:
         make_dataset(root, frames=a.frames)
-        loader = kpx_amd.ImagePairDataLoader(root, 'train', random_order=True, randomness=True)
+        loader = kpx_amd.ImagePairDataLoader(root, 'train', random_order=True, randomness=True, image_size=a.image_size)
         if a.resident:
             store = loader.resident_frames(dev)
             print('resident store: %d frames, %d bytes (%.1f MiB) ingested in %.2f s (%.0f frames/s, header scan + decode + copy)'
                   % (len(store.index.offsets), store.index.total_bytes, store.index.total_bytes / 2.0 ** 20, store.ingest_seconds,
                      len(store.index.offsets) / store.ingest_seconds))
             what = 'resident path'
+            if a.launches:
+                launches(a, loader, store, dev)
         else:
             what = 'CPU pipeline, %d threads' % a.threads
         it = iter(loader.batches(a.batch, dev, num_preprocess_threads=a.threads, resident=a.resident))
         for _ in range(3): next(it)
-        print('input pipeline alone (%s): %.0f pairs/s (batch %d)' % (what, timed(lambda i: next(it), a.batch, a.batches), a.batch))
+        print('input pipeline alone (%s): %.0f pairs/s (batch %d, %d x %d)'
+              % (what, timed(lambda i: next(it), a.batch, a.batches), a.batch, a.image_size, a.image_size))
         if a.train:
-            cfg = {'training': {'lr': {'start_val': 1e-4, 'step': 20000, 'decay': 0.95}, 'batch_size': a.batch}, 'model': {'n_pts': 15},
+            cfg = {'training': {'lr': {'start_val': 1e-4, 'step': 20000, 'decay': 0.95}, 'batch_size': a.batch}, 'model': {'n_pts': a.points},
                    'paths': {'log_dir': '/tmp/kpx_bench', 'vggnet': None}}
             vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(seed=19), device=dev)
-            model = kpx_amd.DetectorTranslatorModel(cfg, device=dev, vgg=vgg, image_size=128); model.build()
+            model = kpx_amd.DetectorTranslatorModel(cfg, device=dev, vgg=vgg, image_size=a.image_size); model.build()
             fixed = {k: v.clone() for k, v in next(it).items()}
             steps = [0]
 

@@ -1051,7 +1051,7 @@ def _save_img_sequence(output_dir, img_seq, rescale=False, raw=False):
 
 
 def main(argv=None):
-    from train import load_config
+    from train import IMAGE_SIZE_HELP, config_image_size, load_config
     parser = ArgumentParser()
     parser.add_argument('--config', type=str, required=True, help='path of the configuration file')
     parser.add_argument('--checkpoint_stage1', type=str, required=True, help='path of the stage1 checkpoint')
@@ -1061,6 +1061,7 @@ def main(argv=None):
     parser.add_argument('--synthetic', type=int, default=0)
     parser.add_argument('--batch', type=int, default=8)             # reference :27
     parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette (the reference draws it unseeded)')
+    parser.add_argument('--image-size', type=int, default=None, metavar='S', help=IMAGE_SIZE_HELP)
     parser.add_argument('--no-save', action='store_true')
     parser.add_argument('--metrics', action='store_true', help='score the predictions: <save_dir>/metrics.npz and metrics.json')
     parser.add_argument('--samples', type=int, default=1, help='rollouts per batch with fresh z (PNGs from the first)')
@@ -1127,9 +1128,11 @@ def main(argv=None):
         parser.error('--rate takes 1..64 (got %d)' % long_rate)
     if (args.resample or 'cubic') not in ('linear', 'cubic'):
         parser.error('--resample takes linear or cubic (got %r)' % args.resample)
-    if 2 * (1 + long_frames * long_rate) * 128 * 128 > 1 << 24:
-        parser.error('--frames x --rate: long.gif would hold %d frames of two 128 x 128 cells, and the colour histogram of one GIF counts '
-                     'at most 2^24 pixels (%d frames)' % (1 + long_frames * long_rate, (1 << 24) // (2 * 128 * 128)))
+    def check_long_gif(side):
+        if 2 * (1 + long_frames * long_rate) * side * side > 1 << 24:
+            parser.error('--frames x --rate: long.gif would hold %d frames of two %d x %d cells, and the colour histogram of one GIF counts '
+                         'at most 2^24 pixels (%d frames)' % (1 + long_frames * long_rate, side, side, (1 << 24) // (2 * side * side)))
+    check_long_gif(128)
     if (args.novelty_sheets or args.novelty_no_mirror) and not args.novelty:
         parser.error('--novelty-sheets and --novelty-no-mirror shape the search of --novelty and need it')
     if args.novelty and args.synthetic:
@@ -1206,6 +1209,9 @@ def main(argv=None):
     if args.samples < 1:
         parser.error('--samples must be >= 1 (got %d)' % args.samples)
     config = load_config(args.config)
+    size = config_image_size(config, args.image_size)
+    if want_long:
+        check_long_gif(size)
     actions = sheet_frames = None
     if args.actions is not None or drive_modes is not None or args.novelty_sheets:
         n_cls_all = config['model'].get('n_action', 9)
@@ -1234,7 +1240,7 @@ def main(argv=None):
     vgg = None
     if args.vgg_metrics:
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev) if args.synthetic_vgg else kpx_amd.Vgg19(vggnet, device=dev)
-    model = kpx_amd.FinalModel(config, device=dev, point_maps=not args.no_save, colors_seed=args.colors_seed)
+    model = kpx_amd.FinalModel(config, device=dev, image_size=size, point_maps=not args.no_save, colors_seed=args.colors_seed)
     print('model initialized')
     model.build(None)
     for p in checkpoints:                                            # reference :76-77: two partial restores by name
@@ -1245,7 +1251,7 @@ def main(argv=None):
     sample_idx, frames, t0 = 0, 0, time.time()
     if not args.synthetic:                       # reference :43-51, :84-130: the test subset through the sequence loader
         loader = kpx_amd.data.SequenceDataLoader(config['paths']['data_dir'], 'test', n_points=config['model']['n_pts'], n_action=n_action,
-                                                 random_order=False, randomness=False, with_image_seq=True)
+                                                 random_order=False, randomness=False, with_image_seq=True, image_size=size)
         scores, n_frames = [], 32
         vgg_scores = [] if args.vgg_metrics else None
         frechet = None
@@ -1421,7 +1427,7 @@ def main(argv=None):
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)
         rs = np.random.RandomState(start)
-        im = (rs.randint(0, 256, size=(bsz, 128, 128, 3)).astype(np.float32) / 255.0 * 2.0 - 1.0)
+        im = (rs.randint(0, 256, size=(bsz, size, size, 3)).astype(np.float32) / 255.0 * 2.0 - 1.0)
         act = np.eye(n_action, dtype=np.float32)[rs.randint(0, n_action, size=bsz)]
         image = torch.from_numpy(im).to(dev)
         if args.drive_only:                  # hold alone, without the model's own rollout

@@ -803,6 +803,24 @@ int kpx_augment_geometry_u8(const unsigned char* frames, const int64_t* frame_of
 int kpx_augment_filter_f32(const unsigned char* tiles, const int32_t* lsum, const int32_t* rows, int n_rows, const float* kernels,
                            float* out, void* stream);
 
+/* The same two launches on square tiles of `side` x `side` pixels (model.image_size; the two entries above are side = 128, bit for bit).
+ * Added to ABI version 25; no signature above changes.
+ *
+ *   side       a multiple of KPX_AUG_BAND in [KPX_AUG_TILE_MIN, KPX_AUG_TILE_MAX]: the tile has side / KPX_AUG_BAND bands
+ *   tiles      uint8 [n_rows][side][side][3], lsum int32 [n_rows][side / KPX_AUG_BAND], out float32 [n_rows][side][side][3]
+ *   band_rows_cap  as above; the workgroup keeps cap * side * 3 bytes in LDS, at most KPX_AUG_LDS_BYTES (above 64 KB the launch opts in
+ *                  with hipFuncAttributeMaxDynamicSharedMemorySize).  The host refuses a video whose band needs more
+ *                  (kpx_amd.resident.check_rows) and the entry answers KPX_EINVAL before any launch.
+ *   Contrast   the degenerate grey is int(mean luminance + 0.5) over side * side pixels, computed as (2 * sum + side^2) / (2 * side^2)
+ *              in integers: exact for every side. */
+#define KPX_AUG_TILE_MIN 32
+#define KPX_AUG_TILE_MAX 256
+#define KPX_AUG_LDS_BYTES 122880
+int kpx_augment_geometry_sq_u8(const unsigned char* frames, const int64_t* frame_off, const int32_t* rows, int n_rows,
+                               const int32_t* resize_tabs, int band_rows_cap, int side, unsigned char* tiles, int32_t* lsum, void* stream);
+int kpx_augment_filter_sq_f32(const unsigned char* tiles, const int32_t* lsum, const int32_t* rows, int n_rows, const float* kernels,
+                              int side, float* out, void* stream);
+
 /* ---- The key-point half of the sequence loader on pseudo labels resident in HBM (ABI 12): what SequenceDataLoader.render does to the
  *      key points with numpy (data/sequence_dataloader.py:105-198: gather 33 sets, rotate, flip, scale; the one-hot action code),
  *      bit for bit, from a table of per-sample decisions the host draws (kpx_amd/resident.py).  One launch per batch.

@@ -188,7 +188,7 @@ class _Joints:
 
 
 def main(argv=None):
-    from train import load_config
+    from train import IMAGE_SIZE_HELP, config_image_size, load_config
     parser = ArgumentParser()
     parser.add_argument('--config', type=str, required=True, help='path of the configuration file')
     parser.add_argument('--checkpoint', type=str, required=True, help='path of the pretrained keypoints detector')
@@ -201,6 +201,7 @@ def main(argv=None):
     parser.add_argument('--stability-seed', type=int, default=None, help='seed of the maps (default 0)')
     parser.add_argument('--stability-sheets', action='store_true', help='one contact sheet per video for its first frame')
     parser.add_argument('--colors_seed', type=int, default=0, help="seed of the sheets' key-point palette")
+    parser.add_argument('--image-size', type=int, default=None, metavar='S', help=IMAGE_SIZE_HELP)
     parser.add_argument('--joints', action='store_true',
                         help='also regress the annotated joints from the key points (fit on train, error and PCK per subset) into '
                              "<paths.log_dir>/joints/ (comparable across this project's checkpoints)")
@@ -238,13 +239,14 @@ def main(argv=None):
     if args.stability_sheets and args.stability_warps is not None and args.stability_warps > 64:
         parser.error('--stability-sheets draws one row per map: at most 64 (got --stability-warps %d)' % args.stability_warps)
     config = load_config(args.config)
+    size = config_image_size(config, args.image_size)
     keypoints_root_dir = osp.join(config['paths']['data_dir'], 'pseudo_labels')
     os.makedirs(keypoints_root_dir, exist_ok=True)
     if not (osp.exists(args.checkpoint) or osp.exists(args.checkpoint + '.index')):      # .npz file or TensorFlow bundle prefix
         raise Exception('checkpoint not found at %s' % args.checkpoint)          # reference :31-32
     import kpx_amd
     dev = torch.device('cuda', 0)
-    model = kpx_amd.KeypointModel(config, device=dev)
+    model = kpx_amd.KeypointModel(config, device=dev, image_size=size)
     print('model initialized')
     model.build(None)
     restored = model.restore(None, args.checkpoint, **({'ema': True} if args.ema else {}))
@@ -261,9 +263,9 @@ def main(argv=None):
     if not args.synthetic:                       # reference :36-37, :79-95: every video of the train and the test subset
         data_dir = config['paths']['data_dir']
         if joints:                               # both listings are read up front only here: no label file at all ends the run before the first video
-            joints.require_labels([v for subset in ('train', 'test') for v in kpx_amd.data.KeypointDataLoader(data_dir, subset).video_ids()])
+            joints.require_labels([v for subset in ('train', 'test') for v in kpx_amd.data.KeypointDataLoader(data_dir, subset, image_size=size).video_ids()])
         for subset in ('train', 'test'):
-            loader = kpx_amd.data.KeypointDataLoader(data_dir, subset)
+            loader = kpx_amd.data.KeypointDataLoader(data_dir, subset, image_size=size)
             for pos, v in enumerate(loader.videos(dev)):
                 outputs = model.run(None, {'image': v['image'][None], 'idx': np.array([v['idx']]), 'len': np.array([v['len']])})
                 _save_output(keypoints_root_dir, outputs)
@@ -283,15 +285,15 @@ def main(argv=None):
     for v in range(args.synthetic):
         rs = np.random.RandomState(v)
         n = int(rs.randint(args.frames // 4, args.frames + 1))
-        im = np.zeros((1, args.frames, 128, 128, 3), np.float32)
-        im[0, :n] = (rs.randint(0, 256, size=(n, 128, 128, 3)).astype(np.float32) / 255.0 * 2.0 - 1.0)
+        im = np.zeros((1, args.frames, size, size, 3), np.float32)
+        im[0, :n] = (rs.randint(0, 256, size=(n, size, size, 3)).astype(np.float32) / 255.0 * 2.0 - 1.0)
         outputs = model.run(None, {'image': torch.from_numpy(im).to(dev), 'idx': np.array([v]), 'len': np.array([n])})
         _save_output(keypoints_root_dir, outputs)
         if stab:
             stab.video('synthetic', outputs['im'][0], outputs['pts'][0], v, n)
         if joints:
-            planted = joints.lib.planted_labels([SYNTHETIC_JOINTS_SEED, v], n, SYNTHETIC_JOINTS, (128, 128))
-            joints.video('test' if v % 2 else 'train', outputs['im'][0], outputs['pts'][0], v, n, (128, 128), labels=planted)
+            planted = joints.lib.planted_labels([SYNTHETIC_JOINTS_SEED, v], n, SYNTHETIC_JOINTS, (size, size))
+            joints.video('test' if v % 2 else 'train', outputs['im'][0], outputs['pts'][0], v, n, (size, size), labels=planted)
         frames += args.frames
     torch.cuda.synchronize()
     print('iteration through synthetic set finished: %d frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))

@@ -2,6 +2,7 @@
 """Training entry point with the reference's CLI (reference: train.py:12-114):
 
     python train.py --mode detector_translator --config configs/penn.yaml [--synthetic] [--steps N]
+    python train.py --mode detector_translator --config configs/penn256.yaml --resident-data      (256 x 256; or --image-size S on any config)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 train.py --mode ... (data parallel)
 
     python train.py --mode action_classifier --config configs/penn.yaml [--synthetic] [--resident-labels] [--steps N]
@@ -56,6 +57,20 @@ def load_config(config_path):
     """reference utils/__init__.py:8-10"""
     with open(config_path, 'r') as f:
         return yaml.load(f, Loader=yaml.FullLoader)
+
+
+def config_image_size(config, override=None):
+    """The side S of the frames the networks see: ``--image-size`` where the command line gives one, else the optional YAML key
+    model.image_size, else 128; checked by the package's one rule (kpx_amd.data.check_image_size: a multiple of 16 in [32, 256], a
+    ``KpxError`` naming the key and the value otherwise).  train.py, evaluate.py, make_pseudo_labels.py and animate.py all come here."""
+    from kpx_amd.data import IMAGE_SIZE, check_image_size
+    if override is not None:
+        return check_image_size(override, '--image-size')
+    return check_image_size((config.get('model') or {}).get('image_size', IMAGE_SIZE))
+
+
+IMAGE_SIZE_HELP = ('side S of the frames the networks see, a multiple of 16 in [32, 256]; overrides model.image_size of the configuration '
+                   '(default 128).  Checkpoints carry no size: one trained at another S loads, with no claim about its quality')
 
 
 def _get_model_by_mode(mode, config, global_step, **kw):
@@ -239,8 +254,9 @@ def _train_motion_generator(args, config, dev, rank, world):
         random.seed(1000 + rank); np.random.seed(1000 + rank)
         if resumed:
             _reseed_loaders(rank, model.global_step)
+        size = config_image_size(config, args.image_size)          # stage 2 trains on key points; the size shapes the start frames of its summaries
         mk = lambda subset, train: kpx_amd.SequenceDataLoader(paths_config['data_dir'], subset, n_points=k, n_action=a,
-                                                              random_order=train, randomness=train)
+                                                              random_order=train, randomness=train, image_size=size)
         train_it = mk('train', True).batches(batch_size, dev, repeat=True, resident=args.resident_labels)
         if os.path.exists(os.path.join(str(paths_config['data_dir']), 'test_set.txt')):
             test_loader = mk('test', False)
@@ -312,6 +328,7 @@ def parse_args(argv=None):
                              'one HIP launch (SequenceDataLoader.batches(resident=True)); the same batches and summaries as without the flag')
     parser.add_argument('--synthetic-vgg', action='store_true', help='He-normal VGG19 weights when paths.vggnet is absent')
     parser.add_argument('--steps', type=int, default=None, help='override training.n_steps')
+    parser.add_argument('--image-size', type=int, default=None, metavar='S', help=IMAGE_SIZE_HELP)
     parser.add_argument('--ckpt-format', choices=['npz', 'tf', 'bundle'], default=os.environ.get('KPX_CKPT_FORMAT', 'npz'),
                         help="checkpoint container: 'tf' = TensorFlow V2 bundle (model.ckpt-N.index / .data-00000-of-00001 + `checkpoint`, the "
                              "layout tf.train.Saver writes and the reference restores, models/base_model.py:74-91); 'npz' (default) = one "
@@ -398,7 +415,9 @@ def main(argv=None):
         if not args.synthetic_vgg:
             raise Exception('file of pretrained vgg19 does not exist at: %s (pass --synthetic-vgg for benchmarking)' % paths_config.get('vggnet'))
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev)
-    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, **_guard_kw(args), **_ema_kw(args), **_clip_kw(args))
+    size = config_image_size(config, args.image_size)
+    model = _get_model_by_mode(args.mode, config, 0, device=dev, vgg=vgg, colors_seed=args.colors_seed, image_size=size,
+                               **_guard_kw(args), **_ema_kw(args), **_clip_kw(args))
     print('model initialized')
     model.build(None)
     batch_size = train_config['batch_size']          # per process, like the reference's single-device batch
@@ -413,10 +432,10 @@ def main(argv=None):
         random.seed(1000 + rank); np.random.seed(1000 + rank)          # different sample streams per data-parallel rank
         if resumed:
             _reseed_loaders(rank, model.global_step)
-        train_it = iter(kpx_amd.ImagePairDataLoader(data_dir, 'train', random_order=True, randomness=True)
+        train_it = iter(kpx_amd.ImagePairDataLoader(data_dir, 'train', random_order=True, randomness=True, image_size=size)
                         .batches(batch_size, dev, repeat=True, shuffle=True, resident=args.resident_data))
         if os.path.exists(os.path.join(str(data_dir), 'test_set.txt')):
-            test_loader = kpx_amd.ImagePairDataLoader(data_dir, 'test', random_order=False, randomness=False)
+            test_loader = kpx_amd.ImagePairDataLoader(data_dir, 'test', random_order=False, randomness=False, image_size=size)
             test_it = lambda: iter(test_loader.batches(batch_size, dev, repeat=False, shuffle=False, resident=args.resident_data))
     n_steps = args.steps if args.steps is not None else train_config['n_steps']
     model.initialize_loggers(paths_config['log_dir'], None)

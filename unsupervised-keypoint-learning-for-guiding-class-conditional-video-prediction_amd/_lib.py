@@ -168,6 +168,8 @@ SIGNATURES = {
     'kpx_crc32c_host': (ctypes.c_uint, [ctypes.c_uint, P, c_size_t]),
     'kpx_augment_geometry_u8': (c_int, [P, P, P, c_int, P, c_int, P, P, P]),
     'kpx_augment_filter_f32': (c_int, [P, P, P, c_int, P, P, P]),
+    'kpx_augment_geometry_sq_u8': (c_int, [P, P, P, c_int, P, c_int, c_int, P, P, P]),
+    'kpx_augment_filter_sq_f32': (c_int, [P, P, P, c_int, P, c_int, P, P]),
     'kpx_keypoint_seq_augment_f32': (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     'kpx_seq_nearest_workspace_bytes': (c_size_t, [c_int, c_int]),
     'kpx_seq_nearest_f32': (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P]),

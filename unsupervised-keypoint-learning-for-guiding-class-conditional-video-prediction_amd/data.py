@@ -45,9 +45,23 @@ _ENHANCERS = {6: (ImageEnhance.Sharpness, 0, 50), 7: (ImageEnhance.Brightness, 7
 PairPlan = namedtuple('PairPlan', 'video im_idx fu_idx angle crop flip filt filt_val')
 
 
-def _resized_size(w, h):
-    """Short side -> 128 with the reference's truncations (:107-111, :137-141)."""
-    ratio = (h if w > h else w) / float(IMAGE_SIZE)
+MIN_IMAGE_SIZE, MAX_IMAGE_SIZE, IMAGE_SIZE_STEP = 32, 256, 16
+
+
+def check_image_size(value, key='model.image_size'):
+    """The one rule for the side S of the frames the networks see: an integer multiple of 16 in [32, 256] (the networks' strided layers
+    halve the side several times and the resident augmentation works in bands of 16 rows) -> int; anything else is a ``KpxError`` naming ``key`` and the
+    value.  A model with a stricter rule adds it here."""
+    ok = isinstance(value, int) and not isinstance(value, bool) and MIN_IMAGE_SIZE <= value <= MAX_IMAGE_SIZE and value % IMAGE_SIZE_STEP == 0
+    if not ok:
+        from ._lib import KpxError
+        raise KpxError('%s = %r: the image size is an integer multiple of %d in [%d, %d]' % (key, value, IMAGE_SIZE_STEP, MIN_IMAGE_SIZE, MAX_IMAGE_SIZE))
+    return int(value)
+
+
+def _resized_size(w, h, image_size=IMAGE_SIZE):
+    """Short side -> image_size with the reference's truncations (:107-111, :137-141)."""
+    ratio = (h if w > h else w) / float(image_size)
     return int(w / ratio), int(h / ratio), ratio
 
 
@@ -62,8 +76,9 @@ def apply_filter(images, filt, filt_val):
 class ImagePairDataLoader(object):
     """Same constructor and methods as the reference class (data/image_pair_dataloader.py:16)."""
 
-    def __init__(self, data_dir, subset, random_order=True, randomness=False, rng=None, np_rng=None):
+    def __init__(self, data_dir, subset, random_order=True, randomness=False, rng=None, np_rng=None, image_size=IMAGE_SIZE):
         self._data_dir = data_dir
+        self.image_size = check_image_size(image_size, 'image_size')
         self._random_order = random_order
         self._randomness = randomness
         self._rng = rng if rng is not None else _random            # the reference uses the global generators
@@ -81,7 +96,7 @@ class ImagePairDataLoader(object):
         return self._total
 
     def get_sample_shape(self):
-        return {'image': [IMAGE_SIZE, IMAGE_SIZE, 3], 'future_image': [IMAGE_SIZE, IMAGE_SIZE, 3]}
+        return {'image': [self.image_size, self.image_size, 3], 'future_image': [self.image_size, self.image_size, 3]}
 
     def get_sample_dtype(self):
         import torch
@@ -129,8 +144,8 @@ class ImagePairDataLoader(object):
             else:
                 with Image.open(self._frame_path(video, im_idx)) as im:              # header only: the crop range needs the size
                     w, h = im.size
-            rw, rh, _ = _resized_size(w, h)
-            crop = rng.randint(0, int((rw if w > h else rh) - IMAGE_SIZE))            # :113 / :143 (int(w/ratio - 128))
+            rw, rh, _ = _resized_size(w, h, self.image_size)
+            crop = rng.randint(0, int((rw if w > h else rh) - self.image_size))       # :113 / :143 (int(w/ratio - 128))
             flip = rng.randint(0, 1)
             filt = rng.randint(0, 9)                                                 # utils/data.py:9
             if filt >= 6:
@@ -139,17 +154,18 @@ class ImagePairDataLoader(object):
 
     # ---- pixels (thread-safe: no shared state, PIL releases the GIL in its C loops)
     def render(self, plan):
-        """-> (image, future_image) uint8 [128,128,3]"""
+        """-> (image, future_image) uint8 [S,S,3], S = image_size"""
         frames = [Image.open(self._frame_path(plan.video, i)) for i in (plan.im_idx, plan.fu_idx)]
         w, h = frames[0].size
+        s = self.image_size
         if self._randomness:
             frames = [f.rotate(plan.angle) for f in frames]                          # :94-95
         landscape = w > h
-        rw, rh, _ = _resized_size(w, h)
+        rw, rh, _ = _resized_size(w, h, s)
         frames = [f.resize([rw, rh]) for f in frames]
         if self._randomness:
             c = plan.crop
-            box = (c, 0, c + IMAGE_SIZE, IMAGE_SIZE) if landscape else (0, c, IMAGE_SIZE, c + IMAGE_SIZE)
+            box = (c, 0, c + s, s) if landscape else (0, c, s, c + s)
             frames = [f.crop(box) for f in frames]
             if plan.flip:
                 frames = [f.transpose(Image.FLIP_LEFT_RIGHT) for f in frames]
@@ -157,15 +173,15 @@ class ImagePairDataLoader(object):
         else:
             # the reference centres on the WIDTH in both branches (:126-131 and :156-161): a portrait frame keeps its top 128 rows
             ox = frames[0].size[0] / 2.0
-            half = IMAGE_SIZE // 2
-            frames = [f.crop((ox - half, 0, ox + half, IMAGE_SIZE)) for f in frames]
+            half = s // 2
+            frames = [f.crop((ox - half, 0, ox + half, s)) for f in frames]
         return tuple(np.asarray(f) for f in frames)
 
     # ---- batches on the device
     def batches(self, batch_size, device, repeat=True, shuffle=False, num_preprocess_threads=8, prefetch=2, resident=False,
                 max_resident_bytes=64 << 30):
         """The reference's get_dataset(batch_size, repeat, shuffle, num_preprocess_threads, prefetch) as an iterator of
-        {'image','future_image'} float32 tensors [B,128,128,3] in [-1,1] living on ``device``.
+        {'image','future_image'} float32 tensors [B,S,S,3] (S = image_size) in [-1,1] living on ``device``.
 
         ``resident=False``: JPEG decode + PIL augmentation on ``num_preprocess_threads`` host threads (the reference maps with 12).
         ``resident=True``: every frame of the subset is decoded once into HBM (at most ``max_resident_bytes``; built on first use, kept
@@ -191,7 +207,7 @@ class ImagePairDataLoader(object):
         if device.type == 'cuda' and device.index is None:
             device = torch.device('cuda', torch.cuda.current_device())
         if self._store is None or self._store.device != device:
-            self._store = ResidentFrames(self._data_dir, self._images, device, max_bytes)
+            self._store = ResidentFrames(self._data_dir, self._images, device, max_bytes, image_size=self.image_size)
             self.attach_frames(self._store.index)
         return self._store
 
@@ -212,7 +228,7 @@ class _DeviceBatcher(object):
         self.on_gpu = self.device.type == 'cuda'
         self.pool = ThreadPoolExecutor(max_workers=max(1, threads))
         self.depth = max(1, prefetch)
-        shape = (2, batch_size, IMAGE_SIZE, IMAGE_SIZE, 3)
+        shape = (2, batch_size, loader.image_size, loader.image_size, 3)
         self.host = [torch.empty(shape, dtype=torch.uint8) for _ in range(self.depth + 1)]
         if self.on_gpu:
             self.host = [h.pin_memory() for h in self.host]
@@ -354,12 +370,13 @@ class _ListedVideos(object):
 class KeypointDataLoader(_ListedVideos):
     """data/keypoint_dataloader.py:16-86: every frame of a video, centre-cropped to 128x128, zero-padded to 663 frames."""
 
-    def __init__(self, data_dir, subset, threads=8):
+    def __init__(self, data_dir, subset, threads=8, image_size=IMAGE_SIZE):
         super(KeypointDataLoader, self).__init__(data_dir, subset)
         self._threads = threads
+        self.image_size = check_image_size(image_size, 'image_size')
 
     def get_sample_shape(self):
-        return {'image': [MIN_IMAGE_SEQ_LEN, IMAGE_SIZE, IMAGE_SIZE, 3], 'len': None, 'idx': None}
+        return {'image': [MIN_IMAGE_SEQ_LEN, self.image_size, self.image_size, 3], 'len': None, 'idx': None}
 
     def get_sample_dtype(self):
         import torch
@@ -369,12 +386,12 @@ class KeypointDataLoader(_ListedVideos):
         return {'image': inputs['image'] * 2.0 - 1.0, 'len': inputs['len'], 'idx': inputs['idx']}
 
     def render_video(self, idx):
-        """-> (uint8 [len,128,128,3], len, video id)"""
+        """-> (uint8 [len,S,S,3], len, video id), S = image_size"""
         video = self._images[idx].split()[0]
         n = self._n_frames(video)
         with self._frame(video, 0) as first:
             w, h = first.size
-        box, ratio = center_crop_box(w, h)
+        box, ratio = center_crop_box(w, h, self.image_size)
         size = [int(w / ratio), int(h / ratio)]
 
         def one(i):
@@ -397,15 +414,15 @@ class KeypointDataLoader(_ListedVideos):
             frames, n, vid = self.render_video(idx)
             seq = frames
             if n < MIN_IMAGE_SEQ_LEN:
-                seq = np.concatenate([frames, np.zeros([MIN_IMAGE_SEQ_LEN - n, IMAGE_SIZE, IMAGE_SIZE, 3])], axis=0)
+                seq = np.concatenate([frames, np.zeros([MIN_IMAGE_SEQ_LEN - n, self.image_size, self.image_size, 3])], axis=0)
             yield {'image': seq / 255.0, 'idx': vid, 'len': n}
 
     def videos(self, device):
-        """Device-side iterator: {'image': float32 [663,128,128,3] in [-1,1] (pad frames = -1 like the reference), 'len', 'idx'}."""
+        """Device-side iterator: {'image': float32 [663,S,S,3] in [-1,1] (pad frames = -1 like the reference), 'len', 'idx'}."""
         for idx in range(self._total):
             frames, n, vid = self.render_video(idx)
             if n < MIN_IMAGE_SEQ_LEN:
-                frames = np.concatenate([frames, np.zeros([MIN_IMAGE_SEQ_LEN - n, IMAGE_SIZE, IMAGE_SIZE, 3], dtype=np.uint8)], axis=0)
+                frames = np.concatenate([frames, np.zeros([MIN_IMAGE_SEQ_LEN - n, self.image_size, self.image_size, 3], dtype=np.uint8)], axis=0)
             yield {'image': _to_device_unit(frames, device), 'len': n, 'idx': vid}
 
 
@@ -416,8 +433,9 @@ class SequenceDataLoader(_ListedVideos):
     """data/sequence_dataloader.py:17-198: start frame + 32 future key-point sets (+ optionally the future frames) of a video."""
 
     def __init__(self, data_dir, subset, n_points, n_action, with_image_seq=False, random_order=True, randomness=False,
-                 rng=None, np_rng=None):
+                 rng=None, np_rng=None, image_size=IMAGE_SIZE):
         super(SequenceDataLoader, self).__init__(data_dir, subset)
+        self.image_size = check_image_size(image_size, 'image_size')
         self.n_points, self.n_action = n_points, n_action
         self._with_image_seq, self._random_order, self._randomness = with_image_seq, random_order, randomness
         self._rng = rng if rng is not None else _random
@@ -431,10 +449,10 @@ class SequenceDataLoader(_ListedVideos):
         return super(SequenceDataLoader, self)._n_frames(video)
 
     def get_sample_shape(self):
-        d = {'image': [IMAGE_SIZE, IMAGE_SIZE, 3], 'keypoints': [self.n_points, 2],
+        d = {'image': [self.image_size, self.image_size, 3], 'keypoints': [self.n_points, 2],
              'real_seq': [N_SEQUENCE_LEN - 1, self.n_points, 2], 'action_code': [self.n_action]}
         if self._with_image_seq:
-            d['real_im_seq'] = [N_SEQUENCE_LEN - 1, IMAGE_SIZE, IMAGE_SIZE, 3]
+            d['real_im_seq'] = [N_SEQUENCE_LEN - 1, self.image_size, self.image_size, 3]
         return d
 
     def get_sample_dtype(self):
@@ -471,12 +489,12 @@ class SequenceDataLoader(_ListedVideos):
         return SeqPlan(idx, video, n, im_idx, angle, flip, scale)
 
     def _start_frame(self, plan):
-        """-> (the start frame as ``render`` delivers it: rotated, centre-cropped to 128 x 128, flipped; resized size; crop box)"""
+        """-> (the start frame as ``render`` delivers it: rotated, centre-cropped to S x S, flipped; resized size; crop box)"""
         image = self._frame(plan.video, plan.im_idx)
         if self._randomness:
             image = image.rotate(plan.angle)
         w, h = image.size
-        box, ratio = center_crop_box(w, h)
+        box, ratio = center_crop_box(w, h, self.image_size)
         size = [int(w / ratio), int(h / ratio)]
         image = image.resize(size).crop(box)
         if self._randomness and plan.flip:
@@ -484,7 +502,7 @@ class SequenceDataLoader(_ListedVideos):
         return image, size, box
 
     def render_start_image(self, plan):
-        """-> uint8 [128,128,3]: ``render(plan)['image']`` alone, without reading the key points"""
+        """-> uint8 [S,S,3]: ``render(plan)['image']`` alone, without reading the key points"""
         return np.asarray(self._start_frame(plan)[0])
 
     def render(self, plan):

@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, check
-from ._args import OPTIONAL, _Scratch, _ptr, _stream, _workspace, check_tensors, scratch      # noqa: F401 (ops._stream, ops.scratch ... are public)
+from ._args import OPTIONAL, _Scratch, _ptr, _stream, _workspace, check_out, check_tensors, scratch      # noqa: F401 (ops._stream, ops.scratch ... are public)
 from .tool_ops import *      # noqa: F401,F403 -- the forward-only wrappers of the evaluation tools and their constants: ops.sheet_paste, ops.MAX_DRAWS ...
 from .tool_ops import seq_nearest, NEAREST_GROUP, NEAREST_MAX_QUERIES, NEAREST_MAX_WINDOWS      # noqa: F401 -- defined in novelty.py, outside tool_ops.__all__
 from .tool_ops import points_resample, points_speed, RESAMPLE_MODES, RESAMPLE_MAX_POINTS, RESAMPLE_MAX_RATE      # noqa: F401 -- defined in resample.py, likewise
@@ -1656,6 +1656,53 @@ def swap_flat_(a, b):
     if lo + a.numel() * 4 > hi:
         raise _lib.KpxError('swap_flat_: the two ranges overlap')
     check(lib.kpx_swap_flat_f32(a.data_ptr(), b.data_ptr(), a.numel(), _stream()), 'kpx_swap_flat_f32')
+
+
+# ----------------------------------------------------------------------------------------------- resident-frame augmentation (kpx_amd.resident)
+AUG_ROW_INTS, AUG_BAND, AUG_MAX_ROWS = 24, 16, 32768             # KPX_AUG_ROW_INTS, KPX_AUG_BAND, KPX_AUG_MAX_ROWS of include/kpx.h
+AUG_TILE_MIN, AUG_TILE_MAX, AUG_LDS_BYTES = 32, 256, 122880      # KPX_AUG_TILE_MIN, KPX_AUG_TILE_MAX, KPX_AUG_LDS_BYTES
+
+
+def _augment_sizes(what, n_rows, side):
+    if not (isinstance(side, int) and AUG_TILE_MIN <= side <= AUG_TILE_MAX and side % AUG_BAND == 0):
+        raise _lib.KpxError('%s: side = %r, the tile side is a multiple of %d in [%d, %d]' % (what, side, AUG_BAND, AUG_TILE_MIN, AUG_TILE_MAX))
+    if not 0 < n_rows <= AUG_MAX_ROWS:
+        raise _lib.KpxError('%s: n_rows = %r outside 1..%d' % (what, n_rows, AUG_MAX_ROWS))
+
+
+def augment_geometry(frames, frame_off, rows, n_rows, resize_tabs, band_rows_cap, side, tiles=None, lsum=None):
+    """Rotate, resize, crop and flip ``n_rows`` resident frames into uint8 tiles [n_rows, side, side, 3] and their per-band luminance sums
+    int32 [n_rows, side / 16] (kpx_augment_geometry_sq_u8).  ``rows``: DEVICE int32 [>= n_rows, 24], validated by the caller
+    (resident.AugmentPlanner.check_rows): the kernel trusts the table."""
+    what = 'augment_geometry'
+    _augment_sizes(what, n_rows, side)
+    if not (AUG_BAND <= band_rows_cap and band_rows_cap * side * 3 <= AUG_LDS_BYTES):
+        raise _lib.KpxError('%s: band_rows_cap = %r: a band keeps cap * %d * 3 bytes in LDS, between %d rows and %d bytes'
+                            % (what, band_rows_cap, side, AUG_BAND, AUG_LDS_BYTES))
+    dev = check_tensors(what, [('frames', frames, torch.uint8, None, 16), ('frame_off', frame_off, torch.int64, None),
+                               ('rows', rows, torch.int32, (None, AUG_ROW_INTS)), ('resize_tabs', resize_tabs, torch.int32, None)])
+    if rows.shape[0] < n_rows:
+        raise _lib.KpxError('%s: rows holds %d rows, n_rows = %d' % (what, rows.shape[0], n_rows))
+    tiles = check_out(what, 'tiles', tiles, torch.uint8, (n_rows, side, side, 3), dev)
+    lsum = check_out(what, 'lsum', lsum, torch.int32, (n_rows, side // AUG_BAND), dev)
+    check(lib.kpx_augment_geometry_sq_u8(frames.data_ptr(), frame_off.data_ptr(), rows.data_ptr(), n_rows, resize_tabs.data_ptr(),
+                                         band_rows_cap, side, tiles.data_ptr(), lsum.data_ptr(), _stream()), 'kpx_augment_geometry_sq_u8')
+    return tiles, lsum
+
+
+def augment_filter(tiles, lsum, rows, n_rows, kernels, side, out=None):
+    """The row's filter on each tile of ``augment_geometry``, then uint8 -> float32 [-1, 1]: [n_rows, side, side, 3]
+    (kpx_augment_filter_sq_f32).  ``kernels``: resident.filter_kernels() on the device."""
+    what = 'augment_filter'
+    _augment_sizes(what, n_rows, side)
+    dev = check_tensors(what, [('tiles', tiles, torch.uint8, (n_rows, side, side, 3)), ('lsum', lsum, torch.int32, (n_rows, side // AUG_BAND)),
+                               ('rows', rows, torch.int32, (None, AUG_ROW_INTS)), ('kernels', kernels, torch.float32, (6, 32))])
+    if rows.shape[0] < n_rows:
+        raise _lib.KpxError('%s: rows holds %d rows, n_rows = %d' % (what, rows.shape[0], n_rows))
+    out = check_out(what, 'out', out, torch.float32, (n_rows, side, side, 3), dev)
+    check(lib.kpx_augment_filter_sq_f32(tiles.data_ptr(), lsum.data_ptr(), rows.data_ptr(), n_rows, kernels.data_ptr(), side, out.data_ptr(),
+                                        _stream()), 'kpx_augment_filter_sq_f32')
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- rollout (forward only)

@@ -4,6 +4,7 @@
 device buffer and produces each batch with two HIP launches that do what ``ImagePairDataLoader.render`` does with PIL -- byte for byte.
 Per step the host draws the ``PairPlan``s exactly as the CPU pipeline does (same code, same generators) and ships one small integer
 table; no JPEG is decoded, no PIL call is made and no pixels cross PCIe.
+The tile side S is the loader's ``image_size`` (default 128): the tables, the rows' validation and the two launches are built for it.
 
 Everything of Pillow's arithmetic that involves double precision is done HERE, in Python floats, and reaches the kernels as integers:
 
@@ -26,12 +27,13 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 from PIL import Image
 
-from .data import IMAGE_SIZE, _KERNEL_FILTERS, _DeviceBatcher, _resized_size, _to_device_unit
+from .data import IMAGE_SIZE, _KERNEL_FILTERS, _DeviceBatcher, _resized_size, _to_device_unit, check_image_size
 
 # mirrors of include/kpx.h (tests/test_resident_cpu.py holds them equal to the header)
 ROW_INTS, FLIP, ROTATE, IDENTITY = 24, 1, 2, 4
 BAND, BANDS, KERNEL_FLOATS = 16, 8, 32
 MAX_SIDE, MAX_TAPS, MAX_BAND_ROWS, MAX_ROWS = 2048, 32, 160, 32768
+TILE_MIN, TILE_MAX, LDS_BYTES = 32, 256, 122880      # the *_sq_* entries: tile sides, and the LDS one workgroup of the geometry kernel may ask for
 (R_FRAME, R_W, R_H, R_X0, R_Y0, R_FLAGS, R_FILT, R_FVAL, R_A0, R_A1, R_A2, R_A3, R_A4, R_A5,
  R_HTAB, R_HSTRIDE, R_VTAB, R_VSTRIDE, R_RW, R_RH) = range(20)
 ALIGN = 16                         # every frame starts at a multiple of 16 bytes
@@ -124,9 +126,9 @@ def filter_kernels():
     return out
 
 
-def centre_origin(rw):
-    """Left edge of ``render``'s centre crop box (ox - 64, 0, ox + 64, 128): PIL rounds the corners with Python's round (ties to even)."""
-    return int(round(rw / 2.0 - IMAGE_SIZE // 2))
+def centre_origin(rw, image_size=IMAGE_SIZE):
+    """Left edge of ``render``'s centre crop box (ox - S/2, 0, ox + S/2, S): PIL rounds the corners with Python's round (ties to even)."""
+    return int(round(rw / 2.0 - image_size // 2))
 
 
 # ------------------------------------------------------------------------------------------------ the store's bookkeeping (no device)
@@ -232,26 +234,33 @@ class ResizeTables(object):
 
 
 class AugmentPlanner(object):
-    """Table rows (include/kpx.h: kpx_augment_geometry_u8) from ``PairPlan``s or by hand, and their validation.  Host only."""
+    """Table rows (include/kpx.h: kpx_augment_geometry_sq_u8) from ``PairPlan``s or by hand, and their validation, for tiles of
+    ``image_size`` x ``image_size``.  Host only.  ``lds_bytes``: what one workgroup of the geometry kernel may keep in LDS; a video whose
+    band needs more is held in the store but refused by ``check_rows`` when a row asks for it."""
 
-    def __init__(self, index):
+    def __init__(self, index, image_size=IMAGE_SIZE, lds_bytes=LDS_BYTES):
         self.index = index
+        self.image_size = s = check_image_size(image_size, 'image_size')
+        self.bands = s // BAND
+        self.lds_bytes = int(lds_bytes)
         self.tables = ResizeTables()
         self._per_video = []
         self._rot = {}
-        cap = BAND
+        self.band_need = []                          # per video: rows of the horizontally resized frame one band reads
         for v in range(len(index.names)):
             w, h = int(index.width[v]), int(index.height[v])
-            rw, rh, _ = _resized_size(w, h)
-            if rw < IMAGE_SIZE or rh < IMAGE_SIZE:
-                raise _error('%s: %d x %d resizes to %d x %d, smaller than the %d x %d crop' % (index.names[v], w, h, rw, rh, IMAGE_SIZE, IMAGE_SIZE))
+            rw, rh, _ = _resized_size(w, h, s)
+            if rw < s or rh < s:
+                raise _error('%s: %d x %d resizes to %d x %d, smaller than the %d x %d crop' % (index.names[v], w, h, rw, rh, s, s))
             ho, hs, _ = self.tables.add(w, rw)
             vo, vs, need = self.tables.add(h, rh)
             if need > MAX_BAND_ROWS:
                 raise _error('%s: a %d-row band of the %d -> %d resize reads %d rows, the kernels take %d' % (index.names[v], BAND, h, rh, need, MAX_BAND_ROWS))
-            cap = max(cap, need)
+            self.band_need.append(need)
             self._per_video.append((w, h, rw, rh, ho, hs, vo, vs))
-        self.band_rows_cap = cap
+        self.band_need = np.array(self.band_need, np.int64).reshape(-1)
+        fits = self.band_need[self.band_need * s * 3 <= self.lds_bytes]
+        self.band_rows_cap = max([BAND] + fits.tolist())         # the launches' LDS: the largest need among the videos check_rows admits
         self._tab_by_offset = {off: (key, stride) for key, (off, stride, _) in self.tables.entries.items()}
 
     def row(self, video, idx, angle=None, x0=0, y0=0, flip=0, filt=-1, filt_val=None):
@@ -284,7 +293,7 @@ class AugmentPlanner(object):
                 x0, y0 = (p.crop, 0) if w > h else (0, p.crop)
                 kw = dict(angle=p.angle, x0=x0, y0=y0, flip=p.flip, filt=p.filt, filt_val=p.filt_val)
             else:
-                kw = dict(x0=centre_origin(rw))                  # render's else branch: centred on the width, the top 128 rows
+                kw = dict(x0=centre_origin(rw, self.image_size))         # render's else branch: centred on the width, the top S rows
             first.append(self.row(p.video, p.im_idx, **kw))
             second.append(self.row(p.video, p.fu_idx, **kw))
         return np.array(first + second, np.int64).astype(np.int32).reshape(-1, ROW_INTS)
@@ -301,6 +310,12 @@ class AugmentPlanner(object):
         video = np.searchsorted(idx.first, frame, side='right') - 1
         if (rows[:, R_W] != idx.width[video]).any() or (rows[:, R_H] != idx.height[video]).any():
             raise _error("augmentation rows: frame size differs from the store's")
+        over = self.band_need[video] * self.image_size * 3 > self.lds_bytes
+        if over.any():
+            v = int(video[np.argmax(over)])
+            raise _error('augmentation rows: %s: a %d-row band of its %d x %d tile reads %d rows of the resized frame = %d bytes of LDS, a '
+                         'workgroup has %d' % (idx.names[v], BAND, self.image_size, self.image_size, self.band_need[v],
+                                               self.band_need[v] * self.image_size * 3, self.lds_bytes))
         if (rows[:, R_FILT] < -1).any() or (rows[:, R_FILT] > 9).any():
             raise _error('augmentation rows: filter id outside -1..9')
         if (rows[:, R_FLAGS] & ~(FLIP | ROTATE | IDENTITY)).any():
@@ -314,7 +329,7 @@ class AugmentPlanner(object):
                 sel = rows[:, tab] == o
                 if known is None or (rows[sel, stride] != known[1]).any() or (rows[sel, n_in] != known[0][0]).any() or (rows[sel, n_out] != known[0][1]).any():
                     raise _error('augmentation rows: resize table does not belong to the frame size')
-            if (rows[:, origin] < 0).any() or (rows[:, origin] + IMAGE_SIZE > rows[:, n_out]).any():
+            if (rows[:, origin] < 0).any() or (rows[:, origin] + self.image_size > rows[:, n_out]).any():
                 raise _error('augmentation rows: crop window outside the resized frame')
         return rows
 
@@ -326,7 +341,7 @@ class ResidentFrames(AugmentPlanner):
     augmentation kernels.  Each data-parallel rank builds its own."""
     STAGE_BYTES = 64 << 20
 
-    def __init__(self, data_dir, listing, device, max_bytes=DEFAULT_MAX_BYTES, threads=16):
+    def __init__(self, data_dir, listing, device, max_bytes=DEFAULT_MAX_BYTES, threads=16, image_size=IMAGE_SIZE):
         import time
         import torch
         device = torch.device(device)
@@ -334,7 +349,7 @@ class ResidentFrames(AugmentPlanner):
             raise _error('resident frames live in HBM: device %s is not a GPU (the package has no CPU fallback)' % device)
         t0 = time.perf_counter()
         index = FrameIndex.scan(data_dir, listing, max_bytes, threads)        # raises before anything is allocated
-        super(ResidentFrames, self).__init__(index)
+        super(ResidentFrames, self).__init__(index, image_size)
         self.data_dir, self.device = data_dir, device
         with torch.cuda.device(device):
             self.frames = torch.empty(max(index.total_bytes, ALIGN), dtype=torch.uint8, device=device)
@@ -383,22 +398,12 @@ class ResidentFrames(AugmentPlanner):
 
     def augment(self, rows_dev, n_rows, out=None):
         """The two launches on the current stream: rows_dev = DEVICE int32 [>= n_rows, ROW_INTS] (validated by the caller with
-        ``check_rows``) -> float32 [n_rows, 128, 128, 3] in [-1, 1]."""
+        ``check_rows``) -> float32 [n_rows, S, S, 3] in [-1, 1], S = image_size."""
         import torch
-        from ._lib import lib, check
-        s = IMAGE_SIZE
+        from . import ops
         with torch.cuda.device(self.device):
-            tiles = torch.empty((n_rows, s, s, 3), dtype=torch.uint8, device=self.device)
-            lsum = torch.empty((n_rows, BANDS), dtype=torch.int32, device=self.device)
-            if out is None:
-                out = torch.empty((n_rows, s, s, 3), dtype=torch.float32, device=self.device)
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            check(lib.kpx_augment_geometry_u8(self.frames.data_ptr(), self.frame_off.data_ptr(), rows_dev.data_ptr(), n_rows,
-                                              self.resize_tabs.data_ptr(), self.band_rows_cap, tiles.data_ptr(), lsum.data_ptr(), stream),
-                  'kpx_augment_geometry_u8')
-            check(lib.kpx_augment_filter_f32(tiles.data_ptr(), lsum.data_ptr(), rows_dev.data_ptr(), n_rows, self.kernels.data_ptr(),
-                                             out.data_ptr(), stream), 'kpx_augment_filter_f32')
-        return out
+            tiles, lsum = ops.augment_geometry(self.frames, self.frame_off, rows_dev, n_rows, self.resize_tabs, self.band_rows_cap, self.image_size)
+            return ops.augment_filter(tiles, lsum, rows_dev, n_rows, self.kernels, self.image_size, out=out)
 
     def augment_rows(self, rows):
         """Host rows (``row`` / ``rows_for_plans``) -> the augmented frames: validation, upload, the two launches."""
@@ -409,7 +414,7 @@ class ResidentFrames(AugmentPlanner):
 
 
 class ResidentBatcher(object):
-    """``batches(..., resident=True)``: the iterator contract of ``_DeviceBatcher`` ({'image', 'future_image'} float32 [B,128,128,3] on
+    """``batches(..., resident=True)``: the iterator contract of ``_DeviceBatcher`` ({'image', 'future_image'} float32 [B,S,S,3] on
     the device; repeat / shuffle; a short last batch) on a ``ResidentFrames`` store.  The plans come from the SAME ``_plan_stream``, so
     both iterators consume ``rng`` / ``np_rng`` identically.  Per batch one pinned int32 table goes to the device asynchronously and the
     two augmentation launches are enqueued on the consumer's stream; the host never waits for the device."""
@@ -454,7 +459,8 @@ class ResidentBatcher(object):
             rows_dev = host.to(self.device, non_blocking=True)
             self.copied[slot] = torch.cuda.Event()
             self.copied[slot].record()
-            both = self.store.augment(rows_dev, 2 * n).view(2, n, IMAGE_SIZE, IMAGE_SIZE, 3)
+            s = self.store.image_size
+            both = self.store.augment(rows_dev, 2 * n).view(2, n, s, s, 3)
         return {'image': both[0], 'future_image': both[1]}
 
 
@@ -669,7 +675,7 @@ class ResidentSeqBatcher(object):
         return out
 
     def start_images(self, n):
-        """float32 [n, 128, 128, 3] in [-1, 1] on the device: the start frames of the first ``n`` samples of the batch most recently
+        """float32 [n, S, S, 3] in [-1, 1] on the device: the start frames of the first ``n`` samples of the batch most recently
         yielded, rendered on the host by the PIL code of ``render`` (what the host feed's 'image' holds for those samples)."""
         plans = self._last[:n]
         if not plans:

@@ -13,7 +13,7 @@ import os.path as osp
 import numpy as np
 
 from . import ops
-from .data import IMAGE_SIZE, N_SEQUENCE_LEN, center_crop_box
+from .data import IMAGE_SIZE, N_SEQUENCE_LEN, center_crop_box, check_image_size
 
 IMAGE_EXTS = ('.jpg', '.jpeg', '.png', '.bmp')
 HIST_MAX_PIXELS = ops.HIST_MAX_PIXELS          # pixels of one GIF: what the uint32 sums of kpx_color_hist_add_u32 hold
@@ -88,28 +88,29 @@ def decode(path):
         return ImageOps.exif_transpose(im).convert('RGB')
 
 
-def fit_image(image, box=None, what='--box'):
-    """upright RGB PIL image -> (uint8 [128,128,3], {'decoded_size', 'box', 'resized_size', 'crop_box'}): the optional crop, then the
-    sequence loader's start-frame arithmetic without randomness"""
+def fit_image(image, box=None, what='--box', image_size=IMAGE_SIZE):
+    """upright RGB PIL image -> (uint8 [S,S,3], {'decoded_size', 'box', 'resized_size', 'crop_box'}), S = image_size: the optional crop,
+    then the sequence loader's start-frame arithmetic without randomness"""
+    image_size = check_image_size(image_size, 'image_size')
     decoded = list(image.size)
     if box is not None:
         check_box(box, image.size[0], image.size[1], what)
         image = image.crop(tuple(box))
     w, h = image.size
-    crop, ratio = center_crop_box(w, h)
+    crop, ratio = center_crop_box(w, h, image_size)
     size = [int(w / ratio), int(h / ratio)]
     out = np.asarray(image.resize(size).crop(crop))
-    assert out.shape == (IMAGE_SIZE, IMAGE_SIZE, 3) and out.dtype == np.uint8
+    assert out.shape == (image_size, image_size, 3) and out.dtype == np.uint8
     return out, {'decoded_size': decoded, 'box': None if box is None else list(box), 'resized_size': size, 'crop_box': list(crop)}
 
 
-def fit(path, box=None, what='--box'):
-    """an image file -> (uint8 [128,128,3], its record for animate.json)"""
+def fit(path, box=None, what='--box', image_size=IMAGE_SIZE):
+    """an image file -> (uint8 [S,S,3], its record for animate.json), S = image_size"""
     try:
         image = decode(path)
     except (OSError, SyntaxError, ValueError) as e:
         raise StillsError('%s cannot be decoded as an image (%s)' % (path, e))
-    u8, info = fit_image(image, box, what='%s of %s' % (what, path))
+    u8, info = fit_image(image, box, what='%s of %s' % (what, path), image_size=image_size)
     return u8, dict(info, source=path)
 
 
