@@ -133,6 +133,18 @@
 29. The rollout of configs[4] (B = 64, replayed HIP graphs) in one process, alternated: frames = 96 beside three 32-frame rollouts, and
    frames = 32, rate = 4 beside four 32-frame rollouts; median ms of each and the quotient.
 
+``--prdc`` measures precision / recall / density / coverage (evaluate.py --prdc) instead:
+
+30. ``ops.prdc`` (four calls of kpx_set_neighbours_f64, two launches each) on a synthetic store of Penn's test-set size -- n = 1 024 real rows,
+   m = 4 096 generated rows (four draws), k = 5, clustered rows of D = 2 560 (key-point space at K = 40) and D = 256 (the recogniser's features)
+   -- device-event time of the whole call and of each of its four searches after warm-up, min / median / max ms, and the fp64 fmas per second of
+   one fma per value, query and reference (the subtractions are not counted).  Beside it, in the same process: (a) a device copy of the rows;
+   (b) the route this replaces on the same device: ``torch.cdist`` in fp64 + ``topk`` + comparisons, once in cdist's default mode (which forms
+   |a|^2 + |b|^2 - 2ab on the matrix pipe at these sizes) and once with ``donot_use_mm_for_euclid_dist`` (direct differences); whether the four
+   scores of each route equal the kernel's is reported, not asserted.
+31. The rollout of configs[4] (B = 64, replayed HIP graph) at n_pts = 40 without and with what --prdc adds per batch and draw (the float32 copy
+   of the draw's key points; the scores are computed once, after the last batch: item 30), alternated; median ms of each and the difference.
+
 Prints one JSON line.
 """
 import argparse
@@ -1422,6 +1434,105 @@ def novelty_rollout_leg(dev, rollouts, store):
             'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
 
 
+PRDC_REAL, PRDC_FAKE, PRDC_K, PRDC_DIMS = 1024, 4096, 5, (2560, 256)
+
+
+def _prdc_rows(dev, n, m, d, seed):
+    """clustered rows (a 2-d latent of four unit Gaussians through a random map, plus noise), float32 values held in fp64: real rows from
+    three of the centres, generated rows from three, two shared"""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    centres = torch.tensor([[0.0, 0.0], [6.0, 0.0], [0.0, 6.0], [6.0, 6.0]], device=dev)
+    proj = torch.randn((2, d), generator=g, device=dev) / 2 ** 0.5
+
+    def draw(count, allowed):
+        c = torch.tensor(allowed, device=dev)[torch.randint(0, len(allowed), (count,), generator=g, device=dev)]
+        z = centres[c] + torch.randn((count, 2), generator=g, device=dev)
+        return (z @ proj + 0.01 * torch.randn((count, d), generator=g, device=dev)).float().double().contiguous()
+    return draw(n, (0, 1, 2)), draw(m, (0, 1, 3))
+
+
+def _prdc_torch_route(real, fake, k, mode):
+    """The four scores by the route the kernel replaces: torch.cdist in fp64, topk, comparisons (distances, not squares: the same order)"""
+    def cdist(a, b):                                      # 1 024 rows a call: the direct mode's launch takes fewer than 2^24 pairs
+        return torch.cat([torch.cdist(a[lo:lo + 1024], b, compute_mode=mode) for lo in range(0, a.shape[0], 1024)])
+
+    def radius(x):
+        d = cdist(x, x)
+        d.fill_diagonal_(float('inf'))
+        return d.topk(k, dim=1, largest=False).values[:, k - 1]
+    rr, fr = radius(real), radius(fake)
+    d = cdist(fake, real)                                                            # [m, n]
+    fake_inside = (d <= rr[None, :]).sum(dim=1)
+    real_inside = (d <= fr[:, None]).sum(dim=0)
+    return {'precision': (fake_inside > 0).double().mean(), 'recall': (real_inside > 0).double().mean(),
+            'density': fake_inside.sum().double() / torch.tensor(float(k * fake.shape[0]), dtype=torch.float64, device=d.device),   # a tensor: a true division, not a multiplication by 1 / (k m)
+            'coverage': (d.min(dim=0).values <= rr).double().mean()}
+
+
+def prdc_kernel_leg(dev, launches):
+    from kpx_amd import ops
+    spread = lambda ms: {'median_ms': round(statistics.median(ms), 3), 'min_ms': round(min(ms), 3), 'max_ms': round(max(ms), 3)}
+    n, m, k = PRDC_REAL, PRDC_FAKE, PRDC_K
+    res = {'n_real': n, 'n_fake': m, 'k': k}
+    for d in PRDC_DIMS:
+        real, fake = _prdc_rows(dev, n, m, d, 17 + d)
+        copy_r, copy_f = torch.empty_like(real), torch.empty_like(fake)
+        us = _event_times(lambda: (copy_r.copy_(real), copy_f.copy_(fake)), launches, dev)
+        entry = {'dim': d, 'rows_mb': round((n + m) * d * 8 / 1e6, 1),
+                 'device_copy_of_rows': dict(spread([v / 1e3 for v in us]), launches=launches,
+                                             gb_per_s=round(2 * (n + m) * d * 8 / (statistics.median(us) * 1e-6) / 1e9, 1))}
+        ms = [v / 1e3 for v in _event_times(lambda: ops.prdc(real, fake, k), launches, dev)]
+        fmas = float(d) * (n * n + m * m + 2 * n * m)
+        entry['prdc'] = dict(spread(ms), launches=launches, fp64_tfma_per_s=round(fmas / (statistics.median(ms) * 1e-3) / 1e12, 2))
+        got = ops.prdc(real, fake, k)
+        skip_r, skip_f = (torch.arange(c, dtype=torch.int32, device=dev) for c in (n, m))
+        searches = (('real_radii', real, real, k, skip_r, None), ('fake_radii', fake, fake, k, skip_f, None),
+                    ('fake_in_real_balls', fake, real, 1, None, got['real_radius2']), ('real_in_fake_balls', real, fake, 1, None, got['fake_radius2']))
+        entry['searches'] = {}
+        for name, q, r, kk, skip, rad in searches:
+            one = [v / 1e3 for v in _event_times(lambda: ops.set_neighbours(q, r, kk, q_skip=skip, r_radius2=rad), launches, dev)]
+            pairs = float(d) * q.shape[0] * r.shape[0]
+            entry['searches'][name] = dict(spread(one), queries=q.shape[0], refs=r.shape[0], k=kk,
+                                           fp64_tfma_per_s=round(pairs / (statistics.median(one) * 1e-3) / 1e12, 2))
+        scores = {s: float(got[s]) for s in ('precision', 'recall', 'density', 'coverage')}
+        entry['scores'] = scores
+        for label, mode in (('torch_cdist_default', 'use_mm_for_euclid_dist_if_necessary'), ('torch_cdist_direct', 'donot_use_mm_for_euclid_dist')):
+            tms = [v / 1e3 for v in _event_times(lambda: _prdc_torch_route(real, fake, k, mode), max(3, launches // 4), dev)]
+            ref = {s: float(v) for s, v in _prdc_torch_route(real, fake, k, mode).items()}
+            entry[label] = dict(spread(tms), launches=max(3, launches // 4), scores_equal_kernel=ref == scores, scores=ref,
+                                kernel_over_torch=round(statistics.median(ms) / statistics.median(tms), 2))
+        res['d%d' % d] = entry
+    return res
+
+
+def prdc_rollout_leg(dev, rollouts):
+    import kpx_amd
+    cfg = {'model': {'n_pts': NOVELTY_K, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    feed = {'image': im, 'action_code': act}
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256)
+    fm.build()
+    for _ in range(3):                                    # eager, capture, one replay
+        o = fm.run(None, feed, z=z)
+    torch.cuda.synchronize(dev)
+    ms, kept = {False: [], True: []}, []
+    for _ in range(rollouts):
+        for on in (False, True):
+            t0 = time.perf_counter()
+            o = fm.run(None, feed, z=z)
+            if on:                                        # evaluate._Prdc._rows: the draw's key points as float32 rows, kept until the end
+                kept.append(o['fut_pt_raw'].reshape(B, -1).to(torch.float32).clone())
+            torch.cuda.synchronize(dev)
+            ms[on].append((time.perf_counter() - t0) * 1e3)
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    return {'batch': B, 'n_points': NOVELTY_K, 'row_values': int(kept[0].shape[1]), 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 1,
+            'off_ms': round(off, 3), 'on_ms': round(on, 3), 'delta_ms': round(on - off, 3), 'overhead_pct': round(100 * (on - off) / off, 2),
+            'off_ms_all': [round(v, 2) for v in ms[False]], 'on_ms_all': [round(v, 2) for v in ms[True]]}
+
+
 def long_kernel_leg(dev, launches):
     from kpx_amd import ops
     g = torch.Generator(device=dev).manual_seed(9)
@@ -1511,7 +1622,18 @@ def main():
     ap.add_argument('--long', action='store_true',
                     help='measure the longer and smoother rollouts (the resample and speed launches beside a device copy, a 96-frame rollout beside '
                          'three 32-frame ones and a rate-4 rollout beside four, all in this process) instead')
+    ap.add_argument('--prdc', action='store_true',
+                    help='measure precision / recall / density / coverage (ops.prdc and its four searches at Penn\'s test-set size beside a device '
+                         'copy and the torch.cdist fp64 route, the cost of --prdc per configs[4] rollout, all in this process) instead')
     args = ap.parse_args()
+    if args.prdc:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        kernels = prdc_kernel_leg(dev, args.launches)
+        torch.cuda.empty_cache()
+        print(json.dumps({'prdc_kernels': kernels, 'prdc_rollout_c4': prdc_rollout_leg(dev, args.rollouts)}))
+        return
     if args.long:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

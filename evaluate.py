@@ -9,6 +9,7 @@
                        [--metrics --action-accuracy CKPT]
                        [--gif [--gif-fps N] [--gif-dither A] [--frames N] [--rate F [--resample linear|cubic]]]
                        [--metrics --novelty [--novelty-sheets] [--novelty-no-mirror]]
+                       [--metrics --prdc [--prdc-k K]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -116,6 +117,21 @@ class.  ``--novelty-sheets`` (at most 31 ``--samples``; not with ``--no-save``) 
 then per draw the rollout and under it its nearest training window (``MotionStore.gather``), as colourised key points at the
 ``--sheet-frames`` frames.  This is the project's own key-point-space quantity, not comparable with published figures.  Without the flags
 every output keeps its bytes.
+
+``--prdc`` (with ``--metrics``; data path only; ``--prdc-k K``, 1..8, default 5) separates the two ways a class-conditional generator fails
+-- collapsing to a few clean modes, or covering every mode and inventing motions beside them -- with the k-nearest-neighbour manifold
+estimates of the literature: precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020).  The rows stay on
+the device as float32 until the last batch -- in key-point space the 32 K 2 future key points (the pseudo labels of the real frames against
+the rollouts), with ``--action-accuracy`` also the recogniser's features (its own classify calls are reused) -- are converted to fp64 once
+and scored once by ``kpx_amd.ops.prdc``: four launches of the exact fp64 all-pairs search ``kpx_amd.ops.set_neighbours`` per comparison.
+Comparisons per space: ``draw0`` (draw 0 against the real rows, equal set sizes: the headline), ``all_draws``, ``ceiling`` (the even real
+samples as generated rows against the odd ones), each again ``_per_class`` (neighbours and balls inside the sample's own class) and with
+``--actions`` ``commanded_<a>`` (the draw-0 rollouts under class a against the real rows of class a).  metrics.npz gains the ``prdc_*``
+arrays (per comparison the four scores, the set sizes, every row's squared radius, inside count and nearest generated row), metrics.json a
+``prdc`` block (``kpx_amd.prdc.summarise``, with ``k``, the set sizes and a definition), and ``<save_dir>/prdc.npz`` keeps the rows, classes
+and parities, which ``python -m kpx_amd.prdc prdc.npz [--k K]`` re-scores on the CPU.  These are the project's own key-point-space and
+recogniser-space quantities, not comparable with published figures; precision and recall are unstable for unequal set sizes.  Without the
+flag every output keeps its bytes.
 """
 import json
 import os
@@ -409,6 +425,7 @@ class _ActionAccuracy:
                                'outer': torch.zeros((u, u), dtype=torch.float64, device=dev)} for name in self.SETS}
         self.own, self.real, self.pred, self.act = [], [], [], []
         self.n_scored = 0
+        self.on_feats = None                         # --prdc: called with (kind, draw, class index, fp32 features) of every classify call made here
 
     def _add(self, name, rows):
         if rows.shape[0]:
@@ -423,6 +440,8 @@ class _ActionAccuracy:
         self.own.append(self.target)
         logits, feats = self.model.classify(batch['real_seq'])
         self.real.append(self.ops.class_scores(logits, self.target, self.confusion['real'], check_target=False))
+        if self.on_feats is not None:
+            self.on_feats('real', None, None, feats)
         feats = feats.double()
         first = self.n_scored % 2                    # the parity of this batch's first sample among all samples
         self._add('real_even', feats[first::2])
@@ -437,6 +456,8 @@ class _ActionAccuracy:
         """One draw of the batch's own rollout, enqueued before the next run() replays the graph over ``fut_pt_raw``."""
         logits, feats = self.model.classify(fut_pt_raw)
         self.ops.class_scores(logits, self.target, self.confusion['pred'], out=tuple(t[draw] for t in self.pred[-1]), check_target=False)
+        if self.on_feats is not None:
+            self.on_feats('fake', draw, None, feats)
         feats = feats.double()
         self._add('pred', feats)
         if draw == 0:
@@ -444,7 +465,9 @@ class _ActionAccuracy:
 
     def class_rollout(self, draw, a, fut_pt_raw):
         """The rollout under the listed class ``a`` at this draw's z, against the class that was commanded."""
-        logits, _ = self.model.classify(fut_pt_raw)
+        logits, feats = self.model.classify(fut_pt_raw)
+        if self.on_feats is not None:
+            self.on_feats('commanded', draw, a, feats)
         target = self.commanded[a].expand(logits.shape[0]).contiguous()
         self.ops.class_scores(logits, target, self.confusion['commanded'], out=tuple(t[draw, a] for t in self.act[-1]), check_target=False)
 
@@ -620,6 +643,66 @@ class _Novelty:
             out['act_nov_d'] = np.ascontiguousarray(np.sqrt(low[1 + d:]).reshape(d, c, s).transpose(2, 1, 0))
             out['act_nov_code'] = np.ascontiguousarray(best[1 + d:].reshape(d, c, s).transpose(2, 1, 0))
         return out
+
+
+class _Prdc:
+    """--prdc: the real and the generated rows of the run in key-point space and, with --action-accuracy, in the recogniser's feature space
+    (its classify calls are reused through ``_ActionAccuracy.on_feats``); float32 on the device until the end, scored once."""
+
+    def __init__(self, kpx_amd, dev, samples, actions, k, accuracy):
+        self.P, self.dev, self.samples, self.actions, self.k = kpx_amd.prdc, dev, samples, actions or [], k
+        self.spaces = ['kp'] + (['cls'] if accuracy is not None else [])
+        self.real = {sp: [] for sp in self.spaces}
+        self.fake = {sp: [[] for _ in range(samples)] for sp in self.spaces}
+        self.commanded = {sp: [[] for _ in self.actions] for sp in self.spaces}
+        self.own = []
+        if accuracy is not None:
+            accuracy.on_feats = self._feats
+
+    @staticmethod
+    def _rows(t):
+        return t.reshape(t.shape[0], -1).to(torch.float32).clone()        # a copy: the rollout's buffers are overwritten by the next replay
+
+    def _add(self, sp, kind, draw, a, t):
+        if kind == 'real':
+            self.real[sp].append(self._rows(t))
+        elif kind == 'fake':
+            self.fake[sp][draw].append(self._rows(t))
+        elif draw == 0:                              # commanded: the draw-0 rollouts under the listed class a
+            self.commanded[sp][a].append(self._rows(t))
+
+    def _feats(self, kind, draw, a, feats):
+        self._add('cls', kind, draw, a, feats)
+
+    def begin_batch(self, batch):
+        self._add('kp', 'real', None, None, batch['real_seq'])
+        self.own.append(batch['action_code'].argmax(dim=1).to(torch.int32))
+
+    def own_draw(self, draw, fut_pt_raw):
+        self._add('kp', 'fake', draw, None, fut_pt_raw)
+
+    def class_rollout(self, draw, a, fut_pt_raw):
+        self._add('kp', 'commanded', draw, a, fut_pt_raw)
+
+    def arrays(self, save_dir):
+        """-> the prdc_* arrays of metrics.npz; writes <save_dir>/prdc.npz (the rows as the float32 they were born as, classes, parities)"""
+        if not self.own:
+            return {'prdc_k': np.int32(self.k)}
+        own = torch.cat(self.own)
+        rows = {'own': own, 'parity': (torch.arange(own.shape[0], device=self.dev) % 2).to(torch.int32)}
+        for sp in self.spaces:
+            rows[sp + '_real'] = torch.cat(self.real[sp])
+            rows[sp + '_fake'] = torch.stack([torch.cat(per_draw) for per_draw in self.fake[sp]])
+            if self.actions:
+                rows[sp + '_commanded'] = torch.stack([torch.cat(per_class) for per_class in self.commanded[sp]])
+        stored = {key: v.cpu().numpy() for key, v in rows.items()}
+        stored['k'] = np.int32(self.k)
+        store = {key: v.double() if v.dtype == torch.float32 else v for key, v in rows.items()}       # to fp64 once
+        if self.actions:
+            stored['actions'] = store['actions'] = np.asarray(self.actions, np.int32)
+        os.makedirs(save_dir, exist_ok=True)
+        np.savez(osp.join(save_dir, 'prdc.npz'), **stored)
+        return self.P.score_store(store, self.k, self.P.prdc)
 
 
 DRIVE_MODES = ('labels', 'hold', 'transfer')                                      # the order of the runs and of the sheet's rows
@@ -878,7 +961,7 @@ def _drive_line(blk):
 
 
 def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None,
-                   frechet=None, accuracy=None, novelty=None):
+                   frechet=None, accuracy=None, novelty=None, prdc=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
@@ -887,7 +970,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     two or more classes {'kp_div', 'div_mse': per batch [draws, B, T]}.
     drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}.
     frechet (--frechet): the accumulators {'real_even', 'real_odd', 'pred', 'pred_draw0'}; also writes frechet.npz.
-    accuracy (--action-accuracy): the _ActionAccuracy of the run.  novelty (--novelty): the _Novelty of the run."""
+    accuracy (--action-accuracy): the _ActionAccuracy of the run.  novelty (--novelty): the _Novelty of the run.  prdc (--prdc): the _Prdc
+    of the run; also writes prdc.npz."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -945,6 +1029,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         if act is None and novelty.actions:
             arrays['actions'] = np.asarray(novelty.actions, np.int32)
         arrays.update(novelty.arrays())
+    if prdc is not None:
+        arrays.update(prdc.arrays(save_dir))
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
@@ -960,6 +1046,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     if novelty is not None:
         res['definition'] += ' ' + NOVELTY_DEFINITION
         res['novelty'] = summarise_novelty(arrays, mirror=novelty.mirror)
+    if prdc is not None:
+        res['prdc'] = prdc.P.summarise(arrays)
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
@@ -995,6 +1083,11 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
                  'copied %s, nn top-1 real %s, predicted %s'
                  % (fmt(blk['pred']['median'], '%.4f'), fmt(blk['real']['median'], '%.4f'), fmt(blk['ratio'], '%.3f'), fmt(blk['copied'], '%.3f'),
                     fmt(blk['nn_top1']['real'], '%.4f'), fmt(blk['nn_top1']['pred'], '%.4f')))
+    if prdc is not None and 'draw0' in res['prdc'].get('kp', {}):
+        blk = res['prdc']['kp']['draw0']
+        line += (', key-point-space manifold scores at k = %d (own quantity, not comparable with published figures) precision %s, recall %s, '
+                 'density %s, coverage %s' % (res['prdc']['k'], fmt(blk['precision'], '%.4f'), fmt(blk['recall'], '%.4f'),
+                                              fmt(blk['density'], '%.4f'), fmt(blk['coverage'], '%.4f')))
     print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
     if drive is not None:
         print(_drive_line(res['drive']))
@@ -1108,6 +1201,12 @@ def main(argv=None):
     parser.add_argument('--novelty-sheets', action='store_true',
                         help='with --novelty: per sample nearest.png, every rollout above its nearest training window (--sheet-frames picks the frames)')
     parser.add_argument('--novelty-no-mirror', action='store_true', help='with --novelty: do not search the mirror images of the training motions')
+    parser.add_argument('--prdc', action='store_true',
+                        help='with --metrics: precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020) of the '
+                             'rollouts against the real motions, from exact fp64 nearest-neighbour searches in HIP, in key-point space and with '
+                             "--action-accuracy in the recogniser's feature space; <save_dir>/prdc.npz keeps the rows.  This project's own "
+                             'quantities: not comparable with published figures')
+    parser.add_argument('--prdc-k', type=int, default=None, metavar='K', help='with --prdc: the neighbour that sets a ball\'s radius, 1..8 (default 5)')
     parser.add_argument('--frames', type=int, default=None,
                         help='with --gif: a second rollout per batch chained to this many predicted frames (a multiple of 32, default 32): '
                              'per sample long.gif and long_points.npy, <save_dir>/long.json with the speed curve and the seam ratio')
@@ -1146,6 +1245,17 @@ def main(argv=None):
         parser.error('--novelty-sheets writes files, and --no-save writes none')
     if args.novelty_sheets and args.samples > 31:
         parser.error('--novelty-sheets draws two rows per draw and holds at most 31 --samples (got %d)' % args.samples)
+    if args.prdc_k is not None and not args.prdc:
+        parser.error('--prdc-k sets the neighbour count of --prdc and needs it')
+    if args.prdc and args.synthetic:
+        parser.error('--prdc compares the rollouts of real videos with their pseudo labels, and --synthetic inputs have neither')
+    if args.prdc and not args.metrics:
+        parser.error('--prdc adds to the scores of --metrics and needs it')
+    if args.prdc and args.drive_only:
+        parser.error("--drive-only skips the model's own rollout, which --prdc is about")
+    prdc_k = 5 if args.prdc_k is None else args.prdc_k
+    if not 1 <= prdc_k <= 8:
+        parser.error('--prdc-k takes 1..8 neighbours (got %d)' % prdc_k)
     if (args.gif_fps is not None or args.gif_dither is not None) and not args.gif:
         parser.error('--gif-fps and --gif-dither shape the files of --gif and need it')
     if args.gif and args.no_save:
@@ -1273,6 +1383,7 @@ def main(argv=None):
         if args.novelty:
             novelty = _Novelty(kpx_amd, config, dev, args.samples, actions, not args.novelty_no_mirror,
                                sheet_frames if args.novelty_sheets else None, model.colors)
+        prdc = _Prdc(kpx_amd, dev, args.samples, actions, prdc_k, accuracy) if args.prdc else None
         n_read = 0                                                       # samples read so far: the listing line of a batch's first sample
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
@@ -1323,13 +1434,15 @@ def main(argv=None):
                     accuracy.begin_batch(batch)
                 if novelty is not None:
                     novelty.begin_batch([line.split()[0] for line in loader._images[n_read - bsz:n_read]], batch)
+                if prdc is not None:
+                    prdc.begin_batch(batch)
             sweep = None
             if actions:
                 sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, batch['image'], batch['real_im_seq'], not args.no_save,
                                     args.samples, batch['real_seq'].contiguous() if args.metrics else None, dev)
                 if args.metrics:
                     action_scores['own'].append(batch['action_code'].clone())
-                hooks = [h.class_rollout for h in (accuracy, novelty) if h is not None]
+                hooks = [h.class_rollout for h in (accuracy, novelty, prdc) if h is not None]
                 if hooks:
                     sweep.on_class = hooks[0] if len(hooks) == 1 else lambda *a: [h(*a) for h in hooks]
             for draw in range(args.samples):
@@ -1352,6 +1465,8 @@ def main(argv=None):
                         accuracy.own_draw(draw, outputs['fut_pt_raw'])
                     if novelty is not None:
                         novelty.own_draw(draw, outputs['fut_pt_raw'])
+                    if prdc is not None:
+                        prdc.own_draw(draw, outputs['fut_pt_raw'])
                     if args.motion_metrics:
                         kpx_amd.ops.flat_copy_tensor(outputs['fut_pt_raw'].contiguous(), kp_pred[draw].data_ptr())
                         if args.samples >= 2:
@@ -1422,7 +1537,7 @@ def main(argv=None):
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
             _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores, frechet,
-                           accuracy, novelty)
+                           accuracy, novelty, prdc)
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

@@ -1003,6 +1003,37 @@ int kpx_seq_nearest_f32(const float* labels, const int64_t* label_off, const int
                         const int32_t* exclude /*[Q] or NULL*/, int Q, int n_points, int n_action, int mirror, void* workspace,
                         size_t workspace_bytes, double* d2 /*[Q,A]*/, int32_t* code /*[Q,A]*/, void* stream);
 
+/* ---- k nearest rows of a set, exact in fp64 (csrc/prdc.hip; evaluate.py --prdc, kpx_amd/prdc.py), DESIGN.md sections 2 and 4.4.  No reference
+ * counterpart.  Added without a version change: no existing signature moves.
+ *
+ *   q           double [M][D], the queries; r double [N][D], the references; both dense
+ *   q_group, r_group   int32 [M] / [N], both or neither: a pair is eligible only when q_group[j] == r_group[i]
+ *   q_skip      int32 [M] or NULL: reference q_skip[j] is not eligible for query j (-1: none)
+ *   r_radius2   double [N] or NULL; inside int32 [M], required exactly when r_radius2 is given
+ *   nn_d2       double [M][k], nn_idx int32 [M][k]
+ *
+ * d2(j, i) = sum_d (q[j,d] - r[i,d])^2 in fp64, the direct form: lane l of one wavefront takes d = l, l + 64, ... in ascending order with
+ * e = q - r, s = fma(e, e, s) from s = 0, and the 64 lane sums are added in the xor butterfly 32, 16, 8, 4, 2, 1; no division.  The bits of
+ * d2(j, i) depend on the two rows and on D alone: not on j, i, M, N or the grid.  A pair is eligible when d2 is finite, i != q_skip[j] and
+ * the groups are absent or equal.  nn_d2[j] / nn_idx[j] hold the k lexicographically lowest (d2, i) of the eligible pairs in ascending order,
+ * +inf / -1 in the places that stay empty, so ties go to the lowest index whatever the order of arrival and a row with a NaN is never chosen.
+ * inside[j] = the number of eligible i with r_radius2[i] finite and d2(j, i) <= r_radius2[i].
+ * Two launches on `stream`, no atomics: per block of KPX_SET_BLOCK references and query one sorted k-list and one count go into `workspace`,
+ * then one thread per query merges the blocks in ascending order (the counts are integer sums).  workspace:
+ * kpx_set_neighbours_workspace_bytes(M, N, k) bytes (0 for sizes out of range), 8-byte aligned.  Capturable.
+ * Limits: 1 <= M <= KPX_SET_MAX_QUERIES, 1 <= N <= KPX_SET_MAX_REFS, 1 <= D <= KPX_SET_MAX_DIM, 1 <= k <= KPX_SET_MAX_K; q, r, r_radius2,
+ * workspace and nn_d2 8-byte aligned, the int32 arrays 4-byte.  Anything else is KPX_EINVAL before any device call. */
+#define KPX_SET_MAX_K 8
+#define KPX_SET_MAX_DIM 16384
+#define KPX_SET_MAX_QUERIES 4096
+#define KPX_SET_MAX_REFS (1 << 20)
+#define KPX_SET_BLOCK 64
+size_t kpx_set_neighbours_workspace_bytes(int M, int N, int k);
+int kpx_set_neighbours_f64(const double* q /*[M,D]*/, int M, const double* r /*[N,D]*/, int N, int D, const int32_t* q_group /*[M] or NULL*/,
+                           const int32_t* r_group /*[N] or NULL*/, const int32_t* q_skip /*[M] or NULL*/, const double* r_radius2 /*[N] or NULL*/,
+                           int k, void* workspace, size_t workspace_bytes, double* nn_d2 /*[M,k]*/, int32_t* nn_idx /*[M,k]*/,
+                           int32_t* inside /*[M] or NULL*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

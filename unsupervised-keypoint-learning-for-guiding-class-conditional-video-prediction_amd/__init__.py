@@ -20,6 +20,7 @@ from . import gif  # noqa: F401
 from . import stills  # noqa: F401
 from . import novelty  # noqa: F401
 from . import resample  # noqa: F401
+from . import prdc  # noqa: F401
 from .data import ImagePairDataLoader, KeypointDataLoader, SequenceDataLoader  # noqa: F401
 
 __all__ = ['BaseModel', 'DetectorTranslatorModel', 'KeypointModel', 'FinalModel', 'MotionGeneratorModel', 'ActionClassifierModel', 'Vgg19', 'FeatureScorer', 'synthetic_vgg19_weights', 'ImagePairDataLoader', 'KeypointDataLoader', 'SequenceDataLoader', 'data', 'resident', 'frechet', 'stability', 'joints', 'layers', 'model_utils',

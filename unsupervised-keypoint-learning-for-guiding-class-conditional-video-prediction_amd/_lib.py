@@ -173,6 +173,8 @@ SIGNATURES = {
     'kpx_keypoint_seq_augment_f32': (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P, P]),
     'kpx_seq_nearest_workspace_bytes': (c_size_t, [c_int, c_int]),
     'kpx_seq_nearest_f32': (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, c_int, c_int, c_int, P, c_size_t, P, P, P]),
+    'kpx_set_neighbours_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'kpx_set_neighbours_f64': (c_int, [P, c_int, P, c_int, c_int, P, P, P, P, c_int, P, c_size_t, P, P, P, P]),
     'kpx_points_resample_f32': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P, P]),
     'kpx_points_speed_f64': (c_int, [P, P, c_int, c_int, c_int, c_double, P, P]),
     'kpx_softmax_xent_fwd_f32': (c_int, [P, P, c_int, c_int, P, P, P]),

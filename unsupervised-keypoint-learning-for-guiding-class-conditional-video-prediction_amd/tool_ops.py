@@ -3,7 +3,7 @@ and the summaries.  None of them runs inside a train step; each is called once p
 ``_args`` (one list of (name, tensor, dtype, shape) per op) and only what is specific to the op -- value ranges, mode rules, table
 read-backs -- is written out.  ``ops`` re-exports every name here: ``ops.sheet_paste``, ``ops.MAX_DRAWS`` ... are the public names.  ``seq_nearest`` (evaluate.py --novelty)
 is written beside its tables in ``novelty`` and reaches ``tool_ops`` and ``ops`` by the import at the end of each; so do ``points_resample``
-and ``points_speed`` of ``resample``.
+and ``points_speed`` of ``resample`` and ``set_neighbours`` and ``prdc`` of ``prdc`` (evaluate.py --prdc).
 """
 import numpy as np
 import torch
@@ -598,3 +598,6 @@ from .novelty import seq_nearest, NEAREST_GROUP, NEAREST_MAX_QUERIES, NEAREST_MA
 
 # ----------------------------------------------------------------------------------------------- key-point resampling in time
 from .resample import points_resample, points_speed, RESAMPLE_MODES, RESAMPLE_MAX_POINTS, RESAMPLE_MAX_RATE      # noqa: E402,F401
+
+# ----------------------------------------------------------------------------------------------- k nearest rows of a set; precision / recall / density / coverage
+from .prdc import set_neighbours, prdc, SET_MAX_K, SET_MAX_DIM, SET_MAX_QUERIES, SET_MAX_REFS      # noqa: E402,F401
