@@ -4,7 +4,7 @@
                       [--box x0,y0,x1,y1] [--actions all|i,j,k] [--samples S] [--seed N] [--overlay R] [--sheet-frames i,j,k]
                       [--driver DIR [--driver-mode relative|absolute] [--driver-scaled] [--driver-box x0,y0,x1,y1]]
                       [--frames N] [--rate F] [--resample linear|cubic]
-                      [--gif-fps N] [--gif-dither A] [--png] [--batch B] [--colors_seed S] [--save_dir D]
+                      [--gif-fps N] [--gif-dither A] [--video [--video-fps N] [--video-quality Q]] [--png] [--batch B] [--colors_seed S] [--save_dir D]
 
 Inputs (``kpx_amd.stills``): each PATH is an image file, a directory (its .jpg .jpeg .png .bmp files in sorted name order) or a .txt manifest
 (one ``path [x0,y0,x1,y1]`` per line, relative to the manifest).  Decoding is PIL's on the host: EXIF orientation applied, then
@@ -28,7 +28,9 @@ animated grid (row = draw, column = class, 33 frames, frame 0 = the still) with 
 classes_overlay.gif, the same grid with the key points marked on the frames (a disc of radius R - 1 with a one-pixel outline,
 ``kpx_amd.ops.cell_frames``), and overlay.png, its first cell at frame 0; classes.png and classes_points.png, the contact sheets of
 evaluate.py --actions for draw 0; with ``--driver`` driven.gif (driver | pred) and driven_overlay.gif; with ``--png`` the frames of every
-rollout as evaluate.py writes them.  <save_dir>/animate.json records the inputs and the settings.  No quality claim is made for images
+rollout as evaluate.py writes them; with ``--video`` every GIF also as a true-colour Motion-JPEG AVI beside it (classes.avi, classes_overlay.avi,
+driven.avi, driven_overlay.avi: the same canvases JPEG-coded on the device, ``kpx_amd.ops.jpeg_encode``; ``--video-fps`` 1..240, default 10,
+times ``--rate``; ``--video-quality`` 1..100, default 90).  <save_dir>/animate.json records the inputs and the settings.  No quality claim is made for images
 outside the training distribution: the overlay is there to judge that.
 """
 import json
@@ -89,6 +91,10 @@ def main(argv=None):
     parser.add_argument('--resample', type=str, default=None, help='linear or cubic (default): how --rate places the key points in between')
     parser.add_argument('--gif-fps', type=int, default=10, help='frames per second, 1..50 (default 10); with --rate F the GIFs play at F times this')
     parser.add_argument('--gif-dither', type=int, default=0, help='amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
+    parser.add_argument('--video', action='store_true',
+                        help='also every GIF as a true-colour Motion-JPEG AVI beside it (classes.avi, ...), JPEG-coded on the device')
+    parser.add_argument('--video-fps', type=int, default=None, help='with --video: frames per second, 1..240 (default 10); with --rate F the AVIs play at F times this')
+    parser.add_argument('--video-quality', type=int, default=None, help='with --video: the JPEG quality, 1..100 (default 90)')
     parser.add_argument('--png', action='store_true', help='also the frames of every rollout as PNGs')
     parser.add_argument('--batch', type=int, default=8)
     parser.add_argument('--colors_seed', type=int, default=0, help='seed of the key-point palette')
@@ -104,6 +110,7 @@ def main(argv=None):
     from train import config_image_size, load_config
     from kpx_amd import stills
     from kpx_amd.gif import DITHER_RANGE, FPS_RANGE, delay_of_fps
+    from kpx_amd.mjpeg import FPS_RANGE as VIDEO_FPS_RANGE, QUALITY_RANGE
 
     # ---- everything that can be refused is refused here, before the device is touched
     if args.checkpoint_stage2 is None and args.driver is None:
@@ -134,6 +141,16 @@ def main(argv=None):
     if args.gif_fps * rate > FPS_RANGE[1]:
         parser.error('--gif-fps %d x --rate %d = %d frames per second, and a GIF plays at most %d: lower --gif-fps'
                      % (args.gif_fps, rate, args.gif_fps * rate, FPS_RANGE[1]))
+    if (args.video_fps is not None or args.video_quality is not None) and not args.video:
+        parser.error('--video-fps and --video-quality shape the files of --video and need it')
+    video_fps, video_quality = 10 if args.video_fps is None else args.video_fps, 90 if args.video_quality is None else args.video_quality
+    if not VIDEO_FPS_RANGE[0] <= video_fps <= VIDEO_FPS_RANGE[1]:
+        parser.error('--video-fps takes %d..%d frames per second (got %d)' % (VIDEO_FPS_RANGE + (video_fps,)))
+    if not QUALITY_RANGE[0] <= video_quality <= QUALITY_RANGE[1]:
+        parser.error('--video-quality takes %d..%d (got %d)' % (QUALITY_RANGE + (video_quality,)))
+    if args.video and video_fps * rate > VIDEO_FPS_RANGE[1]:
+        parser.error('--video-fps %d x --rate %d = %d frames per second, and the AVIs play at most %d: lower --video-fps'
+                     % (video_fps, rate, video_fps * rate, VIDEO_FPS_RANGE[1]))
     n_frames = 1 + n_pred * rate                           # the still, then T' = frames x rate predicted frames
     if not DITHER_RANGE[0] <= args.gif_dither <= DITHER_RANGE[1]:
         parser.error('--gif-dither takes an amplitude in %d..%d (got %d)' % (DITHER_RANGE + (args.gif_dither,)))
@@ -193,6 +210,16 @@ def main(argv=None):
         raise Exception('--overlay marks at most %d key points (the model has %d)' % (ops.CELL_MAX_POINTS, k))
     colors = torch.from_numpy(stills.marker_colors(model.colors)).to(dev) if radius else None
     gifs = kpx_amd.gif.RolloutGifs(args.gif_fps * rate, args.gif_dither)
+    if args.video and actions and max(samples, len(actions)) * size > ops.JPEG_MAX_SIDE:
+        raise Exception('--video: the grid of %d draws x %d classes of %d x %d cells is larger than the %d pixels a side a JPEG frame of '
+                        'classes.avi holds' % (samples, len(actions), size, size, ops.JPEG_MAX_SIDE))
+    video_bytes = {}
+
+    def write_videos(name, canvas):                        # beside <name>.gif, from the same canvas
+        if args.video:
+            video_bytes.setdefault(name, []).extend(
+                stills.write_grid_videos(canvas, [osp.join(d, name + '.avi') for d in dirs], video_fps * rate, video_quality))
+
     rollout = {} if (n_pred, rate) == (32, 1) else {'frames': n_pred, 'rate': rate, 'resample': resample}
     n_cls = len(actions) if actions else 0
     layers = 2 if radius else 1
@@ -254,8 +281,10 @@ def main(argv=None):
                 sweep.run(s, z[0] if n_pred == 32 else z)
             sweep.write_sheets(args.save_dir, start)
             palette_sizes['classes'] += stills.write_grid_gifs(gifs, grid, [osp.join(d, 'classes.gif') for d in dirs])
+            write_videos('classes', grid)
             if over is not None:
                 palette_sizes['classes_overlay'] += stills.write_grid_gifs(gifs, over, [osp.join(d, 'classes_overlay.gif') for d in dirs])
+                write_videos('classes_overlay', over)
                 first = over[:, 0, :size, :size].contiguous().cpu().numpy()
                 for i, d in enumerate(dirs):
                     Image.fromarray(first[i]).save(osp.join(d, 'overlay.png'))
@@ -271,10 +300,12 @@ def main(argv=None):
             ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit')
             ops.cell_frames(pair, image, pred, 0, 1, 'unit')
             palette_sizes['driven'] += stills.write_grid_gifs(gifs, pair, [osp.join(d, 'driven.gif') for d in dirs])
+            write_videos('driven', pair)
             if radius:                                   # the driver's own key points on its cell, the retargeted ones on the rollout
                 ops.cell_frames(pair, d_first, d_seq, 0, 0, 'unit', tile(drv['first_pt']), d_pts, colors=colors, radius=radius)
                 ops.cell_frames(pair, image, pred, 0, 1, 'unit', *marks(out), colors=colors, radius=radius)
                 palette_sizes['driven_overlay'] += stills.write_grid_gifs(gifs, pair, [osp.join(d, 'driven_overlay.gif') for d in dirs])
+                write_videos('driven_overlay', pair)
             write_inputs(out)
             if args.png:
                 host = {key: out[key].cpu().numpy() for _, key, _ in PNG_FOLDERS}
@@ -285,6 +316,8 @@ def main(argv=None):
             'overlay': radius, 'batch': batch, 'palette_sizes': palette_sizes}
     if rollout:
         meta['rollout'] = dict(rollout, gif_fps=args.gif_fps)
+    if args.video:
+        meta['video'] = {'fps': video_fps * rate, 'quality': video_quality, 'bytes': video_bytes}
     if actions:
         meta.update({'actions': actions, 'draws': samples, 'seed': seed, 'grid': [samples, n_cls], 'sheet_frames': sheet_frames})
     if driver is not None:

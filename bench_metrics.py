@@ -7,7 +7,7 @@
 2. The configs[4] rollout (B = 64, replayed HIP graph) without and with scoring its 2 048 predicted frames against real frames, alternated in
    one process; median ms of each and the overhead in %.
 
-    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif | --animate | --guard | --ema]
+    python bench_metrics.py [--launches 40] [--rollouts 10] [--vgg | --motion | --actions | --drive | --frechet | --classifier | --stability | --joints | --gif | --animate | --guard | --ema | --video]
 
 ``--vgg`` measures the VGG feature-space metrics (kpx_feature_pair_metrics_f32, evaluate.py --vgg-metrics) instead:
 
@@ -144,6 +144,16 @@
    scores of each route equal the kernel's is reported, not asserted.
 31. The rollout of configs[4] (B = 64, replayed HIP graph) at n_pts = 40 without and with what --prdc adds per batch and draw (the float32 copy
    of the draw's key points; the scores are computed once, after the last batch: item 30), alternated; median ms of each and the difference.
+
+``--video`` measures the Motion-JPEG AVIs of rollouts (evaluate.py --video) instead:
+
+32. kpx_jpeg_encode_u8 alone on the pred and compare canvases of a configs[4] batch (64 samples of 33 frames of 128 x 128 and 128 x 384,
+   quality 90), in the chunks ``ops.jpeg_encode`` uses: device-event time of all chunks after warm-up, min / median / max ms, beside a device
+   copy of the same canvases; the compressed bytes against the 8-bit RGB bytes.  Then the two routes to JPEG bytes on the host for the same
+   samples, wall-clock ms per sample: ``ops.jpeg_encode`` (kernels, one read of the offsets and one copy of the used bytes per chunk) against
+   the uint8 canvas copied to the host and ``PIL.Image.save(..., 'JPEG', quality=90, subsampling=2)`` per frame on 16 threads.
+33. The configs[4] rollout without anything, with what --gif adds and with what --video adds (``kpx_amd.mjpeg.RolloutVideos.write``: both
+   canvases composed, coded, copied and written as 128 AVI files), alternated in one process; ms per rollout and per sample of each.
 
 Prints one JSON line.
 """
@@ -1054,6 +1064,114 @@ def gif_rollout_leg(dev, rollouts):
             'device_ms_all': [round(v, 1) for v in ms['device']], 'on_ms_all': [round(v, 1) for v in ms['on']]}
 
 
+def video_kernel_leg(dev, launches, quality=90):
+    import io
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from kpx_amd import mjpeg, ops
+    from kpx_amd._lib import lib
+    g = torch.Generator(device=dev).manual_seed(20)
+    compare = _gif_canvas(dev, g)
+    canvases = {'pred': compare[:, :, :, :RES].contiguous(), 'compare': compare}
+    res = {'quality': quality, 'budget_mb': ops.JPEG_BUDGET >> 20}
+    for name, canvas in canvases.items():
+        flat = canvas.view((-1,) + tuple(canvas.shape[2:]))
+        n, h, w = (int(v) for v in flat.shape[:3])
+        bound = int(lib.kpx_jpeg_scan_bound(h, w))
+        per = max(1, ops.JPEG_BUDGET // (int(lib.kpx_jpeg_workspace_bytes(1, h, w)) + bound))
+        scans = torch.empty(min(per, n) * bound, dtype=torch.uint8, device=dev)
+        offsets = torch.empty(min(per, n) + 1, dtype=torch.int64, device=dev)
+        dst = torch.empty_like(canvas)
+
+        def encode_all():
+            for lo in range(0, n, per):
+                m = min(per, n - lo)
+                ops.jpeg_scans(flat[lo:lo + m], quality, scans[:m * bound], offsets[:m + 1])
+
+        leg = {'canvas': list(canvas.shape), 'rgb_mb': round(canvas.numel() / 1e6, 1), 'frames_per_chunk': min(per, n), 'chunks': -(-n // per)}
+        for key, fn in (('device_copy', lambda: dst.copy_(canvas)), ('jpeg_scans', encode_all)):
+            us = _event_times(fn, launches, dev)
+            leg[key] = {'launches': launches, 'median_ms': round(statistics.median(us) / 1e3, 3), 'min_ms': round(min(us) / 1e3, 3),
+                        'max_ms': round(max(us) / 1e3, 3)}
+        leg['jpeg_scans']['over_device_copy'] = round(leg['jpeg_scans']['median_ms'] / leg['device_copy']['median_ms'], 1)
+        leg['jpeg_scans']['rgb_gb_per_s'] = round(canvas.numel() / (leg['jpeg_scans']['median_ms'] * 1e-3) / 1e9, 1)
+        del dst
+        ms = {'device': [], 'host': []}
+        samples = int(canvas.shape[0])
+        for _ in range(3):                                    # the first pair warms both routes up and is dropped
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            mine = ops.jpeg_encode(flat, quality)
+            ms['device'].append((time.perf_counter() - t0) * 1e3 / samples)
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            host = flat.cpu().numpy()
+
+            def save(i):
+                buf = io.BytesIO()
+                Image.fromarray(host[i]).save(buf, 'JPEG', quality=quality, subsampling=2)
+                return buf.tell()
+            with ThreadPoolExecutor(16) as pool:
+                pil_bytes = sum(pool.map(save, range(n)))
+            ms['host'].append((time.perf_counter() - t0) * 1e3 / samples)
+        prefix = len(mjpeg.frame_prefix(h, w, mjpeg.quant_tables(quality))) + 2
+        leg['jpeg_mb'] = round((sum(len(s) for s in mine) + n * prefix) / 1e6, 2)
+        leg['pil_jpeg_mb'] = round(pil_bytes / 1e6, 2)
+        leg['bytes_to_host_over_rgb'] = round(sum(len(s) for s in mine) / canvas.numel(), 4)
+        leg['route_ms_per_sample'] = {'samples': samples, 'device_jpeg_encode_and_copy': round(statistics.median(ms['device'][1:]), 2),
+                                      'host_u8_copy_and_pil_save_16_threads': round(statistics.median(ms['host'][1:]), 2)}
+        res[name] = leg
+    return res
+
+
+def video_rollout_leg(dev, rollouts):
+    import shutil
+    import tempfile
+    import kpx_amd
+    cfg = {'model': {'n_pts': 15, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    real = torch.rand((B, 32, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256, point_maps=True)
+    fm.build()
+    writers = {'gif': kpx_amd.gif.RolloutGifs(10, 0), 'video': kpx_amd.mjpeg.RolloutVideos(10, 90)}
+    out_dir = tempfile.mkdtemp(prefix='kpx_video_bench_')
+
+    def run(mode):
+        o = fm.run(None, {'image': im, 'action_code': act}, z=z)
+        cols = [('real', im, real, 'unit'), ('pred', o['im'], o['pred_im_seq'], 'unit'), ('points', o['current_points'], o['future_points'], 'raw')]
+        if mode != 'off':
+            writers[mode].write(out_dir, 0, cols)
+
+    try:
+        for _ in range(3):                                # eager, capture, one replay
+            run('off')
+        run('gif')
+        run('video')
+        torch.cuda.synchronize(dev)
+        modes = ('off', 'gif', 'video')
+        ms = {m: [] for m in modes}
+        for _ in range(max(1, min(rollouts, 3))):
+            for m in modes:
+                t0 = time.perf_counter()
+                run(m)
+                torch.cuda.synchronize(dev)
+                ms[m].append((time.perf_counter() - t0) * 1e3)
+        size = {ext: sum(os.path.getsize(os.path.join(d, n)) for d, _, names in os.walk(out_dir) for n in names if n.endswith(ext))
+                for ext in ('.gif', '.avi')}
+    finally:
+        shutil.rmtree(out_dir, ignore_errors=True)
+    off, gif, video = (statistics.median(ms[m]) for m in modes)
+    return {'batch': B, 'frames': N_FRAMES, 'graph_replay': len(fm._graphs) == 1, 'files_each': 2 * B, 'gif_mb': round(size['.gif'] / 1e6, 1),
+            'avi_mb': round(size['.avi'] / 1e6, 1), 'off_ms_per_rollout': round(off, 2), 'gif_ms_per_rollout': round(gif, 2),
+            'video_ms_per_rollout': round(video, 2), 'gif_flag_ms_per_rollout': round(gif - off, 2),
+            'video_flag_ms_per_rollout': round(video - off, 2), 'gif_flag_ms_per_sample': round((gif - off) / B, 2),
+            'video_flag_ms_per_sample': round((video - off) / B, 2), 'off_ms_all': [round(v, 1) for v in ms['off']],
+            'gif_ms_all': [round(v, 1) for v in ms['gif']], 'video_ms_all': [round(v, 1) for v in ms['video']]}
+
+
 def animate_kernel_leg(dev, launches):
     from kpx_amd import gif, ops
     t, k = 32, 15
@@ -1625,7 +1743,18 @@ def main():
     ap.add_argument('--prdc', action='store_true',
                     help='measure precision / recall / density / coverage (ops.prdc and its four searches at Penn\'s test-set size beside a device '
                          'copy and the torch.cdist fp64 route, the cost of --prdc per configs[4] rollout, all in this process) instead')
+    ap.add_argument('--video', action='store_true',
+                    help='measure the Motion-JPEG AVIs of rollouts (the JPEG coder beside a device copy and the host PIL route, the cost of '
+                         '--video per configs[4] rollout beside --gif, all in this process) instead')
     args = ap.parse_args()
+    if args.video:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        kernels = video_kernel_leg(dev, min(args.launches, 10))
+        torch.cuda.empty_cache()
+        print(json.dumps({'video_kernels': kernels, 'video_rollout_c4': video_rollout_leg(dev, args.rollouts)}))
+        return
     if args.prdc:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

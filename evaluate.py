@@ -8,6 +8,7 @@
                        [--drive labels,hold,transfer [--drive-scaled] [--drive-only] [--sheet-frames f,g,h]]
                        [--metrics --action-accuracy CKPT]
                        [--gif [--gif-fps N] [--gif-dither A] [--frames N] [--rate F [--resample linear|cubic]]]
+                       [--video [--video-fps N] [--video-quality Q] [--frames N] [--rate F [--resample linear|cubic]]]
                        [--metrics --novelty [--novelty-sheets] [--novelty-no-mirror]]
                        [--metrics --prdc [--prdc-k K]]
 
@@ -93,7 +94,15 @@ stored as the delay round(100 / N) centiseconds; ``--gif-dither A`` (0..64, defa
 before the search.  ``<save_dir>/gif.json`` records the columns, fps, dither, the frame count and the palette size per sample.  DESIGN.md
 section 2 has the definition.  Without the flag every file keeps its bytes.
 
-``--frames N`` / ``--rate F`` (with ``--gif``; data path and ``--synthetic``) add a longer and smoother rollout beside the ordinary one, which
+``--video`` (data path and ``--synthetic``; not with ``--no-save``; with or without ``--gif``) writes the same frames and columns in true
+colour: per sample ``pred.avi`` and ``compare.avi``, Motion-JPEG in an AVI container.  Every frame is a baseline JPEG (4:2:0) whose scan is
+coded on the device (``kpx_amd.ops.jpeg_encode``: integers only), so only compressed bytes cross to the host, where
+``kpx_amd.mjpeg`` adds the headers and the container.  ``--video-fps N`` (1..240, default 10), ``--video-quality Q`` (1..100, default 90:
+the IJG quality scale).  ``<save_dir>/video.json`` records the columns, fps, quality, the frame count and the bytes per file;
+``python -m kpx_amd.mjpeg FILE.avi --png DIR`` unpacks a file without a GPU.  With ``--frames`` / ``--rate`` also ``long.avi``, played at
+F x ``--video-fps`` (a product above 240 is refused; the 2^24-pixel limit of long.gif does not apply to it).
+
+``--frames N`` / ``--rate F`` (with ``--gif`` or ``--video``; data path and ``--synthetic``) add a longer and smoother rollout beside the ordinary one, which
 is produced first and keeps every file, metric and byte.  Per batch a second rollout (``FinalModel.run(frames=N, rate=F, resample=...)``,
 DESIGN.md section 2) chains N / 32 calls of the motion generator -- segment 0 at draw 0's z, the later ones at z from
 ``numpy.random.RandomState(first sample index of the batch)`` -- and puts F - 1 key-point frames between every two (``--resample``, default
@@ -1096,11 +1105,14 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
 class _LongRollout:
     """--frames / --rate: after a batch's ordinary rollout a second one, chained to ``frames`` predicted frames and resampled by ``rate``
     (FinalModel.run(frames=, rate=, resample=)), at the same z for segment 0 and seeded z for the later segments.  Per sample long.gif
-    (pred | points) and long_points.npy [T',K,2]; per run long.json: the mean speed curve and the seam ratio (kpx_amd.resample)."""
+    (with --gif) and long.avi (with --video), both pred | points, and long_points.npy [T',K,2]; per run long.json: the mean speed curve and the seam ratio (kpx_amd.resample)."""
 
-    def __init__(self, kpx_amd, model, frames, rate, resample, fps, dither, dev):
+    def __init__(self, kpx_amd, model, frames, rate, resample, fps, dither, dev, video=None):
         self.kpx, self.model, self.frames, self.rate, self.resample, self.dev = kpx_amd, model, frames, rate, resample, dev
-        self.gifs = kpx_amd.gif.RolloutGifs(fps * rate, dither)        # F times the frames in the same time
+        self.gifs = kpx_amd.gif.RolloutGifs(fps * rate, dither) if fps is not None else None       # F times the frames in the same time
+        self.videos = kpx_amd.mjpeg.RolloutVideos(video[0] * rate, video[1]) if video is not None else None
+        self.compose = (self.gifs or self.videos)._canvas
+        self.bytes = []
         self.speed_sum, self.n, self.sizes = np.zeros(frames * rate, np.float64), 0, []
 
     def run(self, save_dir, first_sample, image, action_code, z):
@@ -1111,15 +1123,20 @@ class _LongRollout:
         out = self.model.run(None, {'image': image, 'action_code': action_code}, z=z_all, frames=self.frames, rate=self.rate, resample=self.resample)
         pts = out['fut_pt_raw'].contiguous()
         speed = ops.points_speed(out['first_pt'].reshape(bsz, -1, 2).contiguous(), pts, float(self.rate))
-        canvas = self.gifs._canvas([(out['im'], out['pred_im_seq'], 'unit'), (out['current_points'], out['future_points'], 'raw')])
-        idx, palettes, sizes = ops.gif_indices(canvas, self.gifs.dither)
-        host, pts_host = self.gifs._host(idx), pts.cpu().numpy()
+        canvas = self.compose([(out['im'], out['pred_im_seq'], 'unit'), (out['current_points'], out['future_points'], 'raw')])
+        pts_host = pts.cpu().numpy()
+        if self.gifs is not None:
+            idx, palettes, sizes = ops.gif_indices(canvas, self.gifs.dither)
+            host = self.gifs._host(idx)
+        if self.videos is not None:
+            self.videos.write_canvas(save_dir, first_sample, 'long', canvas, self.bytes)
         for i in range(bsz):
             d = osp.join(save_dir, '%04d' % (first_sample + i))
             os.makedirs(d, exist_ok=True)
-            self.kpx.gif.write_gif(osp.join(d, 'long.gif'), host[i], palettes[i, :sizes[i]], self.gifs.delay)
+            if self.gifs is not None:
+                self.kpx.gif.write_gif(osp.join(d, 'long.gif'), host[i], palettes[i, :sizes[i]], self.gifs.delay)
+                self.sizes.append(int(sizes[i]))
             np.save(osp.join(d, 'long_points.npy'), pts_host[i])
-            self.sizes.append(int(sizes[i]))
         self.speed_sum += speed.cpu().numpy().sum(0)
         self.n += bsz
         return bsz * self.frames * self.rate
@@ -1128,12 +1145,18 @@ class _LongRollout:
         from kpx_amd.resample import seam_ratio
         speed = self.speed_sum / max(self.n, 1)
         os.makedirs(save_dir, exist_ok=True)
+        doc = {'frames': self.frames, 'rate': self.rate, 'resample': self.resample, 'n_frames': self.frames * self.rate,
+               'columns': ['pred', 'points']}
+        if self.gifs is not None:
+            doc.update({'fps': self.gifs.fps, 'delay_cs': self.gifs.delay})
+        doc.update({'n_samples': self.n, 'speed_unit': 'mean key-point displacement per source frame, in the [-1, 1] coordinates',
+                    'speed': [_json_num(v) for v in speed], 'seam_ratio': seam_ratio(speed, self.frames, self.rate)})
+        if self.gifs is not None:
+            doc['palette_sizes'] = self.sizes
+        if self.videos is not None:
+            doc.update({'video_fps': self.videos.fps, 'video_quality': self.videos.quality, 'video_bytes': self.bytes})
         with open(osp.join(save_dir, 'long.json'), 'w') as f:
-            json.dump({'frames': self.frames, 'rate': self.rate, 'resample': self.resample, 'n_frames': self.frames * self.rate,
-                       'columns': ['pred', 'points'], 'fps': self.gifs.fps, 'delay_cs': self.gifs.delay, 'n_samples': self.n,
-                       'speed_unit': 'mean key-point displacement per source frame, in the [-1, 1] coordinates',
-                       'speed': [_json_num(v) for v in speed], 'seam_ratio': seam_ratio(speed, self.frames, self.rate),
-                       'palette_sizes': self.sizes}, f, indent=1)
+            json.dump(doc, f, indent=1)
 
 
 def _save_img_sequence(output_dir, img_seq, rescale=False, raw=False):
@@ -1194,6 +1217,11 @@ def main(argv=None):
                              'points side by side), quantised to one palette per GIF on the device; <save_dir>/gif.json')
     parser.add_argument('--gif-fps', type=int, default=None, help='with --gif: frames per second, 1..50 (default 10)')
     parser.add_argument('--gif-dither', type=int, default=None, help='with --gif: amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
+    parser.add_argument('--video', action='store_true',
+                        help='per sample pred.avi and compare.avi, the frames and columns of the GIFs in true colour: Motion-JPEG in an AVI, '
+                             'every frame JPEG-coded on the device; <save_dir>/video.json')
+    parser.add_argument('--video-fps', type=int, default=None, help='with --video: frames per second, 1..240 (default 10)')
+    parser.add_argument('--video-quality', type=int, default=None, help='with --video: the JPEG quality, 1..100 (default 90)')
     parser.add_argument('--novelty', action='store_true',
                         help='with --metrics: search every rollout and the real future in the training motions of train_set.txt (the nearest '
                              "window per action class, in HIP) and report how far they lie.  This project's own key-point-space quantity: "
@@ -1208,16 +1236,16 @@ def main(argv=None):
                              'quantities: not comparable with published figures')
     parser.add_argument('--prdc-k', type=int, default=None, metavar='K', help='with --prdc: the neighbour that sets a ball\'s radius, 1..8 (default 5)')
     parser.add_argument('--frames', type=int, default=None,
-                        help='with --gif: a second rollout per batch chained to this many predicted frames (a multiple of 32, default 32): '
-                             'per sample long.gif and long_points.npy, <save_dir>/long.json with the speed curve and the seam ratio')
-    parser.add_argument('--rate', type=int, default=None, help='with --gif: resample the second rollout to F = 1..64 times the frames (default 1); long.gif plays at F x --gif-fps')
+                        help='with --gif or --video: a second rollout per batch chained to this many predicted frames (a multiple of 32, default 32): '
+                             'per sample long.gif / long.avi and long_points.npy, <save_dir>/long.json with the speed curve and the seam ratio')
+    parser.add_argument('--rate', type=int, default=None, help='with --gif or --video: resample the second rollout to F = 1..64 times the frames (default 1); long.gif plays at F x --gif-fps, long.avi at F x --video-fps')
     parser.add_argument('--resample', type=str, default=None, help='with --rate: linear or cubic (default)')
     args = parser.parse_args(argv)
     long_frames, long_rate = 32 if args.frames is None else args.frames, 1 if args.rate is None else args.rate
     want_long = args.frames is not None or args.rate is not None
     if args.resample is not None and args.rate is None:
         parser.error('--resample chooses how --rate places the frames in between and needs it')
-    if want_long and not args.gif:
+    if want_long and not (args.gif or args.video):
         parser.error('--frames and --rate write long.gif beside the files of --gif and need it')
     if want_long and args.drive_only:
         parser.error("--drive-only skips the model's own rollout, which --frames and --rate lengthen")
@@ -1228,7 +1256,7 @@ def main(argv=None):
     if (args.resample or 'cubic') not in ('linear', 'cubic'):
         parser.error('--resample takes linear or cubic (got %r)' % args.resample)
     def check_long_gif(side):
-        if 2 * (1 + long_frames * long_rate) * side * side > 1 << 24:
+        if args.gif and 2 * (1 + long_frames * long_rate) * side * side > 1 << 24:
             parser.error('--frames x --rate: long.gif would hold %d frames of two %d x %d cells, and the colour histogram of one GIF counts '
                          'at most 2^24 pixels (%d frames)' % (1 + long_frames * long_rate, side, side, (1 << 24) // (2 * side * side)))
     check_long_gif(128)
@@ -1266,9 +1294,22 @@ def main(argv=None):
         parser.error('--gif-fps takes 1..50 frames per second (got %d)' % gif_fps)
     if not 0 <= gif_dither <= 64:
         parser.error('--gif-dither takes an amplitude in 0..64 (got %d)' % gif_dither)
-    if want_long and gif_fps * long_rate > 50:
+    if want_long and args.gif and gif_fps * long_rate > 50:
         parser.error('--gif-fps %d x --rate %d = %d frames per second, and a GIF plays at most 50: lower --gif-fps'
                      % (gif_fps, long_rate, gif_fps * long_rate))
+    if (args.video_fps is not None or args.video_quality is not None) and not args.video:
+        parser.error('--video-fps and --video-quality shape the files of --video and need it')
+    if args.video and args.no_save:
+        parser.error('--video writes files, and --no-save writes none')
+    video_fps = 10 if args.video_fps is None else args.video_fps
+    video_quality = 90 if args.video_quality is None else args.video_quality
+    if not 1 <= video_fps <= 240:
+        parser.error('--video-fps takes 1..240 frames per second (got %d)' % video_fps)
+    if not 1 <= video_quality <= 100:
+        parser.error('--video-quality takes 1..100 (got %d)' % video_quality)
+    if want_long and args.video and video_fps * long_rate > 240:
+        parser.error('--video-fps %d x --rate %d = %d frames per second, and long.avi plays at most 240: lower --video-fps'
+                     % (video_fps, long_rate, video_fps * long_rate))
     if args.sheet_frames is not None and args.actions is None and args.drive is None and not args.novelty_sheets:
         parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive / --novelty-sheets and needs it')
     drive_modes = None
@@ -1357,7 +1398,10 @@ def main(argv=None):
         model.restore(None, p, **({'ema': True} if args.ema else {}))
     n_action = config['model']['n_action']
     gifs = kpx_amd.gif.RolloutGifs(gif_fps, gif_dither) if args.gif else None
-    long_run = _LongRollout(kpx_amd, model, long_frames, long_rate, args.resample or 'cubic', gif_fps, gif_dither, dev) if want_long else None
+    videos = kpx_amd.mjpeg.RolloutVideos(video_fps, video_quality) if args.video else None
+    animations = [a for a in (gifs, videos) if a is not None]     # the same canvases, written at the same places
+    long_run = _LongRollout(kpx_amd, model, long_frames, long_rate, args.resample or 'cubic', gif_fps if args.gif else None, gif_dither, dev,
+                            video=(video_fps, video_quality) if args.video else None) if want_long else None
     sample_idx, frames, t0 = 0, 0, time.time()
     if not args.synthetic:                       # reference :43-51, :84-130: the test subset through the sequence loader
         loader = kpx_amd.data.SequenceDataLoader(config['paths']['data_dir'], 'test', n_points=config['model']['n_pts'], n_action=n_action,
@@ -1401,9 +1445,9 @@ def main(argv=None):
                 frames += driven.run(args.save_dir, sample_idx, real_flat, drive_scores)
                 if not args.no_save:
                     driven.write_sheet(args.save_dir, sample_idx)
-                if gifs is not None:
+                for anim in animations:
                     o = driven.first_out
-                    gifs.write(args.save_dir, sample_idx, [('real', batch['image'], batch['real_im_seq'], 'unit'),
+                    anim.write(args.save_dir, sample_idx, [('real', batch['image'], batch['real_im_seq'], 'unit'),
                                                            ('pred', batch['image'], o['pred_im_seq'], 'unit'),
                                                            ('points', o['current_points'], o['future_points'], 'raw')])
                 n_self_driven += bsz if 'transfer' in drive_modes and bsz == 1 else 0
@@ -1498,8 +1542,8 @@ def main(argv=None):
                         _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                         _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                         sample_idx += 1
-                    if gifs is not None:     # before the driven rollouts and the sweep below replay the graph over these outputs
-                        gifs.write(args.save_dir, sample_idx - bsz, [('real', batch['image'], batch['real_im_seq'], 'unit'),
+                    for anim in animations:     # before the driven rollouts and the sweep below replay the graph over these outputs
+                        anim.write(args.save_dir, sample_idx - bsz, [('real', batch['image'], batch['real_im_seq'], 'unit'),
                                                                      ('pred', outputs['im'], outputs['pred_im_seq'], 'unit'),
                                                                      ('points', outputs['current_points'], outputs['future_points'], 'raw')])
                 if drive_modes and draw == 0:    # once per batch: the driven rollouts do not depend on z (their graphs are their own:
@@ -1529,8 +1573,8 @@ def main(argv=None):
         if drive_modes and not args.no_save:
             _write_drive_json(args.save_dir, _drive_rows(drive_modes, True, not args.drive_only), sheet_frames,
                               (model.image_size, model.image_size), drive_modes, args.drive_scaled, n_self_driven)
-        if gifs is not None:
-            gifs.write_json(args.save_dir)
+        for anim in animations:
+            anim.write_json(args.save_dir)
         if long_run is not None:
             long_run.write_json(args.save_dir)
         if args.metrics and args.drive_only:
@@ -1556,9 +1600,9 @@ def main(argv=None):
             frames += driven.run(args.save_dir, sample_idx, None, None)
             if not args.no_save:
                 driven.write_sheet(args.save_dir, sample_idx)
-            if gifs is not None:
+            for anim in animations:
                 o = driven.first_out
-                gifs.write(args.save_dir, sample_idx, [('pred', image, o['pred_im_seq'], 'unit'),
+                anim.write(args.save_dir, sample_idx, [('pred', image, o['pred_im_seq'], 'unit'),
                                                        ('points', o['current_points'], o['future_points'], 'raw')])
             sample_idx += bsz
             continue
@@ -1577,8 +1621,8 @@ def main(argv=None):
                 _save_img_sequence(osp.join(d, 'crude'), o['pred_im_crude'][batch_idx], rescale=True)
                 _save_img_sequence(osp.join(d, 'pred_points'), o['future_points'][batch_idx], rescale=False)
                 sample_idx += 1
-            if gifs is not None:
-                gifs.write(args.save_dir, sample_idx - bsz, [('pred', outputs['im'], outputs['pred_im_seq'], 'unit'),
+            for anim in animations:
+                anim.write(args.save_dir, sample_idx - bsz, [('pred', outputs['im'], outputs['pred_im_seq'], 'unit'),
                                                              ('points', outputs['current_points'], outputs['future_points'], 'raw')])
         if drive_modes:
             first = sample_idx - bsz if not args.no_save else 0
@@ -1601,8 +1645,8 @@ def main(argv=None):
     if drive_modes and not args.no_save:
         _write_drive_json(args.save_dir, _drive_rows(drive_modes, False, not args.drive_only), sheet_frames,
                           (model.image_size, model.image_size), drive_modes, False, 0)
-    if gifs is not None:
-        gifs.write_json(args.save_dir)
+    for anim in animations:
+        anim.write_json(args.save_dir)
     if long_run is not None:
         long_run.write_json(args.save_dir)
     torch.cuda.synchronize()

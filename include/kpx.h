@@ -1034,6 +1034,32 @@ int kpx_set_neighbours_f64(const double* q /*[M,D]*/, int M, const double* r /*[
                            int k, void* workspace, size_t workspace_bytes, double* nn_d2 /*[M,k]*/, int32_t* nn_idx /*[M,k]*/,
                            int32_t* inside /*[M] or NULL*/, void* stream);
 
+/* ---- Motion-JPEG: baseline JPEG scans of 8-bit RGB frames (csrc/mjpeg.hip; evaluate.py --video, animate.py --video, kpx_amd/mjpeg.py), DESIGN.md
+ * sections 2 and 4.4.  No reference counterpart.  Added without a version change, as the entries of csrc/prdc.hip were: no existing signature moves.
+ *
+ *   rgb         uint8 [N][H][W][3], dense, any alignment
+ *   qtables     uint8 [2][64] ON THE HOST (read during the call): the luma and the chroma quantisation table in natural order, each in 1..255
+ *   scans       N * kpx_jpeg_scan_bound(H, W) bytes on the device; offsets int64 [N + 1] on the device
+ *
+ * Frame n's scan -- the bytes between the SOS segment and EOI of a baseline JPEG whose headers kpx_amd.mjpeg.frame_prefix writes -- is
+ * scans[offsets[n] .. offsets[n + 1]), the frames packed back to back, offsets[0] = 0.  Integers only (int32 / int64):
+ *   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32768) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32768) >> 16 (arithmetic shifts), Cb and Cr clamped to [0, 255]; a chroma sample is
+ *   (a + b + c + d + 2) >> 2 over its 2 x 2 clamped values; 128 is subtracted; F = T S T^t with T[u][x] = rint(8192 alpha(u) cos((2x + 1) u pi / 16))
+ *   exactly; the coefficient is sgn(F) floor((|F| + Q 2^25) / (Q 2^26)).  One interleaved scan of 16 x 16 MCUs (four Y blocks in raster order,
+ *   Cb, Cr) coded with the four typical Huffman tables of ITU T.81 Annex K.3 - K.6; a restart interval is one row of MCUs (DRI = W / 16),
+ *   RSTm with m = row & 7 follows every row but the last, the DC predictors restart at 0, the last byte of an interval is padded with 1 bits,
+ *   0x00 follows every 0xFF data byte, 16 zeros are ZRL, EOB is coded unless coefficient 63 is non-zero.
+ * The bytes depend on the pixels and the tables alone, not on N, the grid or the order of execution.  Five launches on `stream`, no allocation,
+ * copy or synchronisation and no atomics (capturable).  workspace: kpx_jpeg_workspace_bytes(N, H, W) bytes (0 for sizes out of range), 8-byte
+ * aligned -- about 4.3 times the frames, and `scans` 3.25 times, so a caller with many frames encodes them in chunks (kpx_amd.ops.jpeg_encode).
+ * Limits: 16 <= H, W <= 4096, both multiples of 16, N >= 1, N H W < 2^31.  KPX_EINVAL before any device call for anything else, a null pointer,
+ * an offsets or workspace that is not 8-byte aligned, a workspace that is too small or a table entry of 0. */
+size_t kpx_jpeg_scan_bound(int H, int W);                 /* bytes that always hold one frame's scan, markers included; 0 for sizes out of range */
+size_t kpx_jpeg_workspace_bytes(int N, int H, int W);
+int kpx_jpeg_encode_u8(const uint8_t* rgb /*[N,H,W,3]*/, int N, int H, int W, const uint8_t* qtables /*HOST [2,64]*/, uint8_t* scans,
+                       int64_t* offsets /*[N+1]*/, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from . import frechet  # noqa: F401
 from . import stability  # noqa: F401
 from . import joints  # noqa: F401
 from . import gif  # noqa: F401
+from . import mjpeg  # noqa: F401
 from . import stills  # noqa: F401
 from . import novelty  # noqa: F401
 from . import resample  # noqa: F401

@@ -185,6 +185,9 @@ SIGNATURES = {
     'kpx_joint_targets_f32': (c_int, [P, P, P, P, c_int, c_int, P, P, P, P]),
     'kpx_joint_moments_add_f64': (c_int, [P, P, P, c_int, c_int, c_int, P, P, P, P]),
     'kpx_joint_scores_f32': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P]),
+    'kpx_jpeg_scan_bound': (c_size_t, [c_int, c_int]),
+    'kpx_jpeg_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'kpx_jpeg_encode_u8': (c_int, [P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

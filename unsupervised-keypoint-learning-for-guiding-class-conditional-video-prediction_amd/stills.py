@@ -160,3 +160,10 @@ def write_grid_gifs(gifs, canvas, paths):
     for i, path in enumerate(paths):
         write_gif(path, host[i], palettes[i, :sizes[i]], gifs.delay)
     return [int(s) for s in sizes]
+
+
+def write_grid_videos(canvas, paths, fps, quality):
+    """canvas uint8 [B, T, H, Wc, 3] on the device -> one Motion-JPEG AVI per sample at paths[b] (``kpx_amd.mjpeg.canvas_avi``: every frame
+    JPEG-coded on the device, only the scans cross to the host) -> the file sizes in bytes"""
+    from .mjpeg import canvas_avi
+    return [canvas_avi(path, canvas[i], fps, quality) for i, path in enumerate(paths)]

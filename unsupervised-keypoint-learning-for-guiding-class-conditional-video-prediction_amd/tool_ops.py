@@ -3,7 +3,8 @@ and the summaries.  None of them runs inside a train step; each is called once p
 ``_args`` (one list of (name, tensor, dtype, shape) per op) and only what is specific to the op -- value ranges, mode rules, table
 read-backs -- is written out.  ``ops`` re-exports every name here: ``ops.sheet_paste``, ``ops.MAX_DRAWS`` ... are the public names.  ``seq_nearest`` (evaluate.py --novelty)
 is written beside its tables in ``novelty`` and reaches ``tool_ops`` and ``ops`` by the import at the end of each; so do ``points_resample``
-and ``points_speed`` of ``resample`` and ``set_neighbours`` and ``prdc`` of ``prdc`` (evaluate.py --prdc).
+and ``points_speed`` of ``resample``, ``set_neighbours`` and ``prdc`` of ``prdc`` (evaluate.py --prdc) and ``jpeg_scans`` and ``jpeg_encode`` of
+``mjpeg`` (evaluate.py --video).
 """
 import numpy as np
 import torch
@@ -601,3 +602,6 @@ from .resample import points_resample, points_speed, RESAMPLE_MODES, RESAMPLE_MA
 
 # ----------------------------------------------------------------------------------------------- k nearest rows of a set; precision / recall / density / coverage
 from .prdc import set_neighbours, prdc, SET_MAX_K, SET_MAX_DIM, SET_MAX_QUERIES, SET_MAX_REFS      # noqa: E402,F401
+
+# evaluate.py --video: the wrappers are written beside the tables and the container in mjpeg.py
+from .mjpeg import jpeg_scans, jpeg_encode, JPEG_MIN_SIDE, JPEG_MAX_SIDE, JPEG_BUDGET      # noqa: E402,F401
