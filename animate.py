@@ -4,6 +4,7 @@
                       [--box x0,y0,x1,y1] [--actions all|i,j,k] [--samples S] [--seed N] [--overlay R] [--sheet-frames i,j,k]
                       [--driver DIR [--driver-mode relative|absolute] [--driver-scaled] [--driver-box x0,y0,x1,y1]]
                       [--frames N] [--rate F] [--resample linear|cubic]
+                      [--interpolate S [--interp-mode lerp|slerp]] [--motion-from DIR --motion-class C]
                       [--gif-fps N] [--gif-dither A] [--video [--video-fps N] [--video-quality Q]] [--png] [--batch B] [--colors_seed S] [--save_dir D]
 
 Inputs (``kpx_amd.stills``): each PATH is an image file, a directory (its .jpg .jpeg .png .bmp files in sorted name order) or a .txt manifest
@@ -22,6 +23,15 @@ calls of the motion generator, each started from the last pose of the one before
 the GIFs at F times ``--gif-fps``, so they last as long as before and only move more smoothly; set ``--gif-fps`` for slow motion.  The GIFs then
 hold 1 + N F frames and ``--sheet-frames`` indexes those.  With ``--driver`` only ``--rate`` applies: the driver's cell repeats each of its
 frames F times.
+
+Latent space (stage 2; 32-frame rollouts only, so not with ``--frames`` / ``--rate``): ``--interpolate S`` (2..64, ``--samples`` >= 2) joins the
+seeded draws 0 and 1 by ``kpx_amd.ops.latent_path`` (``--interp-mode``, default slerp: the great circle; lerp: the straight line) and rolls every
+still out at each of the S steps under each class: interp.gif, one row per step and one column per class, and interp.png, the same grid at
+the last predicted frame -- its first and last rows are the cells of draws 0 and 1.  ``--motion-from DIR --motion-class C`` (not with
+``--driver``; the checkpoint must hold the stage-2 encoder) reads and detects 33 frames of DIR exactly as ``--driver`` does, encodes their
+key points as a motion of class C (``FinalModel.encode``) and rolls every still out at z = mu under each class of ``--actions``: latent.gif
+and latent.png, one column per class.  This replays the motion through the generator's latent space, from the still's own pose; ``--driver``
+copies key points.
 
 Files, under <save_dir>/%04d/ per still in input order: input_im.png and current_points.png as evaluate.py writes them; classes.gif, the
 animated grid (row = draw, column = class, 33 frames, frame 0 = the still) with ONE palette over all cells and frames; with ``--overlay R``
@@ -89,6 +99,12 @@ def main(argv=None):
     parser.add_argument('--frames', type=int, default=None, help='predicted frames before resampling, a multiple of 32 (default 32): N / 32 chained motion-generator calls')
     parser.add_argument('--rate', type=int, default=None, help='1..64 (default 1): F - 1 frames between every two predicted ones; the GIFs play at F x --gif-fps')
     parser.add_argument('--resample', type=str, default=None, help='linear or cubic (default): how --rate places the key points in between')
+    parser.add_argument('--interpolate', type=int, default=None, metavar='S',
+                        help='2..64: also roll every still out at S steps of z between the seeded draws 0 and 1 (needs --samples >= 2): interp.gif, interp.png')
+    parser.add_argument('--interp-mode', type=str, default=None, help='with --interpolate: slerp (default) or lerp')
+    parser.add_argument('--motion-from', type=str, default=None, metavar='DIR',
+                        help='a directory of >= 33 frames of a video whose motion is encoded by the stage-2 encoder and replayed from every still at z = mu: latent.gif, latent.png')
+    parser.add_argument('--motion-class', type=int, default=None, metavar='C', help='with --motion-from: the action class of that motion')
     parser.add_argument('--gif-fps', type=int, default=10, help='frames per second, 1..50 (default 10); with --rate F the GIFs play at F times this')
     parser.add_argument('--gif-dither', type=int, default=0, help='amplitude of the 4x4 ordered dither, 0..64 (default 0: none)')
     parser.add_argument('--video', action='store_true',
@@ -152,6 +168,27 @@ def main(argv=None):
         parser.error('--video-fps %d x --rate %d = %d frames per second, and the AVIs play at most %d: lower --video-fps'
                      % (video_fps, rate, video_fps * rate, VIDEO_FPS_RANGE[1]))
     n_frames = 1 + n_pred * rate                           # the still, then T' = frames x rate predicted frames
+    if args.interp_mode is not None and args.interpolate is None:
+        parser.error('--interp-mode chooses the path of --interpolate and needs it')
+    interp_mode = args.interp_mode or 'slerp'
+    if interp_mode not in ('lerp', 'slerp'):
+        parser.error('--interp-mode takes lerp or slerp (got %r)' % args.interp_mode)
+    if args.interpolate is not None:
+        if not 2 <= args.interpolate <= 64:
+            parser.error('--interpolate takes 2..64 steps (got %d)' % args.interpolate)
+        if args.checkpoint_stage2 is None:
+            parser.error('--interpolate walks the latent space of the motion generator and needs --checkpoint_stage2')
+        if (1 if args.samples is None else args.samples) < 2:
+            parser.error('--interpolate joins the seeded draws 0 and 1 and needs --samples >= 2')
+    if (args.motion_from is None) != (args.motion_class is None):
+        parser.error('--motion-from and --motion-class go together: the encoder reads a motion and its class')
+    if args.motion_from is not None:
+        if args.driver is not None:
+            parser.error('--motion-from replays a motion through the latent space and --driver copies its key points: give one of them')
+        if args.checkpoint_stage2 is None:
+            parser.error('--motion-from encodes the motion with the stage-2 encoder and needs --checkpoint_stage2')
+    if (args.interpolate is not None or args.motion_from is not None) and (n_pred, rate) != (32, 1):
+        parser.error('--interpolate and --motion-from roll one 32-frame segment out at a given z: not with --frames or --rate')
     if not DITHER_RANGE[0] <= args.gif_dither <= DITHER_RANGE[1]:
         parser.error('--gif-dither takes an amplitude in %d..%d (got %d)' % (DITHER_RANGE + (args.gif_dither,)))
     if not 0 <= args.overlay <= stills.MAX_RADIUS:
@@ -182,6 +219,15 @@ def main(argv=None):
             u8, info = stills.fit(path, own, what='--box' if own is box else 'the manifest box', image_size=size)
             fitted.append(u8)
             records.append(info)
+        if args.motion_class is not None and not 0 <= args.motion_class < n_action:
+            raise ValueError('--motion-class takes a class in [0, %d) (got %d)' % (n_action, args.motion_class))
+        if args.interpolate is not None:
+            stills.check_grid(args.interpolate, len(actions), size, size, frames=n_frames)
+        motion = None
+        if args.motion_from is not None:                 # read as --driver reads its frames
+            paths, idx, n_found = stills.driver_frames(args.motion_from, '--motion-from')
+            motion = {'paths': paths, 'frames': idx, 'n_found': n_found,
+                      'u8': np.stack([stills.fit(p, None, what='--motion-from', image_size=size)[0] for p in paths])}
         driver = None
         if args.driver is not None:
             driver_box = stills.parse_box(args.driver_box, '--driver-box') if args.driver_box is not None else None
@@ -201,7 +247,8 @@ def main(argv=None):
     from kpx_amd.data import _to_device_unit
     ops = kpx_amd.ops
     dev = torch.device('cuda', 0)
-    model = kpx_amd.FinalModel(config, device=dev, image_size=size, point_maps=True, colors_seed=args.colors_seed)
+    model = kpx_amd.FinalModel(config, device=dev, image_size=size, point_maps=True, colors_seed=args.colors_seed,
+                               **({'posterior': True} if motion is not None else {}))
     model.build(None)
     for p in checkpoints:
         model.restore(None, p, **({'ema': True} if args.ema else {}))
@@ -213,6 +260,9 @@ def main(argv=None):
     if args.video and actions and max(samples, len(actions)) * size > ops.JPEG_MAX_SIDE:
         raise Exception('--video: the grid of %d draws x %d classes of %d x %d cells is larger than the %d pixels a side a JPEG frame of '
                         'classes.avi holds' % (samples, len(actions), size, size, ops.JPEG_MAX_SIDE))
+    if args.video and args.interpolate is not None and max(args.interpolate, len(actions)) * size > ops.JPEG_MAX_SIDE:
+        raise Exception('--video: the grid of %d steps x %d classes of %d x %d cells is larger than the %d pixels a side a JPEG frame of '
+                        'interp.avi holds' % (args.interpolate, len(actions), size, size, ops.JPEG_MAX_SIDE))
     video_bytes = {}
 
     def write_videos(name, canvas):                        # beside <name>.gif, from the same canvas
@@ -224,6 +274,7 @@ def main(argv=None):
     n_cls = len(actions) if actions else 0
     layers = 2 if radius else 1
     per_still = n_frames * size * size * 3 * layers * ((samples * n_cls if actions else 0) + (2 if driver else 0))
+    per_still += n_frames * size * size * 3 * n_cls * ((args.interpolate or 0) + (1 if motion else 0))
     batch = stills.batch_under(args.batch, per_still)
     zs = None
     if actions:
@@ -234,8 +285,18 @@ def main(argv=None):
         frames = _to_device_unit(driver['u8'], dev)                                        # [33,R,R,3]
         pts = model.detect(frames)                                                         # [33,K,2]
         drv = {'image': frames[:1], 'seq': frames[1:].unsqueeze(0), 'first_pt': pts[:1].contiguous(), 'seq_pt': pts[1:].unsqueeze(0).contiguous()}
+    z_path = z_motion = None
+    if args.interpolate is not None:                   # [S, 1, V]: the steps between the seeded draws 0 and 1 of segment 0
+        z_path = ops.latent_path(zs[0, :1].contiguous(), zs[1, :1].contiguous(), args.interpolate, interp_mode)
+    if motion is not None:
+        frames = _to_device_unit(motion['u8'], dev)                                        # [33,R,R,3]
+        pts = model.detect(frames)                                                         # [33,K,2]
+        code = torch.eye(n_action, dtype=torch.float32, device=dev)[args.motion_class:args.motion_class + 1].contiguous()
+        logit = model.encode(pts[:1].contiguous(), pts[1:].unsqueeze(0).contiguous(), code)
+        z_motion = ops.latent_sample(logit, None, 0.0)                                     # [1, V]: mu
     palette_sizes = {name: [] for name in (['classes'] if actions else []) + (['classes_overlay'] if actions and radius else [])
-                     + (['driven'] if driver else []) + (['driven_overlay'] if driver and radius else [])}
+                     + (['driven'] if driver else []) + (['driven_overlay'] if driver and radius else [])
+                     + (['interp'] if z_path is not None else []) + (['latent'] if z_motion is not None else [])}
     from PIL import Image
 
     for start in range(0, len(fitted), batch):
@@ -288,6 +349,23 @@ def main(argv=None):
                 first = over[:, 0, :size, :size].contiguous().cpu().numpy()
                 for i, d in enumerate(dirs):
                     Image.fromarray(first[i]).save(osp.join(d, 'overlay.png'))
+        for name, z_rows in (('interp', z_path), ('latent', z_motion)):
+            if z_rows is None:
+                continue
+            z_rows = z_rows.reshape(-1, model.vae_dim)                                     # one row of cells per z
+            codes = torch.eye(n_action, dtype=torch.float32, device=dev)[actions]
+            canvas = torch.empty((bsz, n_frames, z_rows.shape[0] * size, n_cls * size, 3), dtype=torch.uint8, device=dev)
+            for r in range(z_rows.shape[0]):
+                z = z_rows[r:r + 1].expand(bsz, -1).contiguous()
+                for a in range(n_cls):
+                    out = model.run(None, {'image': image, 'action_code': codes[a:a + 1].expand(bsz, -1).contiguous()}, z=z)
+                    ops.cell_frames(canvas, image, out['pred_im_seq'].contiguous(), r, a, 'unit')     # before the next run() replays the graph
+                    write_inputs(out)
+            palette_sizes[name] += stills.write_grid_gifs(gifs, canvas, [osp.join(d, name + '.gif') for d in dirs])
+            write_videos(name, canvas)
+            last = canvas[:, n_frames - 1].contiguous().cpu().numpy()                      # the grid at the last predicted frame
+            for i, d in enumerate(dirs):
+                Image.fromarray(last[i]).save(osp.join(d, name + '.png'))
         if drv is not None:
             tile = lambda t: t.expand((bsz,) + tuple(t.shape[1:])).contiguous()
             out = model.run(None, {'image': image}, drive={'mode': driver_mode, 'first': tile(drv['first_pt']), 'seq': tile(drv['seq_pt']),
@@ -320,6 +398,11 @@ def main(argv=None):
         meta['video'] = {'fps': video_fps * rate, 'quality': video_quality, 'bytes': video_bytes}
     if actions:
         meta.update({'actions': actions, 'draws': samples, 'seed': seed, 'grid': [samples, n_cls], 'sheet_frames': sheet_frames})
+    if z_path is not None:
+        meta['interpolate'] = {'steps': args.interpolate, 'mode': interp_mode, 'draws': [0, 1], 'grid': [args.interpolate, n_cls]}
+    if motion is not None:
+        meta['motion_from'] = {'dir': args.motion_from, 'n_found': motion['n_found'], 'frames': motion['frames'], 'files': motion['paths'],
+                               'class': args.motion_class, 'z': 'mu', 'grid': [1, n_cls]}
     if driver is not None:
         meta['driver'] = {'dir': args.driver, 'n_found': driver['n_found'], 'frames': driver['frames'], 'files': driver['paths'],
                           'mode': driver_mode, 'scaled': bool(args.driver_scaled),

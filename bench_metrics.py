@@ -155,6 +155,15 @@
 33. The configs[4] rollout without anything, with what --gif adds and with what --video adds (``kpx_amd.mjpeg.RolloutVideos.write``: both
    canvases composed, coded, copied and written as 128 AVI files), alternated in one process; ms per rollout and per sample of each.
 
+``--posterior`` measures the posterior tools (evaluate.py --posterior) instead:
+
+34. kpx_latent_stats_add_f64 (B = 64, V = 64, nine groups, kl_rows), kpx_latent_sample_f32 and kpx_latent_path_f32 (eight slerp steps): device-event
+   time of each launch after warm-up, min / median / max us, beside a device copy of the logit rows (32 KB) in the same process.  All three are
+   launch-latency-bound at these sizes; the statistics launch is one workgroup by design (determinism).
+35. ``FinalModel.encode`` at B = 64, K = 40 (replayed HIP graph), wall-clock ms, and the rollout of configs[4] at n_pts = 40 without and with what
+   --posterior adds per batch (encode, latent_stats_add, the copy of the rows, z = mu, one more rollout), alternated; median ms of each and the
+   quotient.  The flag adds one rollout: roughly 2 is expected, and there is no target.
+
 Prints one JSON line.
 """
 import argparse
@@ -1706,6 +1715,73 @@ def long_rollout_leg(dev, rollouts):
     return res
 
 
+def posterior_kernel_leg(dev, launches):
+    from kpx_amd import ops, posterior
+    g = torch.Generator(device=dev).manual_seed(11)
+    v, groups, steps = 64, 9, 8
+    logit = torch.rand((B, 2 * v), generator=g, device=dev)
+    eps = torch.randn((B, v), generator=g, device=dev)
+    group = torch.randint(0, groups, (B,), generator=g, device=dev).to(torch.int32)
+    state, counts = posterior.new_state(groups, v, dev)
+    rows, z = torch.empty(B, dtype=torch.float64, device=dev), torch.empty((B, v), device=dev)
+    path, dst = torch.empty((steps, B, v), device=dev), torch.empty_like(logit)
+    stats = lambda us: {'median_us': round(statistics.median(us), 1), 'min_us': round(min(us), 1), 'max_us': round(max(us), 1)}
+    res = {'batch': B, 'vae_dim': v, 'groups': groups, 'path_steps': steps, 'launches': launches, 'logit_kb': round(logit.numel() * 4 / 1e3, 1)}
+    res['stats_add'] = stats(_event_times(lambda: ops.latent_stats_add(logit, state, counts, group, kl_rows=rows), launches, dev))
+    res['sample'] = stats(_event_times(lambda: ops.latent_sample(logit, eps, 1.0, out=z), launches, dev))
+    res['path_slerp'] = stats(_event_times(lambda: ops.latent_path(z, eps, steps, 'slerp', out=path), launches, dev))
+    res['device_copy_of_logit'] = stats(_event_times(lambda: dst.copy_(logit), launches, dev))
+    assert bool(torch.isfinite(state).all()) and bool(torch.isfinite(path).all()) and int(counts[:, 0].sum()) > 0
+    return res
+
+
+def posterior_rollout_leg(dev, rollouts):
+    """encode at B = 64, K = 40, and the configs[4] rollout without and with what --posterior adds per batch: one encode, one
+    latent_stats_add, the copy of the logit rows, z = mu and one more rollout"""
+    import kpx_amd
+    from kpx_amd import ops, posterior
+    k = NOVELTY_K
+    cfg = {'model': {'n_pts': k, 'cell_info': [1024, 1024], 'vae_dim': 64, 'n_action': 9}, 'paths': {'log_dir': '/tmp/kpx_bench'}}
+    g = torch.Generator(device=dev).manual_seed(7)
+    im = torch.rand((B, RES, RES, 3), generator=g, device=dev) * 2 - 1
+    act = torch.eye(9, device=dev)[torch.randint(0, 9, (B,), generator=g, device=dev)]
+    z = torch.randn((B, 64), generator=g, device=dev)
+    kp = torch.rand((B, k, 2), generator=g, device=dev) * 1.6 - 0.8
+    seq = torch.rand((B, 32, k, 2), generator=g, device=dev) * 1.6 - 0.8
+    feed = {'image': im, 'action_code': act}
+    fm = kpx_amd.FinalModel(cfg, device=dev, image_size=RES, frames_per_launch=256, posterior=True)
+    fm.build()
+    state, counts = posterior.new_state(9, 64, dev)
+    group = act.argmax(dim=1).to(torch.int32)
+    for _ in range(3):                                    # eager, capture, one replay
+        fm.run(None, feed, z=z)
+        fm.encode(kp, seq, act)
+    torch.cuda.synchronize(dev)
+    enc = []
+    for _ in range(max(rollouts, 10)):
+        t0 = time.perf_counter()
+        fm.encode(kp, seq, act)
+        torch.cuda.synchronize(dev)
+        enc.append((time.perf_counter() - t0) * 1e3)
+    ms, kept = {False: [], True: []}, []
+    for _ in range(rollouts):
+        for on in (False, True):
+            t0 = time.perf_counter()
+            fm.run(None, feed, z=z)
+            if on:                                        # evaluate._Posterior.end_batch without the files
+                logit = fm.encode(kp, seq, act)
+                ops.latent_stats_add(logit, state, counts, group)
+                kept.append(logit.clone())
+                fm.run(None, feed, z=ops.latent_sample(logit, None, 0.0))
+            torch.cuda.synchronize(dev)
+            ms[on].append((time.perf_counter() - t0) * 1e3)
+    off, on = statistics.median(ms[False]), statistics.median(ms[True])
+    return {'batch': B, 'n_points': k, 'rollouts_each': rollouts, 'graph_replay': len(fm._graphs) == 2 and not fm._graph_failed,
+            'encode_ms': round(statistics.median(enc), 3), 'encode_ms_all': [round(x, 3) for x in enc],
+            'off_ms': round(off, 3), 'on_ms': round(on, 3), 'delta_ms': round(on - off, 3), 'on_over_off': round(on / off, 4),
+            'off_ms_all': [round(x, 2) for x in ms[False]], 'on_ms_all': [round(x, 2) for x in ms[True]]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--launches', type=int, default=40)
@@ -1746,7 +1822,17 @@ def main():
     ap.add_argument('--video', action='store_true',
                     help='measure the Motion-JPEG AVIs of rollouts (the JPEG coder beside a device copy and the host PIL route, the cost of '
                          '--video per configs[4] rollout beside --gif, all in this process) instead')
+    ap.add_argument('--posterior', action='store_true',
+                    help='measure the posterior tools (the three latent launches beside a device copy, FinalModel.encode at B = 64, K = 40, the cost '
+                         'of --posterior per configs[4] rollout, all in this process) instead')
     args = ap.parse_args()
+    if args.posterior:
+        if not torch.cuda.is_available():
+            raise SystemExit('bench_metrics.py needs the MI355X')
+        dev = torch.device('cuda:0')
+        kernels = posterior_kernel_leg(dev, args.launches)
+        print(json.dumps({'posterior_kernels': kernels, 'posterior_rollout_c4': posterior_rollout_leg(dev, args.rollouts)}))
+        return
     if args.video:
         if not torch.cuda.is_available():
             raise SystemExit('bench_metrics.py needs the MI355X')

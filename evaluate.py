@@ -11,6 +11,7 @@
                        [--video [--video-fps N] [--video-quality Q] [--frames N] [--rate F [--resample linear|cubic]]]
                        [--metrics --novelty [--novelty-sheets] [--novelty-no-mirror]]
                        [--metrics --prdc [--prdc-k K]]
+                       [--posterior [--posterior-transfer] [--posterior-au T]]
 
 One source image -> 32 predicted frames per sample (FinalModel).  PNG writer semantics as the reference (:137-156).  Per sample, as the
 reference: input_im.png, real_seq/ (data path only), pred_seq/, mask/, crude/, and the colourised key-points current_points.png and
@@ -141,6 +142,21 @@ arrays (per comparison the four scores, the set sizes, every row's squared radiu
 and parities, which ``python -m kpx_amd.prdc prdc.npz [--k K]`` re-scores on the CPU.  These are the project's own key-point-space and
 recogniser-space quantities, not comparable with published figures; precision and recall are unstable for unequal set sizes.  Without the
 flag every output keeps its bytes.
+
+``--posterior`` (data path only; not with ``--drive-only``; the stage-2 checkpoint must hold ``vae_encoder/*``) reads the one trained network
+the other flags ignore: per batch, after everything else of the batch, ``FinalModel.encode`` maps the pseudo labels of the real motion to
+logit = [mu | sigma], ``kpx_amd.ops.latent_stats_add`` accumulates them per class and latent dimension on the device (fp64, a fixed order:
+a set fed in pieces leaves the bits of one call), and one more rollout runs at z = mu (``kpx_amd.ops.latent_sample(logit, None, 0)``): per
+sample ``post_seq/`` and ``post_points/``; with ``--metrics`` ``post_ssim``, ``post_psnr``, ``post_mse`` [samples, 32] in metrics.npz, with
+``--motion-metrics`` also ``post_kp_l2``; a ``posterior`` block in metrics.json (``kpx_amd.posterior.summarise_posterior`` and
+``summarise_recon``): KL per dimension, active units (``--posterior-au T``, default 0.01), dead mu / sigma shares, the KL of the aggregate
+posterior's marginals to the prior, the same per class, the ``recon`` scores and, with ``--drive hold``, ``z_skill`` = (model - hold) /
+(posterior - hold).  ``--posterior-transfer`` (not with ``--no-save``) also decodes the mu of sample (b + 1) mod B from sample b's image, first
+pose and class: ``post_transfer/`` and the sheet ``posterior.png`` with the rows real | recon | model (draw 0) | driver | transfer at the
+``--sheet-frames`` frames.  ``<save_dir>/posterior.npz`` keeps the logit rows, classes, state and counts, which
+``python -m kpx_amd.posterior posterior.npz [--au T]`` summarises again without a GPU.  Nothing here draws a random number: without the flags
+every output keeps its bytes, and with them every other output does.  This project's own diagnostics on its own pseudo labels, not
+comparable with published figures.
 """
 import json
 import os
@@ -970,7 +986,7 @@ def _drive_line(blk):
 
 
 def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_scores=None, action_scores=None, drive_scores=None,
-                   frechet=None, accuracy=None, novelty=None, prdc=None):
+                   frechet=None, accuracy=None, novelty=None, prdc=None, posterior=None):
     """scores: per batch a device tensor [draws, B * T, 3] = (ssim, mse, psnr); one copy to the host for all of them.
     vgg_scores (--vgg-metrics): per batch a device tensor [draws, B * T, 5, 2] = per layer (cos_layer, l1_layer).
     motion_scores (--motion-metrics): {'kp_l2': per batch [draws, B, T]} and for two or more draws {'kp_div': per batch [B, T], 'div_mse':
@@ -980,7 +996,7 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     drive_scores (--drive labels / hold): {mode: per batch [B * T, 3] = (ssim, mse, psnr)}.
     frechet (--frechet): the accumulators {'real_even', 'real_odd', 'pred', 'pred_draw0'}; also writes frechet.npz.
     accuracy (--action-accuracy): the _ActionAccuracy of the run.  novelty (--novelty): the _Novelty of the run.  prdc (--prdc): the _Prdc
-    of the run; also writes prdc.npz."""
+    of the run; also writes prdc.npz.  posterior (--posterior): the _Posterior of the run; also writes posterior.npz."""
     host = torch.cat(scores, dim=1).cpu().numpy() if scores else np.zeros((n_draws, 0, 3), np.float32)
     arr = host.reshape(n_draws, -1, n_frames, 3).transpose(1, 0, 2, 3)                  # [S, N, T, 3]
     ssim, mse, psnr = (np.ascontiguousarray(arr[..., i]) for i in range(3))
@@ -1040,6 +1056,11 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         arrays.update(novelty.arrays())
     if prdc is not None:
         arrays.update(prdc.arrays(save_dir))
+    posterior_block = None
+    if posterior is not None:
+        posterior_arrays, posterior_block = posterior.finish(save_dir, n_frames, {'ssim': ssim, 'psnr': psnr, 'mse': mse},
+                                                             drive.get('hold') if drive is not None else None)
+        arrays.update(posterior_arrays)
     os.makedirs(save_dir, exist_ok=True)
     np.savez(osp.join(save_dir, 'metrics.npz'), **arrays)
     res = summarise_metrics(ssim, psnr, mse, extras=extras, motion=motion)
@@ -1057,6 +1078,8 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
         res['novelty'] = summarise_novelty(arrays, mirror=novelty.mirror)
     if prdc is not None:
         res['prdc'] = prdc.P.summarise(arrays)
+    if posterior_block is not None:
+        res['posterior'] = posterior_block
     with open(osp.join(save_dir, 'metrics.json'), 'w') as f:
         json.dump(res, f, indent=1, allow_nan=False)
     fmt = lambda v, spec: 'n/a' if v is None else spec % v
@@ -1100,6 +1123,139 @@ def _write_metrics(save_dir, scores, n_draws, n_frames, vgg_scores=None, motion_
     print('%s; %d non-finite frames' % (line, res['n_nonfinite']))
     if drive is not None:
         print(_drive_line(res['drive']))
+    if posterior_block is not None:
+        print(_Posterior.line(posterior_block))
+
+
+POSTERIOR_ROWS = ('real', 'recon', 'model', 'driver', 'transfer')                  # the rows of posterior.png, in order
+
+
+def summarise_recon(post, model=None, hold=None):
+    """The ``recon`` (and ``z_skill``) entries of the ``posterior`` block; numpy only.  post: {'ssim', 'psnr', 'mse'[, 'kp_l2']: [S, T]}, the
+    scores of the rollout at z = mu; model: the model's own {'ssim', 'psnr', 'mse': [S, N, T]}; hold: --drive hold's {'ssim', 'psnr',
+    'mse': [S, T]}, or None when it did not run.  z_skill = (model - hold) / (posterior - hold) on the means, null as summarise_drive's
+    skill is."""
+    out = {'recon': {}}
+    for name, x in post.items():
+        x = np.asarray(x, np.float64)
+        with np.errstate(invalid='ignore', over='ignore'):
+            out['recon'][name] = {'mean': _json_num(x.mean()) if x.size else None,
+                                  'per_frame': [_json_num(v) for v in x.mean(axis=0)] if x.shape[0] else [None] * x.shape[1]}
+    if model is not None and hold is not None:
+        out['z_skill'] = {}
+        for name in DRIVE_METRICS:
+            own, floor = np.asarray(model[name], np.float64), np.asarray(hold[name], np.float64)
+            with np.errstate(invalid='ignore', over='ignore'):
+                m, f = (own.mean() if own.size else np.nan), (floor.mean() if floor.size else np.nan)
+                top = out['recon'][name]['mean']
+                ok = top is not None and np.isfinite(m) and np.isfinite(f) and top != f
+                out['z_skill'][name] = _json_num((m - f) / (top - f)) if ok else None
+    return out
+
+
+class _Posterior:
+    """--posterior: per batch one encode, one latent_stats_add with the sample's class as its group and one more rollout at z = mu (with
+    --posterior-transfer a second one at the mu of the next sample of the batch); the logit rows stay on the device until the last batch.
+    Nothing here draws a random number, and everything runs after the batch's other rollouts have been consumed."""
+
+    def __init__(self, kpx_amd, model, n_action, transfer, au, sheet_frames, save, metrics, motion, dev):
+        self.P, self.ops, self.model, self.n_action, self.transfer, self.au = kpx_amd.posterior, kpx_amd.ops, model, n_action, transfer, au
+        self.sheet_frames, self.save, self.metrics, self.motion, self.dev = sheet_frames, save, metrics, motion, dev
+        self.state, self.counts = self.P.new_state(n_action, model.vae_dim, dev)
+        self.rows, self.classes, self.kl_rows, self.scores, self.kp_l2 = [], [], [], [], []
+        self.sheet = None
+
+    def _paste(self, row, image, seq):
+        r = POSTERIOR_ROWS.index(row)
+        self.ops.sheet_paste(self.sheet, image.unsqueeze(1), [0], r, 0, 'unit')
+        self.ops.sheet_paste(self.sheet, seq, self.sheet_frames, r, 1, 'unit')
+
+    def begin_batch(self, batch):
+        """before the batch's own rollout: the canvas of posterior.png with the rows that need no rollout"""
+        if not (self.transfer and self.save):
+            return
+        image, real = batch['image'].contiguous(), batch['real_im_seq'].contiguous()
+        bsz, (h, w) = image.shape[0], image.shape[1:3]
+        shift = 1 % bsz
+        self.sheet = torch.empty((bsz, len(POSTERIOR_ROWS) * h, (1 + len(self.sheet_frames)) * w, 3), dtype=torch.uint8, device=self.dev)
+        self._paste('real', image, real)
+        self._paste('driver', torch.roll(image, -shift, 0), torch.roll(real, -shift, 0).contiguous())
+
+    def own_draw0(self, outputs):
+        """draw 0 of the batch's own rollout, before anything replays its graph"""
+        if self.sheet is not None:
+            self._paste('model', outputs['im'].contiguous(), outputs['pred_im_seq'].contiguous())
+
+    def end_batch(self, save_dir, first_sample, batch, real_flat):
+        """after everything else of the batch; -> the frames predicted"""
+        ops, bsz = self.ops, batch['image'].shape[0]
+        logit = self.model.encode(batch['keypoints'].contiguous(), batch['real_seq'].contiguous(), batch['action_code'].contiguous())
+        group = batch['action_code'].argmax(dim=1).to(torch.int32)
+        self.kl_rows.append(ops.latent_stats_add(logit, self.state, self.counts, group))
+        self.rows.append(logit.clone())              # a copy: the encoder's buffer is overwritten by the next replay
+        self.classes.append(group)
+        mu = ops.latent_sample(logit, None, 0.0)
+        feed = {'image': batch['image'], 'action_code': batch['action_code']}
+        runs = [('post', mu)] + ([('post_transfer', torch.roll(mu, -(1 % bsz), 0).contiguous())] if self.transfer else [])
+        for name, z in runs:
+            out = self.model.run(None, feed, z=z)
+            pred = out['pred_im_seq'].contiguous()   # consumed before the next run() overwrites the graph's output buffers
+            if name == 'post' and self.metrics:
+                self.scores.append(ops.frame_metrics(pred.reshape(-1, *pred.shape[2:]), real_flat, png8=True))
+                if self.motion:
+                    self.kp_l2.append(ops.keypoint_draw_metrics(out['fut_pt_raw'].contiguous().unsqueeze(0), batch['real_seq'].contiguous(),
+                                                                diversity=False)[0][0])
+            if self.sheet is not None:
+                self._paste('recon' if name == 'post' else 'transfer', batch['image'].contiguous(), pred)
+            if self.save:
+                frames = pred.cpu().numpy()
+                points = out['future_points'].cpu().numpy() if name == 'post' else None
+                for batch_idx in range(bsz):
+                    d = osp.join(save_dir, '%04d' % (first_sample + batch_idx))
+                    _save_img_sequence(osp.join(d, 'post_seq' if name == 'post' else name), frames[batch_idx], rescale=True)
+                    if points is not None:
+                        _save_img_sequence(osp.join(d, 'post_points'), points[batch_idx], rescale=False)
+        if self.sheet is not None:
+            from PIL import Image
+            host = _sheet_to_host(self.sheet)
+            for batch_idx in range(bsz):
+                Image.fromarray(host[batch_idx]).save(osp.join(save_dir, '%04d' % (first_sample + batch_idx), 'posterior.png'))
+            self.sheet = None
+        return bsz * N_FUTURE_FRAMES * len(runs)
+
+    def finish(self, save_dir, n_frames, model_scores=None, hold=None):
+        """after the last batch -> (the post_* arrays of metrics.npz, the ``posterior`` block); writes <save_dir>/posterior.npz"""
+        v = self.model.vae_dim
+        cat = lambda ts, shape, dtype: torch.cat(ts, dim=0).cpu().numpy() if ts else np.zeros(shape, dtype)
+        state, counts = self.state.cpu().numpy(), self.counts.cpu().numpy()
+        os.makedirs(save_dir, exist_ok=True)
+        np.savez(osp.join(save_dir, 'posterior.npz'), logit=cat(self.rows, (0, 2 * v), np.float32), classes=cat(self.classes, (0,), np.int32),
+                 kl_rows=cat(self.kl_rows, (0,), np.float64), state=state, counts=counts, au_threshold=np.float64(self.au))
+        block = self.P.summarise_posterior(state, counts, self.au)
+        arrays = {}
+        if self.metrics:
+            host = cat(self.scores, (0, 3), np.float32).reshape(-1, n_frames, 3)
+            for i, name in enumerate(('ssim', 'mse', 'psnr')):
+                arrays['post_' + name] = np.ascontiguousarray(host[..., i])
+            if self.motion:
+                arrays['post_kp_l2'] = cat(self.kp_l2, (0, n_frames), np.float32).reshape(-1, n_frames)
+            block.update(summarise_recon({key[5:]: x for key, x in arrays.items()}, model_scores, hold))
+        return arrays, block
+
+    @staticmethod
+    def line(block):
+        fmt = lambda x, spec: 'n/a' if x is None else spec % x
+        if not block.get('n'):
+            return 'posterior (own quantity, not comparable with published figures): no rows'
+        text = ('posterior (own quantity, not comparable with published figures): %d rows, KL %s nats, active units %d of %d, dead sigma share %s, '
+                'aggregate KL to the prior %s' % (block['n'], fmt(block['kl_total'], '%.4f'), block['active_units'], block['vae_dim'],
+                                                  fmt(float(np.mean(block['dead_sigma_share'])), '%.3f'),
+                                                  fmt(block['agg_kl_total'], '%.4f')))
+        if 'recon' in block:
+            text += ', recon SSIM %s, PSNR %s dB' % (fmt(block['recon']['ssim']['mean'], '%.4f'), fmt(block['recon']['psnr']['mean'], '%.2f'))
+        if 'z_skill' in block:
+            text += ', z skill SSIM %s, PSNR %s' % (fmt(block['z_skill']['ssim'], '%.3f'), fmt(block['z_skill']['psnr'], '%.3f'))
+        return text
 
 
 class _LongRollout:
@@ -1240,7 +1396,29 @@ def main(argv=None):
                              'per sample long.gif / long.avi and long_points.npy, <save_dir>/long.json with the speed curve and the seam ratio')
     parser.add_argument('--rate', type=int, default=None, help='with --gif or --video: resample the second rollout to F = 1..64 times the frames (default 1); long.gif plays at F x --gif-fps, long.avi at F x --video-fps')
     parser.add_argument('--resample', type=str, default=None, help='with --rate: linear or cubic (default)')
+    parser.add_argument('--posterior', action='store_true',
+                        help='encode the real motion of every sample with the stage-2 encoder (needs a checkpoint with vae_encoder/*): one more '
+                             'rollout at z = mu (post_seq/, post_points/; with --metrics post_ssim ... in metrics.npz), the KL per latent '
+                             'dimension, active units and the distance of the aggregate posterior from the prior (a posterior block in '
+                             "metrics.json), <save_dir>/posterior.npz keeps the rows.  This project's own quantities: not comparable with "
+                             'published figures')
+    parser.add_argument('--posterior-transfer', action='store_true',
+                        help="with --posterior: also decode the mu of the batch's next sample from each sample's image, first pose and class: "
+                             'post_transfer/ and the sheet posterior.png (--sheet-frames picks the frames)')
+    parser.add_argument('--posterior-au', type=float, default=None, metavar='T',
+                        help='with --posterior: a latent unit is active when the variance of its mu over the samples exceeds T (default 0.01)')
     args = parser.parse_args(argv)
+    if (args.posterior_transfer or args.posterior_au is not None) and not args.posterior:
+        parser.error('--posterior-transfer and --posterior-au shape the outputs of --posterior and need it')
+    if args.posterior and args.synthetic:
+        parser.error('--posterior encodes the pseudo labels of real videos, and --synthetic inputs have none')
+    if args.posterior and args.drive_only:
+        parser.error("--drive-only skips the model's own rollout and needs no stage-2 checkpoint, which --posterior reads the encoder from")
+    if args.posterior_transfer and args.no_save:
+        parser.error('--posterior-transfer writes files, and --no-save writes none')
+    posterior_au = 0.01 if args.posterior_au is None else args.posterior_au
+    if not (np.isfinite(posterior_au) and posterior_au >= 0):
+        parser.error('--posterior-au takes a finite threshold >= 0 (got %r)' % args.posterior_au)
     long_frames, long_rate = 32 if args.frames is None else args.frames, 1 if args.rate is None else args.rate
     want_long = args.frames is not None or args.rate is not None
     if args.resample is not None and args.rate is None:
@@ -1310,7 +1488,7 @@ def main(argv=None):
     if want_long and args.video and video_fps * long_rate > 240:
         parser.error('--video-fps %d x --rate %d = %d frames per second, and long.avi plays at most 240: lower --video-fps'
                      % (video_fps, long_rate, video_fps * long_rate))
-    if args.sheet_frames is not None and args.actions is None and args.drive is None and not args.novelty_sheets:
+    if args.sheet_frames is not None and args.actions is None and args.drive is None and not args.novelty_sheets and not args.posterior_transfer:
         parser.error('--sheet-frames picks the frames of the sheets of --actions / --drive / --novelty-sheets and needs it')
     drive_modes = None
     if args.drive is not None:
@@ -1364,7 +1542,7 @@ def main(argv=None):
     if want_long:
         check_long_gif(size)
     actions = sheet_frames = None
-    if args.actions is not None or drive_modes is not None or args.novelty_sheets:
+    if args.actions is not None or drive_modes is not None or args.novelty_sheets or args.posterior_transfer:
         n_cls_all = config['model'].get('n_action', 9)
         try:
             if args.actions is not None:
@@ -1391,7 +1569,8 @@ def main(argv=None):
     vgg = None
     if args.vgg_metrics:
         vgg = kpx_amd.Vgg19(weights=kpx_amd.synthetic_vgg19_weights(), device=dev) if args.synthetic_vgg else kpx_amd.Vgg19(vggnet, device=dev)
-    model = kpx_amd.FinalModel(config, device=dev, image_size=size, point_maps=not args.no_save, colors_seed=args.colors_seed)
+    model = kpx_amd.FinalModel(config, device=dev, image_size=size, point_maps=not args.no_save, colors_seed=args.colors_seed,
+                               **({'posterior': True} if args.posterior else {}))
     print('model initialized')
     model.build(None)
     for p in checkpoints:                                            # reference :76-77: two partial restores by name
@@ -1428,6 +1607,8 @@ def main(argv=None):
             novelty = _Novelty(kpx_amd, config, dev, args.samples, actions, not args.novelty_no_mirror,
                                sheet_frames if args.novelty_sheets else None, model.colors)
         prdc = _Prdc(kpx_amd, dev, args.samples, actions, prdc_k, accuracy) if args.prdc else None
+        posterior = _Posterior(kpx_amd, model, n_action, args.posterior_transfer, posterior_au, sheet_frames, not args.no_save, args.metrics,
+                               args.motion_metrics, dev) if args.posterior else None
         n_read = 0                                                       # samples read so far: the listing line of a batch's first sample
         for batch in loader.batches(args.batch, dev, repeat=False, num_preprocess_threads=12):
             bsz = batch['image'].shape[0]
@@ -1480,6 +1661,8 @@ def main(argv=None):
                     novelty.begin_batch([line.split()[0] for line in loader._images[n_read - bsz:n_read]], batch)
                 if prdc is not None:
                     prdc.begin_batch(batch)
+            if posterior is not None:
+                posterior.begin_batch(batch)
             sweep = None
             if actions:
                 sweep = _ClassSweep(kpx_amd, model, actions, n_action, sheet_frames, batch['image'], batch['real_im_seq'], not args.no_save,
@@ -1546,6 +1729,8 @@ def main(argv=None):
                         anim.write(args.save_dir, sample_idx - bsz, [('real', batch['image'], batch['real_im_seq'], 'unit'),
                                                                      ('pred', outputs['im'], outputs['pred_im_seq'], 'unit'),
                                                                      ('points', outputs['current_points'], outputs['future_points'], 'raw')])
+                if posterior is not None and draw == 0:
+                    posterior.own_draw0(outputs)
                 if drive_modes and draw == 0:    # once per batch: the driven rollouts do not depend on z (their graphs are their own:
                     # this draw's own outputs stay), before the sweep replays the own rollout's graph
                     first = sample_idx - bsz if not args.no_save else 0
@@ -1566,6 +1751,8 @@ def main(argv=None):
                 novelty.end_batch(args.save_dir, n_read - bsz)
             if long_run is not None:         # after everything of the ordinary rollout: its own graph, its own files
                 frames += long_run.run(args.save_dir, sample_idx - bsz, batch['image'], batch['action_code'], z_first)
+            if posterior is not None:        # last: its rollouts replay the ordinary rollout's graph, whose outputs are all consumed by now
+                frames += posterior.end_batch(args.save_dir, sample_idx - bsz if not args.no_save else 0, batch, real_flat if args.metrics else None)
         torch.cuda.synchronize()
         print('iteration through test set finished: %d predicted frames, %.1f frames/sec' % (frames, frames / (time.time() - t0)))
         if actions and not args.no_save:
@@ -1581,7 +1768,9 @@ def main(argv=None):
             _write_drive_only_metrics(args.save_dir, drive_scores, n_frames)
         elif args.metrics:
             _write_metrics(args.save_dir, scores, args.samples, n_frames, vgg_scores, motion_scores, action_scores, drive_scores, frechet,
-                           accuracy, novelty, prdc)
+                           accuracy, novelty, prdc, posterior)
+        elif posterior is not None:          # without --metrics: posterior.npz and the printed line; the block is python -m kpx_amd.posterior's
+            print(_Posterior.line(posterior.finish(args.save_dir, n_frames)[1]))
         return
     for start in range(0, args.synthetic, args.batch):
         bsz = min(args.batch, args.synthetic - start)

@@ -1060,6 +1060,57 @@ size_t kpx_jpeg_workspace_bytes(int N, int H, int W);
 int kpx_jpeg_encode_u8(const uint8_t* rgb /*[N,H,W,3]*/, int N, int H, int W, const uint8_t* qtables /*HOST [2,64]*/, uint8_t* scans,
                        int64_t* offsets /*[N+1]*/, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The approximate posterior of the sequence VAE at inference (csrc/posterior.hip; evaluate.py --posterior, animate.py --interpolate and
+ * --motion-from, kpx_amd/posterior.py), DESIGN.md sections 2 and 4.4.  No reference counterpart: the reference drops vae_encoder at inference.
+ * Added without a version change, as the entries of csrc/prdc.hip and csrc/mjpeg.hip were: no existing signature moves.
+ *
+ * All three read logit = [mu | sigma] fp32 [B][2V], the output of networks.vae_encoder, exactly as kpx_vae_sample_kl_fwd_f32 reads it.
+ * Limits of all three: 1 <= V <= KPX_LATENT_MAX_DIM, B >= 1, B*2V < 2^31; fp32 and int32 arrays 4-byte, fp64 and int64 arrays 8-byte aligned.
+ * Anything else, or a null pointer that is not marked optional, is KPX_EINVAL before any device call.  One launch each on `stream`, no
+ * allocation, copy, synchronisation or atomics (capturable).
+ *
+ * kpx_latent_stats_add_f64 ADDS the B posteriors to a running set.
+ *   group     int32 [B] or NULL.  NULL: every row belongs to group 0 and G must be 1.
+ *   state     double [G][V][KPX_LATENT_STATE_FIELDS], read and written.  Per (group g, dimension v), over the rows added so far:
+ *               [0] sum mu   [1] sum mu^2   [2] sum sigma   [3] sum sigma^2   [4] sum kl   [5] #{mu == 0}   [6] #{sigma == 0}   [7] n
+ *             kl = 0.5 * ((((m * m) + s * s) - log((double)1e-8f + s * s)) - 1.0) with m = (double)mu, s = (double)sigma, every operation in
+ *             fp64 and rounded once in this order (no fma): the term of kpx_vae_sample_kl_fwd_f32 without its fp32 roundings.  The squares of
+ *             fp32 values are exact in fp64.  -0 counts as 0.  The counters [5], [6], [7] are whole numbers held in doubles.
+ *   counts    int64 [G][3], read and written.  [g][0] rows added to group g; [g][1] rows of group g left out because one of their 2V values
+ *             is NaN or +-Inf; [0][2] -- GROUP 0's third field, whatever G is -- rows left out because group[b] lies outside [0, G) (such
+ *             a row has no group of its own; its values are not looked at).  [g][2] for g > 0 is never written.
+ *   kl_rows   double [B] or NULL: sum_v kl of row b -- each wavefront's 64 terms (v = 64 w + lane, zeros past V) in the xor butterfly 32, 16, 8,
+ *             4, 2, 1, then the wavefronts' sums added in ascending w -- or NaN for a row that was left out.  A row's value depends on
+ *             that row and V alone.
+ *   A row that is left out changes nothing but its counter and its kl_rows entry.  Determinism is the contract: each column (g, v) is
+ *   summed in ascending b starting from the value `state` held (one thread owns it for the whole call), so a set fed in pieces of any
+ *   sizes leaves the bits that one call on the concatenation leaves.  G >= 1, G*V*8 < 2^31.
+ *
+ * kpx_latent_sample_f32: z[b][v] = fmaf(fl32(tau * sigma), eps, mu).  eps fp32 [B][V] or NULL.  With eps == NULL or tau == 0, z is mu bit
+ *   for bit and neither sigma nor eps is read, so a NaN there does not reach z.  With tau == 1 it is the z of kpx_vae_sample_kl_fwd_f32
+ *   bit for bit.  A NaN tau is KPX_EINVAL.
+ *
+ * kpx_latent_path_f32: S steps from za to zb, fp32 [B][V] each, out fp32 [S][B][V], 2 <= S <= KPX_LATENT_PATH_MAX_STEPS, S*B*V < 2^31.
+ *   out[0] = za and out[S-1] = zb bit for bit.  Step 0 < s < S-1 stands at t = (double)s / (double)(S - 1) and is
+ *   fl32(ca * (double)a + cb * (double)b), the two products and the sum in fp64, rounded once each (no fma), with
+ *     KPX_LATENT_PATH_LERP    ca = 1 - t, cb = t
+ *     KPX_LATENT_PATH_SLERP   per row: omega = acos(min(max(<a,b> / (sqrt(<a,a>) * sqrt(<b,b>)), -1), 1)), ca = sin((1 - t) * omega) / sin(omega),
+ *                             cb = sin(t * omega) / sin(omega).  The three dot products are fp64 sums of exact products: lane l of one
+ *                             wavefront adds v = l, l + 64, ... in ascending order from 0, then the 64 lane sums in the xor butterfly.
+ *   A SLERP row falls back to LERP (its bits) when <a,a> or <b,b> is not > 0 or when sin(omega) >= KPX_LATENT_PATH_MIN_SIN does not hold:
+ *   that is a = b, but also a = -b (omega = pi), whose path is then the straight line THROUGH 0, and any V = 1 row. */
+#define KPX_LATENT_MAX_DIM 1024
+#define KPX_LATENT_STATE_FIELDS 8
+#define KPX_LATENT_PATH_MAX_STEPS 64
+#define KPX_LATENT_PATH_MIN_SIN 1e-6
+enum { KPX_LATENT_PATH_LERP = 0, KPX_LATENT_PATH_SLERP = 1 };
+int kpx_latent_stats_add_f64(const float* logit /*[B,2V]*/, int B, int V, const int32_t* group /*[B] or NULL*/, int G,
+                             double* state /*[G,V,8]*/, int64_t* counts /*[G,3]*/, double* kl_rows /*[B] or NULL*/, void* stream);
+int kpx_latent_sample_f32(const float* logit /*[B,2V]*/, const float* eps /*[B,V] or NULL*/, float tau, float* z /*[B,V]*/, int B, int V,
+                          void* stream);
+int kpx_latent_path_f32(const float* za /*[B,V]*/, const float* zb /*[B,V]*/, int S, int mode, float* out /*[S,B,V]*/, int B, int V,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

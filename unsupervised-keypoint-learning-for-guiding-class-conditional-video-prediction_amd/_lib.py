@@ -188,6 +188,9 @@ SIGNATURES = {
     'kpx_jpeg_scan_bound': (c_size_t, [c_int, c_int]),
     'kpx_jpeg_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'kpx_jpeg_encode_u8': (c_int, [P, c_int, c_int, c_int, P, P, P, P, c_size_t, P]),
+    'kpx_latent_stats_add_f64': (c_int, [P, c_int, c_int, P, c_int, P, P, P, P]),
+    'kpx_latent_sample_f32': (c_int, [P, P, c_float, P, c_int, c_int, P]),
+    'kpx_latent_path_f32': (c_int, [P, P, c_int, c_int, P, c_int, c_int, P]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

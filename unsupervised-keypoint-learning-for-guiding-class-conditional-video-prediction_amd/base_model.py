@@ -467,10 +467,14 @@ class BaseModel(ABC):
             arrays = read_selected(checkpoint_path)
         else:
             arrays = self.read_checkpoint(checkpoint_path)
+        self._check_restore(arrays, checkpoint_path)
         self.store.load_numpy(arrays, strict=False)
         self._restore_extra(arrays)
         self._restore_ema(arrays, checkpoint_path)
         return sorted(arrays)
+
+    def _check_restore(self, arrays, checkpoint_path):
+        """What a model asks of a checkpoint beyond the reference's restore-by-intersection; raises before anything is loaded."""
 
     @staticmethod
     def read_checkpoint(checkpoint_path):

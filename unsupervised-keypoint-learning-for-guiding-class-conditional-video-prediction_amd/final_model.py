@@ -16,6 +16,11 @@ generator is fed once and then free-runs for 32 steps, so S calls are chained: s
 of frame 32 s in the place of the detected one -- in distribution by construction, which free-running the LSTM past step 32 is not.  The 32 S
 key-point frames then go through ``ops.points_resample`` (F - 1 frames between every two) and everything downstream runs on T' = 32 S F
 frames.  ``frames=32, rate=1`` is the reference's rollout, on the code path it always had.
+
+``FinalModel(posterior=True)`` also declares the stage-2 ``vae_encoder`` (the reference drops it at inference), and ``encode`` reads the
+approximate posterior of a real motion from it: logit = [mu | sigma], the input of ``ops.latent_sample`` / ``ops.latent_stats_add``
+(DESIGN.md section 2).  ``run(z=ops.latent_sample(logit, None, 0))`` is then the reconstruction.  Without the argument the variable set,
+the graphs and every output are what they were.
 """
 import logging
 import os
@@ -40,8 +45,10 @@ log = logging.getLogger('kpx')
 class FinalModel(BaseModel):
     name = 'final'            # reference :21
 
-    def __init__(self, config, device='cuda', image_size=IMAGE_SIZE, frames_per_launch=256, seed=1234, point_maps=False, colors_seed=0):
+    def __init__(self, config, device='cuda', image_size=IMAGE_SIZE, frames_per_launch=256, seed=1234, point_maps=False, colors_seed=0,
+                 posterior=False):
         super(FinalModel, self).__init__(False)
+        self.posterior = bool(posterior)                # also declare vae_encoder: encode()
         model_config = config['model']
         self.log_dir = config['paths']['log_dir']
         self.n_points = model_config['n_pts']
@@ -67,7 +74,75 @@ class FinalModel(BaseModel):
             networks.vae_decoder(Sym(b, self.vae_dim), Sym(b, 2 * k), Sym(b, self.n_action), self.cell_info, self.vae_dim, k)
             joint = Sym(b, self.heat_size, self.heat_size, (emb[-2].shape[-1] + 2 * k + 3) // 4 * 4)
             networks.translator(joint, False, final_res=r, cin=emb[-2].shape[-1] + 2 * k)
+            if self.posterior:            # declared last: the variables above keep their places and their initial values
+                networks.vae_encoder(Sym(b, N_FUTURE_FRAMES, 2 * k), Sym(b, 2 * k), Sym(b, self.n_action), self.cell_info, self.vae_dim)
         self.store.materialise()
+
+    def _check_restore(self, arrays, checkpoint_path):
+        """posterior=True: a stage-2 checkpoint (one that holds vae_decoder variables) must hold every vae_encoder variable too"""
+        if not self.posterior or not any(n.startswith('vae_decoder/') for n in arrays):
+            return
+        missing = [n for n in self.store.specs if n.startswith('vae_encoder/') and n not in arrays]
+        if missing:
+            raise ops._lib.KpxError('FinalModel(posterior=True): %s holds the motion generator without its encoder: %s is missing (and %d more); '
+                                    'encode() needs a checkpoint of train.py --mode motion_generator with vae_encoder/*'
+                                    % (checkpoint_path, missing[0], len(missing) - 1))
+
+    def encode(self, keypoints, real_seq, action_code):
+        """The approximate posterior of a real motion: keypoints [B,K,2] (the first pose), real_seq [B,32,K,2], action_code [B,A], the
+        training graph's inputs in its layout (MotionGeneratorModel._generate) -> logit fp32 [B, 2 vae_dim] = [mu | sigma], the output of
+        ``networks.vae_encoder``.  No gradients, no random numbers.  From the second call on a shape it is one replayed HIP graph, like run():
+        the result then lives in the graph's buffer until the next encode() of that shape."""
+        if not self.posterior:
+            raise ops._lib.KpxError('FinalModel.encode: this model was built without the encoder; construct it with FinalModel(..., posterior=True)')
+        b, k, t = (keypoints.shape[0] if isinstance(keypoints, torch.Tensor) and keypoints.dim() else 0), self.n_points, N_FUTURE_FRAMES
+        feeds = {'keypoints': (keypoints, (b, k, 2)), 'real_seq': (real_seq, (b, t, k, 2)), 'action_code': (action_code, (b, self.n_action))}
+        for name, (v, shape) in feeds.items():
+            if b < 1 or not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or tuple(v.shape) != shape or v.device != keypoints.device:
+                raise ops._lib.KpxError('FinalModel.encode: %s must be an fp32 tensor %s on one device (got %s)'
+                                        % (name, [('B' if b < 1 and i == 0 else s) for i, s in enumerate(shape)],
+                                           '%s %s on %s' % (tuple(v.shape), v.dtype, v.device) if isinstance(v, torch.Tensor) else type(v).__name__))
+        feeds = {name: v for name, (v, _) in feeds.items()}
+        if not (GRAPH and not self._graph_failed and keypoints.is_cuda):
+            return self._encode_eager(**feeds)
+        key = ('encode', b, keypoints.device.index)
+        ent = self._graphs.get(key)
+        if ent is not None and ent[3] != self.store.version:         # the parameters changed since the capture: as in run()
+            del self._graphs[key]
+            self._eager_runs[key] = 0
+            ent = None
+        if ent is None:
+            if self._eager_runs.get(key, 0) < 1:                     # one eager run first, as in run()
+                self._eager_runs[key] = 1
+                return self._encode_eager(**feeds)
+            static = {k_: torch.empty_like(v, memory_format=torch.contiguous_format) for k_, v in feeds.items()}
+            for k_, v in feeds.items():
+                static[k_].copy_(v)
+            graph = torch.cuda.CUDAGraph()
+            try:
+                with torch.cuda.graph(graph):
+                    out = self._encode_eager(**static)
+            except Exception as e:          # noqa: BLE001 -- whatever the runtime refuses: stay on the eager path
+                log.warning('HIP graph capture of the encoder failed (%s: %s); continuing with eager launches', type(e).__name__, e)
+                self._graph_failed = True
+                torch.cuda.synchronize(keypoints.device)
+                self.store.touch()
+                ops.reset_after_failed_capture()
+                return self._encode_eager(**feeds)
+            ent = self._graphs[key] = (graph, static, out, self.store.version)
+        graph, static, out, _ = ent
+        for k_, v in feeds.items():
+            v = v.contiguous()
+            ops.flat_copy_raw(v.data_ptr(), static[k_].data_ptr(), v.numel())
+        graph.replay()
+        return out
+
+    def _encode_eager(self, keypoints, real_seq, action_code):
+        """encode() enqueued launch by launch (also the function a capture records)"""
+        b, k2 = keypoints.shape[0], 2 * self.n_points
+        with variables.as_default(self.store), torch.no_grad():
+            return networks.vae_encoder(real_seq.reshape(b, N_FUTURE_FRAMES, k2), keypoints.reshape(b, k2).contiguous(), action_code.contiguous(),
+                                        self.cell_info, self.vae_dim)
 
     def run(self, sess, feed_dict, z=None, drive=None, frames=N_FUTURE_FRAMES, rate=1, resample='cubic'):
         """reference run (:124-125).  feed_dict: {'image': [B,H,W,3] in [-1,1], 'action_code': [B,n_action] one-hot,

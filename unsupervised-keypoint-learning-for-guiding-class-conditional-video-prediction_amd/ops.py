@@ -29,6 +29,7 @@ from .tool_ops import seq_nearest, NEAREST_GROUP, NEAREST_MAX_QUERIES, NEAREST_M
 from .tool_ops import points_resample, points_speed, RESAMPLE_MODES, RESAMPLE_MAX_POINTS, RESAMPLE_MAX_RATE      # noqa: F401 -- defined in resample.py, likewise
 from .tool_ops import set_neighbours, prdc, SET_MAX_K, SET_MAX_DIM, SET_MAX_QUERIES, SET_MAX_REFS      # noqa: F401 -- defined in prdc.py, likewise
 from .tool_ops import jpeg_scans, jpeg_encode, JPEG_MIN_SIDE, JPEG_MAX_SIDE, JPEG_BUDGET      # noqa: F401 -- defined in mjpeg.py, likewise
+from .tool_ops import latent_stats_add, latent_sample, latent_path, LATENT_MAX_DIM, LATENT_STATE_FIELDS, LATENT_PATH_MAX_STEPS, LATENT_PATH_MODES      # noqa: F401 -- defined in posterior.py, likewise
 
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH = 0, 1, 2, 3
 BN_EPS = 1e-5        # reference: models/networks/layers.py:14

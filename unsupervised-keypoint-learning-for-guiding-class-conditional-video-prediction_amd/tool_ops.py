@@ -4,7 +4,7 @@ and the summaries.  None of them runs inside a train step; each is called once p
 read-backs -- is written out.  ``ops`` re-exports every name here: ``ops.sheet_paste``, ``ops.MAX_DRAWS`` ... are the public names.  ``seq_nearest`` (evaluate.py --novelty)
 is written beside its tables in ``novelty`` and reaches ``tool_ops`` and ``ops`` by the import at the end of each; so do ``points_resample``
 and ``points_speed`` of ``resample``, ``set_neighbours`` and ``prdc`` of ``prdc`` (evaluate.py --prdc) and ``jpeg_scans`` and ``jpeg_encode`` of
-``mjpeg`` (evaluate.py --video).
+``mjpeg`` (evaluate.py --video) and ``latent_stats_add``, ``latent_sample`` and ``latent_path`` of ``posterior`` (evaluate.py --posterior).
 """
 import numpy as np
 import torch
@@ -605,3 +605,7 @@ from .prdc import set_neighbours, prdc, SET_MAX_K, SET_MAX_DIM, SET_MAX_QUERIES,
 
 # evaluate.py --video: the wrappers are written beside the tables and the container in mjpeg.py
 from .mjpeg import jpeg_scans, jpeg_encode, JPEG_MIN_SIDE, JPEG_MAX_SIDE, JPEG_BUDGET      # noqa: E402,F401
+
+# evaluate.py --posterior, animate.py --interpolate / --motion-from: the wrappers are written beside the host-side summary in posterior.py
+from .posterior import (latent_stats_add, latent_sample, latent_path, LATENT_MAX_DIM, LATENT_STATE_FIELDS,      # noqa: E402,F401
+                        LATENT_PATH_MAX_STEPS, LATENT_PATH_MODES)
